@@ -8,8 +8,12 @@ rows ahead); finished frames are spliced, NAL-escaped and exported to host-mappe
 (mv_clusters speculation) and appended to the Annex-B stream by the host while the launch is still running (DESIGN.md
 sections 4-5).  The timed region covers everything after the input is resident: all kernel launches incl. the relaunches
 after a mis-speculated mv_clusters state, the export of the coded slices, the host-side stream assembly.
-The md5 of the timed output is compared with the md5 of the REFERENCE encoder's stream for the same clip
-(tests/golden/golden_big.json: `parity_full_stream`).
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  --full adds what takes runs of its own or
+checks against the reference: the md5 of the timed output against the md5 of the REFERENCE encoder's stream for the same clip
+(tests/golden/golden_big.json: `parity_full_stream`), the per-frame API, the PCIe-inclusive pass, the 8-slice stream, four
+streams at once and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned (the coded stream and the
+per-frame sizes, as float arrays) to DIR/*.npy, so that two builds can be compared output for output.
 
 --gpus N (launched by torch.distributed.run): by default every rank encodes its own clip on its own GPU -- clips are
 independent, no data-path collective (weak scaling); torch.distributed only provides the barrier and the max-reduce.
@@ -232,11 +236,33 @@ def multi_stream_pass(P, frames, w, h, gop, clips=4):
             "note": "aggregate of %d single-slice streams in one launch group on ONE GPU; every stream md5-checked against the reference; not the headline" % clips}
 
 
+DUMP_MAX_ELEMS = {"bitstream": 12 << 20, "frame_bytes": 1 << 20}     # float32 / float64: at most 56 MiB in all
+
+
+def dump_outputs(d, stream, sizes):
+    """what the timed path returned in its last step, as float arrays: the coded stream (one element per byte, float32) and the
+    per-frame sizes (float64).  An array longer than its cap is replaced by a fixed sample (seed 0, positions in stream order)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {"bitstream": np.frombuffer(stream, dtype=np.uint8).astype(np.float32),
+              "frame_bytes": np.asarray(sizes, dtype=np.float64)}
+    for name, v in arrays.items():
+        cap = DUMP_MAX_ELEMS[name]
+        if v.size > cap:
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, cap, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity checks against the reference's stream and the secondary measurements (per-frame API, PCIe-inclusive "
+                         "pass, 8 slices, four streams at once, CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the coded stream and per-frame sizes of the last timed step to DIR/*.npy (float32 / float64)")
     ap.add_argument("--shard", choices=["clips", "stream"], default="clips",
                     help="clips: every rank its own clip (weak scaling, default); stream: the ranks encode GOP blocks of ONE stream (strong scaling)")
     ap.add_argument("--slices", type=int, default=0, help="row-band slices per frame (the reference's --threads build); default one slice")
@@ -250,6 +276,8 @@ def main():
     ap.add_argument("--size", default="%dx%d" % (W, H), help=argparse.SUPPRESS)
     ap.add_argument("--gop", type=int, default=GOP, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     w, h = (int(v) for v in a.size.split("x"))
     nmb = ((w + 15) // 16) * ((h + 15) // 16)
     on_gpu = a.backend == "nccl"
@@ -355,6 +383,15 @@ def main():
             reencoded = ree
         else:
             per_rank = per
+    if a.dump_outputs:
+        # rank 0 writes its clip; in stream mode the whole stream with every rank's frame sizes
+        dump_stream, dump_sizes = out, sizes
+        if stream_mode:
+            all_sizes = [None] * world
+            dist.all_gather_object(all_sizes, sizes)
+            dump_stream, dump_sizes = b"".join(per), [s for r in all_sizes for s in r]
+        if rank == 0:
+            dump_outputs(a.dump_outputs, dump_stream, dump_sizes)
 
     if rank == 0:
         total_frames = a.steps * frames * (1 if stream_mode else world)
@@ -410,13 +447,15 @@ def main():
         if stream_mode:
             line["config"]["stream_md5"] = stream_md5
             line["config"]["frames_encoded_again_per_rank"] = reencoded
-            g = _golden_md5(w, h, frames, gop, QP) if not a.slices else None
-            line["config"]["parity_full_stream"] = (stream_md5 == g) if g else None
+            if a.full:
+                g = _golden_md5(w, h, frames, gop, QP) if not a.slices else None
+                line["config"]["parity_full_stream"] = (stream_md5 == g) if g else None
         elif world == 1:
-            g = _golden_md5(w, h, frames, gop, QP) if not a.slices else None
-            line["config"]["parity_full_stream"] = (hashlib.md5(out).hexdigest() == g) if g else None
+            if a.full:
+                g = _golden_md5(w, h, frames, gop, QP) if not a.slices else None
+                line["config"]["parity_full_stream"] = (hashlib.md5(out).hexdigest() == g) if g else None
             line["config"]["stream_md5"] = hashlib.md5(out).hexdigest()
-        if world == 1 and on_gpu and not a.no_extras and (w, h) == (W, H):
+        if world == 1 and on_gpu and a.full and not a.no_extras and (w, h) == (W, H):
             try:
                 line["dropin_api"] = {"fps": dropin_api_fps(P), "unit": "frames/s", "note": "1080p through H264E_encode, frame by frame (upload + one launch + result per call)"}
             except Exception as e:
@@ -434,7 +473,7 @@ def main():
                 line["multi_stream"] = multi_stream_pass(P, frames, w, h, gop)
             except Exception as e:
                 line["multi_stream"] = {"value": None, "note": "failed: %r" % (e,)}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 cb, ref_bytes = cpu_baseline()
                 line["cpu_baseline"] = cb

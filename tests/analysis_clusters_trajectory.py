@@ -7,8 +7,8 @@ away from its cluster: single outlier macroblocks, once every few frames on synt
 (the candidates are consumed rounded to full samples, h264-lab.h:3498) is what invalidates every frame in flight behind it
 (DESIGN.md 5): the printed `flips`.  On the 1080p bench clip the second cluster hovers around x = 2..3 quarter samples, so most
 moves are flips -- 23 in 600 frames."""
-import sys, numpy as np, ctypes as C
-sys.path.insert(0,'/root/repo/tests')
+import os, sys, numpy as np, ctypes as C
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import oracle_lib, clips
 w,h,n=1920,1080,int(sys.argv[1]) if len(sys.argv) > 1 else 40
 nmbx=120

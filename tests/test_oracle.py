@@ -44,20 +44,31 @@ def test_oracle_matches_reference_golden(g):
         assert data == open(os.path.join(HERE, "golden", g["stream"]), "rb").read()
 
 
-@pytest.mark.skipif(not os.path.exists(oracle_lib.REF_APP), reason="compiled reference (oracle/_ref) not present")
+# what the reference binary wrote for the fresh clips of the side-by-side tests (tests/golden/make_golden_side_by_side.py)
+SIDE = json.load(open(os.path.join(HERE, "golden", "side_by_side.json")))
+
+
+def _md5_len(data):
+    return hashlib.md5(data).hexdigest(), len(data)
+
+
 @pytest.mark.parametrize("qp", [10, 18, 26, 34, 42, 51])
 @pytest.mark.parametrize("mode", ["--gop 30", "--gop 2 --speed 1", "--gop 30 --speed 9"])
 def test_oracle_vs_compiled_reference(tmp_path, qp, mode):
-    """side-by-side with the reference binary on a fresh clip (not in the golden table)"""
+    """side-by-side with the reference binary on a fresh clip (not in the golden table): against its recorded output and, where
+    oracle/_ref is built, against the binary itself"""
     w, h, n = 128, 96, 5
     c = synth.clip(w, h, n, seed=qp)
-    yuv = tmp_path / ("c_%dx%d.yuv" % (w, h))
-    c.tofile(yuv)
-    out = tmp_path / "o.264"
     flags = ("--qp %d " % qp) + mode
-    subprocess.run([oracle_lib.REF_APP, "--input", str(yuv), "--output", str(out)] + flags.split(), check=True, capture_output=True)
     data, _ = oracle_lib.encode_clip(c, w, h, **_flags(flags))
-    assert data == out.read_bytes()
+    want = SIDE["oracle_vs_ref"][flags]
+    assert _md5_len(data) == (want["md5"], want["bytes"])
+    if os.path.exists(oracle_lib.REF_APP):
+        yuv = tmp_path / ("c_%dx%d.yuv" % (w, h))
+        c.tofile(yuv)
+        out = tmp_path / "o.264"
+        subprocess.run([oracle_lib.REF_APP, "--input", str(yuv), "--output", str(out)] + flags.split(), check=True, capture_output=True)
+        assert data == out.read_bytes()
 
 
 def test_gop_chain_handoff():
@@ -104,20 +115,24 @@ def test_oracle_matches_reference_full_length(name):
     assert hashlib.md5(data).hexdigest() == g["md5"]
 
 
-@pytest.mark.skipif(not os.path.exists(oracle_lib.REF_APP_THR), reason="compiled multi-slice reference (oracle/_ref) not present")
 @pytest.mark.parametrize("slices,flags", [(2, "--qp 26 --gop 30"), (3, "--qp 40 --gop 2"), (5, "--qp 18 --gop 30 --speed 2"), (8, "--kbps 200 --gop 30")])
 def test_oracle_row_bands_vs_compiled_reference(tmp_path, slices, flags):
-    """side-by-side with the reference built with -DH264E_MAX_THREADS=8 (oracle/_ref/encode_app_ref_thr) on a fresh clip"""
+    """side-by-side with the reference built with -DH264E_MAX_THREADS=8 (oracle/_ref/encode_app_ref_thr) on a fresh clip: against its
+    recorded output and, where oracle/_ref is built, against the binary itself"""
     w, h, n = 176, 144, 5
     c = clips.make("pan", w, h, n) if slices == 3 else synth.clip(w, h, n, seed=slices)
-    yuv = tmp_path / ("c_%dx%d.yuv" % (w, h))
-    c.tofile(yuv)
-    out = tmp_path / "o.264"
-    subprocess.run([oracle_lib.REF_APP_THR, "--input", str(yuv), "--output", str(out)] + flags.split() + ["--threads", str(slices)], check=True, capture_output=True)
     kw = _flags_big(flags)
     kw["slices"] = slices
     data, _ = oracle_lib.encode_clip(c, w, h, **kw)
-    assert data == out.read_bytes()
+    want = SIDE["row_bands"]["%s --threads %d" % (flags, slices)]
+    assert _md5_len(data) == (want["md5"], want["bytes"])
+    if os.path.exists(oracle_lib.REF_APP_THR):
+        yuv = tmp_path / ("c_%dx%d.yuv" % (w, h))
+        c.tofile(yuv)
+        out = tmp_path / "o.264"
+        subprocess.run([oracle_lib.REF_APP_THR, "--input", str(yuv), "--output", str(out)] + flags.split() + ["--threads", str(slices)], check=True,
+                       capture_output=True)
+        assert data == out.read_bytes()
 
 
 VBV_GOLDEN = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vbv.json")))
