@@ -76,6 +76,7 @@ def load(path=None):
     L.H264E_set_vbv_state.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.H264E_set_vbv_state.restype = None
     L.H264E_set_slices.argtypes = [C.c_void_p, C.c_int]
+    L.H264E_set_denoise.argtypes = [C.c_void_p, C.c_int]
     L.H264E_close.argtypes = [C.c_void_p]
     L.H264E_close.restype = None
     L.H264E_set_device.argtypes = [C.c_int]
@@ -90,6 +91,7 @@ def load(path=None):
     L.H264E_clip_read_recon.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.H264E_clip_set_ssd_output.argtypes = [C.c_void_p, C.c_void_p]
     L.H264E_clip_set_ssd_output.restype = None
+    L.H264E_clip_set_denoise.argtypes = [C.c_void_p, C.c_int]
     L.H264E_clip_revalidate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.H264E_clip_restart.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     L.H264E_clip_close.argtypes = [C.c_void_p]
@@ -106,7 +108,7 @@ def _err(L, what):
 class Encoder:
     """Frame-at-a-time encoder through the reference API: H264E_sizeof -> H264E_init -> H264E_encode."""
 
-    def __init__(self, width, height, gop=20, qp=33, speed=0, kbps=0, const_input=1, vbv_size_bytes=100000 // 8, lib=None, slices=0):
+    def __init__(self, width, height, gop=20, qp=33, speed=0, kbps=0, const_input=1, vbv_size_bytes=100000 // 8, lib=None, slices=0, denoise=False):
         self.L = load(lib)
         self.w, self.h = width, height
         self.cp = CreateParam(width=width, height=height, gop=gop, vbv_size_bytes=vbv_size_bytes, const_input_flag=const_input,
@@ -123,6 +125,8 @@ class Encoder:
             raise _err(self.L, "H264E_init status %d" % st)
         if slices and self.L.H264E_set_slices(self.persist, slices):
             raise H264EError("H264E_set_slices(%d) refused" % slices)
+        if denoise and self.L.H264E_set_denoise(self.persist, 1):       # the reference's temporal_denoise_flag (--denoise)
+            raise _err(self.L, "H264E_set_denoise refused")
         self.rp = RunParam(encode_speed=speed)
         if kbps:
             self.rp.desired_frame_bytes = kbps * 1000 // 8 // 30  # minih264e_test.c:596-600
@@ -177,13 +181,24 @@ class ClipEncoder:
     """Whole-clip streaming encode on one GPU (H264E_clip_* extension): consecutive frames as a temporal wavefront."""
 
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
-                 clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0):
+                 clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
         self.par = ClipParam(width, height, gop, qp, speed, 100000 // 8, device, max_chains, idr_state, (C.c_int32 * 2)(*clusters_in), slices, kbps, resident, keep_records)
         self.c = C.c_void_p()
         if self.L.H264E_clip_open(C.byref(self.c), C.byref(self.par), nframes):
             raise _err(self.L, "H264E_clip_open")
+        if denoise:
+            try:
+                self.set_denoise(True)
+            except H264EError:
+                self.close()
+                raise
+
+    def set_denoise(self, on):
+        """The temporal denoiser (H264E_clip_set_denoise): only while the clip stands at frame 0."""
+        if self.L.H264E_clip_set_denoise(self.c, int(bool(on))):
+            raise _err(self.L, "H264E_clip_set_denoise")
 
     def upload(self, clip, first=0):
         clip = np.ascontiguousarray(clip, dtype=np.uint8)

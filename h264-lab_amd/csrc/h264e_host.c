@@ -499,6 +499,8 @@ typedef struct
     int32_t clusters[2];
     rc_t rc;
     int slices;                             /* row-band slices per frame (H264E_set_slices), 0 / 1 = one */
+    int frames_in;                          /* frames H264E_encode has taken since H264E_init */
+    int denoise, den_started;               /* temporal denoiser on (H264E_set_denoise); its state has left zero */
 } henc_t;
 
 /* The reference API has no destructor and callers simply free() the blob, so nothing that needs
@@ -682,6 +684,21 @@ int H264E_set_slices(H264E_persist_t *p, int nslices)
     return H264E_STATUS_SUCCESS;
 }
 
+/* The reference's temporal denoiser (h264-lab.h:6684-6695, create parameter temporal_denoise_flag, which H264E_init keeps refusing):
+ * before the first frame only; zeroes the state.  Frames with encode_speed < 2 are then denoised on the device and the denoised
+ * picture is encoded; other frames are encoded raw and leave the state alone. */
+int H264E_set_denoise(H264E_persist_t *p, int on)
+{
+    henc_t *e = (henc_t *)p;
+    impl_t mm;
+    g_host_err[0] = 0;
+    if (!impl_of(e, &mm) || e->frames_in) return H264E_STATUS_BAD_PARAMETER;
+    if (on && h264e_hip_denoise_reset(mm.pool)) return H264E_STATUS_BAD_ARGUMENT;
+    e->denoise = !!on;
+    e->den_started = 0;
+    return H264E_STATUS_SUCCESS;
+}
+
 void H264E_set_vbv_state(H264E_persist_t *p, int vbv_size_bytes, int vbv_fullness_bytes)
 {
     henc_t *e = (henc_t *)p;
@@ -702,7 +719,7 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
     impl_t mm, *m = impl_of(e, &mm) ? &mm : NULL;
     uint8_t *out = (uint8_t *)scratch;
     size_t out_pos = 0, cap;
-    int frame_type, key, qp, sp, ss;
+    int frame_type, key, qp, sp, ss, den;
     h264e_hip_task_t task;
     h264e_hip_result_t res;
     const uint8_t *yuv[3];
@@ -747,6 +764,15 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
 
     yuv[0] = in->yuv[0]; yuv[1] = in->yuv[1]; yuv[2] = in->yuv[2];
     memset(&res, 0, sizeof(res));
+    /* h264-lab.h:6684-6695: the denoiser runs first (also in front of a transparent VBV-overflow frame) and its output is what gets encoded */
+    den = e->denoise && opt->encode_speed < 2;
+    if (den)
+    {
+        if (h264e_hip_upload_planes(m->pool, 0, yuv, in->stride) || h264e_hip_denoise_frames(m->pool, 0, 1, !e->den_started)) return H264E_STATUS_BAD_ARGUMENT;
+        e->den_started = 1;
+        task.denoised = 1;
+    }
+    e->frames_in++;
     if (e->param.vbv_size_bytes && e->rc.vbv_bits - opt->desired_frame_bytes*8 > e->param.vbv_size_bytes*8)
     {
         /* h264-lab.h:6497-6510 "encode transparent frame on VBV overflow" -- reachable only right after H264E_set_vbv_state (rc_frame_end
@@ -772,7 +798,7 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
         res.all_skipped = 1;
     } else
     {
-    if (h264e_hip_reset_results(m->pool, 0) || h264e_hip_upload_planes(m->pool, 0, yuv, in->stride)) return H264E_STATUS_BAD_ARGUMENT;
+    if (h264e_hip_reset_results(m->pool, 0) || (!den && h264e_hip_upload_planes(m->pool, 0, yuv, in->stride))) return H264E_STATUS_BAD_ARGUMENT;
     {
         int32_t run[1][2] = { { e->clusters[0], e->clusters[1] } };
         if (step_exact(m->pool, 1, &task, e->seq.nmbx, e->seq.nmby, run, NULL, NULL) || h264e_hip_stream_done(m->pool, 0, &res) != 1) return H264E_STATUS_BAD_ARGUMENT;
@@ -866,7 +892,14 @@ struct H264E_clip_tag
     uint8_t *big; size_t big_cap;           /* scratch: NALs of a frame that did not fit the host mirror */
     h264e_hip_task_t *tasks;                /* scratch [ring] */
     int32_t (*used)[2];                     /* scratch [ring] */
+    /* temporal denoiser (H264E_clip_set_denoise): frames [0, den_done) have been denoised; the denoised picture of frame f lives in the
+     * pool's denoised slot f % resident, the one of den_done - 1 is the state in front of frame den_done */
+    int denoise, den_done;
 };
+
+/* the HBM budget of the slot ring and what one slot takes: two pictures, records, row bit buffers (2 KB per macroblock), arenas */
+#define CLIP_DEV_BUDGET (24.0*1073741824.0)
+static double clip_dev_slot_bytes(int nmb) { return (double)nmb*256.0*3.0 + (double)nmb*(64 + 96 + 8 + 640 + 660 + 2048 + 64) + 65536.0; }
 
 int H264E_struct_size(int which) { return which == 0 ? (int)sizeof(H264E_clip_param_t) : which == 1 ? (int)sizeof(H264E_clip_stats_t) : -1; }
 
@@ -929,8 +962,8 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
          * (measured at 1080p x 600: 8 slices 14.5 -> 18.3 M MB/s, all-intra 14.2 -> 19.6 M, single slice 6.77 -> 6.94 M). */
         {
             const double host_slot = (double)nmb*168.0 + 65536.0 + 4096.0;
-            const double dev_slot = (double)nmb*256.0*3.0 + (double)nmb*(64 + 96 + 8 + 640 + 660 + 2048 + 64) + 65536.0;      /* two pictures, records, row bit buffers (2 KB per macroblock), arenas */
-            const double by_host = 896.0*1048576.0/host_slot, by_dev = 24.0*1073741824.0/dev_slot;
+            const double dev_slot = clip_dev_slot_bytes(nmb);
+            const double by_host = 896.0*1048576.0/host_slot, by_dev = CLIP_DEV_BUDGET/dev_slot;
             int cap = (int)(by_host < by_dev ? by_host : by_dev);
             cap = imin(imax(cap, c->launch_base), 1024);
             c->ring = (par->max_chains > 0 ? par->max_chains : cap) + 1;
@@ -985,6 +1018,11 @@ static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int 
     int done = 0;
     if (!c || first < 0 || n < 0 || first + n > c->nframes) { snprintf(g_host_err, sizeof(g_host_err), "upload: bad frame range"); return -1; }
     if (first + n - c->resident > c->next) { snprintf(g_host_err, sizeof(g_host_err), "upload: input ring full (frames %d.. are not encoded yet)", c->next); return -1; }
+    if (c->denoise && first > 0 && first < c->den_done && first - 1 < c->den_done - c->resident)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "upload: frame %d would be denoised again, but the denoised picture in front of it has left the input ring (rewind and upload from frame 0)", first);
+        return -1;
+    }
     while (done < n)
     {
         const int slot = (first + done) % c->resident, run = imin(n - done, c->resident - slot);
@@ -997,6 +1035,7 @@ static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int 
     }
     if (async) { if (first + n > c->pending_avail) c->pending_avail = first + n; }
     else if (first + n > c->avail) c->avail = first + n;
+    if (first < c->den_done) c->den_done = first;       /* new inputs: their denoised pictures (and all behind them) are made again */
     return 0;
 }
 
@@ -1046,6 +1085,7 @@ int H264E_clip_generate_synth(H264E_clip_t *c, int first, int nframes, int t0, u
         done += run;
     }
     if (first + nframes > c->avail) c->avail = first + nframes;
+    if (first < c->den_done) c->den_done = first;
     return h264e_hip_sync(c->pool);
 }
 
@@ -1119,6 +1159,7 @@ int H264E_clip_read_records(H264E_clip_t *c, int frame, void *dst /* nmb x 8 byt
 int H264E_clip_restart(H264E_clip_t *c, int frame, const int32_t state[2])
 {
     if (!c || !state || frame < 0 || frame > c->avail || frame % c->gop_len) return -1;
+    if (c->denoise && frame) { snprintf(g_host_err, sizeof(g_host_err), "restart: a denoised stream restarts at frame 0 only"); return -1; }
     c->next = frame;
     if (c->resident < c->nframes) c->avail = c->pending_avail = frame;      /* a ring: the inputs from here on have to be uploaded again */
     c->state[0] = state[0]; c->state[1] = state[1];
@@ -1129,6 +1170,33 @@ int H264E_clip_restart(H264E_clip_t *c, int frame, const int32_t state[2])
 }
 
 /* diagnostic (stamps build): per-phase cycle sums since the last call */
+/* The temporal denoiser for the clip encoder (see H264E_set_denoise): while the clip stands at frame 0.  With speed < 2 every frame is
+ * denoised on the device, in stream order, before the launch that first encodes it; the denoised pictures are a pure function of the
+ * inputs, so a rewind keeps them until frames are uploaded again.  Refused together with keep_records (a GOP shard's first frame
+ * would need the denoised picture of the frame in front of it, which lives in another encoder). */
+int H264E_clip_set_denoise(H264E_clip_t *c, int on)
+{
+    g_host_err[0] = 0;
+    if (!c) return -1;
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise: only at frame 0 (after open or rewind)"); return -1; }
+    if (on && c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise: not with keep_records (GOP shards)"); return -1; }
+    if (on && !c->denoise)
+    {
+        /* the denoised frames (one per resident input slot + the zero state) count in the HBM budget that sized the slot ring */
+        const double fsz = (double)c->seq.width*c->seq.height*3/2, den = fsz*(c->resident == 1 ? 3 : c->resident + 1);
+        if (c->par.max_chains <= 0 && (double)c->ring*clip_dev_slot_bytes(c->seq.nmb) + den > CLIP_DEV_BUDGET)
+        {
+            snprintf(g_host_err, sizeof(g_host_err), "set_denoise: %d slots + %.0f MB of denoised frames exceed the %.0f GB budget: open with max_chains or resident_frames",
+                     c->ring, den/1048576.0, CLIP_DEV_BUDGET/1073741824.0);
+            return -1;
+        }
+        if (h264e_hip_denoise_reset(c->pool)) return -1;
+        c->den_done = 0;
+    }
+    c->denoise = !!on;
+    return 0;
+}
+
 int H264E_clip_stamps(H264E_clip_t *c, unsigned long long *dst) { return c ? h264e_hip_stamps_read(c->pool, dst, 1) : -1; }
 
 int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_bytes, int *frame_bytes, int profile, H264E_clip_stats_t *st)
@@ -1217,6 +1285,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
             t->traj_from_device = (i == 0) && c->first_dev;
             t->first_row = (i == 0 && c->first_dev) ? c->first_row : 0;
             t->narrow_window = c->narrow;
+            t->denoised = c->denoise && c->par.speed < 2;
         }
         /* Hedges (rate control): the speculated QP of a frame is usually off by one or two when it is off, so every frame behind the
          * first one is ALSO encoded with the neighbouring QPs, as leaves in spare slots (same reference, same mv_clusters
@@ -1255,6 +1324,13 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         double t_first = 0, t_last = 0;
         int rc_miss = 0, take = -1, moved_from = -1, moved_to = -1, relaunch = 0;
         const char *why = "all frames delivered";       /* what ended the launch (H264E_DEBUG) */
+        /* the denoiser: every frame uploaded so far and not yet denoised, in stream order, before the launch that reads them */
+        if (c->denoise && c->par.speed < 2 && c->den_done < limit)
+        {
+            if (limit - c->den_done > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "denoise: frames %d..%d do not fit the input ring", c->den_done, limit - 1); goto done; }
+            if (h264e_hip_denoise_frames(c->pool, c->den_done % c->resident, limit - c->den_done, c->den_done == 0)) goto done;
+            c->den_done = limit;
+        }
         if (h264e_hip_submit(c->pool, tasks)) goto done;
 
         /* consume the frames in stream order while the launch is still running */

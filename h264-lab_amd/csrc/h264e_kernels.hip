@@ -10,6 +10,8 @@
  *                        (cdna_hip_programming.md Guideline 16 R1).  The finalizer splices the row bit buffers into the
  *                        slice RBSP (there is no separate splice kernel) and exports the frame to host-mapped memory.
  *   h264e_synth_kernel   fills resident input frames with the synth_v1 clip (bench / test input in HBM).
+ *   h264e_denoise_kernel the temporal denoiser (enc_denoise.h) over one frame: raw input + previous denoised picture -> new
+ *                        denoised picture, out of place, one launch per frame in stream order.
  *
  * HIP only (hipcc --offload-arch=gfx950).  The host side of the boundary is h264e_pool.h, included at the end; the test-only
  * emulation of tests/emu compiles the same kernel HEADERS with its own launch functions and never sees this file.
@@ -19,6 +21,7 @@
 #include <string.h>
 #include "enc_row.h"
 #include "enc_selftest.h"
+#include "enc_denoise.h"
 #include "../../include/h264e_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -665,6 +668,22 @@ __global__ void h264e_ssd_kernel(const uint8_t *clip, size_t frame_bytes, int wi
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(out + 3*i + pl, s);
 }
 
+/* the temporal denoiser over one packed I420 frame (width x height): grid.z = plane, grid.y = row, grid.x * 256 lanes x 4 samples along
+ * the row; the gain table is staged in LDS.  in / prev / out are separate frames (no inter-workgroup traffic). */
+__global__ void __launch_bounds__(256) h264e_denoise_kernel(const uint8_t *in, const uint8_t *prev, uint8_t *out, int width, int height)
+{
+    __shared__ uint8_t T[256];
+    const int pl = (int)blockIdx.z, y = (int)blockIdx.y;
+    const int w = width >> (pl ? 1 : 0), h = height >> (pl ? 1 : 0);
+    if (y >= h) return;                         /* chroma planes have half the rows (uniform per workgroup) */
+    T[threadIdx.x] = k_denoise_gain[threadIdx.x];
+    __syncthreads();
+    const size_t off = pl ? (size_t)width*height + (pl == 2 ? (size_t)(width/2)*(height/2) : 0) : 0;
+    const int aligned = !((((uintptr_t)in + off) | ((uintptr_t)prev + off) | ((uintptr_t)out + off) | (uintptr_t)w) & 3);
+    denoise_group((const LDS_AS uint8_t *)T, (const GLOBAL_AS uint8_t *)(in + off), (const GLOBAL_AS uint8_t *)(prev + off), (GLOBAL_AS uint8_t *)(out + off),
+                  w, h, (int)(blockIdx.x*blockDim.x + threadIdx.x), y, aligned);
+}
+
 /* ------------------------------------------------------------------ launches (what h264e_pool.h calls) */
 
 /* variant: 0 = intra frames only (one wave per row, 4 per SIMD), 1 = one wave per row, 2 = two waves per row (3 per SIMD), 3 = the latency variant: four
@@ -705,6 +724,11 @@ static void bk_launch_ssd(int n, const uint8_t *clip, size_t frame_bytes, int wi
 static void bk_launch_nal_selftest(uint8_t *dst, uint32_t cap, const uint8_t *src, uint32_t n, uint32_t *out, hipStream_t st)
 {
     hipLaunchKernelGGL(h264e_nal_escape_selftest_kernel, dim3(1), dim3(64), 0, st, dst, cap, src, n, out);
+}
+static void bk_launch_denoise(const uint8_t *in, const uint8_t *prev, uint8_t *out, int width, int height, hipStream_t st)
+{
+    const unsigned gx = (unsigned)((((width + 3) >> 2) + 255) >> 8);
+    hipLaunchKernelGGL(h264e_denoise_kernel, dim3(gx, (unsigned)height, 3), dim3(256), 0, st, in, prev, out, width, height);
 }
 static void bk_launch_stage_selftest(int stage, const uint8_t *in, const int *args, uint8_t *out, hipStream_t st)
 {

@@ -10,6 +10,7 @@
  */
 #ifndef H264E_POOL_H
 #define H264E_POOL_H
+#include "enc_denoise.h"
 
 static thread_local char g_err[256];       /* per calling thread */
 #define FAIL(...) do { snprintf(g_err, sizeof(g_err), __VA_ARGS__); return -1; } while (0)
@@ -146,6 +147,11 @@ struct h264e_hip_pool
     h264e_geom_t G;
     size_t frame_bytes;
     uint8_t *clip;                       /* device: resident input frames, packed I420 */
+    /* temporal denoiser (h264e_hip_denoise_*): denoised frames parallel to `clip` (slot i = the denoised input slot i), then the zero
+     * state; a single-slot pool ping-pongs two frames instead (den_flip: the current one).  NULL until the denoiser is switched on. */
+    uint8_t *den;
+    int den_frames, den_flip;
+    hipEvent_t ev_copy;                  /* the copy stream's uploads, waited for by a denoise launch */
     h264e_chain_dev_t *chains_host;      /* host mirror of the device descriptors */
     h264e_chain_dev_t *chains_dev;
     h264e_frame_task_t *tasks_dev;       /* ring of TASK_RING task arrays */
@@ -243,10 +249,11 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     host_free(p->hheap);
     free(p->host_rbsp); free(p->host_mbrec); free(p->slot_launch); free(p->order_host);
     dev_free(p->heap);
+    dev_free(p->den);
     if (p->stream)
     {
         for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventDestroy(p->ev[i][k]);
-        (void)hipEventDestroy(p->ev_t0); (void)hipEventDestroy(p->ev_t1); (void)hipEventDestroy(p->ev_prep);
+        (void)hipEventDestroy(p->ev_t0); (void)hipEventDestroy(p->ev_t1); (void)hipEventDestroy(p->ev_prep); (void)hipEventDestroy(p->ev_copy);
         (void)hipStreamDestroy(p->stream);
         if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
         if (p->abort_stream) (void)hipStreamDestroy(p->abort_stream);
@@ -380,7 +387,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     }
     if (hipStreamCreate(&p->stream) != hipSuccess || hipStreamCreate(&p->copy_stream) != hipSuccess || hipStreamCreate(&p->abort_stream) != hipSuccess) { if (p->guarded) process_guard_release(device); free(p); FAIL("hipStreamCreate failed"); }
     for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventCreate(&p->ev[i][k]);
-    (void)hipEventCreate(&p->ev_t0); (void)hipEventCreate(&p->ev_t1); (void)hipEventCreate(&p->ev_prep);
+    (void)hipEventCreate(&p->ev_t0); (void)hipEventCreate(&p->ev_t1); (void)hipEventCreate(&p->ev_prep); (void)hipEventCreate(&p->ev_copy);
     p->chains_host = (h264e_chain_dev_t *)calloc((size_t)nchains, sizeof(h264e_chain_dev_t));
     p->clu_dev = (int32_t **)calloc((size_t)nchains, sizeof(int32_t *));
     p->ref_sel = (int *)calloc((size_t)nchains, sizeof(int));
@@ -533,6 +540,70 @@ extern "C" int h264e_hip_ssd_frames(h264e_hip_pool_t *p, int n, int in0, int in_
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, p->ssd_dev, sizeof(unsigned long long)*3*(size_t)n, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+/* ---- temporal denoiser (enc_denoise.h): one h264e_denoise_kernel launch per frame on the pool's stream, in stream order */
+
+#ifdef H264E_EMU
+/* the emulation's launch: the kernel's per-group code as a lane loop, plane by plane, row by row */
+static void bk_launch_denoise(const uint8_t *in, const uint8_t *prev, uint8_t *out, int width, int height, hipStream_t)
+{
+    for (int pl = 0; pl < 3; pl++)
+    {
+        const int w = width >> (pl ? 1 : 0), h = height >> (pl ? 1 : 0);
+        const size_t off = pl ? (size_t)width*height + (pl == 2 ? (size_t)(width/2)*(height/2) : 0) : 0;
+        const int aligned = !((((uintptr_t)in + off) | ((uintptr_t)prev + off) | ((uintptr_t)out + off) | (uintptr_t)w) & 3);
+        for (int y = 0; y < h; y++)
+            for (int g = 0; g < (w + 3)/4; g++) denoise_group(k_denoise_gain, in + off, prev + off, out + off, w, h, g, y, aligned);
+    }
+}
+#endif
+
+static int den_index(const h264e_hip_pool_t *p, int slot) { return p->frames_resident == 1 ? p->den_flip : slot; }
+static uint8_t *den_frame(const h264e_hip_pool_t *p, int index) { return p->den + p->frame_bytes*(size_t)index; }
+
+extern "C" int h264e_hip_denoise_reset(h264e_hip_pool_t *p)
+{
+    if (!p) FAIL("denoise_reset: null pool");
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->den)
+    {
+        p->den_frames = (p->frames_resident == 1 ? 2 : p->frames_resident) + 1;
+        if (dev_malloc((void **)&p->den, p->frame_bytes*(size_t)p->den_frames)) { p->den = 0; FAIL("denoise: device allocation failed (%d frames)", p->den_frames); }
+    }
+    p->den_flip = 0;
+    HIPCHK(hipMemsetAsync(p->den, 0, p->frame_bytes*(size_t)p->den_frames, p->stream));
+    return 0;
+}
+
+extern "C" int h264e_hip_denoise_frames(h264e_hip_pool_t *p, int first, int n, int from_zero)
+{
+    const int R = p ? p->frames_resident : 0;
+    if (!p || !p->den || first < 0 || first >= R || n < 0 || n > R) FAIL("denoise_frames: bad argument (or the denoiser is not on)");
+    if (!n) return 0;
+    HIPCHK(hipSetDevice(p->device));
+    /* the inputs may have come over the copy stream (h264e_hip_upload_i420_async): the launches wait for everything issued there */
+    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
+    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
+    for (int i = 0; i < n; i++)
+    {
+        const int s = (first + i) % R;
+        const int prev = (i == 0 && from_zero) ? p->den_frames - 1 : R == 1 ? p->den_flip : (s + R - 1) % R;
+        const int out = R == 1 ? p->den_flip ^ 1 : s;
+        bk_launch_denoise(p->clip + p->frame_bytes*(size_t)s, den_frame(p, prev), den_frame(p, out), p->G.width, p->G.height, p->stream);
+        if (R == 1) p->den_flip ^= 1;
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int h264e_hip_read_denoised(h264e_hip_pool_t *p, int slot, uint8_t *dst)
+{
+    if (!p || !dst || !p->den || slot < 0 || slot >= p->frames_resident) FAIL("read_denoised: bad argument (or the denoiser is not on)");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipMemcpy(dst, den_frame(p, den_index(p, slot)), p->frame_bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -904,7 +975,8 @@ extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tas
         if (t.slice_type != 2) all_intra = 0;
         if (t.nslices > max_slices) max_slices = t.nslices;
         if (t.stream_mode && t.walk_quiet) any_leaf = 1;
-        const uint8_t *f = p->clip + p->frame_bytes*(size_t)t.frame_index;
+        if (t.denoised && !p->den) { free(host); FAIL("submit: task %d asks for the denoised picture, but the denoiser is not on", c); }
+        const uint8_t *f = t.denoised ? den_frame(p, den_index(p, t.frame_index)) : p->clip + p->frame_bytes*(size_t)t.frame_index;
         d.in[0] = f; d.in[1] = f + (size_t)G.width*G.height; d.in[2] = d.in[1] + (size_t)(G.width/2)*(G.height/2);
         d.in_stride[0] = G.width; d.in_stride[1] = d.in_stride[2] = G.width/2;
         d.slice_type = t.slice_type; d.qp = t.qp; d.speed = t.speed;

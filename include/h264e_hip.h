@@ -66,6 +66,9 @@ typedef struct
     /* stream mode: 1 = narrow valid window (53 x 52 samples, consecutive frames 4 macroblock steps apart), 0 = the whole
      * 64 x 64 window (7 steps apart); see h264e_dev.h.  Same bits either way. */
     int narrow_window;
+    /* 1 = encode the denoised picture of resident slot frame_index (h264e_hip_denoise_frames) instead of the raw input; the
+     * sums of squared differences (h264e_hip_ssd_frames) keep reading the raw input */
+    int denoised;
 } h264e_hip_task_t;
 
 #define H264E_HIP_MAX_SLICES 16
@@ -106,6 +109,14 @@ int  h264e_hip_upload_planes(h264e_hip_pool_t *pool, int index, const uint8_t *c
 /* fill resident frames [first, first+n) with the synth_v1 test clip ON THE DEVICE (bench input, already in HBM) */
 int  h264e_hip_generate_synth(h264e_hip_pool_t *pool, int first, int nframes, int t0, uint32_t seed);
 int  h264e_hip_submit(h264e_hip_pool_t *pool, const h264e_hip_task_t *tasks /* [nchains] */);
+/* Temporal denoiser (the reference's h264e_denoise_run, enc_denoise.h).  reset: allocates the denoised frames on first use (one per
+ * resident input slot -- two for a single-slot pool, which ping-pongs -- plus the zero state) and zeroes them.  frames: denoises
+ * resident input slots first, first + 1, ... (mod frames_resident) in order on the pool's stream, one kernel launch per frame, after
+ * every upload issued on the copy stream; the first one's previous picture is the zero state (from_zero) or the denoised picture of
+ * the slot in front of it, each later one that of the frame before it.  read_denoised: the denoised picture of a slot (test hook). */
+int  h264e_hip_denoise_reset(h264e_hip_pool_t *pool);
+int  h264e_hip_denoise_frames(h264e_hip_pool_t *pool, int first, int n, int from_zero);
+int  h264e_hip_read_denoised(h264e_hip_pool_t *pool, int slot, uint8_t *dst);
 /* Launch groups: the submits of the member pools (same device, same picture size, one host thread each) are merged into ONE kernel
  * launch per round -- the streams' jobs interleaved in dispatch order, every job with its own pool's buffers / abort word / results --
  * so that independent streams fill each other's pipeline drains.  h264e_hip_submit of a member blocks until all members that are

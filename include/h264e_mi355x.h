@@ -12,9 +12,11 @@
  *
  * Scope: AVC baseline, key and P frames, one reference frame, one slice per frame or N
  * row-band slices (H264E_set_slices / H264E_clip_param_t.slices: the reference's H264E_MAX_THREADS build),
- * constant QP or frame-level rate control.  Long-term reference frame types, SVC layers, the temporal
- * denoiser, MB-level rate control and NALU-size slicing answer H264E_STATUS_BAD_PARAMETER at init /
- * H264E_STATUS_BAD_FRAME_TYPE at encode instead of silently producing a different stream.
+ * constant QP or frame-level rate control, and the reference's temporal denoiser through the extension calls
+ * H264E_set_denoise / H264E_clip_set_denoise (the create parameter temporal_denoise_flag itself is still refused).
+ * Long-term reference frame types, SVC layers, MB-level rate control and NALU-size slicing answer
+ * H264E_STATUS_BAD_PARAMETER at init / H264E_STATUS_BAD_FRAME_TYPE at encode instead of silently producing a
+ * different stream.
  * The encoder needs a HIP device: without one H264E_init fails (H264E_STATUS_BAD_ARGUMENT) -- there is
  * no CPU fallback.
  */
@@ -61,7 +63,7 @@ typedef struct H264E_create_param_tag
     int const_input_flag;                   /* 0: the reconstruction is written back into the input planes */
     int max_long_term_reference_frames;     /* must be 0 */
     int enableNEON;                         /* ignored */
-    int temporal_denoise_flag;              /* must be 0 */
+    int temporal_denoise_flag;              /* must be 0: the denoiser is switched on with H264E_set_denoise() */
     int sps_id;
     int num_layers;                         /* SVC: must be 0 or 1 */
     int inter_layer_pred_flag;
@@ -108,6 +110,11 @@ void H264E_close(H264E_persist_t *enc);
  * the struct ABI; this library keeps the default ABI and takes the number here instead.  0 / 1 = one slice per frame,
  * 2..16 = N slices (deblocking idc 2, contexts / availability / mv_clusters restarted per slice).  Call after H264E_init. */
 int  H264E_set_slices(H264E_persist_t *enc, int nslices);
+/* The reference's temporal denoiser (h264-lab.h:1547-1621, its temporal_denoise_flag): 1 = on, 0 = off.  Only after H264E_init and
+ * before the first H264E_encode; the denoiser's state starts at zero.  Every frame with encode_speed < 2 is then denoised on the
+ * device and the denoised picture is encoded (the reconstruction still goes back to the caller's planes with const_input_flag = 0);
+ * frames with encode_speed >= 2 are encoded raw and leave the state alone.  H264E_STATUS_BAD_PARAMETER after the first frame. */
+int  H264E_set_denoise(H264E_persist_t *enc, int on);
 /* Select the HIP device used by subsequent H264E_init calls of this process (default 0 / $H264E_DEVICE). */
 void H264E_set_device(int device);
 int  H264E_device_count(void);
@@ -193,6 +200,11 @@ int  H264E_clip_download(H264E_clip_t *clip, int first, int nframes, uint8_t *i4
 int  H264E_clip_read_recon(H264E_clip_t *clip, int frame, uint8_t *dst);
 /* per encoded frame [3] sums of squared differences input vs reconstruction (Y, U, V), computed on the device: encode_app --psnr */
 void H264E_clip_set_ssd_output(H264E_clip_t *clip, uint64_t *ssd);
+/* The temporal denoiser for the clip encoder (see H264E_set_denoise; the clip's speed < 2 selects it for every frame): only while the
+ * clip stands at frame 0 (after open or rewind); the denoised pictures are a pure function of the inputs, kept across a rewind and
+ * made again from the first frame that is uploaded again.  The sums of squared differences compare the RAW input with the
+ * reconstruction, as the reference's --psnr does.  Refused with keep_records (GOP shards).  0 = done, -1 = refused. */
+int  H264E_clip_set_denoise(H264E_clip_t *clip, int on);
 /* GOP shards of ONE stream (one clip encoder per shard / GPU, the shard starting at a key frame with first_idr_pic_id_state =
  * its GOP index & 1 and a SPECULATED mv_clusters_in): once the exact state in front of the shard is known, revalidate walks the
  * kept records (keep_records) and either confirms the shard (*restart_frame = -1, end_state = exact state behind it) or names the
