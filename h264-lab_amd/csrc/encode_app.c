@@ -406,7 +406,7 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
     shard_t *sh;
     int32_t state[2] = { 0, 0 };
     if (n <= 0) return 0;
-    if (cmd.kbps) nsh = 1;                  /* rate control state crosses every frame: one shard */
+    if (cmd.kbps || !cmd.qp) nsh = 1;       /* rate control (--qp 0 too: the controller over QP 10..51) state crosses every frame: one shard */
     if (nsh > ngop) nsh = ngop;
     if (ndev < 1) ndev = 1;
     sh = (shard_t *)calloc((size_t)nsh, sizeof(*sh));

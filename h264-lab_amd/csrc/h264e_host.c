@@ -880,6 +880,7 @@ struct H264E_clip_tag
     int launch_base, launch_frames;         /* frames per launch: the pipeline depth after a mis-speculation, growing after clean launches (H264E_clip_open) */
     int stopped_before;                     /* the previous launch was stopped before its last frame (statistics: the next one pays a pipeline refill) */
     long long far_acc; int far_frames;      /* far reads / frames since the last decision */
+    int rc_on;                              /* frame-level rate control: kbps > 0, or qp 0 (QP 10..51 without a byte target, as H264E_encode) */
     rc_t rcs; int rc_frame, rc_qp;          /* rate control: state, the frame rc_frame_start has run for, its QP */
     int rc_last_bytes[2];                   /* size of the last accepted P / key frame: what a frame still in flight is predicted to weigh */
     /* keep_records: what every accepted frame consumed, so that a different start state can be validated later (GOP shards) */
@@ -937,6 +938,9 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     c = (H264E_clip_t *)calloc(1, sizeof(*c));
     if (!c) return -1;
     c->par = *par;
+    /* encode_app passes qp_min = qp_max = --qp to H264E_encode, which widens 0 (and only 0) to 10..51 (h264-lab.h:6707-6715): the
+     * controller picks every QP then; any other value outside 10..51 is a constant QP at the nearer end */
+    c->rc_on = par->kbps > 0 || par->qp == 0;
     c->par.qp = imin(imax(par->qp, 10), 51);
     seq_init(&c->seq, par->width, par->height, par->vbv_size_bytes, 0);
     c->nframes = nframes;
@@ -1103,7 +1107,7 @@ int H264E_clip_read_recon(H264E_clip_t *c, int frame, uint8_t *dst)
     if (!c || !dst || frame < 0 || frame >= c->next || frame < c->next - (c->ring - 1)) return -1;
     /* rate control: the launches' hedge leaves (alternative QPs of frames in flight) are encoded in spare slots of the ring, i.e. over
      * the pictures of older frames -- only the frames accepted since the last launch's first frame are guaranteed to be intact */
-    if (c->par.kbps > 0 && frame < c->recon_floor) return -1;
+    if (c->rc_on && frame < c->recon_floor) return -1;
     return h264e_hip_read_recon_slot(c->pool, frame % c->ring, dst);
 }
 
@@ -1206,7 +1210,8 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
     /* frame-level rate control (encode_app --kbps, minih264e_test.c:596-600: desired_frame_bytes = kbps*1000/8/30, QP 10..50):
      * a frame's QP is a function of the byte count of the frame before it (h264-lab.h:5924-6141) and moves almost every
      * frame: the frames behind the first one of a launch run on a speculated QP (see the launch loop), the controller on the host */
-    const int rc_on = c->par.kbps > 0, desired_frame_bytes = c->par.kbps*1000/8/30, qp_min = rc_on ? 10 : c->par.qp, qp_max = rc_on ? 50 : c->par.qp;
+    const int rc_on = c->rc_on, desired_frame_bytes = c->par.kbps > 0 ? c->par.kbps*1000/8/30 : 0;
+    const int qp_min = rc_on ? 10 : c->par.qp, qp_max = c->par.kbps > 0 ? 50 : rc_on ? 51 : c->par.qp;     /* qp 0: 10..51, h264-lab.h:6707-6715 */
     const int pic_init_qp = imax(imin(30, qp_max), qp_min);     /* h264-lab.h:6768-6770 */
     const int idr_state = c->par.first_idr_pic_id_state & 1;
     const int first = c->next;
@@ -1585,7 +1590,7 @@ int H264E_clip_encode_multi(H264E_clip_t **clips, int nclips, uint8_t **out, con
              * the pipeline depth -- which costs streams WITHOUT staggered events a few percent and gives staggered ones 13 %
              * (measured, 4 different 1080p clips: 12.8 -> 14.6 M MB/s aggregate; 4 identical ones 21.4 -> 20.7 M) */
             saved_base[i] = clips[i]->launch_base;
-            if (n > 1 && clips[i]->par.slices <= 1 && clips[i]->gop_len > 1 && clips[i]->par.kbps == 0)
+            if (n > 1 && clips[i]->par.slices <= 1 && clips[i]->gop_len > 1 && !clips[i]->rc_on)
             {
                 clips[i]->launch_base = imax(8, clips[i]->launch_base/3);
                 clips[i]->launch_frames = imin(clips[i]->launch_frames, clips[i]->launch_base);

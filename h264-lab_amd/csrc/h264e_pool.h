@@ -318,9 +318,9 @@ static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced)
         }
         int empty = 0;
         for (int i = 0; i < 8*jobs; i++) if (!want[i]) empty = 1;
-        if (empty)
+        if (empty && bands < 8)
         {
-            /* fewer bands than XCDs (tiny pictures, H264E_XCD_BANDS < 8): no banding */
+            /* fewer bands than XCDs (H264E_XCD_BANDS < 8): no banding */
             memcpy(ord, tmp, sizeof(uint32_t)*(size_t)total);
             free(q); free(fill); free(want); free(tmp);
             return 0;
@@ -328,6 +328,8 @@ static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced)
         for (int i = 0; i < total; i++)
         {
             const int row = (int)(tmp[i] & 0xffffu), jb = (int)(tmp[i] >> 16), x = (row >= G.nmby ? bands - 1 : imin_h(bands - 1, row*bands/G.nmby)) & 7;
+            /* a picture of fewer than 8 rows leaves queues without a row of this job: they get the job's padding with its first entry */
+            if (row == 0) for (int y = 0; y < 8; y++) if (!want[8*jb + y]) cnt[y] += (size_t)per;
             q[(size_t)x*qlen + cnt[x]++] = tmp[i];
             if (++fill[8*jb + x] == want[8*jb + x]) cnt[x] += (size_t)(per - want[8*jb + x]);        /* the padding stays H264E_ORDER_PAD */
         }

@@ -128,14 +128,16 @@ const char *H264E_last_error(void);
  * controller disagrees. */
 typedef struct
 {
-    int width, height, gop, qp, speed;
+    int width, height, gop, qp, speed;      /* qp: constant QP, clamped to 10..51 -- except 0, which runs the frame-level controller over
+                                               QP 10..51 without a byte target, as qp_min = qp_max = 0 does in H264E_encode (h264-lab.h:6707-6715) */
     int vbv_size_bytes;                     /* SPS level only */
     int device;
     int max_chains;                         /* cap of the slot ring (frame f lives in slot f % K; K - 1 = most frames one launch can hold); 0 = sized by the
                                                memory budget: 622 slots at 1080p, 162 at 4K, 40 at 8K, at most 1024 */
     int first_idr_pic_id_state;             /* enc->next_idr_pic_id before the first frame (0 for a fresh stream) */
     int32_t mv_clusters_in[2];              /* enc->mv_clusters before the first frame (0,0 for a fresh stream) */
-    int slices;                             /* row-band slices per frame: 0 / 1 = one; N = the reference's H264E_MAX_THREADS build with --threads N */
+    int slices;                             /* row-band slices per frame: 0 / 1 = one; N = the reference's H264E_MAX_THREADS build with --threads N;
+                                               N above the macroblock rows R = R slices (the reference codes rows twice there) */
     int kbps;                               /* 0 = constant QP `qp`; > 0 = frame-level rate control as encode_app --kbps (a few frames per launch then, on a speculated QP that is validated against the exact controller) */
     int resident_frames;                    /* input frames kept in HBM (a ring, frame f in slot f % resident_frames); 0 = the whole clip */
     int keep_records;                       /* keep what every frame consumed, for H264E_clip_revalidate (GOP shards of one stream) */

@@ -1087,6 +1087,9 @@ h264o_enc_t *h264o_open(const h264o_param_t *par)
     if (!e) return NULL;
     e->par = *par;
     e->nmbx = (par->width + 15) >> 4; e->nmby = (par->height + 15) >> 4; e->nmb = e->nmbx*e->nmby;
+    /* more row bands than macroblock rows: one per row, as the product does -- the reference's split (H:6526-6534) gives the first
+     * bands no rows, and each of them codes row 0 again */
+    e->par.slices = imin(par->slices, e->nmby);
     e->w = e->nmbx*16; e->h = e->nmby*16;
     e->cropping = !!((par->width | par->height) & 15);
     e->mv_limit.x0 = e->mv_limit.y0 = -14*4;
@@ -1214,7 +1217,7 @@ int h264o_encode(h264o_enc_t *e, const uint8_t *const yuv[3], const int stride[3
     {
         /* one slice, or N row bands (H:6511-6574): every band is a slice of its own -- contexts, availability, skip run and
          * the mv_clusters state restart at its first macroblock (the reference encodes each band with a COPY of the encoder and
-         * throws the copy away, so the parent's mv_clusters never move, H:6526) */
+         * throws the copy away, so the parent's mv_clusters never move, H:6526; par.slices is at most nmby, h264o_open) */
         const int nsl = e->par.slices > 1 ? e->par.slices : 1;
         const mv32 c0 = e->clusters[0], c1 = e->clusters[1];
         int band, row0 = 0;
@@ -1238,7 +1241,7 @@ int h264o_encode(h264o_enc_t *e, const uint8_t *const yuv[3], const int stride[3
             row0 = row1;
         }
         e->slice_start_row = e->slice_start_num = 0;
-        rc_frame_end(e, key, e->par.slices > 1 ? 0 : e->skip_run == e->nmb);       /* the parent's skip_run stays 0 in the threads build (H:6596) */
+        rc_frame_end(e, key, nsl > 1 ? 0 : e->skip_run == e->nmb);      /* the parent's skip_run stays 0 in the threads build (H:6596) */
     }
 
     for (c = 0; c < 3; c++)

@@ -63,7 +63,25 @@ def scene(w, h, n, salt=3):
     return out
 
 
+def ramp(w, h, n, salt=5):
+    """for every even size >= 2 (tiny pictures, strips): a smooth 2-D gradient (a sawtooth over a few hundred samples) plus a little
+    hashed texture in cells of 2x2 samples, moving 5/4 samples across and 3/4 down per frame -- not a whole number of samples --, and
+    chroma that changes slowly"""
+    out = np.empty((n, w * h * 3 // 2), np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.int64)
+    cw, ch = w // 2, h // 2
+    for t in range(n):
+        x4, y4 = 4 * xx + 5 * t, 4 * yy + 3 * t            # the moving content, in quarter samples
+        tex = (synth._h32(((x4 >> 3) + 4099 * (y4 >> 3)).astype(np.uint64) + np.uint64(salt)) & np.uint64(15)).astype(np.int64)
+        out[t, : w * h] = (40 + (3 * x4 + 2 * y4) // 16 % 160 + tex).astype(np.uint8).ravel()
+        u = 120 + ((xx[:ch, :cw] + t) // 4) % 16
+        v = 120 + ((2 * yy[:ch, :cw] + t) // 8) % 12
+        out[t, w * h: w * h + cw * ch] = u.astype(np.uint8).ravel()
+        out[t, w * h + cw * ch:] = v.astype(np.uint8).ravel()
+    return out
+
+
 def make(name, w, h, n):
     if name == "synth":
         return synth.clip(w, h, n)
-    return {"noise": noise, "pan": pan, "extremes": extremes, "scene": scene}[name](w, h, n)
+    return {"noise": noise, "pan": pan, "extremes": extremes, "scene": scene, "ramp": ramp}[name](w, h, n)

@@ -89,6 +89,26 @@ def test_gpus_option_shards_one_stream(tmp_path, name, w, h, n, flags, kw, gpus,
     assert (" 0 frames encoded again" not in last) == redo
 
 
+@pytest.mark.parametrize("name,flags", [("noise_64x48_qp0", None), ("ramp_176x144_qp0", None), ("noise_64x32_thr2", "--qp 26 --gop 30 --threads 3")])
+def test_qp0_and_more_threads_than_rows_match_reference(tmp_path, name, flags):
+    """against the reference's own streams (tests/golden/geometry.json): --qp 0 runs the frame-level controller over QP 10..51
+    (h264-lab.h:6707-6715) in the clip pipeline too, not a constant QP 10; --threads 3 on a picture of two macroblock rows is the
+    reference's --threads 2 stream (the slice count is clamped to the rows) -- the default clip pipeline and the per-frame loop"""
+    import hashlib
+    import json
+    g = {x["name"]: x for x in json.load(open(os.path.join(HERE, "golden", "geometry.json")))}[name]
+    c = clips.make(g["clip"], g["w"], g["h"], g["frames"])
+    yuv = tmp_path / ("c_%dx%d.yuv" % (g["w"], g["h"]))
+    c.tofile(yuv)
+    out = tmp_path / "o.264"
+    for mode in ([], ["--clip", "0"]):
+        r = subprocess.run([APP, "--input", str(yuv), "--output", str(out), "--stats", "x"] + (flags or g["flags"]).split() + mode,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert [l for l in r.stdout.splitlines() if l.startswith("frame=")] == ["frame=%d, bytes=%d" % (i, b) for i, b in enumerate(g["frame_bytes"])]
+        assert hashlib.md5(out.read_bytes()).hexdigest() == g["md5"]
+
+
 def test_refused_options_empty_input_and_upload_failure(tmp_path):
     """the CLI's error paths, none of which may hang or write a different stream: options of the reference that this encoder
     refuses (minih264e_test.c:135 --gen, :163 --denoise) -> exit 1 and no output file; an empty input and --gop 0 -> an empty

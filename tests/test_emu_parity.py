@@ -380,7 +380,8 @@ def test_set_vbv_state_mid_stream_matches_reference(name):
     e.close()
 
 
-@pytest.mark.parametrize("w,h,jobs,narrow", [(1920, 1088, 37, 1), (3840, 2160, 9, 0), (352, 288, 50, 1), (640, 368, 20, 1)])
+@pytest.mark.parametrize("w,h,jobs,narrow", [(1920, 1088, 37, 1), (3840, 2160, 9, 0), (352, 288, 50, 1), (640, 368, 20, 1),
+                                             (16, 16, 40, 1), (7680, 16, 9, 0), (16, 2048, 5, 1), (64, 96, 12, 0)])
 def test_dispatch_order_with_xcd_bands_is_complete_padded_and_dependency_safe(w, h, jobs, narrow):
     """h264e_pool.h build_order (the product's code, through the emulation library): with XCD bands the order is eight per-XCD queues
     dealt round -- slot i belongs to XCD i % 8.  Every (job, row) is there exactly once; a row sits on the XCD of its band; the queues

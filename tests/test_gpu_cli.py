@@ -44,6 +44,26 @@ def test_cli_matches_golden(app, tmp_path, g):
         assert hashlib.md5(out.read_bytes()).hexdigest() == g["md5"]
 
 
+GEOMETRY = {g["name"]: g for g in json.load(open(os.path.join(HERE, "golden", "geometry.json")))}
+
+
+@pytest.mark.parametrize("name,flags", [("noise_64x48_qp0", None), ("ramp_176x144_qp0", None), ("noise_64x32_thr2", "--qp 26 --gop 30 --threads 3")])
+def test_cli_qp0_and_more_threads_than_rows_match_reference(app, tmp_path, name, flags):
+    """--qp 0 is the frame-level controller over QP 10..51 in both modes; --threads above the macroblock rows is the reference's stream
+    for as many slices as rows (tests/golden/geometry.json)"""
+    g = GEOMETRY[name]
+    c = clips.make(g["clip"], g["w"], g["h"], g["frames"])
+    yuv = tmp_path / ("clip_%dx%d.yuv" % (g["w"], g["h"]))
+    yuv.write_bytes(c.tobytes())
+    out = tmp_path / "o.264"
+    for mode in ([], ["--clip", "0"]):
+        r = _run(["--input", str(yuv), "--output", str(out)] + (flags or g["flags"]).split() + mode + ["--stats", "x"], str(tmp_path))
+        text = r.stdout.decode()
+        assert r.returncode == 0, text
+        assert ["frame=%d, bytes=%d" % (i, b) for i, b in enumerate(g["frame_bytes"])] == [l for l in text.splitlines() if l.startswith("frame=")]
+        assert hashlib.md5(out.read_bytes()).hexdigest() == g["md5"]
+
+
 def test_cli_clip_mode_and_quirks(app, tmp_path):
     g = GOLDEN[0]
     c = clips.make(g["clip"], g["w"], g["h"], g["frames"])
