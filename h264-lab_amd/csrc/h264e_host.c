@@ -412,77 +412,48 @@ static void rc_frame_end(rc_t *rc, int nmb, int vbv_size_bytes, int desired_fram
 /* ------------------------------------------------------------------ one frame on one chain, validated */
 
 /*
- * One step (one frame of every active chain) with the mv_clusters speculation made exact.
- * tasks[k].mv_clusters holds the state in front of chain k's frame (run[k]); the kernel uses it for every
- * macroblock.  Chains whose frame moves the state are walked exactly; where a consumed rounded candidate
- * differs, those chains (all of them together, one launch) are encoded again with the walked per-macroblock
- * values, until the walk is consistent -- every pass fixes at least the first offending macroblock of each
- * chain, so this terminates.  run[k] is advanced to the state behind the frame; arr_out[k] (optional) receives
- * the per-macroblock array the final pass used (caller frees) or NULL.
+ * One frame on chain 0 (the frame-at-a-time path) with the mv_clusters speculation made exact.
+ * state[] holds the state in front of the frame; the kernel uses it for every macroblock.  A frame that moves the
+ * state is walked exactly; where a consumed rounded candidate differs, the frame is encoded again with the walked
+ * per-macroblock values, until the walk is consistent -- every pass fixes at least the first offending macroblock,
+ * so this terminates.  state[] is advanced to the state behind the frame.
  */
-static int step_exact(h264e_hip_pool_t *pool, int nchains, h264e_hip_task_t *tasks, int nmbx, int nmby, int32_t (*run)[2],
-                      int32_t **arr_out, int *extra_passes)
+static int frame_exact(h264e_hip_pool_t *pool, h264e_hip_task_t *task, int nmbx, int nmby, int32_t state[2])
 {
     const int nmb = nmbx*nmby;
-    int *flags = (int *)calloc(2*(size_t)nchains, sizeof(int));
-    int32_t **arr = (int32_t **)calloc((size_t)nchains, sizeof(int32_t *));
-    char *todo = (char *)calloc((size_t)nchains, 1);
-    h264e_hip_mbrec_t *rec = NULL;
-    int32_t *traj = NULL;
-    int rc = -1, k, pass, pending = 0;
-    if (!flags || !arr || !todo) goto done;
-    for (k = 0; k < nchains; k++)
+    int32_t *arr = NULL, *traj = NULL;      /* per macroblock: what the last pass consumed (NULL: state[]) / what its walk found */
+    int rc = -1, pass;
+    task->mv_clusters_per_mb = NULL;
+    task->mv_clusters[0] = state[0]; task->mv_clusters[1] = state[1];
+    for (pass = 0;; pass++)
     {
-        tasks[k].mv_clusters_per_mb = NULL;
-        if (tasks[k].active) { tasks[k].mv_clusters[0] = run[k][0]; tasks[k].mv_clusters[1] = run[k][1]; todo[k] = 1; pending++; }
-    }
-    for (pass = 0; pending; pass++)
-    {
+        int32_t cc[2] = { state[0], state[1] };
+        h264e_hip_result_t r1;
+        const h264e_hip_mbrec_t *recs;
         if (pass > nmb + 2) { snprintf(g_host_err, sizeof(g_host_err), "mv_clusters re-encode does not converge"); goto done; }
-        if (h264e_hip_submit(pool, tasks) || h264e_hip_sync(pool)) goto done;
-        for (k = 0; k < nchains; k++)
+        if (h264e_hip_submit(pool, task) || h264e_hip_sync(pool)) goto done;
+        /* results come through host-mapped memory, written by the frame's finalizer workgroup (no device-to-host copies) */
+        if (h264e_hip_stream_done(pool, 0, &r1) != 1) { snprintf(g_host_err, sizeof(g_host_err), "frame did not complete"); goto done; }
+        if (r1.overflow) { snprintf(g_host_err, sizeof(g_host_err), "bit buffer overflow"); goto done; }
+        if (!arr && !r1.clusters_moved) break;                                  /* fixed point: state unchanged */
+        if (!traj) traj = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)nmb);
+        recs = h264e_hip_stream_mbrec(pool, 0);
+        if (!traj || !recs) goto done;
+        if (clusters_walk(cc, recs, nmbx, nmby, task->nslices, arr ? arr : state, arr != NULL, traj) < 0)
         {
-            int32_t cc[2];
-            int bad;
-            h264e_hip_result_t r1;
-            const h264e_hip_mbrec_t *recs;
-            if (!todo[k]) continue;
-            /* results come through host-mapped memory, written by the frame's finalizer workgroup (no device-to-host copies) */
-            if (h264e_hip_stream_done(pool, k, &r1) != 1) { snprintf(g_host_err, sizeof(g_host_err), "frame did not complete"); goto done; }
-            flags[2*k] = r1.clusters_moved; flags[2*k + 1] = r1.overflow;
-            if (flags[2*k + 1]) { snprintf(g_host_err, sizeof(g_host_err), "bit buffer overflow"); goto done; }
-            if (!arr[k] && !flags[2*k]) { todo[k] = 0; tasks[k].active = 0; pending--; continue; }   /* fixed point: state unchanged */
-            if (!traj)
-            {
-                traj = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)nmb);
-                if (!traj) goto done;
-            }
-            recs = h264e_hip_stream_mbrec(pool, k);
-            if (!recs) goto done;
-            cc[0] = run[k][0]; cc[1] = run[k][1];
-            bad = clusters_walk(cc, recs, nmbx, nmby, tasks[k].nslices, arr[k] ? arr[k] : run[k], arr[k] != NULL, traj) >= 0;
-            if (!bad)
-            {
-                run[k][0] = cc[0]; run[k][1] = cc[1];
-                todo[k] = 0; tasks[k].active = 0; pending--;
-                continue;
-            }
-            if (!arr[k]) arr[k] = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)nmb);
-            if (!arr[k]) goto done;
-            memcpy(arr[k], traj, sizeof(int32_t)*2*(size_t)nmb);
-            tasks[k].mv_clusters_per_mb = arr[k];
-            if (h264e_hip_rewind_frame(pool, k, tasks[k].frame_slot)) goto done;
+            state[0] = cc[0]; state[1] = cc[1];
+            break;
         }
+        if (!arr) arr = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)nmb);
+        if (!arr) goto done;
+        memcpy(arr, traj, sizeof(int32_t)*2*(size_t)nmb);
+        task->mv_clusters_per_mb = arr;
+        if (h264e_hip_rewind_frame(pool, 0)) goto done;
     }
-    if (extra_passes) *extra_passes = pass > 0 ? pass - 1 : 0;
     rc = 0;
 done:
     if (rc) h264e_hip_release(pool);
-    for (k = 0; k < nchains && arr; k++)
-    {
-        if (!rc && arr_out) arr_out[k] = arr[k]; else free(arr[k]);
-    }
-    free(flags); free(arr); free(todo); free(rec); free(traj);
+    free(arr); free(traj);
     return rc;
 }
 
@@ -644,7 +615,7 @@ int H264E_init(H264E_persist_t *p, const H264E_create_param_t *par)
     seq_init(&e->seq, par->width, par->height, par->vbv_size_bytes, par->sps_id);
     /* device resources are created outside the lock (slow), registered under it */
     memset(&fresh, 0, sizeof(fresh));
-    if (h264e_hip_pool_create(&fresh.pool, pick_device(), par->width, par->height, 1, 1, 1))
+    if (h264e_hip_pool_create(&fresh.pool, pick_device(), par->width, par->height, 1, 1))
         return H264E_STATUS_BAD_ARGUMENT;       /* no device: the HIP path is the only path */
     fresh.rbsp_cap = (size_t)e->seq.nmb*660 + 8192;
     fresh.rbsp = (uint8_t *)malloc(fresh.rbsp_cap);
@@ -754,7 +725,7 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
                         e->run_param.qp_min, e->run_param.qp_max, key);
 
     memset(&task, 0, sizeof(task));
-    task.active = 1; task.frame_index = 0; task.frame_slot = 0;
+    task.active = 1; task.frame_index = 0;
     task.slice_type = key ? SLICE_I : SLICE_P;
     task.qp = qp; task.speed = opt->encode_speed;
     task.nslices = e->slices > 1 ? imin(e->slices, e->seq.nmby) : 1;
@@ -798,12 +769,8 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
         res.all_skipped = 1;
     } else
     {
-    if (h264e_hip_reset_results(m->pool, 0) || (!den && h264e_hip_upload_planes(m->pool, 0, yuv, in->stride))) return H264E_STATUS_BAD_ARGUMENT;
-    {
-        int32_t run[1][2] = { { e->clusters[0], e->clusters[1] } };
-        if (step_exact(m->pool, 1, &task, e->seq.nmbx, e->seq.nmby, run, NULL, NULL) || h264e_hip_stream_done(m->pool, 0, &res) != 1) return H264E_STATUS_BAD_ARGUMENT;
-        e->clusters[0] = run[0][0]; e->clusters[1] = run[0][1];
-    }
+    if (!den && h264e_hip_upload_planes(m->pool, 0, yuv, in->stride)) return H264E_STATUS_BAD_ARGUMENT;
+    if (frame_exact(m->pool, &task, e->seq.nmbx, e->seq.nmby, e->clusters) || h264e_hip_stream_done(m->pool, 0, &res) != 1) return H264E_STATUS_BAD_ARGUMENT;
     {
         const uint8_t *nals = h264e_hip_stream_rbsp(m->pool, 0);
         size_t w;
@@ -871,7 +838,6 @@ struct H264E_clip_tag
     void (*idle_hook)(void *token); void *idle_token;   /* called while the encoder waits for the GPU (the app feeds uploads from it) */
     int32_t state[2];                       /* exact mv_clusters in front of frame `next` */
     int first_dev;                          /* the next launch's first frame is encoded again with the per-macroblock trajectory its walk left on the device */
-    int32_t *first_arr;                     /* (unused by the streaming path since the walk moved to the device; kept NULL) */
     int first_row;                          /* ... which restarts at this macroblock row */
     int32_t after[2]; int have_after;       /* predicted state behind that frame */
     int narrow;                             /* reference-window geometry in use (h264e_dev.h) */
@@ -916,7 +882,7 @@ void H264E_clip_rewind(H264E_clip_t *c)
     if (!c) return;
     c->next = 0;
     c->state[0] = c->par.mv_clusters_in[0]; c->state[1] = c->par.mv_clusters_in[1];
-    free(c->first_arr); c->first_arr = NULL; c->first_dev = 0;
+    c->first_dev = 0;
     c->first_row = 0; c->have_after = 0; c->recon_floor = 0; c->stopped_before = 0;
     /* reference-window geometry (h264e_dev.h): narrow = consecutive frames 4 macroblock steps apart, as long as vectors rarely
      * reach more than 12 samples right / down of their macroblock; wide (7 steps) for the rest of the clip otherwise.  Large
@@ -984,7 +950,7 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     if (!c->traj || !c->tasks || !c->used) { free(c->traj); free(c->tasks); free(c->used); free(c); return -1; }
     /* the ring is sized for speed, not for need: when the device (or the pinned host memory) cannot spare that much, halve it down
      * to the pipeline depth before giving up */
-    while (h264e_hip_pool_create(&c->pool, par->device, par->width, par->height, c->ring, c->resident, 1))
+    while (h264e_hip_pool_create(&c->pool, par->device, par->width, par->height, c->ring, c->resident))
     {
         if (c->ring <= c->launch_base + 1 || par->max_chains > 0)
         {
@@ -1011,7 +977,7 @@ void H264E_clip_close(H264E_clip_t *c)
     h264e_hip_pool_destroy(c->pool);
     if (c->rec_store) { int f; for (f = 0; f < c->nframes; f++) { free(c->rec_store[f]); if (c->permb_store) free(c->permb_store[f]); } }
     free(c->rec_store); free(c->used_store); free(c->permb_store);
-    free(c->first_arr); free(c->traj); free(c->tasks); free(c->used); free(c->big);
+    free(c->traj); free(c->tasks); free(c->used); free(c->big);
     free(c);
 }
 
@@ -1167,7 +1133,7 @@ int H264E_clip_restart(H264E_clip_t *c, int frame, const int32_t state[2])
     c->next = frame;
     if (c->resident < c->nframes) c->avail = c->pending_avail = frame;      /* a ring: the inputs from here on have to be uploaded again */
     c->state[0] = state[0]; c->state[1] = state[1];
-    free(c->first_arr); c->first_arr = NULL; c->first_dev = 0;
+    c->first_dev = 0;
     c->first_row = 0; c->have_after = 0;
     c->rc_frame = -1;
     return 0;
@@ -1269,7 +1235,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
                 build_qdat(key ? qdat_i : qdat_p, qp, !key);
             }
             qp_task[i & 7] = qp;
-            t->active = 1; t->frame_index = f % c->resident; t->frame_slot = 0;
+            t->active = 1; t->frame_index = f % c->resident;
             t->slice_type = key ? SLICE_I : SLICE_P;
             t->qp = qp; t->speed = c->par.speed;
             /* frame_num restarts at every key frame; idr_pic_id toggles with every key frame (h264-lab.h:6774-6775) */

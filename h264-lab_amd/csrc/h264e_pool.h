@@ -143,7 +143,7 @@ typedef struct h264e_hip_group h264e_hip_group_t;
 
 struct h264e_hip_pool
 {
-    int device, nchains, frames_resident, slots;
+    int device, nchains, frames_resident;
     h264e_geom_t G;
     size_t frame_bytes;
     uint8_t *clip;                       /* device: resident input frames, packed I420 */
@@ -159,11 +159,11 @@ struct h264e_hip_pool
     int *errflag;
     unsigned long long *mb_counter;      /* device: macroblocks reconstructed by this pool's rows, delivered or not (h264e_hip_mb_counter) */
     uint32_t *order;                     /* device [nchains*(nmby+1)] (job << 16) | row in dispatch order of the current launch shape */
+    int *stepflags;                      /* device [nchains][2]: {clusters_moved, overflow} of each job, where the finalizers still write them (nobody reads them) */
     uint32_t *order_host;                /* host copy being built (build_order) */
     int order_jobs, order_narrow, order_sliced;   /* the launch shape `order` holds: jobs, window geometry, row-band slices or not (-1: none yet) */
     size_t order_count;                  /* ... and its entries = the launch's workgroups (banded orders carry padding) */
-    int *stepflags;                      /* [nchains][2]: {clusters_moved, overflow} of the last step, one read per step */
-    /* streaming: per chain slot, host-mapped result buffers the finalizer workgroups fill while the launch runs */
+    /* per chain slot: host-mapped result buffers the finalizer workgroups fill while the launch runs */
     h264e_hostdone_t *host_done;         /* [nchains] */
     uint8_t **host_rbsp;                 /* [nchains], each host_rbsp_cap bytes */
     h264e_hip_mbrec_t **host_mbrec;      /* [nchains], each nmb records */
@@ -342,13 +342,13 @@ static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced)
 }
 
 extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int width, int height, int nchains,
-                                     int frames_resident, int slots)
+                                     int frames_resident)
 {
-    if (!pool || width <= 0 || height <= 0 || ((width | height) & 1) || nchains <= 0 || frames_resident <= 0 || slots <= 0)
+    if (!pool || width <= 0 || height <= 0 || ((width | height) & 1) || nchains <= 0 || frames_resident <= 0)
         FAIL("h264e_hip_pool_create: bad argument");
     h264e_hip_pool_t *p = (h264e_hip_pool_t *)calloc(1, sizeof(*p));
     if (!p) FAIL("out of host memory");
-    p->device = device; p->nchains = nchains; p->frames_resident = frames_resident; p->slots = slots;
+    p->device = device; p->nchains = nchains; p->frames_resident = frames_resident;
     h264e_geom_t &G = p->G;
     G.width = width; G.height = height;
     G.nmbx = (width + 15) >> 4; G.nmby = (height + 15) >> 4; G.nmb = G.nmbx*G.nmby;
@@ -400,7 +400,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     p->host_mbrec = (h264e_hip_mbrec_t **)calloc((size_t)nchains, sizeof(h264e_hip_mbrec_t *));
     int bad = 0;
     const size_t plane = (size_t)G.W*G.H*3/2;
-    const uint32_t arena_cap = (uint32_t)((size_t)slots*((size_t)G.nmb*640 + 1024));
+    const uint32_t arena_cap = (uint32_t)((size_t)G.nmb*640 + 1024);
     /* host-mapped mirror per slot: sized for ordinary frames (160 B per macroblock; a 1080p key frame at QP 26 needs ~20); a
      * frame that does not fit stays in the slot's device NAL arena (worst-case size) and is fetched with a copy */
     const uint32_t nal_cap = (uint32_t)((size_t)G.nmb*660 + 4096);
@@ -443,22 +443,20 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
             C.progress = p->progress_all + (size_t)c*2*G.nmby;
             C.rowbits = (uint32_t *)carve(sizeof(uint32_t)*(size_t)G.nmby*G.row_words, 256);
             C.rowmeta = (h264e_rowmeta_t *)carve(sizeof(h264e_rowmeta_t)*(size_t)G.nmby, 256);
-            C.mbrec = (h264e_mbrec_t *)carve(sizeof(h264e_mbrec_t)*(size_t)G.nmb*slots, 256);
+            C.mbrec = (h264e_mbrec_t *)carve(sizeof(h264e_mbrec_t)*(size_t)G.nmb, 256);
             C.arena = (uint8_t *)carve(arena_cap, 256);
             C.arena_cap = arena_cap;
-            C.nal_arena = slots == 1 ? (uint8_t *)carve(nal_cap, 256) : 0;
-            C.nal_cap = slots == 1 ? nal_cap : 0;
+            C.nal_arena = (uint8_t *)carve(nal_cap, 256);
+            C.nal_cap = nal_cap;
             C.cursor = (uint32_t *)carve(16, 256);
-            C.fout = (h264e_frameout_t *)carve(sizeof(h264e_frameout_t)*(size_t)slots, 256);
+            C.fout = (h264e_frameout_t *)carve(sizeof(h264e_frameout_t), 256);
             C.prof = (unsigned long long *)carve(sizeof(unsigned long long)*48, 256);     /* 0..31 the rows' phases, 32..47 the finalizer's */
             C.far_reads = (int *)carve(16, 256);
             p->clu_dev[c] = (int32_t *)carve(sizeof(int32_t)*2*(size_t)G.nmb, 256);      /* per-macroblock mv_clusters array of a re-encode */
-            p->traj_dev[c] = slots == 1 ? (int32_t *)carve(sizeof(int32_t)*4*(size_t)G.nmb, 256) : 0;   /* two walk trajectories (device-side validation) */
-            if (slots == 1)        /* streaming pools keep one result per chain slot: give each a host-mapped mirror */
-            {
-                p->host_rbsp[c] = (uint8_t *)hcarve(p->host_rbsp_cap + 64);
-                p->host_mbrec[c] = (h264e_hip_mbrec_t *)hcarve(sizeof(h264e_hip_mbrec_t)*(size_t)G.nmb + 64);
-            }
+            p->traj_dev[c] = (int32_t *)carve(sizeof(int32_t)*4*(size_t)G.nmb, 256);    /* two walk trajectories (device-side validation) */
+            /* one result per chain slot, exported by its frame's finalizer to these host-mapped mirrors */
+            p->host_rbsp[c] = (uint8_t *)hcarve(p->host_rbsp_cap + 64);
+            p->host_mbrec[c] = (h264e_hip_mbrec_t *)hcarve(sizeof(h264e_hip_mbrec_t)*(size_t)G.nmb + 64);
         }
         if (!pass)
         {
@@ -967,7 +965,7 @@ extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tas
         h264e_frame_task_t &d = host[c];
         d.active = t.active;
         if (!t.active) continue;
-        if (t.frame_index < 0 || t.frame_index >= p->frames_resident || t.frame_slot < 0 || t.frame_slot >= p->slots ||
+        if (t.frame_index < 0 || t.frame_index >= p->frames_resident ||
             t.qp < 10 || t.qp > 51 || t.hdr_nbits < 0 || t.hdr_nbits > 56 || t.nslices < 0 || t.nslices > H264E_MAX_SLICES || t.nslices > G.nmby)
         {
             free(host);
@@ -993,27 +991,16 @@ extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tas
                 FAIL("submit: bad stream task %d", c);
             }
             d.chain = t.slot;
-            d.arena_reset = 1;
-            if (p->host_rbsp[t.slot] && p->host_mbrec[t.slot])
+            d.abort_word = p->abort_dev;
+            if (t.walk_on_device)
             {
-                d.host_done = p->host_done + t.slot;
-                d.host_rbsp = p->host_rbsp[t.slot]; d.host_rbsp_cap = p->host_rbsp_cap;
-                d.host_mbrec = (h264e_mbrec_t *)p->host_mbrec[t.slot];
-                d.abort_word = p->abort_dev;
-                p->host_done[t.slot].done = 0;
-                p->slot_launch[t.slot] = launch_id;
-                if (t.walk_on_device && p->traj_dev[t.slot])
-                {
-                    d.walk_on_device = 1;
-                    d.walk_quiet = t.walk_quiet;
-                    d.exact_state[0] = t.exact_state[0]; d.exact_state[1] = t.exact_state[1];
-                    d.walk_out = p->walkrec + t.slot;
-                    {
-                        const int par = t.walk_parent > 0 ? t.walk_parent - 1 : c - 1;
-                        d.walk_prev = (par >= 0 && par < c && tasks[par].active && tasks[par].stream_mode && tasks[par].walk_on_device) ? p->walkrec + tasks[par].slot : 0;
-                    }
-                    d.traj_out = p->traj_dev[t.slot] + (size_t)(p->traj_cur[t.slot] ^ 1)*2*G.nmb;
-                }
+                const int par = t.walk_parent > 0 ? t.walk_parent - 1 : c - 1;
+                d.walk_on_device = 1;
+                d.walk_quiet = t.walk_quiet;
+                d.exact_state[0] = t.exact_state[0]; d.exact_state[1] = t.exact_state[1];
+                d.walk_out = p->walkrec + t.slot;
+                d.walk_prev = (par >= 0 && par < c && tasks[par].active && tasks[par].stream_mode && tasks[par].walk_on_device) ? p->walkrec + tasks[par].slot : 0;
+                d.traj_out = p->traj_dev[t.slot] + (size_t)(p->traj_cur[t.slot] ^ 1)*2*G.nmb;
             }
             for (int k = 0; k < 3; k++)
             {
@@ -1028,23 +1015,19 @@ extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tas
             for (int k = 0; k < 3; k++) { d.ref[k] = p->chains_host[c].rec[rs][k]; d.dec[k] = p->chains_host[c].rec[rs ^ 1][k]; }
             d.dep_progress = 0;
             p->ref_sel[c] ^= 1;
-            if (p->host_rbsp[c] && p->host_mbrec[c])
-            {
-                /* one result per chain (slots_per_chain == 1): the finalizer exports it to host-mapped memory like a stream job, so
-                 * the host reads NALs, flags and records without a device-to-host copy */
-                d.arena_reset = 1;
-                d.host_done = p->host_done + c;
-                d.host_rbsp = p->host_rbsp[c]; d.host_rbsp_cap = p->host_rbsp_cap;
-                d.host_mbrec = (h264e_mbrec_t *)p->host_mbrec[c];
-                p->host_done[c].done = 0;
-                p->slot_launch[c] = launch_id;
-            }
         }
+        /* the finalizer exports the slot's result to host-mapped memory: the host reads NALs, flags and records without a
+         * device-to-host copy */
+        d.arena_reset = 1;
+        d.stepflags = p->stepflags + 2*c;
+        d.host_done = p->host_done + d.chain;
+        d.host_rbsp = p->host_rbsp[d.chain]; d.host_rbsp_cap = p->host_rbsp_cap;
+        d.host_mbrec = (h264e_mbrec_t *)p->host_mbrec[d.chain];
+        p->host_done[d.chain].done = 0;
+        p->slot_launch[d.chain] = launch_id;
         d.chain_desc = p->chains_dev + d.chain;
         d.errflag = p->errflag;
         d.mb_counter = p->mb_counter;
-        d.stepflags = p->stepflags + 2*c;
-        d.frame_slot = t.frame_slot;
         d.first_row = (t.stream_mode && t.first_row > 0 && t.first_row < G.nmby) ? t.first_row : 0;
         d.narrow = t.stream_mode && t.narrow_window;
         any_narrow |= d.narrow;
@@ -1059,7 +1042,7 @@ extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tas
         }
         d.clusters[0] = t.mv_clusters[0]; d.clusters[1] = t.mv_clusters[1];
         d.clusters_per_mb = 0;
-        if (t.stream_mode && t.traj_from_device && p->traj_dev[t.slot])
+        if (t.stream_mode && t.traj_from_device)
             d.clusters_per_mb = p->traj_dev[t.slot] + (size_t)p->traj_cur[t.slot]*2*G.nmb;     /* the latest device walk of this slot */
         else if (t.mv_clusters_per_mb)
         {
@@ -1139,19 +1122,11 @@ extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tas
     return 0;
 }
 
-extern "C" int h264e_hip_step_flags(h264e_hip_pool_t *p, int *flags /* [nchains][2] */)
-{
-    if (!p || !flags) FAIL("step_flags: bad argument");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(flags, p->stepflags, sizeof(int)*2*(size_t)p->nchains, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-/* ---- streaming results: valid for pools created with slots_per_chain == 1 and tasks submitted with stream_mode */
+/* ---- results: every job's finalizer exports them to the host-mapped mirrors of its chain slot */
 
 extern "C" int h264e_hip_stream_done(h264e_hip_pool_t *p, int slot, h264e_hip_result_t *res)
 {
-    if (!p || slot < 0 || slot >= p->nchains || !p->host_rbsp[slot]) FAIL("stream_done: bad argument");
+    if (!p || slot < 0 || slot >= p->nchains) FAIL("stream_done: bad argument");
     const volatile h264e_hostdone_t *d = p->host_done + slot;
     const int v = d->done;
     if (v != p->slot_launch[slot] && v != -p->slot_launch[slot]) return 0;      /* not yet */
@@ -1171,7 +1146,7 @@ extern "C" int h264e_hip_stream_done(h264e_hip_pool_t *p, int slot, h264e_hip_re
 
 extern "C" int h264e_hip_stream_fetch_traj(h264e_hip_pool_t *p, int slot, int consumed, int32_t *dst)
 {
-    if (!p || !dst || slot < 0 || slot >= p->nchains || !p->traj_dev[slot]) FAIL("stream_fetch_traj: bad argument");
+    if (!p || !dst || slot < 0 || slot >= p->nchains) FAIL("stream_fetch_traj: bad argument");
     const int32_t *src = p->traj_dev[slot] + (size_t)(p->traj_cur[slot] ^ (consumed ? 1 : 0))*2*p->G.nmb;
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipMemcpy(dst, src, sizeof(int32_t)*2*(size_t)p->G.nmb, hipMemcpyDeviceToHost));
@@ -1198,7 +1173,7 @@ extern "C" const uint8_t *h264e_hip_stream_rbsp(h264e_hip_pool_t *p, int slot)
  * launch is still running (copy stream) */
 extern "C" int h264e_hip_stream_fetch_nals(h264e_hip_pool_t *p, int slot, uint8_t *dst, uint32_t nbytes)
 {
-    if (!p || !dst || slot < 0 || slot >= p->nchains || !p->chains_host[slot].nal_arena || nbytes > p->chains_host[slot].nal_cap) FAIL("stream_fetch_nals: bad argument");
+    if (!p || !dst || slot < 0 || slot >= p->nchains || nbytes > p->chains_host[slot].nal_cap) FAIL("stream_fetch_nals: bad argument");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipMemcpyAsync(dst, p->chains_host[slot].nal_arena, nbytes, hipMemcpyDeviceToHost, p->copy_stream));
     HIPCHK(hipStreamSynchronize(p->copy_stream));
@@ -1240,75 +1215,6 @@ extern "C" int h264e_hip_busy(h264e_hip_pool_t *p)
     return hipStreamQuery(p->stream) == hipErrorNotReady;
 }
 
-extern "C" int h264e_hip_result(h264e_hip_pool_t *p, int chain, int slot, h264e_hip_result_t *res)
-{
-    if (!p || !res || chain < 0 || chain >= p->nchains || slot < 0 || slot >= p->slots) FAIL("result: bad argument");
-    h264e_frameout_t f;
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(&f, p->chains_host[chain].fout + slot, sizeof(f), hipMemcpyDeviceToHost));
-    res->nbytes = f.nbytes; res->all_skipped = f.all_skipped; res->clusters_moved = f.clusters_moved; res->overflow = f.overflow; res->far_reads = f.far_reads;
-    res->nslices = f.nslices;
-    for (int k = 0; k < H264E_HIP_MAX_SLICES; k++) res->slice_nbytes[k] = f.slice_nbytes[k];
-    return 0;
-}
-
-extern "C" int h264e_hip_read_rbsp(h264e_hip_pool_t *p, int chain, int slot, uint8_t *dst, uint32_t cap)
-{
-    if (!p || !dst || chain < 0 || chain >= p->nchains || slot < 0 || slot >= p->slots) FAIL("read_rbsp: bad argument");
-    h264e_frameout_t f;
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(&f, p->chains_host[chain].fout + slot, sizeof(f), hipMemcpyDeviceToHost));
-    if (f.nbytes > cap) FAIL("read_rbsp: destination too small");
-    HIPCHK(hipMemcpy(dst, p->chains_host[chain].arena + f.offset, f.nbytes, hipMemcpyDeviceToHost));
-    return (int)f.nbytes;
-}
-
-extern "C" int h264e_hip_read_chain(h264e_hip_pool_t *p, int chain, int nslots, h264e_hip_result_t *res, uint32_t *offsets,
-                                    uint8_t *arena_dst, uint32_t cap, uint32_t *used)
-{
-    if (!p || !res || !offsets || !arena_dst || chain < 0 || chain >= p->nchains || nslots < 0 || nslots > p->slots) FAIL("read_chain: bad argument");
-    h264e_frameout_t *f = (h264e_frameout_t *)malloc(sizeof(h264e_frameout_t)*(size_t)(nslots ? nslots : 1));
-    uint32_t cur = 0;
-    if (!f) FAIL("out of host memory");
-    if (hipSetDevice(p->device) != hipSuccess ||
-        hipMemcpy(f, p->chains_host[chain].fout, sizeof(h264e_frameout_t)*(size_t)nslots, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&cur, p->chains_host[chain].cursor, 4, hipMemcpyDeviceToHost) != hipSuccess)
-    {
-        free(f);
-        FAIL("read_chain: copy failed");
-    }
-    for (int i = 0; i < nslots; i++)
-    {
-        res[i].nbytes = f[i].nbytes; res[i].all_skipped = f[i].all_skipped; res[i].clusters_moved = f[i].clusters_moved; res[i].overflow = f[i].overflow;
-        res[i].far_reads = f[i].far_reads; res[i].nslices = f[i].nslices;
-        for (int k = 0; k < H264E_HIP_MAX_SLICES; k++) res[i].slice_nbytes[k] = f[i].slice_nbytes[k];
-        offsets[i] = f[i].offset;
-    }
-    free(f);
-    if (cur > cap) FAIL("read_chain: destination too small (%u > %u)", cur, cap);
-    HIPCHK(hipMemcpy(arena_dst, p->chains_host[chain].arena, cur, hipMemcpyDeviceToHost));
-    if (used) *used = cur;
-    return 0;
-}
-
-extern "C" int h264e_hip_read_mbrec(h264e_hip_pool_t *p, int chain, int slot, h264e_hip_mbrec_t *dst)
-{
-    if (!p || !dst || chain < 0 || chain >= p->nchains || slot < 0 || slot >= p->slots) FAIL("read_mbrec: bad argument");
-    const size_t n = sizeof(h264e_mbrec_t)*(size_t)p->G.nmb;
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(dst, p->chains_host[chain].mbrec + (size_t)slot*p->G.nmb, n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int h264e_hip_read_mbrec_all(h264e_hip_pool_t *p, int chain, int nslots, h264e_hip_mbrec_t *dst)
-{
-    if (!p || !dst || chain < 0 || chain >= p->nchains || nslots < 0 || nslots > p->slots) FAIL("read_mbrec_all: bad argument");
-    const size_t n = sizeof(h264e_mbrec_t)*(size_t)p->G.nmb*(size_t)nslots;
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(dst, p->chains_host[chain].mbrec, n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
 extern "C" int h264e_hip_read_recon(h264e_hip_pool_t *p, int chain, uint8_t *dst)
 {
     if (!p || !dst || chain < 0 || chain >= p->nchains) FAIL("read_recon: bad argument");
@@ -1319,21 +1225,10 @@ extern "C" int h264e_hip_read_recon(h264e_hip_pool_t *p, int chain, uint8_t *dst
     return 0;
 }
 
-extern "C" int h264e_hip_reset_results(h264e_hip_pool_t *p, int chain)
+extern "C" int h264e_hip_rewind_frame(h264e_hip_pool_t *p, int chain)
 {
-    if (!p || chain < 0 || chain >= p->nchains) FAIL("reset_results: bad argument");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemsetAsync(p->chains_host[chain].cursor, 0, 16, p->stream));
-    return 0;
-}
-
-extern "C" int h264e_hip_rewind_frame(h264e_hip_pool_t *p, int chain, int slot)
-{
-    if (!p || chain < 0 || chain >= p->nchains || slot < 0 || slot >= p->slots) FAIL("rewind_frame: bad argument");
+    if (!p || chain < 0 || chain >= p->nchains) FAIL("rewind_frame: bad argument");
     p->ref_sel[chain] ^= 1;
-    /* the frame's result is dropped too: the arena cursor goes back to where that result starts */
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpyAsync(p->chains_host[chain].cursor, &p->chains_host[chain].fout[slot].offset, sizeof(uint32_t), hipMemcpyDeviceToDevice, p->stream));
     return 0;
 }
 

@@ -8,12 +8,14 @@
  * Plain pointers and sizes only; no C++ or torch types.
  *
  * A POOL holds `nchains` slots of one picture geometry on one GPU (picture, row bit buffers, per-macroblock
- * records, result buffers).  One h264e_hip_submit() call launches the macroblock kernel once for up to nchains
- * jobs (one wavefront per macroblock row plus one finalizer wavefront per job that splices the slice):
- *  - plain mode: job c is the next frame of independent chain c (reference / reconstruction ping-pong);
+ * records, ONE result).  One h264e_hip_submit() call launches the macroblock kernel once for up to nchains
+ * jobs (one wavefront per macroblock row plus one finalizer wavefront per job that splices the slices and exports
+ * the job's result to the host-mapped mirrors of its slot, where h264e_hip_stream_* picks it up):
+ *  - frame at a time (stream_mode = 0): job c is the next frame of chain c, which keeps two pictures in
+ *    reference / reconstruction ping-pong (H264E_encode);
  *  - stream mode: the jobs are consecutive frames of ONE stream, run as a temporal wavefront (a P frame starts
- *    while its reference frame is a few macroblock rows ahead); finished frames are
- *    exported to host-mapped memory and can be consumed with h264e_hip_stream_* while the launch runs.
+ *    while its reference frame is a few macroblock rows ahead); finished frames can be
+ *    consumed while the launch runs.
  * Calls are asynchronous on the pool's stream until h264e_hip_sync().
  */
 #ifndef H264E_HIP_H
@@ -30,7 +32,6 @@ typedef struct
 {
     int active;                 /* 0: chain idles in this step */
     int frame_index;            /* which resident input frame (see h264e_hip_upload_*) */
-    int frame_slot;             /* where the result goes: 0 .. slots_per_chain-1 */
     int slice_type;             /* 0 = P, 2 = I   (h264-lab.h:3203-3204) */
     int qp;                     /* frame QP, 10..51 */
     int speed;                  /* H264E_run_param_t.encode_speed (h264-lab.h:181) */
@@ -91,9 +92,9 @@ typedef struct
 typedef struct { int32_t mv0; int8_t type; uint8_t used_cand; uint8_t pad[2]; } h264e_hip_mbrec_t;
 
 int  h264e_hip_device_count(void);
-/* frames_resident: input frames kept in HBM; slots_per_chain: results kept per chain between reads */
+/* frames_resident: input frames kept in HBM */
 int  h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int width, int height, int nchains,
-                           int frames_resident, int slots_per_chain);
+                           int frames_resident);
 void h264e_hip_pool_destroy(h264e_hip_pool_t *pool);
 /* packed I420 frames (width*height*3/2 bytes each) from host memory into resident slots first.. */
 int  h264e_hip_upload_i420(h264e_hip_pool_t *pool, int first, int nframes, const uint8_t *host_i420);
@@ -127,11 +128,9 @@ int  h264e_hip_group_join(h264e_hip_group_t *group, h264e_hip_pool_t *pool);
 void h264e_hip_group_leave(h264e_hip_group_t *group, h264e_hip_pool_t *pool);
 void h264e_hip_group_destroy(h264e_hip_group_t *group);
 int  h264e_hip_sync(h264e_hip_pool_t *pool);
-/* {clusters_moved, overflow} of every chain for the LAST submitted step, in one copy (call after h264e_hip_sync) */
-int  h264e_hip_step_flags(h264e_hip_pool_t *pool, int *flags /* [nchains][2] */);
-/* streaming (pools with slots_per_chain == 1, tasks with stream_mode): every job has a finalizer inside the launch that
- * copies its RBSP and macroblock records to host-mapped memory and raises a done word, so the host can consume frame
- * after frame while later frames of the same launch are still running.
+/* results: every job has a finalizer inside the launch that copies its NALs and macroblock records to the host-mapped
+ * mirrors of its chain slot (stream mode: task.slot; else the task's index) and raises a done word, so the host can
+ * consume frame after frame while later frames of the same launch are still running.
  * h264e_hip_stream_done: 0 not finished, 1 finished (res filled), 2 aborted. */
 /* A pool owns its device's launch lock (process-wide, one persistent launch at a time per device) from its first submit until
  * h264e_hip_sync returns; h264e_hip_release gives it back after a failure in between (waits for the stream, reports nothing). */
@@ -150,14 +149,6 @@ int  h264e_hip_stream_copy_picture(h264e_hip_pool_t *pool, int from, int to);
 int  h264e_hip_download_i420(h264e_hip_pool_t *pool, int first, int nframes, uint8_t *host_i420);
 int  h264e_hip_stream_abort(h264e_hip_pool_t *pool);
 int  h264e_hip_busy(h264e_hip_pool_t *pool);
-int  h264e_hip_result(h264e_hip_pool_t *pool, int chain, int slot, h264e_hip_result_t *res);
-int  h264e_hip_read_rbsp(h264e_hip_pool_t *pool, int chain, int slot, uint8_t *dst, uint32_t cap);
-/* all results of a chain in two copies: per-slot result + byte offset into arena_dst, which receives the used part of the arena */
-int  h264e_hip_read_chain(h264e_hip_pool_t *pool, int chain, int nslots, h264e_hip_result_t *res, uint32_t *offsets,
-                          uint8_t *arena_dst, uint32_t cap, uint32_t *used);
-int  h264e_hip_read_mbrec(h264e_hip_pool_t *pool, int chain, int slot, h264e_hip_mbrec_t *dst /* [nmb] */);
-/* records of slots 0..nslots-1 in one copy, dst[nslots][nmb] */
-int  h264e_hip_read_mbrec_all(h264e_hip_pool_t *pool, int chain, int nslots, h264e_hip_mbrec_t *dst);
 /* reconstructed picture of the chain's last frame, coded size, packed I420 */
 int  h264e_hip_read_recon(h264e_hip_pool_t *pool, int chain, uint8_t *dst);
 /* stream pools: the picture of chain slot `slot` (coded size, packed I420) */
@@ -165,11 +156,9 @@ int  h264e_hip_read_recon_slot(h264e_hip_pool_t *pool, int slot, uint8_t *dst);
 /* sums of squared differences between resident input frames and stream pictures, one small kernel per call: frame i uses input
  * slot (in0 + i) % in_mod and picture slot (pic0 + i) % pic_mod; out = host [n][3] (Y, U, V), picture size width x height */
 int  h264e_hip_ssd_frames(h264e_hip_pool_t *pool, int n, int in0, int in_mod, int pic0, int pic_mod, uint64_t *out);
-/* forget the results of a chain (arena cursor back to 0); the reference picture is kept */
-int  h264e_hip_reset_results(h264e_hip_pool_t *pool, int chain);
-/* drop the chain's last submitted frame (result in `slot`): undo the reference/reconstruction swap and give its
- * arena space back, so the frame can be submitted again (re-encode path) */
-int  h264e_hip_rewind_frame(h264e_hip_pool_t *pool, int chain, int slot);
+/* drop the chain's last submitted frame (stream_mode = 0): undo the reference/reconstruction swap, so the frame can be
+ * submitted again (re-encode path) */
+int  h264e_hip_rewind_frame(h264e_hip_pool_t *pool, int chain);
 /* kernel timing on the pool's stream (HIP events around every macroblock-kernel launch) */
 /* macroblocks the pool's rows have reconstructed since the last reset, delivered or thrown away (call after h264e_hip_sync) */
 int h264e_hip_mb_counter(h264e_hip_pool_t *pool, unsigned long long *count, int reset);

@@ -75,7 +75,7 @@ def device_planes(lib, frames, w, h, resident, chunk=None):
     h264e_hip_read_denoised.  lib: path of the product library or of the emulation."""
     import ctypes as C
     L = C.CDLL(lib)
-    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.h264e_hip_pool_destroy.argtypes = [C.c_void_p]
     L.h264e_hip_pool_destroy.restype = None
     L.h264e_hip_upload_i420.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -85,7 +85,7 @@ def device_planes(lib, frames, w, h, resident, chunk=None):
     L.h264e_hip_sync.argtypes = [C.c_void_p]
     L.h264e_hip_last_error.restype = C.c_char_p
     pool = C.c_void_p()
-    assert L.h264e_hip_pool_create(C.byref(pool), 0, w, h, 1, resident, 1) == 0, L.h264e_hip_last_error()
+    assert L.h264e_hip_pool_create(C.byref(pool), 0, w, h, 1, resident) == 0, L.h264e_hip_last_error()
     fsz = w * h * 3 // 2
     chunk = chunk or resident
     out = []

@@ -144,11 +144,11 @@ def test_nal_escape_pass_on_adversarial_payloads():
     import nal_cases
     P = pkg.load_pkg()
     L = P.load(pkg.EMU_LIB)
-    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.h264e_hip_selftest_nal_escape.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.h264e_hip_pool_destroy.argtypes = [C.c_void_p]
     pool = C.c_void_p()
-    assert L.h264e_hip_pool_create(C.byref(pool), 0, 64, 48, 1, 1, 1) == 0
+    assert L.h264e_hip_pool_create(C.byref(pool), 0, 64, 48, 1, 1) == 0
     for p in nal_cases.cases():
         want = nal_cases.escape_ref(p)
         cap = len(p) * 3 // 2 + 64
@@ -390,12 +390,12 @@ def test_dispatch_order_with_xcd_bands_is_complete_padded_and_dependency_safe(w,
     import ctypes as C
     P = pkg.load_pkg()
     L = P.load(pkg.EMU_LIB)
-    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.h264e_hip_pool_destroy.argtypes = [C.c_void_p]
     L.h264e_hip_selftest_order.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t]
     L.h264e_hip_selftest_order.restype = C.c_long
     pool = C.c_void_p()
-    assert L.h264e_hip_pool_create(C.byref(pool), 0, w, h, jobs, 1, 1) == 0
+    assert L.h264e_hip_pool_create(C.byref(pool), 0, w, h, jobs, 1) == 0
     try:
         nmby, lag = (h + 15) // 16, 4 if narrow else 7
         rows = nmby + 1

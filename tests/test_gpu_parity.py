@@ -264,11 +264,11 @@ def test_nal_escape_pass_on_adversarial_payloads(P):
     import ctypes as C
     import nal_cases
     L = P.load()
-    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.h264e_hip_selftest_nal_escape.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.h264e_hip_pool_destroy.argtypes = [C.c_void_p]
     pool = C.c_void_p()
-    assert L.h264e_hip_pool_create(C.byref(pool), 0, 64, 48, 1, 1, 1) == 0
+    assert L.h264e_hip_pool_create(C.byref(pool), 0, 64, 48, 1, 1) == 0
     for p in nal_cases.cases():
         want = nal_cases.escape_ref(p)
         cap = len(p) * 3 // 2 + 64

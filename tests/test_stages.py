@@ -172,11 +172,11 @@ def test_oracle_deblock_macroblock():
 def _hook(libpath):
     P = pkg.load_pkg()
     L = P.load(libpath) if libpath else P.load()
-    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.h264e_hip_selftest_stage.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.POINTER(C.c_int), C.c_char_p, C.c_uint32]
     L.h264e_hip_pool_destroy.argtypes = [C.c_void_p]
     pool = C.c_void_p()
-    assert L.h264e_hip_pool_create(C.byref(pool), 0, 64, 48, 1, 1, 1) == 0
+    assert L.h264e_hip_pool_create(C.byref(pool), 0, 64, 48, 1, 1) == 0
 
     def run(stage, data, args, nout):
         a = (C.c_int * 24)(*(list(args) + [0] * (24 - len(args))))
