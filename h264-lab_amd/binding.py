@@ -3,6 +3,7 @@
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -51,6 +52,118 @@ class ClipStats(C.Structure):
                 ("relaunches_timed", C.c_int), ("processed_mbs", C.c_longlong), ("delivered_mbs", C.c_longlong), ("first_frame_ms_after_relaunch", C.c_double)]
 
 
+class DevFrame(C.Structure):  # H264E_dev_frame_t: a frame in device memory (checked against H264E_struct_size(2) at load)
+    _fields_ = [("format", C.c_int), ("pixel_bytes", C.c_int), ("plane", C.c_void_p * 3), ("stride", C.c_int * 3), ("producer_stream", C.c_void_p)]
+
+
+DEV_FORMAT_I420, DEV_FORMAT_NV12, DEV_FORMAT_RGB = 0, 1, 2
+_DEV_FORMATS = {"i420": DEV_FORMAT_I420, "nv12": DEV_FORMAT_NV12, "rgb": DEV_FORMAT_RGB}
+
+
+def hip_runtimes():
+    """the HIP runtime libraries mapped into this process (see _share_torch_runtime: more than one is a broken process)"""
+    try:
+        with open("/proc/self/maps") as f:
+            return sorted({line.split()[-1] for line in f if "/libamdhip64.so" in line})
+    except OSError:
+        return []
+
+
+def _one_runtime():
+    r = hip_runtimes()
+    if len(r) > 1:
+        raise H264EError("device input: two HIP runtimes are loaded (%s): memory and streams of one are unknown to the other.  Load the "
+                         "library that owns the frames BEFORE this one (and do not set H264E_SYSTEM_HIP=1 next to torch), so that one runtime serves both" % ", ".join(r))
+
+
+def _dev_array(a):
+    """(pointer, shape, strides in bytes, producer stream or None) of one device array: an object with data_ptr() / stride() / shape
+    (a torch tensor), one with __cuda_array_interface__, or an explicit (pointer, row stride in bytes) pair -- whose shape is not
+    known, so nothing about it is checked here."""
+    if isinstance(a, (tuple, list)) and len(a) == 2 and all(isinstance(x, int) for x in a):
+        return int(a[0]), None, (int(a[1]),), None
+    if hasattr(a, "data_ptr") and hasattr(a, "stride"):
+        if a.element_size() != 1:
+            raise H264EError("device input must be 8-bit samples, not %s" % (getattr(a, "dtype", "?"),))
+        stream = None
+        torch = sys.modules.get("torch")            # never imported here: a tensor in hand means the caller has
+        if torch is not None and getattr(a, "is_cuda", False):
+            stream = torch.cuda.current_stream(a.device)
+        return int(a.data_ptr()), tuple(a.shape), tuple(int(x) for x in a.stride()), stream
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is not None:
+        if cai["typestr"] not in ("|u1", "<u1", ">u1", "|i1"):
+            raise H264EError("device input must be 8-bit samples, not %s" % cai["typestr"])
+        shape = tuple(cai["shape"])
+        strides = cai.get("strides")
+        if strides is None:
+            strides, acc = [], 1
+            for d in reversed(shape):
+                strides.insert(0, acc)
+                acc *= d
+        st = cai.get("stream")
+        return int(cai["data"][0]), shape, tuple(int(x) for x in strides), (st if st not in (None, 1, 2) else None)
+    raise H264EError("device input: expected a tensor, an object with __cuda_array_interface__ or a (pointer, stride) pair, got %r" % type(a))
+
+
+def _dev_plane(a, rows, row_bytes, what):
+    """one 2-D plane (or (h, w, c) pixels, c = the last axis): (pointer, row stride, stream)"""
+    ptr, shape, strides, stream = _dev_array(a)
+    if shape is not None:
+        inner = 1
+        for d in shape[1:]:
+            inner *= d
+        dense = all(strides[i] == (strides[i + 1] * shape[i + 1]) for i in range(1, len(shape) - 1)) and strides[-1] == 1
+        if len(shape) < 2 or shape[0] != rows or inner != row_bytes or not dense:
+            raise H264EError("device input: %s must be %d rows of %d contiguous bytes, got shape %r strides %r" % (what, rows, row_bytes, shape, strides))
+    return ptr, strides[0], stream
+
+
+def dev_frame(frame, fmt, w, h, stream=None):
+    """H264E_dev_frame_t for one frame of a w x h picture.  fmt "i420": three 2-D planes (y, u, v) or one packed (h*3/2, w) array;
+    "nv12": (y of (h, w), uv of (h/2, w)); "rgb": one (h, w, 3 | 4) array.  Arrays: torch tensors, anything with
+    __cuda_array_interface__, or (pointer, row stride in bytes) pairs.  stream: the hipStream_t (an int) that writes the frame; by
+    default torch's current stream for torch tensors.  Returns (DevFrame, the objects that must stay alive during the call)."""
+    f = _DEV_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+    pb, planes = 0, []
+    _one_runtime()
+    if f == DEV_FORMAT_I420:
+        if isinstance(frame, (tuple, list)) and len(frame) == 3:
+            planes = [_dev_plane(frame[0], h, w, "Y"), _dev_plane(frame[1], h // 2, w // 2, "U"), _dev_plane(frame[2], h // 2, w // 2, "V")]
+        else:
+            ptr, shape, strides, st = _dev_array(frame)
+            if shape is not None and (tuple(shape) != (h * 3 // 2, w) or tuple(strides) != (w, 1)):
+                raise H264EError("device input: packed I420 must be a contiguous (%d, %d) array, got shape %r strides %r" % (h * 3 // 2, w, shape, strides))
+            if shape is None and strides[0] != w:
+                raise H264EError("device input: packed I420 has row stride %d, got %d" % (w, strides[0]))
+            planes = [(ptr, w, st), (ptr + w * h, w // 2, st), (ptr + w * h + (w // 2) * (h // 2), w // 2, st)]
+    elif f == DEV_FORMAT_NV12:
+        if not isinstance(frame, (tuple, list)) or len(frame) != 2:
+            raise H264EError("device input: NV12 takes (y, uv)")
+        planes = [_dev_plane(frame[0], h, w, "Y"), _dev_plane(frame[1], h // 2, w, "UV")]
+    elif f == DEV_FORMAT_RGB:
+        ptr, shape, strides, st = _dev_array(frame)
+        if shape is None:
+            raise H264EError("device input: RGB needs an array with a shape (h, w, 3 | 4)")
+        pb = shape[-1] if len(shape) == 3 else 0
+        planes = [_dev_plane(frame, h, w * pb, "RGB")]
+    else:
+        raise H264EError("device input: unknown format %r" % (fmt,))
+    d = DevFrame(format=f, pixel_bytes=pb)
+    for k, (ptr, stride, _) in enumerate(planes):
+        d.plane[k], d.stride[k] = ptr, stride
+    if stream is None:
+        # torch's current stream; its default stream has handle 0, which the C API reads as "the caller has synchronised": make it so
+        for st in {id(p[2]): p[2] for p in planes if p[2] is not None}.values():
+            handle = getattr(st, "cuda_stream", st)
+            if handle:
+                stream = handle
+            elif hasattr(st, "synchronize"):
+                st.synchronize()
+    d.producer_stream = int(stream) if stream else None
+    return d, frame
+
+
 def lib_path():
     return os.environ.get("H264E_LIB", _DEFAULT_LIB)
 
@@ -63,12 +176,35 @@ def build():
 _libs = {}
 
 
+def _share_torch_runtime(path):
+    """One HIP runtime per process, whichever of torch and this library comes first.  torch ships a libamdhip64.so of its own and its
+    libraries ask the loader for that FILE; this library asks for the soname libamdhip64.so.7.  torch first: torch's copy serves both.
+    Library first: the system copy is bound, torch maps its own next to it, and that second runtime finds no device at all (measured
+    on an MI355X: hipErrorNoDevice at torch's first stream).  So where a torch installation with a runtime of its own exists, that file
+    is mapped BEFORE the library is (torch is only located, not imported): the library then binds to it by soname, and a later
+    `import torch` finds the same file already mapped.  H264E_SYSTEM_HIP=1 keeps the system runtime."""
+    if os.environ.get("H264E_SYSTEM_HIP") == "1" or hip_runtimes():
+        return
+    try:
+        with open(path, "rb") as f:
+            if b"libamdhip64.so" not in f.read():
+                return                      # (the emulation libraries: no HIP runtime at all)
+        import importlib.util
+        spec = importlib.util.find_spec("torch")
+        rt = os.path.join(os.path.dirname(spec.origin), "lib", "libamdhip64.so") if spec and spec.origin else None
+        if rt and os.path.exists(rt):
+            C.CDLL(rt, mode=C.RTLD_GLOBAL)
+    except (OSError, ImportError, ValueError):
+        pass                                # no torch, or no runtime of its own: the system's
+
+
 def load(path=None):
     path = path or lib_path()
     if path in _libs:
         return _libs[path]
     if not os.path.exists(path):
         raise H264EError("HIP library %s not built: run `make -C h264-lab_amd/csrc` (there is no CPU fallback)" % path)
+    _share_torch_runtime(path)
     L = C.CDLL(path)
     L.H264E_sizeof.argtypes = [C.POINTER(CreateParam), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.H264E_init.argtypes = [C.c_void_p, C.POINTER(CreateParam)]
@@ -97,6 +233,17 @@ def load(path=None):
     L.H264E_clip_close.argtypes = [C.c_void_p]
     L.H264E_clip_close.restype = None
     L.h264e_hip_device_count.restype = C.c_int
+    L.H264E_struct_size.argtypes = [C.c_int]
+    if L.H264E_struct_size(2) != C.sizeof(DevFrame):
+        raise H264EError("%s: H264E_dev_frame_t has %d bytes, this binding's mirror %d" % (path, L.H264E_struct_size(2), C.sizeof(DevFrame)))
+    L.H264E_encode_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RunParam), C.POINTER(DevFrame), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.H264E_clip_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(DevFrame)]
+    L.H264E_clip_download.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.H264E_dev_malloc.argtypes = [C.c_int, C.c_size_t]
+    L.H264E_dev_malloc.restype = C.c_void_p
+    L.H264E_dev_free.argtypes = [C.c_void_p]
+    L.H264E_dev_free.restype = None
+    L.H264E_dev_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     _libs[path] = L
     return L
 
@@ -161,6 +308,17 @@ class Encoder:
             raise _err(self.L, "H264E_encode status %d" % st)
         return C.string_at(data, n.value)
 
+    def encode_device(self, frame, fmt, frame_type=FRAME_TYPE_DEFAULT, stream=None):
+        """H264E_encode_device: the frame is taken from GPU memory (see dev_frame for what `frame` may be: fmt "i420", "nv12" or "rgb");
+        needs const_input=1.  The frame's memory may be reused as soon as this returns."""
+        d, _keep = dev_frame(frame, fmt, self.w, self.h, stream)
+        self.rp.frame_type = frame_type
+        data, n = C.c_void_p(), C.c_int()
+        st = self.L.H264E_encode_device(self.persist, self.scratch, C.byref(self.rp), C.byref(d), C.byref(data), C.byref(n))
+        if st:
+            raise _err(self.L, "H264E_encode_device status %d" % st)
+        return C.string_at(data, n.value)
+
     def set_vbv_state(self, vbv_size_bytes, vbv_fullness_bytes):
         """H264E_set_vbv_state (h264-lab.h:6898-6913)"""
         self.L.H264E_set_vbv_state(self.persist, vbv_size_bytes, vbv_fullness_bytes)
@@ -205,6 +363,22 @@ class ClipEncoder:
         n = clip.size // (self.w * self.h * 3 // 2)
         if self.L.H264E_clip_upload(self.c, first, n, clip.ctypes.data):
             raise _err(self.L, "H264E_clip_upload")
+
+    def upload_device(self, frames, fmt, first=0, stream=None):
+        """H264E_clip_upload_device: `frames` is a sequence of frames in GPU memory (see dev_frame: fmt "i420", "nv12" or "rgb"), frame
+        first + i from frames[i].  Their memory may be reused as soon as this returns."""
+        made = [dev_frame(f, fmt, self.w, self.h, stream) for f in frames]
+        arr = (DevFrame * max(len(made), 1))(*[m[0] for m in made])
+        if self.L.H264E_clip_upload_device(self.c, first, len(made), arr):
+            raise _err(self.L, "H264E_clip_upload_device")
+
+    def download(self, first=0, nframes=None):
+        """the resident input frames (packed I420) back to the host: whole-clip residency only"""
+        n = self.n - first if nframes is None else nframes
+        buf = np.empty((n, self.w * self.h * 3 // 2), np.uint8)
+        if self.L.H264E_clip_download(self.c, first, n, buf.ctypes.data):
+            raise _err(self.L, "H264E_clip_download")
+        return buf
 
     def generate_synth(self, first=0, nframes=None, t0=0, seed=1):
         if self.L.H264E_clip_generate_synth(self.c, first, self.n if nframes is None else nframes, t0, seed):

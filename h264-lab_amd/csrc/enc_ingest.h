@@ -1,0 +1,132 @@
+/*
+ * enc_ingest.h -- device-resident input: one source frame in HBM (I420, NV12 or interleaved RGB, arbitrary row strides) into the
+ * encoder's resident input slot, packed I420 (width*height luma, then two (width/2)*(height/2) chroma planes, rows packed: exactly
+ * what h264e_hip_upload_i420 leaves there), per sample group.
+ *
+ *   - I420: three planes, each with its own pointer and stride: a strided copy;
+ *   - NV12: a luma plane and one plane of interleaved U,V pairs: the chroma rows are de-interleaved;
+ *   - RGB:  interleaved 8-bit R,G,B, pixel_bytes = 3 or 4 (a fourth byte is ignored), BT.601 limited range in integers -- the
+ *     reference has no colour conversion, this IS the definition (tests/ingest_model.py restates it):
+ *         Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16                                  per pixel,
+ *         m = (a + b + c + d + 2) >> 2                                                 per channel over each 2x2 block, then
+ *         U = ((-38 Rm - 74 Gm + 112 Bm + 128) >> 8) + 128,  V = ((112 Rm - 94 Gm - 18 Bm + 128) >> 8) + 128
+ *     (arithmetic shifts; Y lands in 16..235, U and V in 16..240: nothing to clamp).  Width and height are even, so every block is whole.
+ *
+ * One lane makes four consecutive output samples of one row: ingest_luma for the Y plane, ingest_chroma for the same four samples of
+ * U AND V (both come from the same source bytes in NV12 and RGB).  Source bytes are fetched as dwords where the lane's source address
+ * is dword aligned and the group is whole, byte by byte otherwise (101-byte chroma rows, 3-byte pixels on odd strides, the last group
+ * of a row); the four output samples go out as one dword under the same rule.  Only raw addresses: nothing here knows how the source
+ * was allocated.  h264e_kernels.hip runs it as h264e_ingest_kernel, h264e_pool.h's emulation launch (H264E_EMU) as a lane loop.
+ */
+#ifndef H264E_ENC_INGEST_H
+#define H264E_ENC_INGEST_H
+#include "wave.h"
+
+#define H264E_INGEST_I420 0
+#define H264E_INGEST_NV12 1
+#define H264E_INGEST_RGB  2
+
+typedef struct
+{
+    const uint8_t *plane[3];
+    int stride[3];                      /* bytes from row to row */
+    int format, pixel_bytes;            /* H264E_INGEST_*; bytes per RGB pixel (3 or 4), ignored otherwise */
+    int width, height;                  /* luma samples: both even */
+} h264e_ingest_src_t;
+
+/* the first nb of NB source bytes at p into v, byte k in bits 8*(k & 3) of v[k >> 2]: dwords where p is dword aligned and all NB
+ * bytes are wanted, else byte loads (never a byte beyond p + nb: the last row may end with its allocation) */
+template <int NB> DEV void ing_fetch(const gu8 *p, int nb, uint32_t *v)
+{
+    EMU_GLOBAL(p, (size_t)nb);
+    if (nb == NB && !((uintptr_t)p & 3))
+    {
+        for (int i = 0; i < NB/4; i++) v[i] = *(const GLOBAL_AS uint32_t *)(p + 4*i);
+        return;
+    }
+    for (int i = 0; i < NB/4; i++) v[i] = 0;
+    for (int k = 0; k < NB; k++) if (k < nb) v[k >> 2] |= (uint32_t)p[k] << (8*(k & 3));
+}
+DEV int ing_byte(const uint32_t *v, int k) { return (int)((v[k >> 2] >> (8*(k & 3))) & 255u); }
+
+/* n <= 4 output samples (packed in o) to d: one dword where d is dword aligned and n = 4 */
+DEV void ing_store(gu8 *d, int n, uint32_t o)
+{
+    EMU_GLOBAL(d, (size_t)n);
+    if (n == 4 && !((uintptr_t)d & 3)) { *(GLOBAL_AS uint32_t *)d = o; return; }
+    for (int k = 0; k < 4; k++) if (k < n) d[k] = (uint8_t)(o >> (8*k));
+}
+
+/* the matrix rows: results are in 16..240 by construction (no clamp); the opaque barrier keeps hipcc from folding shift + pack into
+ * v_ashr_pk_u8_i32 (tests/test_isa_tripwire.py) */
+DEV uint32_t ing_y(int r, int g, int b) { return (uint32_t)(opaque_int((66*r + 129*g + 25*b + 128) >> 8) + 16); }
+DEV uint32_t ing_u(int r, int g, int b) { return (uint32_t)(opaque_int((-38*r - 74*g + 112*b + 128) >> 8) + 128); }
+DEV uint32_t ing_v(int r, int g, int b) { return (uint32_t)(opaque_int((112*r - 94*g - 18*b + 128) >> 8) + 128); }
+
+/* PB = bytes per pixel: four luma samples from four pixels */
+template <int PB> DEV uint32_t ing_rgb_luma(const gu8 *p, int n)
+{
+    uint32_t v[PB], o = 0;
+    ing_fetch<4*PB>(p, n*PB, v);
+    for (int k = 0; k < 4; k++) o |= ing_y(ing_byte(v, PB*k), ing_byte(v, PB*k + 1), ing_byte(v, PB*k + 2)) << (8*k);
+    return o;
+}
+
+/* ... and four U and four V samples from the 8 x 2 pixels at p0 (even row) and p1 (the row below it) */
+template <int PB> DEV void ing_rgb_chroma(const gu8 *p0, const gu8 *p1, int n, uint32_t &ou, uint32_t &ov)
+{
+    uint32_t a[2*PB], b[2*PB];
+    ing_fetch<8*PB>(p0, 2*n*PB, a);
+    ing_fetch<8*PB>(p1, 2*n*PB, b);
+    ou = ov = 0;
+    for (int k = 0; k < 4; k++)
+    {
+        int m[3];
+        for (int ch = 0; ch < 3; ch++)
+            m[ch] = (ing_byte(a, 2*PB*k + ch) + ing_byte(a, 2*PB*k + PB + ch) + ing_byte(b, 2*PB*k + ch) + ing_byte(b, 2*PB*k + PB + ch) + 2) >> 2;
+        ou |= ing_u(m[0], m[1], m[2]) << (8*k);
+        ov |= ing_v(m[0], m[1], m[2]) << (8*k);
+    }
+}
+
+/* luma samples 4g .. min(4g + 3, width - 1) of row y into the slot at dst */
+DEV void ingest_luma(const h264e_ingest_src_t &S, GLOBAL_AS uint8_t *dst, int g, int y)
+{
+    const int x0 = 4*g;
+    if (x0 >= S.width || y >= S.height) return;
+    const int n = S.width - x0 < 4 ? S.width - x0 : 4;
+    const gu8 *row = (const gu8 *)S.plane[0] + (size_t)y*(size_t)S.stride[0];
+    uint32_t o;
+    if (S.format == H264E_INGEST_RGB) o = S.pixel_bytes == 4 ? ing_rgb_luma<4>(row + (size_t)x0*4, n) : ing_rgb_luma<3>(row + (size_t)x0*3, n);
+    else ing_fetch<4>(row + x0, n, &o);
+    ing_store(dst + (size_t)y*(size_t)S.width + x0, n, o);
+}
+
+/* chroma samples 4g .. of chroma row y (width/2 x height/2 samples per plane), U and V */
+DEV void ingest_chroma(const h264e_ingest_src_t &S, GLOBAL_AS uint8_t *dst, int g, int y)
+{
+    const int cw = S.width >> 1, ch = S.height >> 1, x0 = 4*g;
+    if (x0 >= cw || y >= ch) return;
+    const int n = cw - x0 < 4 ? cw - x0 : 4;
+    uint32_t ou, ov;
+    if (S.format == H264E_INGEST_RGB)
+    {
+        const gu8 *p0 = (const gu8 *)S.plane[0] + (size_t)(2*y)*(size_t)S.stride[0] + (size_t)(2*x0)*(size_t)S.pixel_bytes, *p1 = p0 + S.stride[0];
+        if (S.pixel_bytes == 4) ing_rgb_chroma<4>(p0, p1, n, ou, ov); else ing_rgb_chroma<3>(p0, p1, n, ou, ov);
+    } else if (S.format == H264E_INGEST_NV12)
+    {
+        uint32_t v[2];
+        ing_fetch<8>((const gu8 *)S.plane[1] + (size_t)y*(size_t)S.stride[1] + 2*x0, 2*n, v);
+        ou = ov = 0;
+        for (int k = 0; k < 4; k++) { ou |= (uint32_t)ing_byte(v, 2*k) << (8*k); ov |= (uint32_t)ing_byte(v, 2*k + 1) << (8*k); }
+    } else
+    {
+        ing_fetch<4>((const gu8 *)S.plane[1] + (size_t)y*(size_t)S.stride[1] + x0, n, &ou);
+        ing_fetch<4>((const gu8 *)S.plane[2] + (size_t)y*(size_t)S.stride[2] + x0, n, &ov);
+    }
+    gu8 *du = dst + (size_t)S.width*(size_t)S.height + (size_t)y*(size_t)cw + x0;
+    ing_store(du, n, ou);
+    ing_store(du + (size_t)cw*(size_t)ch, n, ov);
+}
+
+#endif

@@ -683,8 +683,18 @@ void H264E_set_vbv_state(H264E_persist_t *p, int vbv_size_bytes, int vbv_fullnes
     }
 }
 
-int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_param_t *opt, H264E_io_yuv_t *in,
-                 unsigned char **coded_data, int *sizeof_coded_data)
+/* the frame into the pool's input slot: from the caller's host planes, or from device memory (H264E_encode_device) */
+static int put_frame(h264e_hip_pool_t *pool, const H264E_io_yuv_t *in, const H264E_dev_frame_t *dev)
+{
+    const uint8_t *yuv[3];
+    if (dev) return h264e_hip_ingest_device(pool, 0, dev->format, dev->plane, dev->stride, dev->pixel_bytes, dev->producer_stream);
+    yuv[0] = in->yuv[0]; yuv[1] = in->yuv[1]; yuv[2] = in->yuv[2];
+    return h264e_hip_upload_planes(pool, 0, yuv, in->stride);
+}
+
+/* H264E_encode (dev = NULL) and H264E_encode_device (in = NULL) */
+static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_param_t *opt, H264E_io_yuv_t *in, const H264E_dev_frame_t *dev,
+                        unsigned char **coded_data, int *sizeof_coded_data)
 {
     henc_t *e = (henc_t *)p;
     impl_t mm, *m = impl_of(e, &mm) ? &mm : NULL;
@@ -693,9 +703,18 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
     int frame_type, key, qp, sp, ss, den;
     h264e_hip_task_t task;
     h264e_hip_result_t res;
-    const uint8_t *yuv[3];
     g_host_err[0] = 0;
-    if (!m || !scratch || !in || !coded_data || !sizeof_coded_data) return H264E_STATUS_BAD_ARGUMENT;
+    if (!m || !scratch || (!in && !dev) || !coded_data || !sizeof_coded_data) return H264E_STATUS_BAD_ARGUMENT;
+    if (dev)
+    {
+        if (!e->param.const_input_flag)
+        {
+            snprintf(g_host_err, sizeof(g_host_err), "H264E_encode_device needs const_input_flag = 1: the reconstruction is not written back to device planes");
+            return H264E_STATUS_BAD_PARAMETER;
+        }
+        /* refused before the stream state moves */
+        if (h264e_hip_ingest_check(m->pool, 0, dev->format, dev->plane, dev->stride, dev->pixel_bytes)) return H264E_STATUS_BAD_ARGUMENT;
+    }
     ref_sizes(&e->param, &sp, &ss);
     cap = (size_t)ss;
     if (opt) e->run_param = *opt;
@@ -733,13 +752,12 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
                       (opt->encode_speed == 8 || opt->encode_speed == 10), task.nslices, &task.hdr_nal, &task.hdr_bits, &task.hdr_nbits);
     build_qdat(task.qdat, qp, !key);
 
-    yuv[0] = in->yuv[0]; yuv[1] = in->yuv[1]; yuv[2] = in->yuv[2];
     memset(&res, 0, sizeof(res));
     /* h264-lab.h:6684-6695: the denoiser runs first (also in front of a transparent VBV-overflow frame) and its output is what gets encoded */
     den = e->denoise && opt->encode_speed < 2;
     if (den)
     {
-        if (h264e_hip_upload_planes(m->pool, 0, yuv, in->stride) || h264e_hip_denoise_frames(m->pool, 0, 1, !e->den_started)) return H264E_STATUS_BAD_ARGUMENT;
+        if (put_frame(m->pool, in, dev) || h264e_hip_denoise_frames(m->pool, 0, 1, !e->den_started)) return H264E_STATUS_BAD_ARGUMENT;
         e->den_started = 1;
         task.denoised = 1;
     }
@@ -769,7 +787,7 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
         res.all_skipped = 1;
     } else
     {
-    if (!den && h264e_hip_upload_planes(m->pool, 0, yuv, in->stride)) return H264E_STATUS_BAD_ARGUMENT;
+    if (!den && put_frame(m->pool, in, dev)) return H264E_STATUS_BAD_ARGUMENT;
     if (frame_exact(m->pool, &task, e->seq.nmbx, e->seq.nmby, e->clusters) || h264e_hip_stream_done(m->pool, 0, &res) != 1) return H264E_STATUS_BAD_ARGUMENT;
     {
         const uint8_t *nals = h264e_hip_stream_rbsp(m->pool, 0);
@@ -791,7 +809,7 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
 
     rc_frame_end(&e->rc, e->seq.nmb, e->param.vbv_size_bytes, opt->desired_frame_bytes, (int)out_pos, key, res.all_skipped);
 
-    if (!e->param.const_input_flag)
+    if (!e->param.const_input_flag && in)
     {
         /* h264-lab.h:6719-6723: the reconstruction replaces the caller's input picture (encode_app --psnr relies on it) */
         int c, y;
@@ -809,6 +827,23 @@ int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_p
     *sizeof_coded_data = (int)out_pos;
     return H264E_STATUS_SUCCESS;
 }
+
+int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_param_t *opt, H264E_io_yuv_t *in,
+                 unsigned char **coded_data, int *sizeof_coded_data)
+{
+    return encode_frame(p, scratch, opt, in, NULL, coded_data, sizeof_coded_data);
+}
+
+/* H264E_encode with the frame taken from device memory by the ingest kernel (enc_ingest.h) instead of a host-to-device copy */
+int H264E_encode_device(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_param_t *opt, const H264E_dev_frame_t *frame,
+                        unsigned char **coded_data, int *sizeof_coded_data)
+{
+    return encode_frame(p, scratch, opt, NULL, frame, coded_data, sizeof_coded_data);
+}
+
+void *H264E_dev_malloc(int device, size_t bytes) { g_host_err[0] = 0; return h264e_hip_dev_malloc(device, bytes); }
+void H264E_dev_free(void *p) { h264e_hip_dev_free(p); }
+int H264E_dev_memcpy(void *dst, const void *src, size_t bytes, int to_device) { g_host_err[0] = 0; return h264e_hip_dev_memcpy(dst, src, bytes, to_device); }
 
 /* ------------------------------------------------------------------ whole-clip encode: temporal wavefront */
 
@@ -868,7 +903,7 @@ struct H264E_clip_tag
 #define CLIP_DEV_BUDGET (24.0*1073741824.0)
 static double clip_dev_slot_bytes(int nmb) { return (double)nmb*256.0*3.0 + (double)nmb*(64 + 96 + 8 + 640 + 660 + 2048 + 64) + 65536.0; }
 
-int H264E_struct_size(int which) { return which == 0 ? (int)sizeof(H264E_clip_param_t) : which == 1 ? (int)sizeof(H264E_clip_stats_t) : -1; }
+int H264E_struct_size(int which) { return which == 0 ? (int)sizeof(H264E_clip_param_t) : which == 1 ? (int)sizeof(H264E_clip_stats_t) : which == 2 ? (int)sizeof(H264E_dev_frame_t) : -1; }
 
 static double now_ms(void)
 {
@@ -981,11 +1016,9 @@ void H264E_clip_close(H264E_clip_t *c)
     free(c);
 }
 
-/* frames [first, first + n) of the stream into their ring slots; a slot may only be overwritten once its old frame is encoded */
-static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int async)
+/* may frames [first, first + n) of the stream go into their ring slots?  A slot may only be overwritten once its old frame is encoded */
+static int clip_put_allowed(const H264E_clip_t *c, int first, int n)
 {
-    const size_t fsz = (size_t)c->seq.width*c->seq.height*3/2;
-    int done = 0;
     if (!c || first < 0 || n < 0 || first + n > c->nframes) { snprintf(g_host_err, sizeof(g_host_err), "upload: bad frame range"); return -1; }
     if (first + n - c->resident > c->next) { snprintf(g_host_err, sizeof(g_host_err), "upload: input ring full (frames %d.. are not encoded yet)", c->next); return -1; }
     if (c->denoise && first > 0 && first < c->den_done && first - 1 < c->den_done - c->resident)
@@ -993,6 +1026,16 @@ static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int 
         snprintf(g_host_err, sizeof(g_host_err), "upload: frame %d would be denoised again, but the denoised picture in front of it has left the input ring (rewind and upload from frame 0)", first);
         return -1;
     }
+    return 0;
+}
+
+/* frames [first, first + n) of the stream into their ring slots */
+static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int async)
+{
+    size_t fsz;
+    int done = 0;
+    if (clip_put_allowed(c, first, n)) return -1;
+    fsz = (size_t)c->seq.width*c->seq.height*3/2;
     while (done < n)
     {
         const int slot = (first + done) % c->resident, run = imin(n - done, c->resident - slot);
@@ -1013,6 +1056,24 @@ int H264E_clip_upload(H264E_clip_t *c, int first, int nframes, const uint8_t *i4
 {
     if (clip_put(c, first, nframes, i420, 0)) return -1;
     return h264e_hip_sync(c->pool);
+}
+
+/* The same from device memory: one ingest kernel per frame on the pool's copy stream (enc_ingest.h), all of them complete on return.
+ * Every frame is checked before the first one is launched, so a refused call leaves the input ring as it was. */
+int H264E_clip_upload_device(H264E_clip_t *c, int first, int nframes, const H264E_dev_frame_t *frames)
+{
+    int i, rc = 0;
+    g_host_err[0] = 0;
+    if (clip_put_allowed(c, first, nframes)) return -1;
+    if (!frames) { snprintf(g_host_err, sizeof(g_host_err), "upload_device: null argument"); return -1; }
+    for (i = 0; i < nframes; i++)
+        if (h264e_hip_ingest_check(c->pool, (first + i) % c->resident, frames[i].format, frames[i].plane, frames[i].stride, frames[i].pixel_bytes)) return -1;
+    for (i = 0; i < nframes && !rc; i++)
+        rc = h264e_hip_ingest_device_async(c->pool, (first + i) % c->resident, frames[i].format, frames[i].plane, frames[i].stride, frames[i].pixel_bytes, frames[i].producer_stream);
+    if (h264e_hip_upload_wait(c->pool) || rc) return -1;        /* (after a failure too: what was launched has read its source) */
+    if (first + nframes > c->avail) c->avail = first + nframes;
+    if (first < c->den_done) c->den_done = first;
+    return 0;
 }
 
 /* the same from pinned host memory (H264E_clip_host_alloc) on the pool's copy stream: returns at once, the frames count as

@@ -12,6 +12,7 @@
  *   h264e_synth_kernel   fills resident input frames with the synth_v1 clip (bench / test input in HBM).
  *   h264e_denoise_kernel the temporal denoiser (enc_denoise.h) over one frame: raw input + previous denoised picture -> new
  *                        denoised picture, out of place, one launch per frame in stream order.
+ *   h264e_ingest_kernel  device-resident input (enc_ingest.h): one I420 / NV12 / RGB frame in HBM -> the packed I420 input slot.
  *
  * HIP only (hipcc --offload-arch=gfx950).  The host side of the boundary is h264e_pool.h, included at the end; the test-only
  * emulation of tests/emu compiles the same kernel HEADERS with its own launch functions and never sees this file.
@@ -22,6 +23,7 @@
 #include "enc_row.h"
 #include "enc_selftest.h"
 #include "enc_denoise.h"
+#include "enc_ingest.h"
 #include "../../include/h264e_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -684,6 +686,15 @@ __global__ void __launch_bounds__(256) h264e_denoise_kernel(const uint8_t *in, c
                   w, h, (int)(blockIdx.x*blockDim.x + threadIdx.x), y, aligned);
 }
 
+/* device-resident input over one frame: grid.z = 0 luma / 1 both chroma planes, grid.y = row, grid.x * 256 lanes x 4 samples along the
+ * row.  Every workgroup reads its own source bytes and writes its own bytes of the slot (no inter-workgroup traffic). */
+__global__ void __launch_bounds__(256) h264e_ingest_kernel(h264e_ingest_src_t S, uint8_t *dst)
+{
+    const int g = (int)(blockIdx.x*blockDim.x + threadIdx.x), y = (int)blockIdx.y;
+    if (blockIdx.z == 0) ingest_luma(S, (GLOBAL_AS uint8_t *)dst, g, y);
+    else ingest_chroma(S, (GLOBAL_AS uint8_t *)dst, g, y);
+}
+
 /* ------------------------------------------------------------------ launches (what h264e_pool.h calls) */
 
 /* variant: 0 = intra frames only (one wave per row, 4 per SIMD), 1 = one wave per row, 2 = two waves per row (3 per SIMD), 3 = the latency variant: four
@@ -729,6 +740,11 @@ static void bk_launch_denoise(const uint8_t *in, const uint8_t *prev, uint8_t *o
 {
     const unsigned gx = (unsigned)((((width + 3) >> 2) + 255) >> 8);
     hipLaunchKernelGGL(h264e_denoise_kernel, dim3(gx, (unsigned)height, 3), dim3(256), 0, st, in, prev, out, width, height);
+}
+static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t st)
+{
+    const unsigned gx = (unsigned)((((S.width + 3) >> 2) + 255) >> 8);
+    hipLaunchKernelGGL(h264e_ingest_kernel, dim3(gx, (unsigned)S.height, 2), dim3(256), 0, st, S, dst);
 }
 static void bk_launch_stage_selftest(int stage, const uint8_t *in, const int *args, uint8_t *out, hipStream_t st)
 {

@@ -2,7 +2,8 @@
  * h264e_pool.h -- host side of the device boundary (include/h264e_hip.h): pools, launch groups, submits, results.
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
- * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it:
+ * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
+ * defines bk_launch_denoise and bk_launch_ingest; the emulation's versions of those two are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -11,6 +12,7 @@
 #ifndef H264E_POOL_H
 #define H264E_POOL_H
 #include "enc_denoise.h"
+#include "enc_ingest.h"
 
 static thread_local char g_err[256];       /* per calling thread */
 #define FAIL(...) do { snprintf(g_err, sizeof(g_err), __VA_ARGS__); return -1; } while (0)
@@ -152,6 +154,7 @@ struct h264e_hip_pool
     uint8_t *den;
     int den_frames, den_flip;
     hipEvent_t ev_copy;                  /* the copy stream's uploads, waited for by a denoise launch */
+    hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
     h264e_chain_dev_t *chains_host;      /* host mirror of the device descriptors */
     h264e_chain_dev_t *chains_dev;
     h264e_frame_task_t *tasks_dev;       /* ring of TASK_RING task arrays */
@@ -254,6 +257,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     {
         for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventDestroy(p->ev[i][k]);
         (void)hipEventDestroy(p->ev_t0); (void)hipEventDestroy(p->ev_t1); (void)hipEventDestroy(p->ev_prep); (void)hipEventDestroy(p->ev_copy);
+        (void)hipEventDestroy(p->ev_ingest[0]); (void)hipEventDestroy(p->ev_ingest[1]);
         (void)hipStreamDestroy(p->stream);
         if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
         if (p->abort_stream) (void)hipStreamDestroy(p->abort_stream);
@@ -390,6 +394,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     if (hipStreamCreate(&p->stream) != hipSuccess || hipStreamCreate(&p->copy_stream) != hipSuccess || hipStreamCreate(&p->abort_stream) != hipSuccess) { if (p->guarded) process_guard_release(device); free(p); FAIL("hipStreamCreate failed"); }
     for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventCreate(&p->ev[i][k]);
     (void)hipEventCreate(&p->ev_t0); (void)hipEventCreate(&p->ev_t1); (void)hipEventCreate(&p->ev_prep); (void)hipEventCreate(&p->ev_copy);
+    (void)hipEventCreate(&p->ev_ingest[0]); (void)hipEventCreate(&p->ev_ingest[1]);
     p->chains_host = (h264e_chain_dev_t *)calloc((size_t)nchains, sizeof(h264e_chain_dev_t));
     p->clu_dev = (int32_t **)calloc((size_t)nchains, sizeof(int32_t *));
     p->ref_sel = (int *)calloc((size_t)nchains, sizeof(int));
@@ -627,6 +632,119 @@ extern "C" int h264e_hip_upload_planes(h264e_hip_pool_t *p, int index, const uin
         HIPCHK(hipMemcpy2DAsync(d, (size_t)w, yuv[c], (size_t)stride[c], (size_t)w, (size_t)h, hipMemcpyHostToDevice, p->stream));
         d += (size_t)w*h;
     }
+    return 0;
+}
+
+/* ---- device-resident input (enc_ingest.h): one h264e_ingest_kernel launch per frame on the pool's copy stream, where the asynchronous
+ * uploads are ordered too, so that it overlaps with a macroblock launch on the encode stream like they do */
+
+#ifdef H264E_EMU
+/* the emulation's launch: the kernel's per-group code as a lane loop, row by row */
+static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t)
+{
+    for (int y = 0; y < S.height; y++)
+        for (int g = 0; g < (S.width + 3)/4; g++) { ingest_luma(S, dst, g, y); ingest_chroma(S, dst, g, y); }
+}
+#else
+/* the product refuses what the runtime does not know as device memory of this pool's device, and a plane that does not lie inside ONE
+ * allocation from its first to its last byte: a host address or a read beyond the allocation is a memory fault in the kernel, not an
+ * error code (the kernel itself only sees raw addresses) */
+static int ingest_is_device_memory(const h264e_hip_pool_t *p, const void *q, size_t nbytes)
+{
+    hipPointerAttribute_t a;
+    hipDeviceptr_t base = 0;
+    size_t size = 0;
+    memset(&a, 0, sizeof(a));
+    if (hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (a.type != hipMemoryTypeDevice || a.device != p->device) return 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)q) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return (const char *)q >= (const char *)base && (const char *)q + nbytes <= (const char *)base + size;
+}
+#endif
+
+/* everything that is refused, without a launch; fills the kernel's view of the source */
+static int ingest_check(const h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, h264e_ingest_src_t *S)
+{
+    if (!p || !planes || !strides) FAIL("ingest_device: null argument");
+    if (slot < 0 || slot >= p->frames_resident) FAIL("ingest_device: slot %d outside the %d resident frames", slot, p->frames_resident);
+    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12 && format != H264E_INGEST_RGB) FAIL("ingest_device: unknown format %d", format);
+    if (format == H264E_INGEST_RGB && pixel_bytes != 3 && pixel_bytes != 4) FAIL("ingest_device: RGB pixels of %d bytes (3 or 4)", pixel_bytes);
+    memset(S, 0, sizeof(*S));
+    S->format = format; S->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1;
+    S->width = p->G.width; S->height = p->G.height;
+    const int nplanes = format == H264E_INGEST_I420 ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
+    for (int k = 0; k < nplanes; k++)
+    {
+        /* bytes and rows of source plane k: RGB pixels; full-size luma; half-size chroma (NV12: U,V pairs, so `width` bytes again) */
+        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12) ? S->width : S->width/2;
+        if (!planes[k]) FAIL("ingest_device: plane %d is NULL", k);
+        if (strides[k] < row_bytes) FAIL("ingest_device: stride %d of plane %d is below its %d row bytes", strides[k], k, row_bytes);
+#ifndef H264E_EMU
+        const int rows = k == 0 ? S->height : S->height/2;
+        const void *q = planes[k];
+        if (!ingest_is_device_memory(p, q, (size_t)(rows - 1)*(size_t)strides[k] + (size_t)row_bytes))
+            FAIL("ingest_device: plane %d (%p, %d rows %d bytes apart) is not memory of device %d, or not inside one allocation", k, planes[k], rows, strides[k], p->device);
+#endif
+        S->plane[k] = (const uint8_t *)planes[k]; S->stride[k] = strides[k];
+    }
+    return 0;
+}
+
+extern "C" int h264e_hip_ingest_check(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes)
+{
+    h264e_ingest_src_t S;
+    if (p) (void)hipSetDevice(p->device);
+    return ingest_check(p, slot, format, planes, strides, pixel_bytes, &S);
+}
+
+/* the checks, then the launch on the copy stream behind (a) everything queued on the producer's stream so far and (b), while no macroblock
+ * launch of this pool is in flight, everything queued on the pool's own stream (h264e_hip_upload_i420 / upload_planes / generate_synth
+ * into the same slot).  A launch in flight does not read the slot: the caller keeps the bounded-ring rule of H264E_clip_upload. */
+static int ingest_enqueue(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream)
+{
+    h264e_ingest_src_t S;
+    if (p) HIPCHK(hipSetDevice(p->device));
+    if (ingest_check(p, slot, format, planes, strides, pixel_bytes, &S)) return -1;
+    if (producer_stream)
+    {
+        HIPCHK(hipEventRecord(p->ev_ingest[0], (hipStream_t)producer_stream));
+        HIPCHK(hipStreamWaitEvent(p->copy_stream, p->ev_ingest[0], 0));
+    }
+    if (!p->pending)
+    {
+        HIPCHK(hipEventRecord(p->ev_ingest[1], p->stream));
+        HIPCHK(hipStreamWaitEvent(p->copy_stream, p->ev_ingest[1], 0));
+    }
+    bk_launch_ingest(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int h264e_hip_ingest_device_async(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream)
+{
+    return ingest_enqueue(p, slot, format, planes, strides, pixel_bytes, producer_stream);
+}
+
+extern "C" int h264e_hip_ingest_device(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream)
+{
+    if (ingest_enqueue(p, slot, format, planes, strides, pixel_bytes, producer_stream)) return -1;
+    HIPCHK(hipStreamSynchronize(p->copy_stream));
+    return 0;
+}
+
+/* plain device memory for callers without a HIP toolchain of their own (H264E_dev_malloc / _free / _memcpy) */
+extern "C" void *h264e_hip_dev_malloc(int device, size_t bytes)
+{
+    void *q = 0;
+    if (hipSetDevice(device) != hipSuccess) { snprintf(g_err, sizeof(g_err), "dev_malloc: hipSetDevice(%d) failed", device); return 0; }
+    if (dev_malloc(&q, bytes)) { snprintf(g_err, sizeof(g_err), "dev_malloc: no %zu bytes on device %d", bytes, device); return 0; }
+    return q;
+}
+extern "C" void h264e_hip_dev_free(void *q) { dev_free(q); }
+extern "C" int h264e_hip_dev_memcpy(void *dst, const void *src, size_t bytes, int to_device)
+{
+    if (!dst || !src) FAIL("dev_memcpy: null argument");
+    HIPCHK(hipMemcpy(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
     return 0;
 }
 

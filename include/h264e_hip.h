@@ -20,6 +20,7 @@
  */
 #ifndef H264E_HIP_H
 #define H264E_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -107,6 +108,23 @@ void *h264e_hip_host_alloc(size_t bytes);
 void h264e_hip_host_free(void *p);
 /* one frame from three planes with arbitrary strides (the H264E_io_yuv_t of the drop-in API) */
 int  h264e_hip_upload_planes(h264e_hip_pool_t *pool, int index, const uint8_t *const yuv[3], const int stride[3]);
+/* Device-resident input (enc_ingest.h): one frame that already lies in this pool's device memory -- format 0 = I420 (three planes),
+ * 1 = NV12 (Y, interleaved UV), 2 = interleaved RGB of pixel_bytes 3 or 4 (BT.601 limited range, integer) -- into resident slot `slot`,
+ * by ONE kernel launch on the pool's copy stream.  planes / strides: a pointer and a row stride in bytes (>= the row's bytes) per
+ * source plane; unused entries are ignored.  producer_stream: the hipStream_t whose queued work writes the source (the launch waits
+ * for everything queued there so far), or NULL when the caller has synchronised.  Returns when the slot has been written: the source
+ * may be reused at once.  Refused without a launch: a NULL plane, a short stride, an unknown format / pixel_bytes, a slot out of range,
+ * and a plane that the runtime does not report as memory of the pool's device.  The slot must not be the input of a frame that a
+ * running launch still encodes (the bounded-ring rule of H264E_clip_upload).
+ * _async: the same without the final wait; h264e_hip_upload_wait() completes every ingest issued so far.
+ * _check: the refusals alone (0 = this frame would be accepted), nothing is launched. */
+int  h264e_hip_ingest_check(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes);
+int  h264e_hip_ingest_device(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
+int  h264e_hip_ingest_device_async(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
+/* plain device memory and blocking copies, for callers that have no HIP toolchain of their own (to_device: 1 host -> device, 0 back) */
+void *h264e_hip_dev_malloc(int device, size_t bytes);
+void h264e_hip_dev_free(void *p);
+int  h264e_hip_dev_memcpy(void *dst, const void *src, size_t bytes, int to_device);
 /* fill resident frames [first, first+n) with the synth_v1 test clip ON THE DEVICE (bench input, already in HBM) */
 int  h264e_hip_generate_synth(h264e_hip_pool_t *pool, int first, int nframes, int t0, uint32_t seed);
 int  h264e_hip_submit(h264e_hip_pool_t *pool, const h264e_hip_task_t *tasks /* [nchains] */);

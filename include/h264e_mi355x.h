@@ -160,7 +160,40 @@ typedef struct
     double first_frame_ms_after_relaunch;                       /* SUM over relaunches_timed launches of: submit -> first accepted frame (host wall clock) */
 } H264E_clip_stats_t;
 
-/* sizeof of the extension structs as THIS build sees them (0: H264E_clip_param_t, 1: H264E_clip_stats_t): lets a binding in another language check its mirror */
+/* Device-resident input: a frame that already lies in the memory of the encoder's GPU (left there by a decoder, a renderer, a
+ * capture path, a torch model) is taken from there by one small kernel, without a trip through host memory.
+ *   format I420: plane[0..2] = Y, U, V, each with its own stride (separately allocated, padded planes are fine);
+ *          NV12: plane[0] = Y, plane[1] = interleaved U,V pairs;
+ *          RGB:  plane[0] = interleaved 8-bit R,G,B of pixel_bytes 3 or 4 (a fourth byte is ignored), converted to BT.601 limited
+ *                range in integers: Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16 per pixel; chroma from the rounded 2x2 mean of each
+ *                channel, m = (a + b + c + d + 2) >> 2: U = ((-38 Rm - 74 Gm + 112 Bm + 128) >> 8) + 128,
+ *                V = ((112 Rm - 94 Gm - 18 Bm + 128) >> 8) + 128 (arithmetic shifts).
+ * stride: bytes from row to row, at least the row's bytes; no alignment is asked of pointers or strides.  producer_stream: the
+ * hipStream_t on which the work that writes the frame was queued -- the encoder waits for everything queued there so far -- or NULL
+ * when the caller has synchronised.  Every call that takes such frames returns when they have been read: the memory may be reused
+ * at once.  The pointers must be device memory of the encoder's GPU; anything else is refused (H264E_last_error says why). */
+#define H264E_DEV_FORMAT_I420 0
+#define H264E_DEV_FORMAT_NV12 1
+#define H264E_DEV_FORMAT_RGB  2
+typedef struct
+{
+    int format;                             /* H264E_DEV_FORMAT_* */
+    int pixel_bytes;                        /* RGB: 3 or 4; ignored otherwise */
+    const void *plane[3];
+    int stride[3];
+    void *producer_stream;
+} H264E_dev_frame_t;
+/* H264E_encode with the frame taken from the device: rate control, slices, denoiser, nalu_callback and frame types as there.  The
+ * encoder must have been created with const_input_flag = 1 (the reconstruction is not written back to the device):
+ * H264E_STATUS_BAD_PARAMETER otherwise.  A frame that is refused (H264E_STATUS_BAD_ARGUMENT) leaves the stream where it was. */
+int  H264E_encode_device(H264E_persist_t *enc, H264E_scratch_t *scratch, const H264E_run_param_t *run_param,
+                         const H264E_dev_frame_t *frame, unsigned char **coded_data, int *sizeof_coded_data);
+/* device memory and blocking copies for callers without a HIP toolchain (to_device: 1 = host to device, 0 = device to host) */
+void *H264E_dev_malloc(int device, size_t bytes);
+void  H264E_dev_free(void *p);
+int   H264E_dev_memcpy(void *dst, const void *src, size_t bytes, int to_device);
+
+/* sizeof of the extension structs as THIS build sees them (0: H264E_clip_param_t, 1: H264E_clip_stats_t, 2: H264E_dev_frame_t): lets a binding in another language check its mirror */
 int  H264E_struct_size(int which);
 
 typedef struct H264E_clip_tag H264E_clip_t;
@@ -170,6 +203,9 @@ int  H264E_clip_open(H264E_clip_t **clip, const H264E_clip_param_t *par, int nfr
  * With a bounded input ring (resident_frames) a frame can be uploaded once frame (f - resident_frames) has been encoded. */
 int  H264E_clip_upload(H264E_clip_t *clip, int first, int nframes, const uint8_t *i420);
 int  H264E_clip_generate_synth(H264E_clip_t *clip, int first, int nframes, int t0, uint32_t seed);
+/* the same from device memory: frames[i] is frame first + i (frame range, ring and "uploading frame f again makes f onward new" rules
+ * of H264E_clip_upload).  Returns when the frames have been read; all of them are checked before the first is touched. */
+int  H264E_clip_upload_device(H264E_clip_t *clip, int first, int nframes, const H264E_dev_frame_t *frames);
 /* the same from pinned host memory on the copy engine, overlapping with a running encode; H264E_clip_upload_wait() completes it */
 void *H264E_clip_host_alloc(size_t bytes);
 void  H264E_clip_host_free(void *p);
