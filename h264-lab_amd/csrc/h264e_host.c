@@ -472,6 +472,7 @@ typedef struct
     int slices;                             /* row-band slices per frame (H264E_set_slices), 0 / 1 = one */
     int frames_in;                          /* frames H264E_encode has taken since H264E_init */
     int denoise, den_started;               /* temporal denoiser on (H264E_set_denoise); its state has left zero */
+    int parent_all_skipped;                 /* row bands: what the reference's parent encoder holds in mb.skip_run == nmb (encode_frame) */
 } henc_t;
 
 /* The reference API has no destructor and callers simply free() the blob, so nothing that needs
@@ -717,7 +718,11 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
     }
     ref_sizes(&e->param, &sp, &ss);
     cap = (size_t)ss;
-    if (opt) e->run_param = *opt;
+    /* frame types outside this encode path (I, DROPPABLE, GOLDEN, RECOVERY, CUSTOM) are refused before anything moves: the stored run
+     * parameters included, so a later run_param == NULL repeats the last ACCEPTED call */
+    frame_type = (opt ? opt : &e->run_param)->frame_type;
+    if (frame_type != H264E_FRAME_TYPE_DEFAULT && frame_type != H264E_FRAME_TYPE_KEY && frame_type != H264E_FRAME_TYPE_P) return H264E_STATUS_BAD_FRAME_TYPE;
+    if (opt) e->run_param = *opt;                                                         /* h264-lab.h:6701-6705 */
     opt = &e->run_param;
     if (!e->run_param.qp_max || e->run_param.qp_max > 51) e->run_param.qp_max = 51;       /* h264-lab.h:6707-6715 */
     if (!e->run_param.qp_min || e->run_param.qp_min < 10) e->run_param.qp_min = 10;
@@ -729,7 +734,6 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
 
     frame_type = opt->frame_type;
     if (frame_type == H264E_FRAME_TYPE_DEFAULT) frame_type = e->frame_num ? H264E_FRAME_TYPE_P : H264E_FRAME_TYPE_KEY;
-    if (frame_type != H264E_FRAME_TYPE_KEY && frame_type != H264E_FRAME_TYPE_P) return H264E_STATUS_BAD_FRAME_TYPE;
     key = frame_type == H264E_FRAME_TYPE_KEY;
     if (key)
     {
@@ -762,11 +766,12 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
         task.denoised = 1;
     }
     e->frames_in++;
-    if (e->param.vbv_size_bytes && e->rc.vbv_bits - opt->desired_frame_bytes*8 > e->param.vbv_size_bytes*8)
+    if (e->param.vbv_size_bytes && !key && e->rc.vbv_bits - opt->desired_frame_bytes*8 > e->param.vbv_size_bytes*8)
     {
         /* h264-lab.h:6497-6510 "encode transparent frame on VBV overflow" -- reachable only right after H264E_set_vbv_state (rc_frame_end
-         * clamps the fullness to the VBV size): one slice whose whole payload is a skip run over the picture (written for key frames
-         * too), the reference picture as the reconstruction.  Nothing for the device to do: the pool's reference / reconstruction pair is
+         * clamps the fullness to the VBV size): one slice whose whole payload is a skip run over the picture, the reference picture as
+         * the reconstruction.  P frames only: h264-lab.h:6497 asks for !long_term_idx_use, which is -1 on a key frame (:6738), so a key
+         * frame is coded in full however far the VBV has overflowed.  Nothing for the device to do: the pool's reference / reconstruction pair is
          * simply not swapped, so the next frame predicts from the same picture; mv_clusters do not move (no macroblock was encoded). */
         uint8_t rb[32];
         hbits_t b;
@@ -807,7 +812,11 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
     }
     }
 
-    rc_frame_end(&e->rc, e->seq.nmb, e->param.vbv_size_bytes, opt->desired_frame_bytes, (int)out_pos, key, res.all_skipped);
+    /* h264-lab.h:6596 reads the PARENT encoder's mb.skip_run.  One slice: this frame's.  Row bands are coded by copies of the encoder
+     * (:6526-6560), so the parent keeps what it had: 0 at first, and nmb from a transparent frame on -- every later frame of a row-band
+     * stream then ends like an all-skipped one */
+    if (task.nslices == 1 || res.all_skipped) e->parent_all_skipped = res.all_skipped;
+    rc_frame_end(&e->rc, e->seq.nmb, e->param.vbv_size_bytes, opt->desired_frame_bytes, (int)out_pos, key, e->parent_all_skipped);
 
     if (!e->param.const_input_flag && in)
     {

@@ -52,6 +52,12 @@ int  h264o_encode(h264o_enc_t *e, const uint8_t *const yuv[3], const int stride[
 int  h264o_get_qp(const h264o_enc_t *e);        /* QP of the last encoded frame */
 /* H:6898-6913 H264E_set_vbv_state (vbv_fullness_bytes < 0: no change) */
 void h264o_set_vbv_state(h264o_enc_t *e, int vbv_size_bytes, int vbv_fullness_bytes);
+/* H:6701-6715 the run parameters of the NEXT h264o_encode: frame_type 0 DEFAULT / 2 P / 6 KEY (anything else: returns 3 and changes
+ * nothing), encode_speed, desired_frame_bytes (0 = no byte target), the QP window (repaired like the reference's);
+ * use_stored != 0 = a NULL run_param: the stored copy is used again and the other arguments are ignored */
+int  h264o_set_run_param(h264o_enc_t *e, int frame_type, int speed, int desired_frame_bytes, int qp_min, int qp_max, int use_stored);
+/* const_input_flag = 0: what the last frame left in the caller's planes -- the reconstruction, packed I420 width x height */
+void h264o_get_written_back(const h264o_enc_t *e, uint8_t *dst);
 void h264o_get_chain(const h264o_enc_t *e, h264o_chain_t *c);
 void h264o_set_chain(h264o_enc_t *e, const h264o_chain_t *c);
 /* copy of the last reconstructed (deblocked) frame, I420 w x h of the CODED size; returns coded w/h */

@@ -54,6 +54,8 @@ struct h264o_enc
     /* frame-level rate control (H:686-699) */
     struct { int vbv_bits, qp_smooth, dqp_smooth, max_dqp, bit_budget, vbv_target_level; } rc;
     int desired_frame_bytes, qp_min, qp_max;
+    int parent_all_skipped;                             /* row bands: the parent encoder's mb.skip_run == nmb (h264o_encode) */
+    int run_frame_type;                                 /* H:183 run_param.frame_type of the stored copy: 0 DEFAULT, 2 P, 6 KEY */
 };
 
 typedef struct
@@ -1166,6 +1168,34 @@ void h264o_set_vbv_state(h264o_enc_t *e, int vbv_size_bytes, int vbv_fullness_by
     }
 }
 
+/* H:6701-6715: the encoder keeps a copy of the run parameters (a NULL run_param reuses it) and repairs its QP window in place.
+ * Frame types other than DEFAULT / P / KEY are outside this restatement, as they are outside the product: status 3
+ * (H264E_STATUS_BAD_FRAME_TYPE) and the stored copy is left alone. */
+int h264o_set_run_param(h264o_enc_t *e, int frame_type, int speed, int desired_frame_bytes, int qp_min, int qp_max, int use_stored)
+{
+    if (use_stored) return 0;
+    if (frame_type != 0 && frame_type != 2 && frame_type != 6) return 3;
+    e->run_frame_type = frame_type;
+    e->speed = speed;
+    e->desired_frame_bytes = desired_frame_bytes;
+    e->qp_min = qp_min; e->qp_max = qp_max;
+    if (!e->qp_max || e->qp_max > 51) e->qp_max = 51;            /* H:6707-6715 */
+    if (!e->qp_min || e->qp_min < 10) e->qp_min = 10;
+    return 0;
+}
+
+/* what H264E_encode leaves in the caller's planes with const_input_flag = 0 (H:6719-6723: the reconstruction is built in place of
+ * the input; after a transparent frame it is a copy of the reference picture, H:6505-6508): packed I420 of the DISPLAY size */
+void h264o_get_written_back(const h264o_enc_t *e, uint8_t *dst)
+{
+    int c, y;
+    for (c = 0; c < 3; c++)
+    {
+        int w = e->par.width >> (c ? 1 : 0), h = e->par.height >> (c ? 1 : 0);
+        for (y = 0; y < h; y++, dst += w) memcpy(dst, e->ref[c] + (size_t)y*e->stride[c], (size_t)w);
+    }
+}
+
 const h264o_mbtrace_t *h264o_get_trace(const h264o_enc_t *e, int *nmb) { if (nmb) *nmb = e->nmb; return e->trace; }
 
 void h264o_get_recon(const h264o_enc_t *e, uint8_t *dst, int *cw, int *ch)
@@ -1184,13 +1214,15 @@ void h264o_get_recon(const h264o_enc_t *e, uint8_t *dst, int *cw, int *ch)
 /* H:6654-6861 H264E_encode + H:6477-6626 H264E_encode_one + H:6409-6461 encode_slice */
 int h264o_encode(h264o_enc_t *e, const uint8_t *const yuv[3], const int stride[3], uint8_t **out, int *out_bytes)
 {
-    int key = e->frame_num == 0, c, x, y;
+    /* H:6725-6730: DEFAULT takes the frame type from frame_num; an explicit KEY or P overrides it */
+    int key = e->run_frame_type ? e->run_frame_type == 6 : e->frame_num == 0, c, x, y;
+    if (!key && !e->pic_init_qp) return 3;                        /* H:6801-6804: a P frame before any key frame */
     for (c = 0; c < 3; c++) { e->in[c] = yuv[c]; e->in_stride[c] = stride[c]; }
     e->out_pos = 0;
     e->no_deblock = (e->speed == 8 || e->speed == 10);
     if (key)
     {
-        e->pic_init_qp = imax(imin(30, e->qp_max), e->qp_min);
+        e->pic_init_qp = imax(imin(30, e->qp_max), e->qp_min);    /* H:6768-6770: min with qp_max first, then max with qp_min */
         e->next_idr_pic_id ^= 1;
         e->frame_num = 0;
         write_sps(e);
@@ -1199,11 +1231,12 @@ int h264o_encode(h264o_enc_t *e, const uint8_t *const yuv[3], const int stride[3
     e->slice_type = key ? SLICE_I : SLICE_P;
     rc_frame_start(e, key);
 
-    if (e->par.vbv_size_bytes && e->rc.vbv_bits - e->desired_frame_bytes*8 > e->par.vbv_size_bytes*8)
+    if (e->par.vbv_size_bytes && !key && e->rc.vbv_bits - e->desired_frame_bytes*8 > e->par.vbv_size_bytes*8)
     {
         /* H:6497-6510 "encode transparent frame on VBV overflow" (reachable only right after H264E_set_vbv_state: rc_frame_end clamps
-         * the fullness to the VBV size): slice header, one skip run over the whole picture -- written for key frames too --, and the
-         * reference picture as the reconstruction */
+         * the fullness to the VBV size): slice header, one skip run over the whole picture, and the reference picture as the
+         * reconstruction.  P frames only: H:6497 asks for !long_term_idx_use, and a key frame has long_term_idx_use = -1 (H:6738), so
+         * a key frame is coded in full however far the VBV has overflowed */
         e->slice_start_row = e->slice_start_num = 0;
         write_slice_header(e, key);
         e->skip_run = e->nmb;
@@ -1212,6 +1245,7 @@ int h264o_encode(h264o_enc_t *e, const uint8_t *const yuv[3], const int stride[3
         for (c = 0; c < 3; c++)
             for (y = 0; y < (e->nmby*16 >> (c ? 1 : 0)); y++)
                 memcpy(e->dec[c] + (size_t)y*e->stride[c], e->ref[c] + (size_t)y*e->stride[c], (size_t)(e->nmbx*16 >> (c ? 1 : 0)));
+        e->parent_all_skipped = 1;
         rc_frame_end(e, key, 1);
     } else
     {
@@ -1241,7 +1275,10 @@ int h264o_encode(h264o_enc_t *e, const uint8_t *const yuv[3], const int stride[3
             row0 = row1;
         }
         e->slice_start_row = e->slice_start_num = 0;
-        rc_frame_end(e, key, nsl > 1 ? 0 : e->skip_run == e->nmb);      /* the parent's skip_run stays 0 in the threads build (H:6596) */
+        /* H:6596 reads the PARENT's skip_run, which the threads build's band copies never touch: it keeps what it had -- 0, or nmb
+         * from a transparent frame on (H:6502), and every later frame then ends like an all-skipped one */
+        if (nsl == 1) e->parent_all_skipped = e->skip_run == e->nmb;
+        rc_frame_end(e, key, e->parent_all_skipped);
     }
 
     for (c = 0; c < 3; c++)
@@ -1249,7 +1286,7 @@ int h264o_encode(h264o_enc_t *e, const uint8_t *const yuv[3], const int stride[3
         uint8_t *t = e->ref[c]; e->ref[c] = e->dec[c]; e->dec[c] = t;      /* H:3580-3596 */
         extend_borders(e->ref[c], e->w >> (c ? 1 : 0), e->h >> (c ? 1 : 0), e->stride[c], GUARD >> (c ? 1 : 0));
     }
-    if (++e->frame_num >= e->par.gop && e->par.gop) e->frame_num = 0;
+    if (++e->frame_num >= e->par.gop && e->par.gop && e->run_frame_type == 0) e->frame_num = 0;      /* H:6611: only a DEFAULT frame restarts the GOP */
     e->frames_done++;
     *out = e->out;
     *out_bytes = (int)e->out_pos;

@@ -17,6 +17,7 @@ CASES = {
     "cif_size_then_fullness": (352, 288, 40, 30, 500, [(10, 25000, -1), (20, 12500, 3000)]),
     "cif_level_changes_at_the_key_frame": (352, 288, 36, 12, 500, [(5, 500000, -1), (14, 500000, 20000), (30, 12500, 0)]),     # a larger VBV raises the SPS level at the next key frame
     "cif_overflow_transparent_frames": (352, 288, 24, 30, 300, [(6, 12500, 40000), (15, 6000, 30000)]),     # fullness far above the size: the reference codes transparent frames (h264-lab.h:6497-6510)
+    "qcif_overflow_on_key_frames": (176, 144, 30, 12, 200, [(0, 12500, 40000), (5, 12500, 40000), (12, 12500, 40000), (24, 6000, 30000)]),  # key frames 0, 12, 24 are coded in full (h264-lab.h:6497: !long_term_idx_use), the P frame 5 is transparent
     "qcif_no_vbv": (176, 144, 20, 30, 200, [(4, 0, -1), (12, 12500, 1000)]),                                 # vbv_size 0 switches the VBV terms of the controller off
 }
 

@@ -37,6 +37,9 @@ def lib():
         _lib.h264o_encode_clip.argtypes = [C.POINTER(Param), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
         _lib.h264o_set_vbv_state.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _lib.h264o_set_vbv_state.restype = None
+        _lib.h264o_set_run_param.argtypes = [C.c_void_p] + [C.c_int] * 6
+        _lib.h264o_get_written_back.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.h264o_get_written_back.restype = None
         _lib.h264o_get_chain.argtypes = [C.c_void_p, C.POINTER(Chain)]
         _lib.h264o_set_chain.argtypes = [C.c_void_p, C.POINTER(Chain)]
         _lib.h264o_get_recon.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -159,3 +159,34 @@ def test_oracle_set_vbv_state_matches_reference(name):
     o = oracle_lib.Encoder(g["w"], g["h"], gop=g["gop"], kbps=g["kbps"])
     _run_vbv_case(o, g)
     o.close()
+
+
+import run_param_cases
+
+RUN_PARAMS = run_param_cases.load()
+API_HARNESS = os.path.join(oracle_lib.ROOT, "oracle", "_ref", "api_harness")
+
+
+def test_run_param_fixture_contains_what_it_is_for():
+    """tests/golden/run_params.json, as committed: a transparent P frame, an overflow event on each kind of key frame that the
+    reference coded in full, a frame_num wrap, key frames on both sides of QP 30, refused calls (one in front of a NULL run_param), a NULL
+    call after a stored KEY"""
+    run_param_cases.check_coverage(RUN_PARAMS)
+    assert sum(1 for c in RUN_PARAMS.values() if c["create"][0] == 1920) == 2
+    assert {c["create"][6] for c in RUN_PARAMS.values()} >= {1, 2, 3} and any(c["create"][5] for c in RUN_PARAMS.values())
+
+
+@pytest.mark.parametrize("name", sorted(RUN_PARAMS))
+def test_oracle_per_frame_run_params_match_reference(tmp_path, name):
+    """the oracle's restatement of how H264E_encode reads its run parameters per frame (h264-lab.h:6701-6775, :6497, :6611): sizes, bytes
+    and written-back reconstruction of every frame against the reference's own answers -- and, where oracle/_ref is built, against
+    the binary itself on the same script"""
+    case = RUN_PARAMS[name]
+    got = run_param_cases.replay_oracle(case)
+    run_param_cases.compare(case, got, "oracle, " + name)
+    harness = API_HARNESS + ("_thr" if case["create"][6] > 1 else "")
+    if os.path.exists(harness):
+        script, out = tmp_path / "script.txt", tmp_path / "o.264"
+        script.write_text(run_param_cases.script_text(case))
+        subprocess.run([harness, str(script), str(out)], check=True, capture_output=True)
+        assert b"".join(d for _, d, _ in got) == out.read_bytes()
