@@ -57,6 +57,7 @@ class DevFrame(C.Structure):  # H264E_dev_frame_t: a frame in device memory (che
 
 
 DEV_FORMAT_I420, DEV_FORMAT_NV12, DEV_FORMAT_RGB = 0, 1, 2
+H264E_SCENECUT_DEFAULT = 128        # include/h264e_mi355x.h
 _DEV_FORMATS = {"i420": DEV_FORMAT_I420, "nv12": DEV_FORMAT_NV12, "rgb": DEV_FORMAT_RGB}
 
 
@@ -228,6 +229,12 @@ def load(path=None):
     L.H264E_clip_set_ssd_output.argtypes = [C.c_void_p, C.c_void_p]
     L.H264E_clip_set_ssd_output.restype = None
     L.H264E_clip_set_denoise.argtypes = [C.c_void_p, C.c_int]
+    L.H264E_clip_set_key_frames.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
+    L.H264E_clip_set_scenecut.argtypes = [C.c_void_p, C.c_int]
+    L.H264E_clip_read_scenecut.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.H264E_clip_scenecut_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
+    L.H264E_clip_position.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.H264E_clip_position.restype = None
     L.H264E_clip_revalidate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.H264E_clip_restart.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     L.H264E_clip_close.argtypes = [C.c_void_p]
@@ -339,24 +346,55 @@ class ClipEncoder:
     """Whole-clip streaming encode on one GPU (H264E_clip_* extension): consecutive frames as a temporal wavefront."""
 
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
-                 clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False):
+                 clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
         self.par = ClipParam(width, height, gop, qp, speed, 100000 // 8, device, max_chains, idr_state, (C.c_int32 * 2)(*clusters_in), slices, kbps, resident, keep_records)
         self.c = C.c_void_p()
         if self.L.H264E_clip_open(C.byref(self.c), C.byref(self.par), nframes):
             raise _err(self.L, "H264E_clip_open")
-        if denoise:
-            try:
+        try:
+            if denoise:
                 self.set_denoise(True)
-            except H264EError:
-                self.close()
-                raise
+            if key_frames:
+                self.set_key_frames(key_frames)
+            if scenecut:
+                self.set_scenecut(scenecut)
+        except H264EError:
+            self.close()
+            raise
 
     def set_denoise(self, on):
         """The temporal denoiser (H264E_clip_set_denoise): only while the clip stands at frame 0."""
         if self.L.H264E_clip_set_denoise(self.c, int(bool(on))):
             raise _err(self.L, "H264E_clip_set_denoise")
+
+    def set_key_frames(self, frames):
+        """Key frames in addition to the periodic ones (H264E_clip_set_key_frames): an ascending list of frame numbers, [] clears it;
+        only while the clip stands at frame 0."""
+        frames = [int(f) for f in frames]
+        if self.L.H264E_clip_set_key_frames(self.c, (C.c_int * max(len(frames), 1))(*frames), len(frames)):
+            raise _err(self.L, "H264E_clip_set_key_frames")
+
+    def set_scenecut(self, threshold=H264E_SCENECUT_DEFAULT):
+        """Scene-cut detection (H264E_clip_set_scenecut): threshold in 1/1024 of the picture, 0 = off; only while the clip stands at frame 0."""
+        if self.L.H264E_clip_set_scenecut(self.c, int(threshold)):
+            raise _err(self.L, "H264E_clip_set_scenecut")
+
+    def read_scenecut(self):
+        """(dist, is_cut) of the frames encoded so far: D(f) as int32, and whether the detector made f a key frame, as bool"""
+        nxt = C.c_int()
+        self.L.H264E_clip_position(self.c, C.byref(nxt), None)
+        dist, cut = np.zeros(nxt.value, np.int32), np.zeros(nxt.value, np.uint8)
+        if self.L.H264E_clip_read_scenecut(self.c, 0, nxt.value, dist.ctypes.data, cut.ctypes.data):
+            raise _err(self.L, "H264E_clip_read_scenecut")
+        return dist, cut.astype(bool)
+
+    def scenecut_time(self):
+        """(HIP-event milliseconds inside the detector's kernel launches since open, frames they analysed)"""
+        ms, n = C.c_double(), C.c_longlong()
+        self.L.H264E_clip_scenecut_time(self.c, C.byref(ms), C.byref(n))
+        return ms.value, n.value
 
     def upload(self, clip, first=0):
         clip = np.ascontiguousarray(clip, dtype=np.uint8)

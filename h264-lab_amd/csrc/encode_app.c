@@ -18,6 +18,10 @@
  * (H264E_clip_*: consecutive frames as a temporal wavefront on the GPU, same bitstream, bounded host memory whatever the file size;
  * --kbps, --threads, --psnr, --stats work there too), --clip 0 runs the reference's own loop over H264E_encode, one frame per call; --chains N bounds the frames in flight per launch; --gpus N cuts the file into N
  * GOP-aligned blocks, one clip encoder per block and GPU, with the mv_clusters state handed over and validated at every boundary.
+ * --keyframes f1,f2,... codes the listed frames (ascending) as key frames in addition to the periodic ones (H264E_clip_set_key_frames);
+ * --scenecut N switches the scene-cut detector on with threshold N (H264E_clip_set_scenecut; a value that is not a positive number, as in
+ * `--scenecut x`, selects H264E_SCENECUT_DEFAULT) and adds ONE stdout line, "scene cuts: f1 f2 ..." or "scene cuts: none".  Both belong
+ * to the clip path: with --clip 0, with --gpus stream sharding or on an input that is not seekable they end the run (error line, exit 1).
  */
 #define _FILE_OFFSET_BITS 64
 #include <math.h>
@@ -31,6 +35,7 @@ static struct
     char input_file[1024], output_file[1024], recon_file[1024];
     int have_input, have_output;
     int gop, qp, kbps, max_frames, speed, stats, psnr, device, clip, chains, threads, gpus;
+    int scenecut, nkey, key_frames[1024];   /* --scenecut threshold (0 = off), --keyframes list */
     int unsupported;                    /* a reference option this encoder refuses was given: no stream is written, exit 1 */
 } cmd;
 
@@ -47,6 +52,25 @@ static void parse_long(const char *p, const char *val)
                starts("gen", p) ? "libm-generated synthetic input" : "temporal denoiser");
         cmd.unsupported = 1;
     }
+    else if (starts("keyframes", p))
+    {
+        const char *q = v;
+        cmd.nkey = 0;
+        while (*q)
+        {
+            char *end;
+            const long f = strtol(q, &end, 10);
+            if (end == q || (*end && *end != ',') || cmd.nkey >= (int)(sizeof(cmd.key_frames)/sizeof(cmd.key_frames[0])))
+            {
+                printf("ERROR: --keyframes takes a comma-separated list of frame numbers, got %s\n", v);
+                cmd.unsupported = 1;
+                break;
+            }
+            cmd.key_frames[cmd.nkey++] = (int)f;
+            q = *end ? end + 1 : end;
+        }
+    }
+    else if (starts("scenecut", p)) cmd.scenecut = atoi(v) > 0 ? atoi(v) : H264E_SCENECUT_DEFAULT;
     else if (starts("gop", p)) cmd.gop = atoi(v);
     else if (starts("qp", p)) cmd.qp = atoi(v);
     else if (starts("kbps", p)) cmd.kbps = atoi(v);
@@ -97,7 +121,8 @@ static int read_cmdline(int argc, char **argv)
                "    4sif cif sif pal ntsc d1 16cif 16sif 720p 4SVGA 4XGA 16VGA 16VGA\n"
                "Options (every --option takes a value):\n"
                "    --input,  -i <f>  --output, -o <f>  --gop <n>  --qp <n>  --kbps <n>  --maxframes <n>\n"
-               "    --speed <n>  --threads <n>  --stats x  --psnr x  --device <n>  --clip 0|1  --chains <n>  --gpus <n>\n");
+               "    --speed <n>  --threads <n>  --stats x  --psnr x  --device <n>  --clip 0|1  --chains <n>  --gpus <n>\n"
+               "    --keyframes f1,f2,...  --scenecut <threshold|x>   (clip path only)\n");
         return 0;
     }
     return 1;
@@ -424,6 +449,8 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
         s->par.first_idr_pic_id_state = g0 & 1;         /* idr_pic_id toggles with every key frame (h264-lab.h:6774) */
         s->par.keep_records = nsh > 1;
         if (shard_open(s)) goto out;
+        if (cmd.nkey && H264E_clip_set_key_frames(s->clip, cmd.key_frames, cmd.nkey)) { printf("ERROR: --keyframes: %s\n", H264E_last_error()); goto out; }
+        if (cmd.scenecut && H264E_clip_set_scenecut(s->clip, cmd.scenecut)) { printf("ERROR: --scenecut: %s\n", H264E_last_error()); goto out; }
         g0 = g1;
     }
     if (nsh == 1) sh[0].rc = shard_encode_from(sh, 0);
@@ -471,6 +498,16 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
         }
     }
     if (cmd.psnr) psnr_print();
+    if (cmd.scenecut)
+    {
+        uint8_t *cut = (uint8_t *)calloc((size_t)n, 1);
+        int any = 0;
+        if (!cut || H264E_clip_read_scenecut(sh[0].clip, 0, n, NULL, cut)) { printf("ERROR: %s\n", cut ? H264E_last_error() : "not enough memory"); free(cut); goto out; }
+        printf("scene cuts:");
+        for (f = 0; f < n; f++) if (cut[f]) { printf(" %d", f); any = 1; }
+        printf(any ? "\n" : " none\n");
+        free(cut);
+    }
     for (k = 0; k < nsh; k++)
         fprintf(stderr, "clip%s: %d frames%s, %d in flight per launch, %d launches (%d after a mis-speculated mv_clusters state), encode %.1f ms, input ring %d frames, staging 2 x %d frames%s\n",
                 nsh > 1 ? " shard" : "", sh[k].nframes, nsh > 1 ? " on its GPU" : "", sh[k].chains, sh[k].rounds, sh[k].relaunches, sh[k].enc_ms,
@@ -500,6 +537,11 @@ int main(int argc, char **argv)
     int w = 352, h = 288, i, frames = 0, frame_size, sizeof_persist = 0, sizeof_scratch = 0, error, sizeof_coded_data;
 
     if (!read_cmdline(argc, argv)) return 1;
+    if ((cmd.nkey || cmd.scenecut) && (cmd.gpus > 1 || cmd.clip == 0 || !cmd.max_frames))
+    {
+        printf("ERROR: --keyframes / --scenecut belong to the clip path: not with %s\n", cmd.gpus > 1 ? "--gpus stream sharding" : "--clip 0 (or --maxframes 0)");
+        return 1;
+    }
     guess_format(cmd.input_file, &w, &h);
     fin = fopen(cmd.input_file, "rb");
     if (!fin) { printf("ERROR: cant open input file %s\n", cmd.input_file); return 1; }
@@ -535,6 +577,7 @@ int main(int argc, char **argv)
             return r;
         }
         if (cmd.gpus > 1) { printf("ERROR: --gpus needs a seekable input file\n"); return 1; }
+        if (cmd.nkey || cmd.scenecut) { printf("ERROR: --keyframes / --scenecut need a seekable input file (the clip path)\n"); return 1; }
         clearerr(fin);
     }
 

@@ -872,7 +872,7 @@ struct H264E_clip_tag
 {
     H264E_clip_param_t par;
     seq_t seq;
-    int nframes, gop_len, ring;
+    int nframes, ring;
     int resident;                           /* input frames kept in HBM (ring): frame f lives in slot f % resident */
     h264e_hip_pool_t *pool;
     /* ---- stream state, kept across H264E_clip_encode calls */
@@ -906,7 +906,51 @@ struct H264E_clip_tag
     /* temporal denoiser (H264E_clip_set_denoise): frames [0, den_done) have been denoised; the denoised picture of frame f lives in the
      * pool's denoised slot f % resident, the one of den_done - 1 is the state in front of frame den_done */
     int denoise, den_done;
+    /* The key-frame schedule: what H264E_encode would make of frame f when it is handed H264E_FRAME_TYPE_KEY on the frames of the
+     * explicit list (H264E_clip_set_key_frames) and on the detected scene cuts, and H264E_FRAME_TYPE_DEFAULT on all others
+     * (h264-lab.h:6725-6775, :6611-6614).  [nframes + 1]; built by clip_sched_build, the ONLY place that knows the rule; everything
+     * that needs a frame's kind, frame_num or idr_pic_id reads it here. */
+    struct clip_sched { uint8_t key, idr; int frame_num; } *sched;      /* idr: parity of the key frames up to and including this one */
+    int *forced, nforced;                   /* the explicit list, ascending */
+    int all_key;                            /* every frame is a key frame (launches as long as memory allows: nothing to mis-speculate) */
+    /* scene-cut detection (H264E_clip_set_scenecut, enc_scenecut.h): frames [0, sc_done) have their luma histogram on the host; re-uploading
+     * frame f makes f onward stale, a rewind keeps them.  The arrays exist once the detector has been switched on. */
+    int scenecut, sc_done;                  /* threshold (0 = off) */
+    uint32_t *sc_hist;                      /* [nframes][64] */
+    int *sc_dist; uint8_t *sc_cut;          /* [nframes] D(f); f was made a key frame by the detector */
+    double sc_kernel_ms; long long sc_frames;   /* HIP-event time of the detector's launches and the frames they analysed, since open */
 };
+
+/* The schedule rule, once.  frame_num restarts at every key frame, and so does the periodic counter: the next periodic key frame
+ * comes `gop` frames after the last key frame of either kind.  The wrap of the counter (h264-lab.h:6611) happens only on a DEFAULT
+ * call: with gop = 1 the frame behind a forced key frame is a P frame.  A detected cut is a forced key frame on a frame that would
+ * not be one anyway. */
+static void clip_sched_build(H264E_clip_t *c)
+{
+    const int gop = c->par.gop;
+    int f, k = 0, fn = 0, parity = 0, all = 1;
+    for (f = 0; f <= c->nframes; f++)
+    {
+        int forced, key;
+        while (k < c->nforced && c->forced[k] < f) k++;
+        forced = k < c->nforced && c->forced[k] == f;
+        if (c->sc_cut && f < c->nframes)
+        {
+            c->sc_cut[f] = (uint8_t)(!forced && fn && c->scenecut && f < c->sc_done && c->sc_dist[f] > c->scenecut);
+            forced |= c->sc_cut[f];
+        }
+        key = forced || fn == 0;
+        if (key) { fn = 0; parity ^= 1; }
+        c->sched[f].key = (uint8_t)key; c->sched[f].idr = (uint8_t)parity; c->sched[f].frame_num = fn;
+        if (f < c->nframes) all &= key;
+        if (++fn >= gop && gop && !forced) fn = 0;
+    }
+    c->all_key = all;
+}
+
+/* frames per launch at frame 0: optimistic where mis-speculations are rare by construction (row bands restart the state, intra frames
+ * do not read it): as long as memory allows; else the pipeline depth, growing with every clean launch */
+static void clip_launch_frames_reset(H264E_clip_t *c) { c->launch_frames = (c->par.slices > 1 || c->all_key) ? c->ring - 1 : c->launch_base; }
 
 /* the HBM budget of the slot ring and what one slot takes: two pictures, records, row bit buffers (2 KB per macroblock), arenas */
 #define CLIP_DEV_BUDGET (24.0*1073741824.0)
@@ -933,9 +977,7 @@ void H264E_clip_rewind(H264E_clip_t *c)
      * pictures already fill the GPU's resident workgroups with the wide geometry: the narrow one only pays below ~12k macroblocks */
     c->narrow_ok = c->narrow = (getenv("H264E_WIDE_WINDOW") || c->seq.nmb > 12000) ? 0 : 1;
     c->wide_until = 0; c->wide_hold = 30; c->far_acc = 0; c->far_frames = 0;
-    /* optimistic where mis-speculations are rare by construction (row bands restart the state, intra frames do not read it): as long
-     * as memory allows; else the pipeline depth, growing with every clean launch */
-    c->launch_frames = (c->par.slices > 1 || c->gop_len == 1) ? c->ring - 1 : c->launch_base;
+    clip_launch_frames_reset(c);
     memset(&c->rcs, 0, sizeof(c->rcs));
     c->rc_frame = -1; c->rc_qp = c->par.qp; c->rc_last_bytes[0] = c->rc_last_bytes[1] = 0;
 }
@@ -954,7 +996,6 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     c->par.qp = imin(imax(par->qp, 10), 51);
     seq_init(&c->seq, par->width, par->height, par->vbv_size_bytes, 0);
     c->nframes = nframes;
-    c->gop_len = par->gop ? par->gop : (1 << 30);
     /* ring of picture / result slots = frames per launch + 1.  Not bounded by residency: workgroups only wait for lower
      * block indices, so a launch larger than the GPU simply streams through it in order. */
     /* default: 96 frames per launch at 1080p and above; small pictures have short pipelines and cheap slots, so they get
@@ -991,14 +1032,16 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     c->traj = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)c->seq.nmb);
     c->tasks = (h264e_hip_task_t *)calloc((size_t)c->ring, sizeof(*c->tasks));
     c->used = (int32_t (*)[2])calloc((size_t)c->ring, sizeof(int32_t[2]));
-    if (!c->traj || !c->tasks || !c->used) { free(c->traj); free(c->tasks); free(c->used); free(c); return -1; }
+    c->sched = (struct clip_sched *)calloc((size_t)nframes + 1, sizeof(*c->sched));
+    if (!c->traj || !c->tasks || !c->used || !c->sched) { free(c->traj); free(c->tasks); free(c->used); free(c->sched); free(c); return -1; }
+    clip_sched_build(c);
     /* the ring is sized for speed, not for need: when the device (or the pinned host memory) cannot spare that much, halve it down
      * to the pipeline depth before giving up */
     while (h264e_hip_pool_create(&c->pool, par->device, par->width, par->height, c->ring, c->resident))
     {
         if (c->ring <= c->launch_base + 1 || par->max_chains > 0)
         {
-            free(c->traj); free(c->tasks); free(c->used); free(c);
+            free(c->traj); free(c->tasks); free(c->used); free(c->sched); free(c);
             return -1;
         }
         c->ring = imax(c->launch_base + 1, c->ring/2);
@@ -1022,6 +1065,7 @@ void H264E_clip_close(H264E_clip_t *c)
     if (c->rec_store) { int f; for (f = 0; f < c->nframes; f++) { free(c->rec_store[f]); if (c->permb_store) free(c->permb_store[f]); } }
     free(c->rec_store); free(c->used_store); free(c->permb_store);
     free(c->traj); free(c->tasks); free(c->used); free(c->big);
+    free(c->sched); free(c->forced); free(c->sc_hist); free(c->sc_dist); free(c->sc_cut);
     free(c);
 }
 
@@ -1058,6 +1102,7 @@ static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int 
     if (async) { if (first + n > c->pending_avail) c->pending_avail = first + n; }
     else if (first + n > c->avail) c->avail = first + n;
     if (first < c->den_done) c->den_done = first;       /* new inputs: their denoised pictures (and all behind them) are made again */
+    if (first < c->sc_done) c->sc_done = first;         /* ... and their histograms */
     return 0;
 }
 
@@ -1082,6 +1127,7 @@ int H264E_clip_upload_device(H264E_clip_t *c, int first, int nframes, const H264
     if (h264e_hip_upload_wait(c->pool) || rc) return -1;        /* (after a failure too: what was launched has read its source) */
     if (first + nframes > c->avail) c->avail = first + nframes;
     if (first < c->den_done) c->den_done = first;
+    if (first < c->sc_done) c->sc_done = first;
     return 0;
 }
 
@@ -1126,6 +1172,7 @@ int H264E_clip_generate_synth(H264E_clip_t *c, int first, int nframes, int t0, u
     }
     if (first + nframes > c->avail) c->avail = first + nframes;
     if (first < c->den_done) c->den_done = first;
+    if (first < c->sc_done) c->sc_done = first;
     return h264e_hip_sync(c->pool);
 }
 
@@ -1170,11 +1217,12 @@ int H264E_clip_revalidate(H264E_clip_t *c, const int32_t exact_in[2], int *resta
     *restart_frame = -1;
     for (f = 0; f < c->next; f++)
     {
-        if (f % c->gop_len == 0) { gop_state[0] = s[0]; gop_state[1] = s[1]; }
+        if (c->sched[f].key) { gop_state[0] = s[0]; gop_state[1] = s[1]; }
         if (!c->rec_store[f]) return -1;
         if (clusters_walk(s, c->rec_store[f], c->seq.nmbx, c->seq.nmby, nslices, c->permb_store[f] ? c->permb_store[f] : c->used_store[f], c->permb_store[f] != NULL, NULL) >= 0)
         {
-            *restart_frame = f - f % c->gop_len;
+            while (!c->sched[f].key) f--;
+            *restart_frame = f;
             if (restart_state) { restart_state[0] = gop_state[0]; restart_state[1] = gop_state[1]; }
             return 0;
         }
@@ -1198,7 +1246,7 @@ int H264E_clip_read_records(H264E_clip_t *c, int frame, void *dst /* nmb x 8 byt
  * next H264E_clip_encode calls (their inputs must be resident / uploaded again) */
 int H264E_clip_restart(H264E_clip_t *c, int frame, const int32_t state[2])
 {
-    if (!c || !state || frame < 0 || frame > c->avail || frame % c->gop_len) return -1;
+    if (!c || !state || frame < 0 || frame > c->avail || frame > c->nframes || !c->sched[frame].key) return -1;
     if (c->denoise && frame) { snprintf(g_host_err, sizeof(g_host_err), "restart: a denoised stream restarts at frame 0 only"); return -1; }
     c->next = frame;
     if (c->resident < c->nframes) c->avail = c->pending_avail = frame;      /* a ring: the inputs from here on have to be uploaded again */
@@ -1237,11 +1285,112 @@ int H264E_clip_set_denoise(H264E_clip_t *c, int on)
     return 0;
 }
 
+/* The key-frame schedule of the clip: frames[0..n) become key frames in addition to the periodic ones, exactly as
+ * H264E_FRAME_TYPE_KEY on those frames does in H264E_encode.  While the clip stands at frame 0; kept across a rewind; n = 0 clears
+ * the list.  Refused with keep_records: GOP shards (H264E_clip_revalidate / _restart) assume fixed GOP blocks. */
+int H264E_clip_set_key_frames(H264E_clip_t *c, const int *frames, int n)
+{
+    int *copy = NULL, i;
+    g_host_err[0] = 0;
+    if (!c || n < 0 || (n && !frames)) { snprintf(g_host_err, sizeof(g_host_err), "set_key_frames: bad argument"); return -1; }
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_key_frames: only at frame 0 (after open or rewind)"); return -1; }
+    if (c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_key_frames: not with keep_records (GOP shards assume fixed GOP blocks)"); return -1; }
+    for (i = 0; i < n; i++)
+    {
+        if (frames[i] < 0 || frames[i] >= c->nframes) { snprintf(g_host_err, sizeof(g_host_err), "set_key_frames: frame %d is outside the clip (%d frames)", frames[i], c->nframes); return -1; }
+        if (i && frames[i] <= frames[i - 1]) { snprintf(g_host_err, sizeof(g_host_err), "set_key_frames: the list must be ascending (%d after %d)", frames[i], frames[i - 1]); return -1; }
+    }
+    if (n)
+    {
+        copy = (int *)malloc(sizeof(int)*(size_t)n);
+        if (!copy) { snprintf(g_host_err, sizeof(g_host_err), "out of host memory"); return -1; }
+        memcpy(copy, frames, sizeof(int)*(size_t)n);
+    }
+    free(c->forced);
+    c->forced = copy; c->nforced = n;
+    clip_sched_build(c);
+    clip_launch_frames_reset(c);
+    return 0;
+}
+
+/* Scene-cut detection (enc_scenecut.h): threshold in 1/1024 of the picture, 0 = off.  While the clip stands at frame 0; refused with
+ * keep_records like the explicit list.  Histograms that were made before stay valid: only the cuts are decided again. */
+int H264E_clip_set_scenecut(H264E_clip_t *c, int threshold)
+{
+    g_host_err[0] = 0;
+    if (!c || threshold < 0) { snprintf(g_host_err, sizeof(g_host_err), "set_scenecut: bad argument"); return -1; }
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_scenecut: only at frame 0 (after open or rewind)"); return -1; }
+    if (threshold && c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_scenecut: not with keep_records (GOP shards assume fixed GOP blocks)"); return -1; }
+    if (threshold && !c->sc_hist)
+    {
+        c->sc_hist = (uint32_t *)calloc((size_t)c->nframes*64, sizeof(uint32_t));
+        c->sc_dist = (int *)calloc((size_t)c->nframes, sizeof(int));
+        c->sc_cut = (uint8_t *)calloc((size_t)c->nframes, 1);
+        c->sc_done = 0;
+        if (!c->sc_hist || !c->sc_dist || !c->sc_cut)
+        {
+            free(c->sc_hist); free(c->sc_dist); free(c->sc_cut);
+            c->sc_hist = NULL; c->sc_dist = NULL; c->sc_cut = NULL;
+            snprintf(g_host_err, sizeof(g_host_err), "out of host memory");
+            return -1;
+        }
+    }
+    c->scenecut = threshold;
+    clip_sched_build(c);
+    clip_launch_frames_reset(c);
+    return 0;
+}
+
+int H264E_clip_read_scenecut(H264E_clip_t *c, int first, int n, int *dist, uint8_t *is_cut)
+{
+    int i;
+    g_host_err[0] = 0;
+    if (!c || !c->sc_dist) { snprintf(g_host_err, sizeof(g_host_err), "read_scenecut: the detector has not been switched on"); return -1; }
+    if (first < 0 || n < 0 || first + n > c->sc_done) { snprintf(g_host_err, sizeof(g_host_err), "read_scenecut: frames %d..%d have not been analysed (%d have)", first, first + n - 1, c->sc_done); return -1; }
+    for (i = 0; i < n; i++)
+    {
+        if (dist) dist[i] = c->sc_dist[first + i];
+        if (is_cut) is_cut[i] = c->sc_cut[first + i];
+    }
+    return 0;
+}
+
+/* diagnostic (tools/scenecut_probe.py): HIP-event time of the detector's kernel launches since open, and the frames they analysed */
+int H264E_clip_scenecut_time(H264E_clip_t *c, double *kernel_ms, long long *frames)
+{
+    if (!c) return -1;
+    if (kernel_ms) *kernel_ms = c->sc_kernel_ms;
+    if (frames) *frames = c->sc_frames;
+    return 0;
+}
+
+/* the detector's pre-pass: the histograms of the frames uploaded so far and not yet analysed, read back, D(f) from consecutive
+ * records, and the schedule with the cuts among them -- all before the tasks of the launch that first encodes them are built */
+static int clip_scenecut_analyse(H264E_clip_t *c, int limit)
+{
+    const int a = c->sc_done;
+    float ms = 0;
+    int f, b;
+    if (limit - a > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "scenecut: frames %d..%d do not fit the input ring", a, limit - 1); return -1; }
+    if (h264e_hip_scenecut_frames(c->pool, a % c->resident, limit - a, c->sc_hist + (size_t)a*64, &ms)) return -1;
+    for (f = a; f < limit; f++)
+    {
+        const uint32_t *h = c->sc_hist + (size_t)f*64;
+        uint64_t sum = 0;
+        for (b = 0; f && b < 64; b++) sum += h[b] > h[b - 64] ? h[b] - h[b - 64] : h[b - 64] - h[b];
+        c->sc_dist[f] = (int)(sum*1024u/(2u*(uint64_t)c->seq.width*(uint64_t)c->seq.height));
+    }
+    c->sc_kernel_ms += ms; c->sc_frames += limit - a;
+    c->sc_done = limit;
+    clip_sched_build(c);
+    return 0;
+}
+
 int H264E_clip_stamps(H264E_clip_t *c, unsigned long long *dst) { return c ? h264e_hip_stamps_read(c->pool, dst, 1) : -1; }
 
 int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_bytes, int *frame_bytes, int profile, H264E_clip_stats_t *st)
 {
-    const int nmb = c->seq.nmb, G = c->gop_len, K = c->ring, no_deblock = (c->par.speed == 8 || c->par.speed == 10);
+    const int nmb = c->seq.nmb, K = c->ring, no_deblock = (c->par.speed == 8 || c->par.speed == 10);
     const int nslices = c->par.slices > 1 ? imin(imin(c->par.slices, H264E_HIP_MAX_SLICES), c->seq.nmby) : 1;
     /* frame-level rate control (encode_app --kbps, minih264e_test.c:596-600: desired_frame_bytes = kbps*1000/8/30, QP 10..50):
      * a frame's QP is a function of the byte count of the frame before it (h264-lab.h:5924-6141) and moves almost every
@@ -1280,26 +1429,29 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         int qp_task[8];
         rc_t rc_ahead;
         int nvalid = 0;
+        const struct clip_sched *sched = c->sched;
         t0 = now_ms();
+        /* scene cuts among the frames this launch may hold are in the schedule before its tasks are built */
+        if (c->scenecut && c->sc_done < limit && clip_scenecut_analyse(c, limit)) goto done;
         memset(tasks, 0, sizeof(*tasks)*(size_t)K);
         if (rc_on) qp = c->rc_qp;               /* (the task loop of the previous launch left a speculated value here) */
         if (rc_on && c->rc_frame != n)
         {
-            const int key = (n % G) == 0;
+            const int key = sched[n].key;
             qp = c->rc_qp = rc_frame_start(&c->rcs, c->par.gop, nmb, c->par.vbv_size_bytes, desired_frame_bytes, qp_min, qp_max, key);
             build_qdat(key ? qdat_i : qdat_p, qp, !key);
             c->rc_frame = n;
         } else if (rc_on)
-            build_qdat((n % G) == 0 ? qdat_i : qdat_p, qp, (n % G) != 0);
+            build_qdat(sched[n].key ? qdat_i : qdat_p, qp, !sched[n].key);
         rc_ahead = c->rcs;
         for (i = 0; i < F; i++)
         {
             h264e_hip_task_t *t = tasks + i;
-            const int f = n + i, key = (f % G) == 0;
+            const int f = n + i, key = sched[f].key;
             if (rc_on && i > 0)
             {
                 /* the controller, run ahead: the frame in front is predicted to weigh what the last frame of its kind did */
-                const int pkey = ((f - 1) % G) == 0, pred = c->rc_last_bytes[pkey] > 0 ? c->rc_last_bytes[pkey] : desired_frame_bytes;
+                const int pkey = sched[f - 1].key, pred = c->rc_last_bytes[pkey] > 0 ? c->rc_last_bytes[pkey] : desired_frame_bytes;
                 rc_frame_end(&rc_ahead, nmb, c->par.vbv_size_bytes, desired_frame_bytes, pred, pkey, 0);
                 qp = rc_frame_start(&rc_ahead, c->par.gop, nmb, c->par.vbv_size_bytes, desired_frame_bytes, qp_min, qp_max, key);
                 build_qdat(key ? qdat_i : qdat_p, qp, !key);
@@ -1310,7 +1462,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
             t->qp = qp; t->speed = c->par.speed;
             /* frame_num restarts at every key frame; idr_pic_id toggles with every key frame (h264-lab.h:6774-6775) */
             t->nslices = nslices;
-            slice_header_bits(&c->seq, key, f % G, (idr_state ^ ((f/G + 1) & 1)), qp, pic_init_qp, no_deblock, nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
+            slice_header_bits(&c->seq, key, sched[f].frame_num, idr_state ^ sched[f].idr, qp, pic_init_qp, no_deblock, nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
             memcpy(t->qdat, key ? qdat_i : qdat_p, sizeof(t->qdat));
             t->stream_mode = 1; t->slot = f % K;
             t->ref_slot = key ? -1 : (f - 1) % K;
@@ -1341,7 +1493,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
             for (k = 1; k < F; k++)
                 for (a = 0; a < rc_hedge; a++)
                 {
-                    const int q = qp_task[k & 7] + dq[a], f = n + k, key = (f % G) == 0, j = F + nh;
+                    const int q = qp_task[k & 7] + dq[a], f = n + k, key = sched[f].key, j = F + nh;
                     h264e_hip_task_t *t = tasks + j;
                     uint16_t qd[2][42];
                     if (q < qp_min || q > qp_max || nh >= 32 || j + 2 >= K) continue;
@@ -1349,7 +1501,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
                     build_qdat(qd, q, !key);
                     t->qp = q;
                     memcpy(t->qdat, qd, sizeof(t->qdat));
-                    slice_header_bits(&c->seq, key, f % G, (idr_state ^ ((f/G + 1) & 1)), q, pic_init_qp, no_deblock, nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
+                    slice_header_bits(&c->seq, key, sched[f].frame_num, idr_state ^ sched[f].idr, q, pic_init_qp, no_deblock, nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
                     t->slot = (n + j) % K;              /* a slot no frame of this launch owns */
                     t->walk_parent = k;                 /* = index of the chain's frame in front of it, + 1 */
                     t->walk_quiet = 1;                  /* its own validation failing stops nobody else */
@@ -1378,7 +1530,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         for (i = 0; i < F || take >= 0; i++)
         {
             const int is_hedge = take >= 0, ti = is_hedge ? take : i;
-            const int f = is_hedge ? n + hedge_level[take - F] : n + i, key = (f % G) == 0, slot = tasks[ti].slot, per_mb = (ti == 0 && c->first_dev);
+            const int f = is_hedge ? n + hedge_level[take - F] : n + i, key = sched[f].key, slot = tasks[ti].slot, per_mb = (ti == 0 && c->first_dev);
             h264e_hip_result_t r1;
             int dn, idle = 0;
             int32_t cc[2];
@@ -1463,10 +1615,12 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
                 {
                     rc_frame_end(&c->rcs, nmb, c->par.vbv_size_bytes, desired_frame_bytes, (int)(pos - start), key, r1.all_skipped);
                     c->rc_last_bytes[key] = (int)(pos - start);
-                    if (f + 1 < c->nframes)
+                    /* (scene-cut detection: a frame that has not been analysed has no kind yet -- the launch that analyses it runs its
+                     * rc_frame_start, on the same controller state) */
+                    if (f + 1 < c->nframes && (!c->scenecut || f + 1 < c->sc_done))
                     {
                         /* the exact QP of the next frame; a frame of this launch that was given another one is stopped */
-                        const int nkey = ((f + 1) % G) == 0;
+                        const int nkey = sched[f + 1].key;
                         qp = c->rc_qp = rc_frame_start(&c->rcs, c->par.gop, nmb, c->par.vbv_size_bytes, desired_frame_bytes, qp_min, qp_max, nkey);
                         c->rc_frame = f + 1;
                         if (is_hedge) rc_miss = 1;                  /* a leaf has nothing behind it */
@@ -1563,7 +1717,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         if (!h264e_hip_mb_counter(c->pool, &pm, 1)) stats.processed_mbs = (long long)pm;
     }
     stats.mv_clusters_out[0] = c->state[0]; stats.mv_clusters_out[1] = c->state[1];
-    stats.next_idr_pic_id_state = idr_state ^ (((c->next + G - 1)/G) & 1);
+    stats.next_idr_pic_id_state = c->next ? idr_state ^ c->sched[c->next - 1].idr : idr_state;
     h264e_hip_profile_read(c->pool, &stats.mb_kernel_ms, &stats.splice_kernel_ms, &stats.kernel_launches);
     if (out_bytes) *out_bytes = pos;
     rc = 0;
@@ -1626,7 +1780,7 @@ int H264E_clip_encode_multi(H264E_clip_t **clips, int nclips, uint8_t **out, con
              * the pipeline depth -- which costs streams WITHOUT staggered events a few percent and gives staggered ones 13 %
              * (measured, 4 different 1080p clips: 12.8 -> 14.6 M MB/s aggregate; 4 identical ones 21.4 -> 20.7 M) */
             saved_base[i] = clips[i]->launch_base;
-            if (n > 1 && clips[i]->par.slices <= 1 && clips[i]->gop_len > 1 && !clips[i]->rc_on)
+            if (n > 1 && clips[i]->par.slices <= 1 && !clips[i]->all_key && !clips[i]->rc_on)
             {
                 clips[i]->launch_base = imax(8, clips[i]->launch_base/3);
                 clips[i]->launch_frames = imin(clips[i]->launch_frames, clips[i]->launch_base);

@@ -13,6 +13,7 @@
  *   h264e_denoise_kernel the temporal denoiser (enc_denoise.h) over one frame: raw input + previous denoised picture -> new
  *                        denoised picture, out of place, one launch per frame in stream order.
  *   h264e_ingest_kernel  device-resident input (enc_ingest.h): one I420 / NV12 / RGB frame in HBM -> the packed I420 input slot.
+ *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
  *
  * HIP only (hipcc --offload-arch=gfx950).  The host side of the boundary is h264e_pool.h, included at the end; the test-only
  * emulation of tests/emu compiles the same kernel HEADERS with its own launch functions and never sees this file.
@@ -24,6 +25,7 @@
 #include "enc_selftest.h"
 #include "enc_denoise.h"
 #include "enc_ingest.h"
+#include "enc_scenecut.h"
 #include "../../include/h264e_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -695,6 +697,38 @@ __global__ void __launch_bounds__(256) h264e_ingest_kernel(h264e_ingest_src_t S,
     else ingest_chroma(S, (GLOBAL_AS uint8_t *)dst, g, y);
 }
 
+/* the luma histogram of one resident input frame (enc_scenecut.h): the plane's dwords are dealt to the workgroups in chunks of 256 lanes x
+ * SCENECUT_UNROLL dwords (all loads of a chunk issued before the first sample is counted), every workgroup counts into its own LDS histogram
+ * and adds its 64 sums to the frame's record (zeroed by the host in front of the launch) */
+#define SCENECUT_UNROLL 8
+__global__ void __launch_bounds__(256) h264e_scenecut_kernel(const uint8_t *luma, uint32_t nbytes, int *record)
+{
+    __shared__ uint32_t hist[SCENECUT_LDS_DWORDS];
+    for (int k = (int)threadIdx.x; k < SCENECUT_LDS_DWORDS; k += 256) hist[k] = 0;
+    __syncthreads();
+    const gu8 *plane = (const gu8 *)luma;
+    const uint32_t ndw = scenecut_dwords(plane, nbytes);
+    const int rep = (int)(threadIdx.x & (SCENECUT_REPLICAS - 1));
+    for (uint32_t c0 = blockIdx.x*(256u*SCENECUT_UNROLL); c0 < ndw; c0 += gridDim.x*(256u*SCENECUT_UNROLL))
+    {
+        uint32_t v[SCENECUT_UNROLL];
+#pragma unroll
+        for (int k = 0; k < SCENECUT_UNROLL; k++)
+        {
+            const uint32_t i = c0 + 256u*(uint32_t)k + threadIdx.x;
+            v[k] = i < ndw ? scenecut_load(plane, i) : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < SCENECUT_UNROLL; k++)
+        {
+            const uint32_t i = c0 + 256u*(uint32_t)k + threadIdx.x;
+            if (i < ndw) scenecut_count((LDS_AS uint32_t *)hist, plane, nbytes, i, v[k], rep);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < SCENECUT_BINS) scenecut_flush((const LDS_AS uint32_t *)hist, (GLOBAL_AS int *)record, (int)threadIdx.x);
+}
+
 /* ------------------------------------------------------------------ launches (what h264e_pool.h calls) */
 
 /* variant: 0 = intra frames only (one wave per row, 4 per SIMD), 1 = one wave per row, 2 = two waves per row (3 per SIMD), 3 = the latency variant: four
@@ -745,6 +779,14 @@ static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStrea
 {
     const unsigned gx = (unsigned)((((S.width + 3) >> 2) + 255) >> 8);
     hipLaunchKernelGGL(h264e_ingest_kernel, dim3(gx, (unsigned)S.height, 2), dim3(256), 0, st, S, dst);
+}
+/* one workgroup per chunk, at most 256 (one per CU): at most 256 adders per record word, 254 at 1080p */
+static void bk_launch_scenecut(const uint8_t *luma, uint32_t nbytes, int *record, hipStream_t st)
+{
+    const uint32_t ndw = (nbytes + 9) >> 2, per_wg = 256*SCENECUT_UNROLL;
+    uint32_t wgs = (ndw + per_wg - 1)/per_wg;
+    if (wgs > 256) wgs = 256;
+    hipLaunchKernelGGL(h264e_scenecut_kernel, dim3(wgs ? wgs : 1), dim3(256), 0, st, luma, nbytes, record);
 }
 static void bk_launch_stage_selftest(int stage, const uint8_t *in, const int *args, uint8_t *out, hipStream_t st)
 {

@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise and bk_launch_ingest; the emulation's versions of those two are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest and bk_launch_scenecut; the emulation's versions of those three are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -13,6 +13,7 @@
 #define H264E_POOL_H
 #include "enc_denoise.h"
 #include "enc_ingest.h"
+#include "enc_scenecut.h"
 
 static thread_local char g_err[256];       /* per calling thread */
 #define FAIL(...) do { snprintf(g_err, sizeof(g_err), __VA_ARGS__); return -1; } while (0)
@@ -153,7 +154,9 @@ struct h264e_hip_pool
      * state; a single-slot pool ping-pongs two frames instead (den_flip: the current one).  NULL until the denoiser is switched on. */
     uint8_t *den;
     int den_frames, den_flip;
-    hipEvent_t ev_copy;                  /* the copy stream's uploads, waited for by a denoise launch */
+    hipEvent_t ev_copy;                  /* the copy stream's uploads, waited for by a denoise / scene-cut launch */
+    hipEvent_t ev_sc[2];                 /* around the scene-cut launches of one call (their HIP-event time) */
+    int *sc_rec;                         /* device [frames_resident][64]: luma histogram records of the scene-cut detector; NULL until it is switched on */
     hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
     h264e_chain_dev_t *chains_host;      /* host mirror of the device descriptors */
     h264e_chain_dev_t *chains_dev;
@@ -253,11 +256,13 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     free(p->host_rbsp); free(p->host_mbrec); free(p->slot_launch); free(p->order_host);
     dev_free(p->heap);
     dev_free(p->den);
+    dev_free(p->sc_rec);
     if (p->stream)
     {
         for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventDestroy(p->ev[i][k]);
         (void)hipEventDestroy(p->ev_t0); (void)hipEventDestroy(p->ev_t1); (void)hipEventDestroy(p->ev_prep); (void)hipEventDestroy(p->ev_copy);
         (void)hipEventDestroy(p->ev_ingest[0]); (void)hipEventDestroy(p->ev_ingest[1]);
+        (void)hipEventDestroy(p->ev_sc[0]); (void)hipEventDestroy(p->ev_sc[1]);
         (void)hipStreamDestroy(p->stream);
         if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
         if (p->abort_stream) (void)hipStreamDestroy(p->abort_stream);
@@ -395,6 +400,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventCreate(&p->ev[i][k]);
     (void)hipEventCreate(&p->ev_t0); (void)hipEventCreate(&p->ev_t1); (void)hipEventCreate(&p->ev_prep); (void)hipEventCreate(&p->ev_copy);
     (void)hipEventCreate(&p->ev_ingest[0]); (void)hipEventCreate(&p->ev_ingest[1]);
+    (void)hipEventCreate(&p->ev_sc[0]); (void)hipEventCreate(&p->ev_sc[1]);
     p->chains_host = (h264e_chain_dev_t *)calloc((size_t)nchains, sizeof(h264e_chain_dev_t));
     p->clu_dev = (int32_t **)calloc((size_t)nchains, sizeof(int32_t *));
     p->ref_sel = (int *)calloc((size_t)nchains, sizeof(int));
@@ -609,6 +615,54 @@ extern "C" int h264e_hip_read_denoised(h264e_hip_pool_t *p, int slot, uint8_t *d
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipStreamSynchronize(p->stream));
     HIPCHK(hipMemcpy(dst, den_frame(p, den_index(p, slot)), p->frame_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* ---- scene-cut detection (enc_scenecut.h): one h264e_scenecut_kernel launch per frame on the pool's stream */
+
+#ifdef H264E_EMU
+/* the emulation's launch: the kernel's per-dword code as a lane loop over one workgroup, then its flush */
+static void bk_launch_scenecut(const uint8_t *luma, uint32_t nbytes, int *record, hipStream_t)
+{
+    uint32_t *hist = (uint32_t *)calloc(SCENECUT_LDS_DWORDS, sizeof(uint32_t));
+    if (!hist) return;
+    const uint32_t ndw = scenecut_dwords(luma, nbytes);
+    for (uint32_t i = 0; i < ndw; i++) scenecut_count(hist, luma, nbytes, i, scenecut_load(luma, i), (int)(i & (SCENECUT_REPLICAS - 1)));
+    for (int b = 0; b < SCENECUT_BINS; b++) scenecut_flush(hist, record, b);
+    free(hist);
+}
+#endif
+
+extern "C" int h264e_hip_scenecut_frames(h264e_hip_pool_t *p, int first, int n, uint32_t *hist, float *kernel_ms)
+{
+    const int R = p ? p->frames_resident : 0;
+    if (!p || !hist || first < 0 || first >= R || n < 0 || n > R) FAIL("scenecut_frames: bad argument");
+    if (kernel_ms) *kernel_ms = 0;
+    if (!n) return 0;
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->sc_rec && dev_malloc((void **)&p->sc_rec, sizeof(int)*SCENECUT_BINS*(size_t)R)) { p->sc_rec = 0; FAIL("scenecut: device allocation failed (%d records)", R); }
+    /* the inputs may have come over the copy stream (asynchronous uploads, device input): the launches wait for everything issued there */
+    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
+    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
+    HIPCHK(hipEventRecord(p->ev_sc[0], p->stream));
+    for (int done = 0; done < n;)
+    {
+        const int s = (first + done) % R, run = imin_h(n - done, R - s);
+        HIPCHK(hipMemsetAsync(p->sc_rec + (size_t)s*SCENECUT_BINS, 0, sizeof(int)*SCENECUT_BINS*(size_t)run, p->stream));
+        for (int i = 0; i < run; i++)
+            bk_launch_scenecut(p->clip + p->frame_bytes*(size_t)(s + i), (uint32_t)((size_t)p->G.width*p->G.height), p->sc_rec + (size_t)(s + i)*SCENECUT_BINS, p->stream);
+        HIPCHK(hipGetLastError());
+        done += run;
+    }
+    HIPCHK(hipEventRecord(p->ev_sc[1], p->stream));
+    for (int done = 0; done < n;)
+    {
+        const int s = (first + done) % R, run = imin_h(n - done, R - s);
+        HIPCHK(hipMemcpyAsync(hist + (size_t)done*SCENECUT_BINS, p->sc_rec + (size_t)s*SCENECUT_BINS, sizeof(int)*SCENECUT_BINS*(size_t)run, hipMemcpyDeviceToHost, p->stream));
+        done += run;
+    }
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, p->ev_sc[0], p->ev_sc[1]));
     return 0;
 }
 

@@ -136,6 +136,11 @@ int  h264e_hip_submit(h264e_hip_pool_t *pool, const h264e_hip_task_t *tasks /* [
 int  h264e_hip_denoise_reset(h264e_hip_pool_t *pool);
 int  h264e_hip_denoise_frames(h264e_hip_pool_t *pool, int first, int n, int from_zero);
 int  h264e_hip_read_denoised(h264e_hip_pool_t *pool, int slot, uint8_t *dst);
+/* Scene-cut detection (enc_scenecut.h): the 64-bin luma histograms (Y >> 2) of resident input slots first, first + 1, ... (mod
+ * frames_resident), one kernel launch per frame on the pool's stream after every upload issued on the copy stream, read back into
+ * hist [n][64] on return (the call waits for the stream).  The device records are allocated on first use.  kernel_ms (optional): the HIP-event
+ * time of the launches of this call. */
+int  h264e_hip_scenecut_frames(h264e_hip_pool_t *pool, int first, int n, uint32_t *hist, float *kernel_ms);
 /* Launch groups: the submits of the member pools (same device, same picture size, one host thread each) are merged into ONE kernel
  * launch per round -- the streams' jobs interleaved in dispatch order, every job with its own pool's buffers / abort word / results --
  * so that independent streams fill each other's pipeline drains.  h264e_hip_submit of a member blocks until all members that are

@@ -243,6 +243,31 @@ void H264E_clip_set_ssd_output(H264E_clip_t *clip, uint64_t *ssd);
  * made again from the first frame that is uploaded again.  The sums of squared differences compare the RAW input with the
  * reconstruction, as the reference's --psnr does.  Refused with keep_records (GOP shards).  0 = done, -1 = refused. */
 int  H264E_clip_set_denoise(H264E_clip_t *clip, int on);
+/* Key frames where the caller wants them (a receiver asked for one, a splice point, a chapter mark): frames[0..n) (ascending, inside
+ * the clip) are coded as key frames in addition to the periodic ones.  The stream is exactly what H264E_encode writes for the same
+ * pictures with frame_type = H264E_FRAME_TYPE_KEY on the listed frames and H264E_FRAME_TYPE_DEFAULT on all others (h264-lab.h:6725-6775,
+ * :6611-6614): SPS / PPS in front of every key frame, frame_num and the periodic GOP counter restart there (the next periodic key
+ * frame comes `gop` frames after the last key frame of either kind), idr_pic_id toggles per key frame; with gop = 1 the frame behind a
+ * forced key frame is a P frame, as in the reference.  Only while the clip stands at frame 0 (after open or rewind); a rewind keeps
+ * the list, n = 0 clears it.  Refused with keep_records (GOP shards assume fixed GOP blocks), for a frame outside the clip and for a
+ * list that is not ascending; a refusal changes nothing.  0 = done, -1 = refused (H264E_last_error says why). */
+int  H264E_clip_set_key_frames(H264E_clip_t *clip, const int *frames, int n);
+/* Scene-cut detection, which fills the same schedule: threshold in 1/1024 of the picture (0 = off, H264E_SCENECUT_DEFAULT = 128).  With
+ * H_f[b] = the number of luma samples of the RAW input frame f (width x height, before the denoiser) with Y >> 2 == b (b = 0..63) and
+ *     D(f) = (sum over b of |H_f[b] - H_(f-1)[b]|) * 1024 / (2 * width * height)       (floor; D(0) = 0),
+ * frame f > 0 becomes a key frame when D(f) > threshold, unless it is one already (periodic, or on the explicit list).  The reference has
+ * no detector: this integer definition is the definition (tests/scenecut_model.py restates it).  The histograms are made on the
+ * device by one small kernel per frame in front of the launch that first encodes the frame (enc_scenecut.h); uploading frame f again
+ * makes f onward new, a rewind keeps them.  At 352x288 and above the test clips stay at or below 21 between consecutive frames and
+ * reach 280 at a hard cut, which is where the default comes from; pictures of a few thousand samples have noisy histograms (64x48: a
+ * pan reaches 160) and are no basis for claims about detection.  Same rules as H264E_clip_set_key_frames for when it may be called. */
+#define H264E_SCENECUT_DEFAULT 128
+int  H264E_clip_set_scenecut(H264E_clip_t *clip, int threshold);
+/* what the detector saw: D(f) for frames [first, first + n) and whether f was made a key frame by it (either pointer may be NULL).
+ * Only frames that an H264E_clip_encode call has reached (or analysed in front of its launch); -1 otherwise, or when the detector was never on. */
+int  H264E_clip_read_scenecut(H264E_clip_t *clip, int first, int n, int *dist, uint8_t *is_cut);
+/* diagnostic: HIP-event time of the detector's kernel launches since open, and the frames they analysed (tools/scenecut_probe.py) */
+int  H264E_clip_scenecut_time(H264E_clip_t *clip, double *kernel_ms, long long *frames);
 /* GOP shards of ONE stream (one clip encoder per shard / GPU, the shard starting at a key frame with first_idr_pic_id_state =
  * its GOP index & 1 and a SPECULATED mv_clusters_in): once the exact state in front of the shard is known, revalidate walks the
  * kept records (keep_records) and either confirms the shard (*restart_frame = -1, end_state = exact state behind it) or names the
