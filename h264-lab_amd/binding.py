@@ -56,6 +56,10 @@ class DevFrame(C.Structure):  # H264E_dev_frame_t: a frame in device memory (che
     _fields_ = [("format", C.c_int), ("pixel_bytes", C.c_int), ("plane", C.c_void_p * 3), ("stride", C.c_int * 3), ("producer_stream", C.c_void_p)]
 
 
+class DevWindow(C.Structure):  # H264E_dev_window_t: the source's size and the window of it that is reduced to the encoder's picture
+    _fields_ = [(n, C.c_int) for n in ("src_width", "src_height", "crop_x", "crop_y", "crop_width", "crop_height")]
+
+
 DEV_FORMAT_I420, DEV_FORMAT_NV12, DEV_FORMAT_RGB = 0, 1, 2
 H264E_SCENECUT_DEFAULT = 128        # include/h264e_mi355x.h
 _DEV_FORMATS = {"i420": DEV_FORMAT_I420, "nv12": DEV_FORMAT_NV12, "rgb": DEV_FORMAT_RGB}
@@ -165,6 +169,20 @@ def dev_frame(frame, fmt, w, h, stream=None):
     return d, frame
 
 
+def dev_window(src_size, crop, w, h):
+    """(DevWindow or None, (width, height) of the frames to describe): None when neither src_size nor crop is given -- the frames have the
+    picture's size and go through the plain ingest"""
+    if src_size is None and crop is None:
+        return None, (w, h)
+    sw, sh = (int(v) for v in (src_size if src_size is not None else (w, h)))
+    win = DevWindow(sw, sh, 0, 0, 0, 0)
+    if crop is not None:
+        win.crop_x, win.crop_y, win.crop_width, win.crop_height = (int(v) for v in crop)
+        if win.crop_width == 0:
+            raise H264EError("device input: a crop of width 0 (leave crop out for the whole source)")
+    return win, (sw, sh)
+
+
 def lib_path():
     return os.environ.get("H264E_LIB", _DEFAULT_LIB)
 
@@ -245,6 +263,9 @@ def load(path=None):
         raise H264EError("%s: H264E_dev_frame_t has %d bytes, this binding's mirror %d" % (path, L.H264E_struct_size(2), C.sizeof(DevFrame)))
     L.H264E_encode_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RunParam), C.POINTER(DevFrame), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.H264E_clip_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(DevFrame)]
+    L.H264E_encode_device_scaled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RunParam), C.POINTER(DevFrame), C.POINTER(DevWindow), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.H264E_clip_upload_device_scaled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(DevFrame), C.POINTER(DevWindow)]
+    L.H264E_clip_input_time.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.H264E_clip_download.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.H264E_dev_malloc.argtypes = [C.c_int, C.c_size_t]
     L.H264E_dev_malloc.restype = C.c_void_p
@@ -315,15 +336,20 @@ class Encoder:
             raise _err(self.L, "H264E_encode status %d" % st)
         return C.string_at(data, n.value)
 
-    def encode_device(self, frame, fmt, frame_type=FRAME_TYPE_DEFAULT, stream=None):
+    def encode_device(self, frame, fmt, frame_type=FRAME_TYPE_DEFAULT, stream=None, src_size=None, crop=None):
         """H264E_encode_device: the frame is taken from GPU memory (see dev_frame for what `frame` may be: fmt "i420", "nv12" or "rgb");
-        needs const_input=1.  The frame's memory may be reused as soon as this returns."""
-        d, _keep = dev_frame(frame, fmt, self.w, self.h, stream)
+        needs const_input=1.  The frame's memory may be reused as soon as this returns.  src_size=(w, h): the frame has that size and is
+        reduced to the encoder's picture (H264E_encode_device_scaled), crop=(x, y, w, h): only that window of it."""
+        win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)
+        d, _keep = dev_frame(frame, fmt, sw, sh, stream)
         self.rp.frame_type = frame_type
         data, n = C.c_void_p(), C.c_int()
-        st = self.L.H264E_encode_device(self.persist, self.scratch, C.byref(self.rp), C.byref(d), C.byref(data), C.byref(n))
+        if win is not None:
+            st = self.L.H264E_encode_device_scaled(self.persist, self.scratch, C.byref(self.rp), C.byref(d), C.byref(win), C.byref(data), C.byref(n))
+        else:
+            st = self.L.H264E_encode_device(self.persist, self.scratch, C.byref(self.rp), C.byref(d), C.byref(data), C.byref(n))
         if st:
-            raise _err(self.L, "H264E_encode_device status %d" % st)
+            raise _err(self.L, "H264E_encode_device%s status %d" % ("_scaled" if win is not None else "", st))
         return C.string_at(data, n.value)
 
     def set_vbv_state(self, vbv_size_bytes, vbv_fullness_bytes):
@@ -402,13 +428,25 @@ class ClipEncoder:
         if self.L.H264E_clip_upload(self.c, first, n, clip.ctypes.data):
             raise _err(self.L, "H264E_clip_upload")
 
-    def upload_device(self, frames, fmt, first=0, stream=None):
+    def upload_device(self, frames, fmt, first=0, stream=None, src_size=None, crop=None):
         """H264E_clip_upload_device: `frames` is a sequence of frames in GPU memory (see dev_frame: fmt "i420", "nv12" or "rgb"), frame
-        first + i from frames[i].  Their memory may be reused as soon as this returns."""
-        made = [dev_frame(f, fmt, self.w, self.h, stream) for f in frames]
+        first + i from frames[i].  Their memory may be reused as soon as this returns.  src_size=(w, h): the frames have that size and are
+        reduced to the clip's picture (H264E_clip_upload_device_scaled), crop=(x, y, w, h): only that window of them."""
+        win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)
+        made = [dev_frame(f, fmt, sw, sh, stream) for f in frames]
         arr = (DevFrame * max(len(made), 1))(*[m[0] for m in made])
-        if self.L.H264E_clip_upload_device(self.c, first, len(made), arr):
+        if win is not None:
+            if self.L.H264E_clip_upload_device_scaled(self.c, first, len(made), arr, C.byref(win)):
+                raise _err(self.L, "H264E_clip_upload_device_scaled")
+        elif self.L.H264E_clip_upload_device(self.c, first, len(made), arr):
             raise _err(self.L, "H264E_clip_upload_device")
+
+    def input_time(self, enable=True):
+        """(HIP-event milliseconds inside the ingest / scale launches of the device uploads timed so far, their frames); switches the
+        timing of later uploads on or off"""
+        ms, n = C.c_double(), C.c_longlong()
+        self.L.H264E_clip_input_time(self.c, int(bool(enable)), C.byref(ms), C.byref(n))
+        return ms.value, n.value
 
     def download(self, first=0, nframes=None):
         """the resident input frames (packed I420) back to the host: whole-clip residency only"""
@@ -501,3 +539,33 @@ class ClipEncoder:
             self.close()
         except Exception:
             pass
+
+
+def encode_ladder(frames, fmt, src_size, rungs, crop=None, **common):
+    """One source in GPU memory, several encodes of it at different sizes.  frames: the device frames (see dev_frame), all of
+    src_size=(w, h); rungs: a list of (width, height, dict of ClipEncoder options); crop=(x, y, w, h): the window of the source that every
+    rung shows; common: ClipEncoder options of all rungs (a rung's own win).  One ClipEncoder per rung is fed from the same frames -- by
+    the scaling kernel, or the plain ingest where a rung has the window's size -- rungs of equal picture size are encoded at the same
+    time (ClipEncoder.encode_multi), the others one after another.  Returns one (bytes, sizes, stats) per rung, in the order given."""
+    frames = list(frames)
+    sw, sh = (int(v) for v in src_size)
+    encs, out = [], [None] * len(rungs)
+    try:
+        for w, h, opts in rungs:
+            ce = ClipEncoder(w, h, len(frames), **dict(common, **(opts or {})))
+            encs.append(ce)
+            if crop is None and (w, h) == (sw, sh):
+                ce.upload_device(frames, fmt)
+            else:
+                ce.upload_device(frames, fmt, src_size=(sw, sh), crop=crop)
+        groups = {}
+        for i, ce in enumerate(encs):
+            groups.setdefault((ce.w, ce.h), []).append(i)
+        for idx in groups.values():
+            res = ClipEncoder.encode_multi([encs[i] for i in idx]) if len(idx) > 1 else [encs[idx[0]].encode()]
+            for i, r in zip(idx, res):
+                out[i] = r
+    finally:
+        for ce in encs:
+            ce.close()
+    return out

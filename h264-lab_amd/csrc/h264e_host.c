@@ -685,17 +685,18 @@ void H264E_set_vbv_state(H264E_persist_t *p, int vbv_size_bytes, int vbv_fullnes
 }
 
 /* the frame into the pool's input slot: from the caller's host planes, or from device memory (H264E_encode_device) */
-static int put_frame(h264e_hip_pool_t *pool, const H264E_io_yuv_t *in, const H264E_dev_frame_t *dev)
+static int put_frame(h264e_hip_pool_t *pool, const H264E_io_yuv_t *in, const H264E_dev_frame_t *dev, const H264E_dev_window_t *win)
 {
     const uint8_t *yuv[3];
+    if (dev && win) return h264e_hip_scale_device(pool, 0, dev->format, dev->plane, dev->stride, (const int *)win, dev->producer_stream);
     if (dev) return h264e_hip_ingest_device(pool, 0, dev->format, dev->plane, dev->stride, dev->pixel_bytes, dev->producer_stream);
     yuv[0] = in->yuv[0]; yuv[1] = in->yuv[1]; yuv[2] = in->yuv[2];
     return h264e_hip_upload_planes(pool, 0, yuv, in->stride);
 }
 
-/* H264E_encode (dev = NULL) and H264E_encode_device (in = NULL) */
+/* H264E_encode (dev = NULL), H264E_encode_device (in = NULL) and H264E_encode_device_scaled (in = NULL, a window) */
 static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_param_t *opt, H264E_io_yuv_t *in, const H264E_dev_frame_t *dev,
-                        unsigned char **coded_data, int *sizeof_coded_data)
+                        const H264E_dev_window_t *win, unsigned char **coded_data, int *sizeof_coded_data)
 {
     henc_t *e = (henc_t *)p;
     impl_t mm, *m = impl_of(e, &mm) ? &mm : NULL;
@@ -714,7 +715,8 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
             return H264E_STATUS_BAD_PARAMETER;
         }
         /* refused before the stream state moves */
-        if (h264e_hip_ingest_check(m->pool, 0, dev->format, dev->plane, dev->stride, dev->pixel_bytes)) return H264E_STATUS_BAD_ARGUMENT;
+        if (win ? h264e_hip_scale_check(m->pool, 0, dev->format, dev->plane, dev->stride, (const int *)win)
+                : h264e_hip_ingest_check(m->pool, 0, dev->format, dev->plane, dev->stride, dev->pixel_bytes)) return H264E_STATUS_BAD_ARGUMENT;
     }
     ref_sizes(&e->param, &sp, &ss);
     cap = (size_t)ss;
@@ -761,7 +763,7 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
     den = e->denoise && opt->encode_speed < 2;
     if (den)
     {
-        if (put_frame(m->pool, in, dev) || h264e_hip_denoise_frames(m->pool, 0, 1, !e->den_started)) return H264E_STATUS_BAD_ARGUMENT;
+        if (put_frame(m->pool, in, dev, win) || h264e_hip_denoise_frames(m->pool, 0, 1, !e->den_started)) return H264E_STATUS_BAD_ARGUMENT;
         e->den_started = 1;
         task.denoised = 1;
     }
@@ -792,7 +794,7 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
         res.all_skipped = 1;
     } else
     {
-    if (!den && put_frame(m->pool, in, dev)) return H264E_STATUS_BAD_ARGUMENT;
+    if (!den && put_frame(m->pool, in, dev, win)) return H264E_STATUS_BAD_ARGUMENT;
     if (frame_exact(m->pool, &task, e->seq.nmbx, e->seq.nmby, e->clusters) || h264e_hip_stream_done(m->pool, 0, &res) != 1) return H264E_STATUS_BAD_ARGUMENT;
     {
         const uint8_t *nals = h264e_hip_stream_rbsp(m->pool, 0);
@@ -840,14 +842,26 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
 int H264E_encode(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_param_t *opt, H264E_io_yuv_t *in,
                  unsigned char **coded_data, int *sizeof_coded_data)
 {
-    return encode_frame(p, scratch, opt, in, NULL, coded_data, sizeof_coded_data);
+    return encode_frame(p, scratch, opt, in, NULL, NULL, coded_data, sizeof_coded_data);
 }
 
 /* H264E_encode with the frame taken from device memory by the ingest kernel (enc_ingest.h) instead of a host-to-device copy */
 int H264E_encode_device(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_param_t *opt, const H264E_dev_frame_t *frame,
                         unsigned char **coded_data, int *sizeof_coded_data)
 {
-    return encode_frame(p, scratch, opt, NULL, frame, coded_data, sizeof_coded_data);
+    return encode_frame(p, scratch, opt, NULL, frame, NULL, coded_data, sizeof_coded_data);
+}
+
+/* ... by the scaling kernel (enc_scale.h): a window of a frame of another size, reduced to the encoder's picture */
+int H264E_encode_device_scaled(H264E_persist_t *p, H264E_scratch_t *scratch, const H264E_run_param_t *opt, const H264E_dev_frame_t *frame,
+                               const H264E_dev_window_t *win, unsigned char **coded_data, int *sizeof_coded_data)
+{
+    if (!frame || !win)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "H264E_encode_device_scaled: null %s", frame ? "window" : "frame");
+        return H264E_STATUS_BAD_ARGUMENT;
+    }
+    return encode_frame(p, scratch, opt, NULL, frame, win, coded_data, sizeof_coded_data);
 }
 
 void *H264E_dev_malloc(int device, size_t bytes) { g_host_err[0] = 0; return h264e_hip_dev_malloc(device, bytes); }
@@ -874,6 +888,9 @@ struct H264E_clip_tag
     seq_t seq;
     int nframes, ring;
     int resident;                           /* input frames kept in HBM (ring): frame f lives in slot f % resident */
+    int time_input;                         /* H264E_clip_input_time: time the launches of the device uploads */
+    double input_ms;
+    long long input_frames;
     h264e_hip_pool_t *pool;
     /* ---- stream state, kept across H264E_clip_encode calls */
     int next;                               /* next frame to encode */
@@ -1112,22 +1129,58 @@ int H264E_clip_upload(H264E_clip_t *c, int first, int nframes, const uint8_t *i4
     return h264e_hip_sync(c->pool);
 }
 
-/* The same from device memory: one ingest kernel per frame on the pool's copy stream (enc_ingest.h), all of them complete on return.
- * Every frame is checked before the first one is launched, so a refused call leaves the input ring as it was. */
-int H264E_clip_upload_device(H264E_clip_t *c, int first, int nframes, const H264E_dev_frame_t *frames)
+/* The same from device memory: one ingest kernel per frame on the pool's copy stream (enc_ingest.h) -- with a window one scaling kernel
+ * (enc_scale.h) -- all of them complete on return.  Every frame is checked before the first one is launched, so a refused call leaves
+ * the input ring as it was. */
+static int clip_put_device(H264E_clip_t *c, int first, int nframes, const H264E_dev_frame_t *frames, const H264E_dev_window_t *win)
 {
     int i, rc = 0;
-    g_host_err[0] = 0;
+    double ms = 0;
     if (clip_put_allowed(c, first, nframes)) return -1;
-    if (!frames) { snprintf(g_host_err, sizeof(g_host_err), "upload_device: null argument"); return -1; }
     for (i = 0; i < nframes; i++)
-        if (h264e_hip_ingest_check(c->pool, (first + i) % c->resident, frames[i].format, frames[i].plane, frames[i].stride, frames[i].pixel_bytes)) return -1;
+    {
+        const H264E_dev_frame_t *f = &frames[i];
+        if (win ? h264e_hip_scale_check(c->pool, (first + i) % c->resident, f->format, f->plane, f->stride, (const int *)win)
+                : h264e_hip_ingest_check(c->pool, (first + i) % c->resident, f->format, f->plane, f->stride, f->pixel_bytes)) return -1;
+    }
+    if (c->time_input && h264e_hip_copy_timer_start(c->pool)) return -1;
     for (i = 0; i < nframes && !rc; i++)
-        rc = h264e_hip_ingest_device_async(c->pool, (first + i) % c->resident, frames[i].format, frames[i].plane, frames[i].stride, frames[i].pixel_bytes, frames[i].producer_stream);
+    {
+        const H264E_dev_frame_t *f = &frames[i];
+        rc = win ? h264e_hip_scale_device_async(c->pool, (first + i) % c->resident, f->format, f->plane, f->stride, (const int *)win, f->producer_stream)
+                 : h264e_hip_ingest_device_async(c->pool, (first + i) % c->resident, f->format, f->plane, f->stride, f->pixel_bytes, f->producer_stream);
+    }
+    if (c->time_input && !h264e_hip_copy_timer_stop(c->pool, &ms)) { c->input_ms += ms; c->input_frames += i; }
     if (h264e_hip_upload_wait(c->pool) || rc) return -1;        /* (after a failure too: what was launched has read its source) */
     if (first + nframes > c->avail) c->avail = first + nframes;
     if (first < c->den_done) c->den_done = first;
     if (first < c->sc_done) c->sc_done = first;
+    return 0;
+}
+
+int H264E_clip_upload_device(H264E_clip_t *c, int first, int nframes, const H264E_dev_frame_t *frames)
+{
+    g_host_err[0] = 0;
+    if (clip_put_allowed(c, first, nframes)) return -1;
+    if (!frames) { snprintf(g_host_err, sizeof(g_host_err), "upload_device: null argument"); return -1; }
+    return clip_put_device(c, first, nframes, frames, NULL);
+}
+
+int H264E_clip_upload_device_scaled(H264E_clip_t *c, int first, int nframes, const H264E_dev_frame_t *frames, const H264E_dev_window_t *win)
+{
+    g_host_err[0] = 0;
+    if (clip_put_allowed(c, first, nframes)) return -1;
+    if (!frames || !win) { snprintf(g_host_err, sizeof(g_host_err), "upload_device_scaled: null %s", frames ? "window" : "frames"); return -1; }
+    return clip_put_device(c, first, nframes, frames, win);
+}
+
+/* diagnostic: HIP-event time of the ingest / scale launches of the device uploads made while `enable` was set */
+int H264E_clip_input_time(H264E_clip_t *c, int enable, double *kernel_ms, long long *frames)
+{
+    if (!c) return -1;
+    c->time_input = enable != 0;
+    if (kernel_ms) *kernel_ms = c->input_ms;
+    if (frames) *frames = c->input_frames;
     return 0;
 }
 

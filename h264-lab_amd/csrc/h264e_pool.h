@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest and bk_launch_scenecut; the emulation's versions of those three are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_scale and bk_launch_scenecut; the emulation's versions of those four are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -13,6 +13,7 @@
 #define H264E_POOL_H
 #include "enc_denoise.h"
 #include "enc_ingest.h"
+#include "enc_scale.h"
 #include "enc_scenecut.h"
 
 static thread_local char g_err[256];       /* per calling thread */
@@ -158,6 +159,7 @@ struct h264e_hip_pool
     hipEvent_t ev_sc[2];                 /* around the scene-cut launches of one call (their HIP-event time) */
     int *sc_rec;                         /* device [frames_resident][64]: luma histogram records of the scene-cut detector; NULL until it is switched on */
     hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
+    hipEvent_t ev_in[2];                 /* h264e_hip_copy_timer_*: around a caller's launches on the copy stream */
     h264e_chain_dev_t *chains_host;      /* host mirror of the device descriptors */
     h264e_chain_dev_t *chains_dev;
     h264e_frame_task_t *tasks_dev;       /* ring of TASK_RING task arrays */
@@ -261,7 +263,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     {
         for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventDestroy(p->ev[i][k]);
         (void)hipEventDestroy(p->ev_t0); (void)hipEventDestroy(p->ev_t1); (void)hipEventDestroy(p->ev_prep); (void)hipEventDestroy(p->ev_copy);
-        (void)hipEventDestroy(p->ev_ingest[0]); (void)hipEventDestroy(p->ev_ingest[1]);
+        (void)hipEventDestroy(p->ev_ingest[0]); (void)hipEventDestroy(p->ev_ingest[1]); (void)hipEventDestroy(p->ev_in[0]); (void)hipEventDestroy(p->ev_in[1]);
         (void)hipEventDestroy(p->ev_sc[0]); (void)hipEventDestroy(p->ev_sc[1]);
         (void)hipStreamDestroy(p->stream);
         if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
@@ -399,7 +401,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     if (hipStreamCreate(&p->stream) != hipSuccess || hipStreamCreate(&p->copy_stream) != hipSuccess || hipStreamCreate(&p->abort_stream) != hipSuccess) { if (p->guarded) process_guard_release(device); free(p); FAIL("hipStreamCreate failed"); }
     for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventCreate(&p->ev[i][k]);
     (void)hipEventCreate(&p->ev_t0); (void)hipEventCreate(&p->ev_t1); (void)hipEventCreate(&p->ev_prep); (void)hipEventCreate(&p->ev_copy);
-    (void)hipEventCreate(&p->ev_ingest[0]); (void)hipEventCreate(&p->ev_ingest[1]);
+    (void)hipEventCreate(&p->ev_ingest[0]); (void)hipEventCreate(&p->ev_ingest[1]); (void)hipEventCreate(&p->ev_in[0]); (void)hipEventCreate(&p->ev_in[1]);
     (void)hipEventCreate(&p->ev_sc[0]); (void)hipEventCreate(&p->ev_sc[1]);
     p->chains_host = (h264e_chain_dev_t *)calloc((size_t)nchains, sizeof(h264e_chain_dev_t));
     p->clu_dev = (int32_t **)calloc((size_t)nchains, sizeof(int32_t *));
@@ -699,6 +701,25 @@ static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStrea
     for (int y = 0; y < S.height; y++)
         for (int g = 0; g < (S.width + 3)/4; g++) { ingest_luma(S, dst, g, y); ingest_chroma(S, dst, g, y); }
 }
+/* ... and the scaler's (enc_scale.h): tile by tile, each of the kernel's three steps as a lane loop over the tile's LDS */
+static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t)
+{
+    ScaleLds *L = (ScaleLds *)malloc(sizeof(ScaleLds));
+    if (!L) return;
+    for (int comp = 0; comp < 3; comp++)
+        for (int ty = 0; ty < (S.dh + S.th - 1)/S.th; ty++)
+            for (int tx = 0; tx < (S.dw + SCL_TW - 1)/SCL_TW; tx++)
+            {
+                ScaleTile T;
+                if (!scale_tile(S, comp, tx, ty, T)) continue;
+                memset(L, 0xEE, sizeof(*L));
+                for (int t = 0; t < 256; t++) scale_tables(L, T, t);
+                const int items = scale_src_rows(L, T) << 6;
+                for (int it = 0; it < items; it++) scale_hpass(L, S.c[comp], T, it);
+                for (int it = 0; it < T.nrows*16; it++) scale_vpass(L, T, dst + scale_plane_offset(S, comp), it);
+            }
+    free(L);
+}
 #else
 /* the product refuses what the runtime does not know as device memory of this pool's device, and a plane that does not lie inside ONE
  * allocation from its first to its last byte: a host address or a read beyond the allocation is a memory fault in the kernel, not an
@@ -754,11 +775,9 @@ extern "C" int h264e_hip_ingest_check(h264e_hip_pool_t *p, int slot, int format,
 /* the checks, then the launch on the copy stream behind (a) everything queued on the producer's stream so far and (b), while no macroblock
  * launch of this pool is in flight, everything queued on the pool's own stream (h264e_hip_upload_i420 / upload_planes / generate_synth
  * into the same slot).  A launch in flight does not read the slot: the caller keeps the bounded-ring rule of H264E_clip_upload. */
-static int ingest_enqueue(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream)
+/* the copy stream waits for the producer's stream and, while no launch is in flight, for the pool's own */
+static int ingest_order(h264e_hip_pool_t *p, void *producer_stream)
 {
-    h264e_ingest_src_t S;
-    if (p) HIPCHK(hipSetDevice(p->device));
-    if (ingest_check(p, slot, format, planes, strides, pixel_bytes, &S)) return -1;
     if (producer_stream)
     {
         HIPCHK(hipEventRecord(p->ev_ingest[0], (hipStream_t)producer_stream));
@@ -769,6 +788,15 @@ static int ingest_enqueue(h264e_hip_pool_t *p, int slot, int format, const void 
         HIPCHK(hipEventRecord(p->ev_ingest[1], p->stream));
         HIPCHK(hipStreamWaitEvent(p->copy_stream, p->ev_ingest[1], 0));
     }
+    return 0;
+}
+
+static int ingest_enqueue(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream)
+{
+    h264e_ingest_src_t S;
+    if (p) HIPCHK(hipSetDevice(p->device));
+    if (ingest_check(p, slot, format, planes, strides, pixel_bytes, &S)) return -1;
+    if (ingest_order(p, producer_stream)) return -1;
     bk_launch_ingest(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
     HIPCHK(hipGetLastError());
     return 0;
@@ -783,6 +811,108 @@ extern "C" int h264e_hip_ingest_device(h264e_hip_pool_t *p, int slot, int format
 {
     if (ingest_enqueue(p, slot, format, planes, strides, pixel_bytes, producer_stream)) return -1;
     HIPCHK(hipStreamSynchronize(p->copy_stream));
+    return 0;
+}
+
+/* ---- device-resident input of another size (enc_scale.h): one h264e_scale_kernel launch per frame, ordered like the ingest */
+
+/* everything that is refused, without a launch; fills the kernel's view of the source.  win = {src_width, src_height, crop_x, crop_y,
+ * crop_width, crop_height}, crop_width 0 = the whole source.  Plane extents come from the SOURCE size and the window: what must be
+ * device memory inside one allocation is [the window's first byte, the last byte of its last row] of every plane. */
+static int scale_check(const h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], const int *win, h264e_scale_src_t *S)
+{
+    if (!p || !planes || !strides || !win) FAIL("scale_device: null argument");
+    if (slot < 0 || slot >= p->frames_resident) FAIL("scale_device: slot %d outside the %d resident frames", slot, p->frames_resident);
+    if (format == H264E_INGEST_RGB) FAIL("scale_device: RGB (format %d) cannot be combined with a window: convert at the picture's size, or hand over I420 / NV12", format);
+    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12) FAIL("scale_device: unknown format %d", format);
+    const int srcw = win[0], srch = win[1], dw = p->G.width, dh = p->G.height;
+    if (srcw <= 0 || srch <= 0) FAIL("scale_device: source of %d x %d samples", srcw, srch);
+    const int cx = win[4] ? win[2] : 0, cy = win[4] ? win[3] : 0, sw = win[4] ? win[4] : srcw, sh = win[4] ? win[5] : srch;
+    if (cx < 0 || (cx & 1)) FAIL("scale_device: crop_x %d (even, not negative)", cx);
+    if (cy < 0 || (cy & 1)) FAIL("scale_device: crop_y %d (even, not negative)", cy);
+    if (sw <= 0 || (sw & 1)) FAIL("scale_device: window width %d (even, positive)", sw);
+    if (sh <= 0 || (sh & 1)) FAIL("scale_device: window height %d (even, positive)", sh);
+    if (sw > SCL_MAX_DIM) FAIL("scale_device: window width %d above %d", sw, SCL_MAX_DIM);
+    if (sh > SCL_MAX_DIM) FAIL("scale_device: window height %d above %d", sh, SCL_MAX_DIM);
+    if (cx > srcw - sw) FAIL("scale_device: window columns %d..%d leave the source's %d", cx, cx + sw - 1, srcw);
+    if (cy > srch - sh) FAIL("scale_device: window rows %d..%d leave the source's %d", cy, cy + sh - 1, srch);
+    if (sw < dw) FAIL("scale_device: window width %d below the picture's %d (no upscaling)", sw, dw);
+    if (sh < dh) FAIL("scale_device: window height %d below the picture's %d (no upscaling)", sh, dh);
+    if (sw > SCL_MAX_RATIO*dw) FAIL("scale_device: window width %d is more than %d times the picture's %d", sw, SCL_MAX_RATIO, dw);
+    if (sh > SCL_MAX_RATIO*dh) FAIL("scale_device: window height %d is more than %d times the picture's %d", sh, SCL_MAX_RATIO, dh);
+    memset(S, 0, sizeof(*S));
+    S->sw = sw; S->sh = sh; S->dw = dw; S->dh = dh;
+    S->th = (int)((long long)(SCL_ROWS - 2)*dh/sh);            /* th*sh/dh + 2 source rows at most: <= SCL_ROWS */
+    if (S->th > SCL_TH_MAX) S->th = SCL_TH_MAX;
+    const int nplanes = format == H264E_INGEST_I420 ? 3 : 2, cw = (srcw + 1)/2;
+    for (int k = 0; k < nplanes; k++)
+    {
+        /* bytes of a source row, and the window in this plane: x0 bytes into row y0, wbytes x rows */
+        const int nv = k && format == H264E_INGEST_NV12;
+        const int row_bytes = k == 0 ? srcw : nv ? 2*cw : cw;
+        const int x0 = k == 0 ? cx : nv ? cx : cx/2, y0 = k == 0 ? cy : cy/2, wbytes = k == 0 ? sw : nv ? sw : sw/2, rows = k == 0 ? sh : sh/2;
+        if (!planes[k]) FAIL("scale_device: plane %d is NULL", k);
+        if (strides[k] < row_bytes) FAIL("scale_device: stride %d of plane %d is below the %d bytes of a source row", strides[k], k, row_bytes);
+        const uint8_t *lo = (const uint8_t *)planes[k] + (size_t)y0*(size_t)strides[k] + (size_t)x0;
+        const size_t nbytes = (size_t)(rows - 1)*(size_t)strides[k] + (size_t)wbytes;
+#ifndef H264E_EMU
+        if (!ingest_is_device_memory(p, lo, nbytes))
+            FAIL("scale_device: plane %d (%p, source %d x %d, window %d x %d at (%d, %d), rows %d bytes apart) is not memory of device %d, or not inside one allocation",
+                 k, planes[k], srcw, srch, sw, sh, cx, cy, strides[k], p->device);
+#endif
+        for (int c = k; c < (nv ? 3 : k + 1); c++)
+        {
+            S->c[c].base = lo + (nv && c == 2 ? 1 : 0); S->c[c].lo = lo; S->c[c].hi = lo + nbytes;
+            S->c[c].stride = strides[k]; S->c[c].step = nv ? 2 : 1;
+        }
+    }
+    return 0;
+}
+
+extern "C" int h264e_hip_scale_check(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], const int *win)
+{
+    h264e_scale_src_t S;
+    if (p) (void)hipSetDevice(p->device);
+    return scale_check(p, slot, format, planes, strides, win, &S);
+}
+
+extern "C" int h264e_hip_scale_device_async(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], const int *win, void *producer_stream)
+{
+    h264e_scale_src_t S;
+    if (p) HIPCHK(hipSetDevice(p->device));
+    if (scale_check(p, slot, format, planes, strides, win, &S)) return -1;
+    if (ingest_order(p, producer_stream)) return -1;
+    bk_launch_scale(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int h264e_hip_scale_device(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], const int *win, void *producer_stream)
+{
+    if (h264e_hip_scale_device_async(p, slot, format, planes, strides, win, producer_stream)) return -1;
+    HIPCHK(hipStreamSynchronize(p->copy_stream));
+    return 0;
+}
+
+/* HIP-event time of what the caller queues on the copy stream between the two calls (ingest and scale launches: the probes) */
+extern "C" int h264e_hip_copy_timer_start(h264e_hip_pool_t *p)
+{
+    if (!p) FAIL("copy_timer_start: null pool");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipEventRecord(p->ev_in[0], p->copy_stream));
+    return 0;
+}
+
+extern "C" int h264e_hip_copy_timer_stop(h264e_hip_pool_t *p, double *ms)
+{
+    if (!p || !ms) FAIL("copy_timer_stop: null argument");
+    float f = 0;
+    *ms = 0;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipEventRecord(p->ev_in[1], p->copy_stream));
+    HIPCHK(hipEventSynchronize(p->ev_in[1]));
+    HIPCHK(hipEventElapsedTime(&f, p->ev_in[0], p->ev_in[1]));
+    *ms = f;
     return 0;
 }
 

@@ -121,6 +121,18 @@ int  h264e_hip_upload_planes(h264e_hip_pool_t *pool, int index, const uint8_t *c
 int  h264e_hip_ingest_check(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes);
 int  h264e_hip_ingest_device(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
 int  h264e_hip_ingest_device_async(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
+/* Device-resident input of another size (enc_scale.h): a window of an I420 or NV12 source frame is reduced to the pool's picture by an
+ * exact area filter, by ONE kernel launch on the copy stream, ordered and completed like h264e_hip_ingest_device.  win = six ints:
+ * src_width, src_height, crop_x, crop_y, crop_width, crop_height (crop_width 0 = the whole source).  Refused without a launch, besides
+ * what the ingest refuses: RGB, an odd or negative window value, a window that leaves the source, is smaller than the picture, larger
+ * than 4096 samples or more than 16 times the picture in an axis, and a plane whose bytes from the window's first to its last -- by the
+ * SOURCE's size and stride -- are not inside one allocation of the pool's device. */
+int  h264e_hip_scale_check(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], const int *win);
+int  h264e_hip_scale_device(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], const int *win, void *producer_stream);
+int  h264e_hip_scale_device_async(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], const int *win, void *producer_stream);
+/* HIP-event time of what is queued on the copy stream between the two calls (the ingest / scale launches of the probes); _stop waits */
+int  h264e_hip_copy_timer_start(h264e_hip_pool_t *pool);
+int  h264e_hip_copy_timer_stop(h264e_hip_pool_t *pool, double *ms);
 /* plain device memory and blocking copies, for callers that have no HIP toolchain of their own (to_device: 1 host -> device, 0 back) */
 void *h264e_hip_dev_malloc(int device, size_t bytes);
 void h264e_hip_dev_free(void *p);

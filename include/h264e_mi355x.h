@@ -188,6 +188,21 @@ typedef struct
  * H264E_STATUS_BAD_PARAMETER otherwise.  A frame that is refused (H264E_STATUS_BAD_ARGUMENT) leaves the stream where it was. */
 int  H264E_encode_device(H264E_persist_t *enc, H264E_scratch_t *scratch, const H264E_run_param_t *run_param,
                          const H264E_dev_frame_t *frame, unsigned char **coded_data, int *sizeof_coded_data);
+/* Device-resident input of another size: a window of the source frame is reduced to the encoder's picture on the way into the encoder,
+ * by one small kernel (a 4K render streamed at 1080p, the rungs of a ladder from one source, a region of a larger surface).  The frame
+ * is described as above, its planes having the SOURCE's size; the window is crop_width x crop_height luma samples at (crop_x, crop_y),
+ * crop_width = 0 meaning the whole source.  The filter is an exact area (box) filter per plane -- the reference has no scaler, this
+ * integer definition is the definition (tests/scale_model.py restates it): with the plane window Sw x Sh, the destination Dw x Dh,
+ *     wx(i,k)  = max(0, min((i+1) Sw, (k+1) Dw) - max(i Sw, k Dw))        (wy(j,l) likewise with Sh, Dh),
+ *     out(i,j) = floor((sum_l sum_k wy(j,l) wx(i,k) src(crop_x + k, crop_y + l) + ((Sw Sh) >> 1)) / (Sw Sh)),
+ * so equal sizes copy (a pure crop) and 2:1 is (a + b + c + d + 2) >> 2.  Chroma planes: the same with every value halved; the
+ * half-sample shift of the chroma siting is ignored.  NV12 chroma is de-interleaved.  Refused (H264E_last_error names the value): RGB
+ * with a window, odd or negative crop values, a window that leaves the source, is smaller than the picture in an axis (no upscaling),
+ * larger than 4096 samples or more than 16 times the picture in an axis, a stride below the source row's bytes, and planes that are
+ * not device memory of the encoder's GPU from the window's first byte to its last. */
+typedef struct { int src_width, src_height, crop_x, crop_y, crop_width, crop_height; } H264E_dev_window_t;   /* crop_width = 0: the whole source */
+int  H264E_encode_device_scaled(H264E_persist_t *enc, H264E_scratch_t *scratch, const H264E_run_param_t *run_param,
+                                const H264E_dev_frame_t *frame, const H264E_dev_window_t *win, unsigned char **coded_data, int *sizeof_coded_data);
 /* device memory and blocking copies for callers without a HIP toolchain (to_device: 1 = host to device, 0 = device to host) */
 void *H264E_dev_malloc(int device, size_t bytes);
 void  H264E_dev_free(void *p);
@@ -206,6 +221,11 @@ int  H264E_clip_generate_synth(H264E_clip_t *clip, int first, int nframes, int t
 /* the same from device memory: frames[i] is frame first + i (frame range, ring and "uploading frame f again makes f onward new" rules
  * of H264E_clip_upload).  Returns when the frames have been read; all of them are checked before the first is touched. */
 int  H264E_clip_upload_device(H264E_clip_t *clip, int first, int nframes, const H264E_dev_frame_t *frames);
+/* ... every frame a source of another size, all reduced through the same window (see H264E_dev_window_t); same rules */
+int  H264E_clip_upload_device_scaled(H264E_clip_t *clip, int first, int nframes, const H264E_dev_frame_t *frames, const H264E_dev_window_t *win);
+/* diagnostic: enable != 0 times the kernel launches of later device uploads with HIP events; kernel_ms / frames: the totals since open
+ * (tools/scale_probe.py) */
+int  H264E_clip_input_time(H264E_clip_t *clip, int enable, double *kernel_ms, long long *frames);
 /* the same from pinned host memory on the copy engine, overlapping with a running encode; H264E_clip_upload_wait() completes it */
 void *H264E_clip_host_alloc(size_t bytes);
 void  H264E_clip_host_free(void *p);
