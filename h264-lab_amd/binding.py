@@ -60,9 +60,9 @@ class DevWindow(C.Structure):  # H264E_dev_window_t: the source's size and the w
     _fields_ = [(n, C.c_int) for n in ("src_width", "src_height", "crop_x", "crop_y", "crop_width", "crop_height")]
 
 
-DEV_FORMAT_I420, DEV_FORMAT_NV12, DEV_FORMAT_RGB = 0, 1, 2
+DEV_FORMAT_I420, DEV_FORMAT_NV12, DEV_FORMAT_RGB, DEV_FORMAT_RGBP = 0, 1, 2, 3
 H264E_SCENECUT_DEFAULT = 128        # include/h264e_mi355x.h
-_DEV_FORMATS = {"i420": DEV_FORMAT_I420, "nv12": DEV_FORMAT_NV12, "rgb": DEV_FORMAT_RGB}
+_DEV_FORMATS = {"i420": DEV_FORMAT_I420, "nv12": DEV_FORMAT_NV12, "rgb": DEV_FORMAT_RGB, "rgbp": DEV_FORMAT_RGBP}
 
 
 def hip_runtimes():
@@ -111,6 +111,19 @@ def _dev_array(a):
     raise H264EError("device input: expected a tensor, an object with __cuda_array_interface__ or a (pointer, stride) pair, got %r" % type(a))
 
 
+def _require_uint8(a):
+    """planar RGB takes unsigned 8-bit samples only: anything else is refused here, with its type in the message"""
+    if hasattr(a, "data_ptr") and hasattr(a, "stride"):
+        ok, name = str(getattr(a, "dtype", "")).endswith("uint8"), getattr(a, "dtype", "?")
+    elif getattr(a, "__cuda_array_interface__", None) is not None:
+        name = a.__cuda_array_interface__["typestr"]
+        ok = name in ("|u1", "<u1", ">u1")
+    else:
+        return
+    if not ok:
+        raise H264EError("device input: planar RGB must be uint8 samples, not %s" % (name,))
+
+
 def _dev_plane(a, rows, row_bytes, what):
     """one 2-D plane (or (h, w, c) pixels, c = the last axis): (pointer, row stride, stream)"""
     ptr, shape, strides, stream = _dev_array(a)
@@ -126,7 +139,8 @@ def _dev_plane(a, rows, row_bytes, what):
 
 def dev_frame(frame, fmt, w, h, stream=None):
     """H264E_dev_frame_t for one frame of a w x h picture.  fmt "i420": three 2-D planes (y, u, v) or one packed (h*3/2, w) array;
-    "nv12": (y of (h, w), uv of (h/2, w)); "rgb": one (h, w, 3 | 4) array.  Arrays: torch tensors, anything with
+    "nv12": (y of (h, w), uv of (h/2, w)); "rgb": one (h, w, 3 | 4) array; "rgbp": one uint8 (3, h, w) array (CHW: any channel and row
+    strides, so views work without a copy) or three 2-D planes (r, g, b).  Arrays: torch tensors, anything with
     __cuda_array_interface__, or (pointer, row stride in bytes) pairs.  stream: the hipStream_t (an int) that writes the frame; by
     default torch's current stream for torch tensors.  Returns (DevFrame, the objects that must stay alive during the call)."""
     f = _DEV_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
@@ -152,6 +166,18 @@ def dev_frame(frame, fmt, w, h, stream=None):
             raise H264EError("device input: RGB needs an array with a shape (h, w, 3 | 4)")
         pb = shape[-1] if len(shape) == 3 else 0
         planes = [_dev_plane(frame, h, w * pb, "RGB")]
+    elif f == DEV_FORMAT_RGBP:
+        if isinstance(frame, (tuple, list)) and len(frame) == 3:
+            for a in frame:
+                _require_uint8(a)
+            planes = [_dev_plane(a, h, w, what) for a, what in zip(frame, "RGB")]
+        else:
+            _require_uint8(frame)
+            ptr, shape, strides, st = _dev_array(frame)
+            if shape is None or tuple(shape) != (3, h, w) or strides[2] != 1:
+                raise H264EError("device input: planar RGB must be a (3, %d, %d) array whose last axis is contiguous (any channel and row strides), "
+                                 "or three (%d, %d) planes, got shape %r strides %r" % (h, w, h, w, shape, strides))
+            planes = [(ptr + c * strides[0], strides[1], st) for c in range(3)]
     else:
         raise H264EError("device input: unknown format %r" % (fmt,))
     d = DevFrame(format=f, pixel_bytes=pb)
@@ -337,7 +363,7 @@ class Encoder:
         return C.string_at(data, n.value)
 
     def encode_device(self, frame, fmt, frame_type=FRAME_TYPE_DEFAULT, stream=None, src_size=None, crop=None):
-        """H264E_encode_device: the frame is taken from GPU memory (see dev_frame for what `frame` may be: fmt "i420", "nv12" or "rgb");
+        """H264E_encode_device: the frame is taken from GPU memory (see dev_frame for what `frame` may be: fmt "i420", "nv12", "rgb" or "rgbp");
         needs const_input=1.  The frame's memory may be reused as soon as this returns.  src_size=(w, h): the frame has that size and is
         reduced to the encoder's picture (H264E_encode_device_scaled), crop=(x, y, w, h): only that window of it."""
         win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)
@@ -429,7 +455,7 @@ class ClipEncoder:
             raise _err(self.L, "H264E_clip_upload")
 
     def upload_device(self, frames, fmt, first=0, stream=None, src_size=None, crop=None):
-        """H264E_clip_upload_device: `frames` is a sequence of frames in GPU memory (see dev_frame: fmt "i420", "nv12" or "rgb"), frame
+        """H264E_clip_upload_device: `frames` is a sequence of frames in GPU memory (see dev_frame: fmt "i420", "nv12", "rgb" or "rgbp"), frame
         first + i from frames[i].  Their memory may be reused as soon as this returns.  src_size=(w, h): the frames have that size and are
         reduced to the clip's picture (H264E_clip_upload_device_scaled), crop=(x, y, w, h): only that window of them."""
         win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)

@@ -1,5 +1,5 @@
 /*
- * enc_ingest.h -- device-resident input: one source frame in HBM (I420, NV12 or interleaved RGB, arbitrary row strides) into the
+ * enc_ingest.h -- device-resident input: one source frame in HBM (I420, NV12, interleaved or planar RGB, arbitrary row strides) into the
  * encoder's resident input slot, packed I420 (width*height luma, then two (width/2)*(height/2) chroma planes, rows packed: exactly
  * what h264e_hip_upload_i420 leaves there), per sample group.
  *
@@ -11,6 +11,8 @@
  *         m = (a + b + c + d + 2) >> 2                                                 per channel over each 2x2 block, then
  *         U = ((-38 Rm - 74 Gm + 112 Bm + 128) >> 8) + 128,  V = ((112 Rm - 94 Gm - 18 Bm + 128) >> 8) + 128
  *     (arithmetic shifts; Y lands in 16..235, U and V in 16..240: nothing to clamp).  Width and height are even, so every block is whole.
+ *   - RGBP: planar 8-bit R, G, B (a CHW tensor, or three allocations), each plane with its own pointer and stride; the same arithmetic,
+ *     so byte for byte what RGB gives for the same image.
  *
  * One lane makes four consecutive output samples of one row: ingest_luma for the Y plane, ingest_chroma for the same four samples of
  * U AND V (both come from the same source bytes in NV12 and RGB).  Source bytes are fetched as dwords where the lane's source address
@@ -25,12 +27,13 @@
 #define H264E_INGEST_I420 0
 #define H264E_INGEST_NV12 1
 #define H264E_INGEST_RGB  2
+#define H264E_INGEST_RGBP 3
 
 typedef struct
 {
     const uint8_t *plane[3];
     int stride[3];                      /* bytes from row to row */
-    int format, pixel_bytes;            /* H264E_INGEST_*; bytes per RGB pixel (3 or 4), ignored otherwise */
+    int format, pixel_bytes;            /* H264E_INGEST_*; bytes per interleaved RGB pixel (3 or 4), ignored otherwise */
     int width, height;                  /* luma samples: both even */
 } h264e_ingest_src_t;
 
@@ -89,6 +92,30 @@ template <int PB> DEV void ing_rgb_chroma(const gu8 *p0, const gu8 *p1, int n, u
     }
 }
 
+/* the same from three planes: four luma samples from the four bytes at r, g and b */
+DEV uint32_t ing_rgbp_luma(const gu8 *r, const gu8 *g, const gu8 *b, int n)
+{
+    uint32_t v[3], o = 0;
+    ing_fetch<4>(r, n, &v[0]);
+    ing_fetch<4>(g, n, &v[1]);
+    ing_fetch<4>(b, n, &v[2]);
+    for (int k = 0; k < 4; k++) o |= ing_y(ing_byte(&v[0], k), ing_byte(&v[1], k), ing_byte(&v[2], k)) << (8*k);
+    return o;
+}
+
+/* four U and four V samples from the 2x2 block means of three channels: a[ch] holds 8 samples of the even row, b[ch] of the row below */
+DEV void ing_rgbp_matrix(const uint32_t a[3][2], const uint32_t b[3][2], uint32_t &ou, uint32_t &ov)
+{
+    ou = ov = 0;
+    for (int k = 0; k < 4; k++)
+    {
+        int m[3];
+        for (int ch = 0; ch < 3; ch++) m[ch] = (ing_byte(a[ch], 2*k) + ing_byte(a[ch], 2*k + 1) + ing_byte(b[ch], 2*k) + ing_byte(b[ch], 2*k + 1) + 2) >> 2;
+        ou |= ing_u(m[0], m[1], m[2]) << (8*k);
+        ov |= ing_v(m[0], m[1], m[2]) << (8*k);
+    }
+}
+
 /* luma samples 4g .. min(4g + 3, width - 1) of row y into the slot at dst */
 DEV void ingest_luma(const h264e_ingest_src_t &S, GLOBAL_AS uint8_t *dst, int g, int y)
 {
@@ -98,6 +125,8 @@ DEV void ingest_luma(const h264e_ingest_src_t &S, GLOBAL_AS uint8_t *dst, int g,
     const gu8 *row = (const gu8 *)S.plane[0] + (size_t)y*(size_t)S.stride[0];
     uint32_t o;
     if (S.format == H264E_INGEST_RGB) o = S.pixel_bytes == 4 ? ing_rgb_luma<4>(row + (size_t)x0*4, n) : ing_rgb_luma<3>(row + (size_t)x0*3, n);
+    else if (S.format == H264E_INGEST_RGBP)
+        o = ing_rgbp_luma(row + x0, (const gu8 *)S.plane[1] + (size_t)y*(size_t)S.stride[1] + x0, (const gu8 *)S.plane[2] + (size_t)y*(size_t)S.stride[2] + x0, n);
     else ing_fetch<4>(row + x0, n, &o);
     ing_store(dst + (size_t)y*(size_t)S.width + x0, n, o);
 }
@@ -113,6 +142,16 @@ DEV void ingest_chroma(const h264e_ingest_src_t &S, GLOBAL_AS uint8_t *dst, int 
     {
         const gu8 *p0 = (const gu8 *)S.plane[0] + (size_t)(2*y)*(size_t)S.stride[0] + (size_t)(2*x0)*(size_t)S.pixel_bytes, *p1 = p0 + S.stride[0];
         if (S.pixel_bytes == 4) ing_rgb_chroma<4>(p0, p1, n, ou, ov); else ing_rgb_chroma<3>(p0, p1, n, ou, ov);
+    } else if (S.format == H264E_INGEST_RGBP)
+    {
+        uint32_t a[3][2], b[3][2];
+        for (int c = 0; c < 3; c++)
+        {
+            const gu8 *p0 = (const gu8 *)S.plane[c] + (size_t)(2*y)*(size_t)S.stride[c] + 2*x0;
+            ing_fetch<8>(p0, 2*n, a[c]);
+            ing_fetch<8>(p0 + S.stride[c], 2*n, b[c]);
+        }
+        ing_rgbp_matrix(a, b, ou, ov);
     } else if (S.format == H264E_INGEST_NV12)
     {
         uint32_t v[2];

@@ -24,7 +24,8 @@
  *                 their weights, rounded, divided by Sw Sh (a float estimate, corrected to the exact quotient), out as one dword.
  * No byte outside [first byte of the window's first row, last byte of its last row] is read -- the padding between the window's rows
  * may be (aligned dwords), so a source may end with its allocation; nothing is asked of the alignment of pointers or strides.
- * h264e_kernels.hip runs it as h264e_scale_kernel, h264e_pool.h's emulation launch (H264E_EMU) as lane loops.
+ * h264e_kernels.hip runs it as h264e_scale_kernel, h264e_pool.h's emulation launch (H264E_EMU) as lane loops.  Planar RGB sources go
+ * through the same steps per channel and are converted from LDS: enc_scale_rgb.h.
  */
 #ifndef H264E_ENC_SCALE_H
 #define H264E_ENC_SCALE_H
@@ -146,12 +147,11 @@ DEV uint32_t scl_div(uint32_t n, uint32_t d, float rd)
     return q;
 }
 
-/* step 3, item = row*16 + g: destination samples 4g .. 4g + 3 of one row of the tile into the slot's plane at dst (rows packed) */
-DEV void scale_vpass(const LDS_AS ScaleLds *L, const ScaleTile &T, GLOBAL_AS uint8_t *dst, int item)
+/* four destination samples (columns x0 .. x0 + 3 of row jj of the tile), packed: the column sums of the row's taps from LDS with their weights,
+ * rounded and divided */
+DEV uint32_t scale_vrow(const LDS_AS ScaleLds *L, const ScaleTile &T, int jj, int x0)
 {
-    const int jj = item >> 4, x0 = 4*(item & 15);
-    if (jj >= T.nrows || x0 >= T.ncols) return;
-    const int n = T.ncols - x0 < 4 ? T.ncols - x0 : 4, l0 = L->rl0[jj], l1 = L->rl1[jj], lbase = L->rl0[0];
+    const int l0 = L->rl0[jj], l1 = L->rl1[jj], lbase = L->rl0[0];
     const uint32_t dh = (uint32_t)T.dh, b0 = (uint32_t)(T.j0 + jj)*(uint32_t)T.sh, b1 = b0 + (uint32_t)T.sh;
     uint32_t acc[4] = { 0, 0, 0, 0 };
     for (int l = l0; l <= l1; l++)
@@ -164,7 +164,16 @@ DEV void scale_vpass(const LDS_AS ScaleLds *L, const ScaleTile &T, GLOBAL_AS uin
     const float rd = 1.0f/(float)area;
     uint32_t o = 0;
     for (int k = 0; k < 4; k++) o |= scl_div(acc[k] + (area >> 1), area, rd) << (8*k);
-    ing_store((gu8 *)dst + (size_t)(T.j0 + jj)*(size_t)T.dw + T.i0 + x0, n, o);
+    return o;
+}
+
+/* step 3, item = row*16 + g: destination samples 4g .. 4g + 3 of one row of the tile into the slot's plane at dst (rows packed) */
+DEV void scale_vpass(const LDS_AS ScaleLds *L, const ScaleTile &T, GLOBAL_AS uint8_t *dst, int item)
+{
+    const int jj = item >> 4, x0 = 4*(item & 15);
+    if (jj >= T.nrows || x0 >= T.ncols) return;
+    const int n = T.ncols - x0 < 4 ? T.ncols - x0 : 4;
+    ing_store((gu8 *)dst + (size_t)(T.j0 + jj)*(size_t)T.dw + T.i0 + x0, n, scale_vrow(L, T, jj, x0));
 }
 
 /* where plane `comp` of the packed I420 slot starts */

@@ -14,6 +14,7 @@
  *                        denoised picture, out of place, one launch per frame in stream order.
  *   h264e_ingest_kernel  device-resident input (enc_ingest.h): one I420 / NV12 / RGB frame in HBM -> the packed I420 input slot.
  *   h264e_scale_kernel   the same for a source of another size (enc_scale.h): a window of an I420 / NV12 frame, box-filtered down to the slot.
+ *   h264e_scale_rgb_kernel  ... of a planar RGB frame (enc_scale_rgb.h): the three channels box-filtered into LDS, converted to I420 from there.
  *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
  *
  * HIP only (hipcc --offload-arch=gfx950).  The host side of the boundary is h264e_pool.h, included at the end; the test-only
@@ -27,6 +28,7 @@
 #include "enc_denoise.h"
 #include "enc_ingest.h"
 #include "enc_scale.h"
+#include "enc_scale_rgb.h"
 #include "enc_scenecut.h"
 #include "../../include/h264e_hip.h"
 
@@ -717,6 +719,28 @@ __global__ void __launch_bounds__(256) h264e_scale_kernel(h264e_scale_src_t S, u
     for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_vpass(L, T, (GLOBAL_AS uint8_t *)(dst + scale_plane_offset(S, comp)), it);
 }
 
+/* planar RGB input of another size (enc_scale_rgb.h): grid.x / grid.y = the tile of 64 x S.th destination pixels, all three output planes
+ * of it.  The taps once, then per channel the horizontal sums and the vertical pass into the LDS tile (hsum is reused, hence the second
+ * barrier), then the conversion from LDS.  Every workgroup reads its own source bytes and writes its own bytes of the slot. */
+__global__ void __launch_bounds__(256) h264e_scale_rgb_kernel(h264e_scale_src_t S, uint8_t *dst)
+{
+    __shared__ __attribute__((aligned(16))) ScaleRgbLds lds;
+    LDS_AS ScaleRgbLds *L = (LDS_AS ScaleRgbLds *)&lds;
+    ScaleTile T;
+    if (!scale_tile(S, 0, (int)blockIdx.x, (int)blockIdx.y, T)) return;
+    scale_tables(&L->s, T, (int)threadIdx.x);
+    __syncthreads();
+    const int items = scale_src_rows(&L->s, T) << 6;
+    for (int ch = 0; ch < 3; ch++)
+    {
+        for (int it = (int)threadIdx.x; it < items; it += 256) scale_hpass(&L->s, S.c[ch], T, it);
+        __syncthreads();
+        for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_rgb_vpass(L, T, ch, it);
+        __syncthreads();
+    }
+    for (int it = (int)threadIdx.x; it < scale_rgb_items(T); it += 256) scale_rgb_convert(L, T, (GLOBAL_AS uint8_t *)dst, it);
+}
+
 /* the luma histogram of one resident input frame (enc_scenecut.h): the plane's dwords are dealt to the workgroups in chunks of 256 lanes x
  * SCENECUT_UNROLL dwords (all loads of a chunk issued before the first sample is counted), every workgroup counts into its own LDS histogram
  * and adds its 64 sums to the frame's record (zeroed by the host in front of the launch) */
@@ -803,6 +827,10 @@ static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStrea
 static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t st)
 {
     hipLaunchKernelGGL(h264e_scale_kernel, dim3((unsigned)((S.dw + SCL_TW - 1)/SCL_TW), (unsigned)((S.dh + S.th - 1)/S.th), 3), dim3(256), 0, st, S, dst);
+}
+static void bk_launch_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t st)
+{
+    hipLaunchKernelGGL(h264e_scale_rgb_kernel, dim3((unsigned)((S.dw + SCL_TW - 1)/SCL_TW), (unsigned)((S.dh + S.th - 1)/S.th), 1), dim3(256), 0, st, S, dst);
 }
 /* one workgroup per chunk, at most 256 (one per CU): at most 256 adders per record word, 254 at 1080p */
 static void bk_launch_scenecut(const uint8_t *luma, uint32_t nbytes, int *record, hipStream_t st)

@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_scale and bk_launch_scenecut; the emulation's versions of those four are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_scale, bk_launch_scale_rgb and bk_launch_scenecut; the emulation's versions of those five are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -14,6 +14,7 @@
 #include "enc_denoise.h"
 #include "enc_ingest.h"
 #include "enc_scale.h"
+#include "enc_scale_rgb.h"
 #include "enc_scenecut.h"
 
 static thread_local char g_err[256];       /* per calling thread */
@@ -720,6 +721,28 @@ static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_
             }
     free(L);
 }
+/* ... and the planar RGB scaler's (enc_scale_rgb.h): per tile the taps, per channel the two passes into the LDS tile, then the conversion */
+static void bk_launch_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t)
+{
+    ScaleRgbLds *L = (ScaleRgbLds *)malloc(sizeof(ScaleRgbLds));
+    if (!L) return;
+    for (int ty = 0; ty < (S.dh + S.th - 1)/S.th; ty++)
+        for (int tx = 0; tx < (S.dw + SCL_TW - 1)/SCL_TW; tx++)
+        {
+            ScaleTile T;
+            if (!scale_tile(S, 0, tx, ty, T)) continue;
+            memset(L, 0xEE, sizeof(*L));
+            for (int t = 0; t < 256; t++) scale_tables(&L->s, T, t);
+            const int items = scale_src_rows(&L->s, T) << 6;
+            for (int ch = 0; ch < 3; ch++)
+            {
+                for (int it = 0; it < items; it++) scale_hpass(&L->s, S.c[ch], T, it);
+                for (int it = 0; it < T.nrows*16; it++) scale_rgb_vpass(L, T, ch, it);
+            }
+            for (int it = 0; it < scale_rgb_items(T); it++) scale_rgb_convert(L, T, dst, it);
+        }
+    free(L);
+}
 #else
 /* the product refuses what the runtime does not know as device memory of this pool's device, and a plane that does not lie inside ONE
  * allocation from its first to its last byte: a host address or a read beyond the allocation is a memory fault in the kernel, not an
@@ -742,20 +765,20 @@ static int ingest_check(const h264e_hip_pool_t *p, int slot, int format, const v
 {
     if (!p || !planes || !strides) FAIL("ingest_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("ingest_device: slot %d outside the %d resident frames", slot, p->frames_resident);
-    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12 && format != H264E_INGEST_RGB) FAIL("ingest_device: unknown format %d", format);
+    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12 && format != H264E_INGEST_RGB && format != H264E_INGEST_RGBP) FAIL("ingest_device: unknown format %d", format);
     if (format == H264E_INGEST_RGB && pixel_bytes != 3 && pixel_bytes != 4) FAIL("ingest_device: RGB pixels of %d bytes (3 or 4)", pixel_bytes);
     memset(S, 0, sizeof(*S));
     S->format = format; S->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1;
     S->width = p->G.width; S->height = p->G.height;
-    const int nplanes = format == H264E_INGEST_I420 ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
+    const int nplanes = format == H264E_INGEST_I420 || format == H264E_INGEST_RGBP ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
     for (int k = 0; k < nplanes; k++)
     {
-        /* bytes and rows of source plane k: RGB pixels; full-size luma; half-size chroma (NV12: U,V pairs, so `width` bytes again) */
-        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12) ? S->width : S->width/2;
+        /* bytes and rows of source plane k: RGB pixels; full-size luma and R, G, B planes; half-size chroma (NV12: U,V pairs, so `width` bytes again) */
+        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP) ? S->width : S->width/2;
         if (!planes[k]) FAIL("ingest_device: plane %d is NULL", k);
         if (strides[k] < row_bytes) FAIL("ingest_device: stride %d of plane %d is below its %d row bytes", strides[k], k, row_bytes);
 #ifndef H264E_EMU
-        const int rows = k == 0 ? S->height : S->height/2;
+        const int rows = k == 0 || format == H264E_INGEST_RGBP ? S->height : S->height/2;
         const void *q = planes[k];
         if (!ingest_is_device_memory(p, q, (size_t)(rows - 1)*(size_t)strides[k] + (size_t)row_bytes))
             FAIL("ingest_device: plane %d (%p, %d rows %d bytes apart) is not memory of device %d, or not inside one allocation", k, planes[k], rows, strides[k], p->device);
@@ -814,7 +837,8 @@ extern "C" int h264e_hip_ingest_device(h264e_hip_pool_t *p, int slot, int format
     return 0;
 }
 
-/* ---- device-resident input of another size (enc_scale.h): one h264e_scale_kernel launch per frame, ordered like the ingest */
+/* ---- device-resident input of another size (enc_scale.h, enc_scale_rgb.h): one h264e_scale_kernel or h264e_scale_rgb_kernel launch per frame,
+ * ordered like the ingest */
 
 /* everything that is refused, without a launch; fills the kernel's view of the source.  win = {src_width, src_height, crop_x, crop_y,
  * crop_width, crop_height}, crop_width 0 = the whole source.  Plane extents come from the SOURCE size and the window: what must be
@@ -823,8 +847,8 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int format, const vo
 {
     if (!p || !planes || !strides || !win) FAIL("scale_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("scale_device: slot %d outside the %d resident frames", slot, p->frames_resident);
-    if (format == H264E_INGEST_RGB) FAIL("scale_device: RGB (format %d) cannot be combined with a window: convert at the picture's size, or hand over I420 / NV12", format);
-    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12) FAIL("scale_device: unknown format %d", format);
+    if (format == H264E_INGEST_RGB) FAIL("scale_device: interleaved RGB (format %d) cannot be combined with a window: convert at the picture's size, or hand over planar RGB (format %d), I420 or NV12", format, H264E_INGEST_RGBP);
+    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12 && format != H264E_INGEST_RGBP) FAIL("scale_device: unknown format %d", format);
     const int srcw = win[0], srch = win[1], dw = p->G.width, dh = p->G.height;
     if (srcw <= 0 || srch <= 0) FAIL("scale_device: source of %d x %d samples", srcw, srch);
     const int cx = win[4] ? win[2] : 0, cy = win[4] ? win[3] : 0, sw = win[4] ? win[4] : srcw, sh = win[4] ? win[5] : srch;
@@ -844,13 +868,15 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int format, const vo
     S->sw = sw; S->sh = sh; S->dw = dw; S->dh = dh;
     S->th = (int)((long long)(SCL_ROWS - 2)*dh/sh);            /* th*sh/dh + 2 source rows at most: <= SCL_ROWS */
     if (S->th > SCL_TH_MAX) S->th = SCL_TH_MAX;
-    const int nplanes = format == H264E_INGEST_I420 ? 3 : 2, cw = (srcw + 1)/2;
+    const int rgbp = format == H264E_INGEST_RGBP;
+    if (rgbp) S->th &= ~1;                                      /* a tile of all three output planes: whole 2x2 blocks (>= 4 rows at 16:1) */
+    const int nplanes = format == H264E_INGEST_NV12 ? 2 : 3, cw = (srcw + 1)/2;
     for (int k = 0; k < nplanes; k++)
     {
-        /* bytes of a source row, and the window in this plane: x0 bytes into row y0, wbytes x rows */
-        const int nv = k && format == H264E_INGEST_NV12;
-        const int row_bytes = k == 0 ? srcw : nv ? 2*cw : cw;
-        const int x0 = k == 0 ? cx : nv ? cx : cx/2, y0 = k == 0 ? cy : cy/2, wbytes = k == 0 ? sw : nv ? sw : sw/2, rows = k == 0 ? sh : sh/2;
+        /* bytes of a source row, and the window in this plane: x0 bytes into row y0, wbytes x rows (planar RGB: every plane as luma) */
+        const int nv = k && format == H264E_INGEST_NV12, full = k == 0 || rgbp;
+        const int row_bytes = full ? srcw : nv ? 2*cw : cw;
+        const int x0 = full ? cx : nv ? cx : cx/2, y0 = full ? cy : cy/2, wbytes = full ? sw : nv ? sw : sw/2, rows = full ? sh : sh/2;
         if (!planes[k]) FAIL("scale_device: plane %d is NULL", k);
         if (strides[k] < row_bytes) FAIL("scale_device: stride %d of plane %d is below the %d bytes of a source row", strides[k], k, row_bytes);
         const uint8_t *lo = (const uint8_t *)planes[k] + (size_t)y0*(size_t)strides[k] + (size_t)x0;
@@ -882,7 +908,8 @@ extern "C" int h264e_hip_scale_device_async(h264e_hip_pool_t *p, int slot, int f
     if (p) HIPCHK(hipSetDevice(p->device));
     if (scale_check(p, slot, format, planes, strides, win, &S)) return -1;
     if (ingest_order(p, producer_stream)) return -1;
-    bk_launch_scale(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
+    if (format == H264E_INGEST_RGBP) bk_launch_scale_rgb(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
+    else bk_launch_scale(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

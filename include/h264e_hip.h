@@ -109,7 +109,8 @@ void h264e_hip_host_free(void *p);
 /* one frame from three planes with arbitrary strides (the H264E_io_yuv_t of the drop-in API) */
 int  h264e_hip_upload_planes(h264e_hip_pool_t *pool, int index, const uint8_t *const yuv[3], const int stride[3]);
 /* Device-resident input (enc_ingest.h): one frame that already lies in this pool's device memory -- format 0 = I420 (three planes),
- * 1 = NV12 (Y, interleaved UV), 2 = interleaved RGB of pixel_bytes 3 or 4 (BT.601 limited range, integer) -- into resident slot `slot`,
+ * 1 = NV12 (Y, interleaved UV), 2 = interleaved RGB of pixel_bytes 3 or 4 (BT.601 limited range, integer), 3 = planar RGB (three planes
+ * R, G, B, the same arithmetic) -- into resident slot `slot`,
  * by ONE kernel launch on the pool's copy stream.  planes / strides: a pointer and a row stride in bytes (>= the row's bytes) per
  * source plane; unused entries are ignored.  producer_stream: the hipStream_t whose queued work writes the source (the launch waits
  * for everything queued there so far), or NULL when the caller has synchronised.  Returns when the slot has been written: the source
@@ -122,9 +123,10 @@ int  h264e_hip_ingest_check(h264e_hip_pool_t *pool, int slot, int format, const 
 int  h264e_hip_ingest_device(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
 int  h264e_hip_ingest_device_async(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
 /* Device-resident input of another size (enc_scale.h): a window of an I420 or NV12 source frame is reduced to the pool's picture by an
- * exact area filter, by ONE kernel launch on the copy stream, ordered and completed like h264e_hip_ingest_device.  win = six ints:
+ * exact area filter, by ONE kernel launch on the copy stream, ordered and completed like h264e_hip_ingest_device.  Planar RGB (format 3,
+ * enc_scale_rgb.h): each channel is reduced by that filter at luma geometry, the result converted as the ingest does.  win = six ints:
  * src_width, src_height, crop_x, crop_y, crop_width, crop_height (crop_width 0 = the whole source).  Refused without a launch, besides
- * what the ingest refuses: RGB, an odd or negative window value, a window that leaves the source, is smaller than the picture, larger
+ * what the ingest refuses: interleaved RGB, an odd or negative window value, a window that leaves the source, is smaller than the picture, larger
  * than 4096 samples or more than 16 times the picture in an axis, and a plane whose bytes from the window's first to its last -- by the
  * SOURCE's size and stride -- are not inside one allocation of the pool's device. */
 int  h264e_hip_scale_check(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], const int *win);

@@ -168,6 +168,9 @@ typedef struct
  *                range in integers: Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16 per pixel; chroma from the rounded 2x2 mean of each
  *                channel, m = (a + b + c + d + 2) >> 2: U = ((-38 Rm - 74 Gm + 112 Bm + 128) >> 8) + 128,
  *                V = ((112 Rm - 94 Gm - 18 Bm + 128) >> 8) + 128 (arithmetic shifts).
+ *          RGBP: plane[0..2] = the R, G and B planes, 8 bits per sample, each with its own pointer and stride (a CHW tensor, three
+ *                allocations, padded or odd strides and addresses); pixel_bytes is ignored.  The same arithmetic: byte for byte what
+ *                RGB gives for the same image.
  * stride: bytes from row to row, at least the row's bytes; no alignment is asked of pointers or strides.  producer_stream: the
  * hipStream_t on which the work that writes the frame was queued -- the encoder waits for everything queued there so far -- or NULL
  * when the caller has synchronised.  Every call that takes such frames returns when they have been read: the memory may be reused
@@ -175,10 +178,11 @@ typedef struct
 #define H264E_DEV_FORMAT_I420 0
 #define H264E_DEV_FORMAT_NV12 1
 #define H264E_DEV_FORMAT_RGB  2
+#define H264E_DEV_FORMAT_RGBP 3
 typedef struct
 {
     int format;                             /* H264E_DEV_FORMAT_* */
-    int pixel_bytes;                        /* RGB: 3 or 4; ignored otherwise */
+    int pixel_bytes;                        /* RGB: 3 or 4; ignored otherwise (RGBP included) */
     const void *plane[3];
     int stride[3];
     void *producer_stream;
@@ -196,7 +200,11 @@ int  H264E_encode_device(H264E_persist_t *enc, H264E_scratch_t *scratch, const H
  *     wx(i,k)  = max(0, min((i+1) Sw, (k+1) Dw) - max(i Sw, k Dw))        (wy(j,l) likewise with Sh, Dh),
  *     out(i,j) = floor((sum_l sum_k wy(j,l) wx(i,k) src(crop_x + k, crop_y + l) + ((Sw Sh) >> 1)) / (Sw Sh)),
  * so equal sizes copy (a pure crop) and 2:1 is (a + b + c + d + 2) >> 2.  Chroma planes: the same with every value halved; the
- * half-sample shift of the chroma siting is ignored.  NV12 chroma is de-interleaved.  Refused (H264E_last_error names the value): RGB
+ * half-sample shift of the chroma siting is ignored.  NV12 chroma is de-interleaved.  RGBP: each of R, G, B is reduced by that filter
+ * from the window to Dw x Dh (rounded to 8 bits, all three at luma geometry), and the conversion above is applied to that RGB picture --
+ * the order a caller scaling and converting in two steps would use; chroma is the matrix of the rounded 2x2 mean of already rounded
+ * samples (tests/rgbp_model.py restates it).  A pure crop equals the plain ingest of the cropped region, a constant colour stays the
+ * same at every ratio.  Refused (H264E_last_error names the value): interleaved RGB
  * with a window, odd or negative crop values, a window that leaves the source, is smaller than the picture in an axis (no upscaling),
  * larger than 4096 samples or more than 16 times the picture in an axis, a stride below the source row's bytes, and planes that are
  * not device memory of the encoder's GPU from the window's first byte to its last. */

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""What device-resident input costs and saves at 1080p (synth_v1, QP 26, GOP 30).  Per format (I420, NV12, RGB 3 and 4 bytes per pixel):
+"""What device-resident input costs and saves at 1080p (synth_v1, QP 26, GOP 30).  Per format (I420, NV12, RGB 3 and 4 bytes per pixel,
+planar RGB from a CHW tensor, and "rgbp_via_permute": the same CHW tensor turned into HWC by torch's permute().contiguous() and handed
+over as interleaved RGB, the two steps the planar format replaces):
 the time per frame of H264E_clip_upload_device over `--frames` frames handed over in one call (one ingest kernel launch per frame, one
 wait at the end: launch + kernel, host wall clock around a call that ends in a device synchronise), next to H264E_clip_upload of the
 same frames from host memory -- the copy it replaces.  Then the per-frame API: H264E_encode (host planes) against H264E_encode_device
@@ -41,9 +43,12 @@ def sources(torch, c, fmt):
     if fmt == "nv12":
         pairs = [M.i420_to_nv12(f, W, H) for f in c]
         return [(torch.from_numpy(y).cuda(), torch.from_numpy(uv).cuda()) for y, uv in pairs], "nv12", c
-    pb = 3 if fmt == "rgb3" else 4
+    pb = 4 if fmt == "rgb4" else 3
     rgb = M.rgb_clip(W, H, 2, pb)
     model = np.stack([M.rgb_to_i420(rgb[i % 2]) for i in range(len(c))])
+    if fmt in ("rgbp", "rgbp_via_permute"):
+        ts = [torch.from_numpy(np.ascontiguousarray(rgb[i].transpose(2, 0, 1))).cuda() for i in range(2)]
+        return [ts[i % 2] for i in range(len(c))], "rgbp", model
     ts = [torch.from_numpy(rgb[i]).cuda() for i in range(2)]
     return [ts[i % 2] for i in range(len(c))], "rgb", model
 
@@ -58,14 +63,17 @@ def main():
     P = pkg.load_pkg()
     c = host_frames(P, max(a.frames, a.perframe))
     line = {"clip": "1080p synth_v1, QP %d, GOP %d" % (QP, GOP), "frames": a.frames, "reps": a.reps, "formats": {}}
-    for fmt in ("i420", "nv12", "rgb3", "rgb4"):
+    for fmt in ("i420", "nv12", "rgb3", "rgb4", "rgbp", "rgbp_via_permute"):
         src, name, model = sources(torch, c[: a.frames], fmt)
         torch.cuda.synchronize()
         ce = P.ClipEncoder(W, H, a.frames, gop=GOP, qp=QP)
         dev_ms, host_ms = [], []
         for _ in range(a.reps + 1):                     # the first repetition warms up (code object, page tables)
             t0 = time.perf_counter()
-            ce.upload_device(src, name)
+            if fmt == "rgbp_via_permute":
+                ce.upload_device([t.permute(1, 2, 0).contiguous() for t in src], "rgb")
+            else:
+                ce.upload_device(src, name)
             t1 = time.perf_counter()
             assert np.array_equal(ce.download(0, 1)[0], model[0])
             t2 = time.perf_counter()

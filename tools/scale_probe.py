@@ -5,7 +5,10 @@ plain ingest (enc_ingest.h) of a 3840x2160 I420 frame, which reads the same 12.4
 (distinct source tensors, one kernel launch each, back to back on the encoder's copy stream); the events are recorded on that stream
 around the launches alone (H264E_clip_input_time).  `--warmup` calls are thrown away, the median of `--reps` calls is reported, the
 cases alternate within every repetition.  The slot of the first frame of every case is compared with tests/scale_model.py before
-anything is timed.  Prints one JSON line.
+anything is timed.  Planar RGB (enc_scale_rgb.h, h264e_scale_rgb_kernel): 3840x2160 "rgbp" -> 1920x1080 from CHW tensors (24.9 MB of
+source), and at 1920x1080 the plain "rgbp" ingest next to the interleaved "rgb" ingest of the same image and to the copy a caller
+without the planar format pays first, torch's permute(1, 2, 0).contiguous() of the CHW frame (torch events around a batch of them).
+Prints one JSON line.
 
     python tools/scale_probe.py [--batch 8] [--reps 25] [--warmup 3]
 """
@@ -20,15 +23,41 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import pkg  # noqa: E402
+import rgbp_model as R  # noqa: E402
 import scale_model as M  # noqa: E402
 
+# name, format, source size, picture size, crop
 CASES = [
-    ("ingest_3840x2160", (3840, 2160), (3840, 2160), None),
-    ("scale_3840x2160_to_1920x1080", (3840, 2160), (1920, 1080), None),
-    ("scale_1920x1080_to_1280x720", (1920, 1080), (1280, 720), None),
-    ("scale_1920x1080_to_640x360", (1920, 1080), (640, 360), None),
-    ("crop_1920x1080_of_3840x2160", (3840, 2160), (1920, 1080), (960, 540, 1920, 1080)),
+    ("ingest_3840x2160", "i420", (3840, 2160), (3840, 2160), None),
+    ("scale_3840x2160_to_1920x1080", "i420", (3840, 2160), (1920, 1080), None),
+    ("scale_1920x1080_to_1280x720", "i420", (1920, 1080), (1280, 720), None),
+    ("scale_1920x1080_to_640x360", "i420", (1920, 1080), (640, 360), None),
+    ("crop_1920x1080_of_3840x2160", "i420", (3840, 2160), (1920, 1080), (960, 540, 1920, 1080)),
+    ("rgbp_scale_3840x2160_to_1920x1080", "rgbp", (3840, 2160), (1920, 1080), None),
+    ("rgbp_crop_1920x1080_of_3840x2160", "rgbp", (3840, 2160), (1920, 1080), (960, 540, 1920, 1080)),
+    ("rgbp_ingest_1920x1080", "rgbp", (1920, 1080), (1920, 1080), None),
+    ("rgb3_ingest_1920x1080", "rgb", (1920, 1080), (1920, 1080), None),
 ]
+
+
+def make_sources(torch, rng, fmt, size, batch):
+    """(host arrays, device tensors) of `batch` distinct random frames"""
+    w, h = size
+    if fmt == "i420":
+        host = [rng.integers(0, 256, (h * 3 // 2, w), dtype=np.uint8) for _ in range(batch)]
+    else:
+        host = [rng.integers(0, 256, (3, h, w), dtype=np.uint8) for _ in range(batch)]
+        if fmt == "rgb":
+            host = [np.ascontiguousarray(x.transpose(1, 2, 0)) for x in host]
+    return host, [torch.from_numpy(x).cuda() for x in host]
+
+
+def model(fmt, host, size, dw, dh, crop, plain):
+    if fmt == "i420":
+        return host.ravel() if plain else M.scale_frame(host, size[0], size[1], dw, dh, crop)
+    if fmt == "rgb":
+        return R.to_i420(host.transpose(2, 0, 1))
+    return R.to_i420(host) if plain else R.scale_to_i420(host, dw, dh, crop)
 
 
 def main():
@@ -42,34 +71,46 @@ def main():
     assert P.load().h264e_hip_device_count() > 0, "no HIP device visible"
     rng = np.random.default_rng(3)
     sources, runs = {}, []
-    for size in sorted({c[1] for c in CASES}):
-        w, h = size
-        host = [rng.integers(0, 256, (h * 3 // 2, w), dtype=np.uint8) for _ in range(a.batch)]
-        sources[size] = (host, [torch.from_numpy(x).cuda() for x in host])
+    for fmt, size in sorted({(c[1], c[2]) for c in CASES}):
+        sources[fmt, size] = make_sources(torch, rng, fmt, size, a.batch)
     torch.cuda.synchronize()
-    for name, size, (dw, dh), crop in CASES:
-        host, dev = sources[size]
+    for name, fmt, size, (dw, dh), crop in CASES:
+        host, dev = sources[fmt, size]
         ce = P.ClipEncoder(dw, dh, a.batch, gop=30, qp=26)
-        kw = {} if name.startswith("ingest") else dict(src_size=size, crop=crop)
-        ce.upload_device(dev, "i420", **kw)
-        want = host[0].ravel() if name.startswith("ingest") else M.scale_frame(host[0], size[0], size[1], dw, dh, crop)
-        assert np.array_equal(ce.download(0, 1)[0], want), name + ": the slot differs from the model"
+        plain = "ingest" in name
+        kw = {} if plain else dict(src_size=size, crop=crop)
+        ce.upload_device(dev, fmt, **kw)
+        assert np.array_equal(ce.download(0, 1)[0], model(fmt, host[0], size, dw, dh, crop, plain)), name + ": the slot differs from the model"
         ce.input_time(True)
-        runs.append((name, ce, dev, kw, []))
+        runs.append((name, fmt, ce, dev, kw, []))
+    chw = sources["rgbp", (1920, 1080)][1]
+    permute_ms, ev = [], (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     for rep in range(a.warmup + a.reps):
-        for name, ce, dev, kw, ms in runs:
+        for name, fmt, ce, dev, kw, ms in runs:
             before = ce.input_time(True)
-            ce.upload_device(dev, "i420", **kw)
+            ce.upload_device(dev, fmt, **kw)
             after = ce.input_time(True)
             assert after[1] - before[1] == a.batch
             if rep >= a.warmup:
                 ms.append((after[0] - before[0]) / a.batch)
+        ev[0].record()
+        hwc = [t.permute(1, 2, 0).contiguous() for t in chw]
+        ev[1].record()
+        ev[1].synchronize()
+        del hwc
+        if rep >= a.warmup:
+            permute_ms.append(ev[0].elapsed_time(ev[1]) / a.batch)
     line = {"batch": a.batch, "reps": a.reps, "warmup": a.warmup, "us_per_frame": {}, "min_max_us": {}}
-    for name, ce, _, _, ms in runs:
-        ce.close()
+    for name, _, ce, _, _, ms in runs + [("torch_permute_contiguous_1920x1080", None, None, None, None, permute_ms)]:
+        if ce is not None:
+            ce.close()
         line["us_per_frame"][name] = round(1e3 * statistics.median(ms), 2)
         line["min_max_us"][name] = [round(1e3 * min(ms), 2), round(1e3 * max(ms), 2)]
-    line["scale_4k_to_1080p_over_ingest_4k"] = round(line["us_per_frame"]["scale_3840x2160_to_1920x1080"] / line["us_per_frame"]["ingest_3840x2160"], 3)
+    us = line["us_per_frame"]
+    line["scale_4k_to_1080p_over_ingest_4k"] = round(us["scale_3840x2160_to_1920x1080"] / us["ingest_3840x2160"], 3)
+    line["rgbp_scale_4k_to_1080p_over_i420_scale"] = round(us["rgbp_scale_3840x2160_to_1920x1080"] / us["scale_3840x2160_to_1920x1080"], 3)
+    line["rgbp_ingest_over_rgb3_ingest_1080p"] = round(us["rgbp_ingest_1920x1080"] / us["rgb3_ingest_1920x1080"], 3)
+    line["permute_then_rgb3_ingest_over_rgbp_ingest_1080p"] = round((us["torch_permute_contiguous_1920x1080"] + us["rgb3_ingest_1920x1080"]) / us["rgbp_ingest_1920x1080"], 3)
     print(json.dumps(line))
 
 
