@@ -195,6 +195,34 @@ def dev_frame(frame, fmt, w, h, stream=None):
     return d, frame
 
 
+MATRIX_UNSPECIFIED, MATRIX_BT709, MATRIX_BT601 = 0, 1, 6       # include/h264e_mi355x.h (H.264 Table E-5)
+_COLORS = {"bt709": (MATRIX_BT709, 0), "bt601": (MATRIX_BT601, 0), "bt709-full": (MATRIX_BT709, 1), "bt601-full": (MATRIX_BT601, 1)}
+
+
+def color_pair(color):
+    """(matrix, full_range) of a colour option: "bt709", "bt601", "bt709-full", "bt601-full", or such a pair (the library checks the values)"""
+    if isinstance(color, str):
+        if color not in _COLORS:
+            raise H264EError("color %r: one of %s, or a (matrix, full_range) pair" % (color, ", ".join(sorted(_COLORS))))
+        return _COLORS[color]
+    try:
+        matrix, full = color
+        return int(matrix), int(full)
+    except (TypeError, ValueError):
+        raise H264EError("color %r: one of %s, or a (matrix, full_range) pair" % (color, ", ".join(sorted(_COLORS))))
+
+
+def fps_pair(fps):
+    """(num, den) of a frame-rate option: an int, or a (num, den) pair"""
+    if isinstance(fps, (tuple, list)):
+        if len(fps) != 2:
+            raise H264EError("fps %r: an int or a (num, den) pair" % (fps,))
+        return int(fps[0]), int(fps[1])
+    if isinstance(fps, bool) or not isinstance(fps, (int, np.integer)):
+        raise H264EError("fps %r: an int or a (num, den) pair" % (fps,))
+    return int(fps), 1
+
+
 def dev_window(src_size, crop, w, h):
     """(DevWindow or None, (width, height) of the frames to describe): None when neither src_size nor crop is given -- the frames have the
     picture's size and go through the plain ingest"""
@@ -258,6 +286,10 @@ def load(path=None):
     L.H264E_set_vbv_state.restype = None
     L.H264E_set_slices.argtypes = [C.c_void_p, C.c_int]
     L.H264E_set_denoise.argtypes = [C.c_void_p, C.c_int]
+    L.H264E_set_color.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.H264E_set_frame_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.H264E_clip_set_color.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.H264E_clip_set_frame_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.H264E_close.argtypes = [C.c_void_p]
     L.H264E_close.restype = None
     L.H264E_set_device.argtypes = [C.c_int]
@@ -309,7 +341,8 @@ def _err(L, what):
 class Encoder:
     """Frame-at-a-time encoder through the reference API: H264E_sizeof -> H264E_init -> H264E_encode."""
 
-    def __init__(self, width, height, gop=20, qp=33, speed=0, kbps=0, const_input=1, vbv_size_bytes=100000 // 8, lib=None, slices=0, denoise=False):
+    def __init__(self, width, height, gop=20, qp=33, speed=0, kbps=0, const_input=1, vbv_size_bytes=100000 // 8, lib=None, slices=0, denoise=False,
+                 color=None, fps=None):
         self.L = load(lib)
         self.w, self.h = width, height
         self.cp = CreateParam(width=width, height=height, gop=gop, vbv_size_bytes=vbv_size_bytes, const_input_flag=const_input,
@@ -328,6 +361,10 @@ class Encoder:
             raise H264EError("H264E_set_slices(%d) refused" % slices)
         if denoise and self.L.H264E_set_denoise(self.persist, 1):       # the reference's temporal_denoise_flag (--denoise)
             raise _err(self.L, "H264E_set_denoise refused")
+        if color is not None:
+            self.set_color(color)
+        if fps is not None:
+            self.set_frame_rate(fps)
         self.rp = RunParam(encode_speed=speed)
         if kbps:
             self.rp.desired_frame_bytes = kbps * 1000 // 8 // 30  # minih264e_test.c:596-600
@@ -378,6 +415,19 @@ class Encoder:
             raise _err(self.L, "H264E_encode_device%s status %d" % ("_scaled" if win is not None else "", st))
         return C.string_at(data, n.value)
 
+    def set_color(self, color):
+        """H264E_set_color: how RGB / RGBP device input is converted and what every SPS signals ("bt709", "bt601", "bt709-full",
+        "bt601-full" or a (matrix, full_range) pair; (0, 0) = the default); only before the first frame."""
+        st = self.L.H264E_set_color(self.persist, *color_pair(color))
+        if st:
+            raise _err(self.L, "H264E_set_color status %d" % st)
+
+    def set_frame_rate(self, fps):
+        """H264E_set_frame_rate: an int or a (num, den) pair, (0, 0) = none; only before the first frame."""
+        st = self.L.H264E_set_frame_rate(self.persist, *fps_pair(fps))
+        if st:
+            raise _err(self.L, "H264E_set_frame_rate status %d" % st)
+
     def set_vbv_state(self, vbv_size_bytes, vbv_fullness_bytes):
         """H264E_set_vbv_state (h264-lab.h:6898-6913)"""
         self.L.H264E_set_vbv_state(self.persist, vbv_size_bytes, vbv_fullness_bytes)
@@ -398,7 +448,8 @@ class ClipEncoder:
     """Whole-clip streaming encode on one GPU (H264E_clip_* extension): consecutive frames as a temporal wavefront."""
 
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
-                 clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0):
+                 clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0,
+                 color=None, fps=None):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
         self.par = ClipParam(width, height, gop, qp, speed, 100000 // 8, device, max_chains, idr_state, (C.c_int32 * 2)(*clusters_in), slices, kbps, resident, keep_records)
@@ -412,6 +463,10 @@ class ClipEncoder:
                 self.set_key_frames(key_frames)
             if scenecut:
                 self.set_scenecut(scenecut)
+            if color is not None:
+                self.set_color(color)
+            if fps is not None:
+                self.set_frame_rate(fps)
         except H264EError:
             self.close()
             raise
@@ -420,6 +475,17 @@ class ClipEncoder:
         """The temporal denoiser (H264E_clip_set_denoise): only while the clip stands at frame 0."""
         if self.L.H264E_clip_set_denoise(self.c, int(bool(on))):
             raise _err(self.L, "H264E_clip_set_denoise")
+
+    def set_color(self, color):
+        """H264E_clip_set_color (see Encoder.set_color): only while the clip stands at frame 0, and BEFORE the frames are uploaded --
+        frames in the input ring keep the bytes they were converted to."""
+        if self.L.H264E_clip_set_color(self.c, *color_pair(color)):
+            raise _err(self.L, "H264E_clip_set_color")
+
+    def set_frame_rate(self, fps):
+        """H264E_clip_set_frame_rate: an int or a (num, den) pair, (0, 0) = none; only while the clip stands at frame 0."""
+        if self.L.H264E_clip_set_frame_rate(self.c, *fps_pair(fps)):
+            raise _err(self.L, "H264E_clip_set_frame_rate")
 
     def set_key_frames(self, frames):
         """Key frames in addition to the periodic ones (H264E_clip_set_key_frames): an ascending list of frame numbers, [] clears it;

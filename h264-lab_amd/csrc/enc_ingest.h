@@ -5,12 +5,14 @@
  *
  *   - I420: three planes, each with its own pointer and stride: a strided copy;
  *   - NV12: a luma plane and one plane of interleaved U,V pairs: the chroma rows are de-interleaved;
- *   - RGB:  interleaved 8-bit R,G,B, pixel_bytes = 3 or 4 (a fourth byte is ignored), BT.601 limited range in integers -- the
- *     reference has no colour conversion, this IS the definition (tests/ingest_model.py restates it):
+ *   - RGB:  interleaved 8-bit R,G,B, pixel_bytes = 3 or 4 (a fourth byte is ignored), BT.601 limited range in integers unless the caller
+ *     chose another matrix -- the reference has no colour conversion, this IS the definition (tests/ingest_model.py restates it):
  *         Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16                                  per pixel,
  *         m = (a + b + c + d + 2) >> 2                                                 per channel over each 2x2 block, then
  *         U = ((-38 Rm - 74 Gm + 112 Bm + 128) >> 8) + 128,  V = ((112 Rm - 94 Gm - 18 Bm + 128) >> 8) + 128
  *     (arithmetic shifts; Y lands in 16..235, U and V in 16..240: nothing to clamp).  Width and height are even, so every block is whole.
+ *     The nine coefficients and the luma offset are launch arguments (h264e_color_t: BT.601 or BT.709, limited or full range, the rows
+ *     of DESIGN.md 4.5f, tests/color_model.py); every row keeps its results inside 8 bits without a clamp.
  *   - RGBP: planar 8-bit R, G, B (a CHW tensor, or three allocations), each plane with its own pointer and stride; the same arithmetic,
  *     so byte for byte what RGB gives for the same image.
  *
@@ -29,12 +31,17 @@
 #define H264E_INGEST_RGB  2
 #define H264E_INGEST_RGBP 3
 
+/* the RGB -> YCbCr matrix in 1/256: Y = ((y . RGB + 128) >> 8) + yo, U = ((u . RGBm + 128) >> 8) + 128, V likewise.  Wave-uniform launch
+ * arguments: they sit in SGPRs and feed the 24-bit multiplies directly (every coefficient is below 2^8 in magnitude) */
+typedef struct { int y[3], u[3], v[3], yo; } h264e_color_t;
+
 typedef struct
 {
     const uint8_t *plane[3];
     int stride[3];                      /* bytes from row to row */
     int format, pixel_bytes;            /* H264E_INGEST_*; bytes per interleaved RGB pixel (3 or 4), ignored otherwise */
     int width, height;                  /* luma samples: both even */
+    h264e_color_t cm;                   /* RGB / RGBP only */
 } h264e_ingest_src_t;
 
 /* the first nb of NB source bytes at p into v, byte k in bits 8*(k & 3) of v[k >> 2]: dwords where p is dword aligned and all NB
@@ -60,59 +67,66 @@ DEV void ing_store(gu8 *d, int n, uint32_t o)
     for (int k = 0; k < 4; k++) if (k < n) d[k] = (uint8_t)(o >> (8*k));
 }
 
-/* the matrix rows: results are in 16..240 by construction (no clamp); the opaque barrier keeps hipcc from folding shift + pack into
- * v_ashr_pk_u8_i32 (tests/test_isa_tripwire.py) */
-DEV uint32_t ing_y(int r, int g, int b) { return (uint32_t)(opaque_int((66*r + 129*g + 25*b + 128) >> 8) + 16); }
-DEV uint32_t ing_u(int r, int g, int b) { return (uint32_t)(opaque_int((-38*r - 74*g + 112*b + 128) >> 8) + 128); }
-DEV uint32_t ing_v(int r, int g, int b) { return (uint32_t)(opaque_int((112*r - 94*g - 18*b + 128) >> 8) + 128); }
+/* the matrix rows: results are in 0..255 by construction of every row the host hands over (no clamp); the opaque barrier keeps hipcc from
+ * folding shift + pack into v_ashr_pk_u8_i32 (tests/test_isa_tripwire.py) */
+DEV int ing_row(const int *c, int r, int g, int b) { return opaque_int((mul24(c[0], r) + mul24(c[1], g) + mul24(c[2], b) + 128) >> 8); }
+DEV uint32_t ing_y(const h264e_color_t &C, int r, int g, int b) { return (uint32_t)(ing_row(C.y, r, g, b) + C.yo); }
+DEV uint32_t ing_u(const h264e_color_t &C, int r, int g, int b) { return (uint32_t)(ing_row(C.u, r, g, b) + 128); }
+DEV uint32_t ing_v(const h264e_color_t &C, int r, int g, int b) { return (uint32_t)(ing_row(C.v, r, g, b) + 128); }
 
 /* PB = bytes per pixel: four luma samples from four pixels */
-template <int PB> DEV uint32_t ing_rgb_luma(const gu8 *p, int n)
+template <int PB> DEV uint32_t ing_rgb_luma(const h264e_color_t &C, const gu8 *p, int n)
 {
     uint32_t v[PB], o = 0;
     ing_fetch<4*PB>(p, n*PB, v);
-    for (int k = 0; k < 4; k++) o |= ing_y(ing_byte(v, PB*k), ing_byte(v, PB*k + 1), ing_byte(v, PB*k + 2)) << (8*k);
+#pragma unroll
+    for (int k = 0; k < 4; k++) o |= ing_y(C, ing_byte(v, PB*k), ing_byte(v, PB*k + 1), ing_byte(v, PB*k + 2)) << (8*k);
     return o;
 }
 
 /* ... and four U and four V samples from the 8 x 2 pixels at p0 (even row) and p1 (the row below it) */
-template <int PB> DEV void ing_rgb_chroma(const gu8 *p0, const gu8 *p1, int n, uint32_t &ou, uint32_t &ov)
+template <int PB> DEV void ing_rgb_chroma(const h264e_color_t &C, const gu8 *p0, const gu8 *p1, int n, uint32_t &ou, uint32_t &ov)
 {
     uint32_t a[2*PB], b[2*PB];
     ing_fetch<8*PB>(p0, 2*n*PB, a);
     ing_fetch<8*PB>(p1, 2*n*PB, b);
     ou = ov = 0;
+#pragma unroll
     for (int k = 0; k < 4; k++)
     {
         int m[3];
+#pragma unroll
         for (int ch = 0; ch < 3; ch++)
             m[ch] = (ing_byte(a, 2*PB*k + ch) + ing_byte(a, 2*PB*k + PB + ch) + ing_byte(b, 2*PB*k + ch) + ing_byte(b, 2*PB*k + PB + ch) + 2) >> 2;
-        ou |= ing_u(m[0], m[1], m[2]) << (8*k);
-        ov |= ing_v(m[0], m[1], m[2]) << (8*k);
+        ou |= ing_u(C, m[0], m[1], m[2]) << (8*k);
+        ov |= ing_v(C, m[0], m[1], m[2]) << (8*k);
     }
 }
 
 /* the same from three planes: four luma samples from the four bytes at r, g and b */
-DEV uint32_t ing_rgbp_luma(const gu8 *r, const gu8 *g, const gu8 *b, int n)
+DEV uint32_t ing_rgbp_luma(const h264e_color_t &C, const gu8 *r, const gu8 *g, const gu8 *b, int n)
 {
     uint32_t v[3], o = 0;
     ing_fetch<4>(r, n, &v[0]);
     ing_fetch<4>(g, n, &v[1]);
     ing_fetch<4>(b, n, &v[2]);
-    for (int k = 0; k < 4; k++) o |= ing_y(ing_byte(&v[0], k), ing_byte(&v[1], k), ing_byte(&v[2], k)) << (8*k);
+#pragma unroll
+    for (int k = 0; k < 4; k++) o |= ing_y(C, ing_byte(&v[0], k), ing_byte(&v[1], k), ing_byte(&v[2], k)) << (8*k);
     return o;
 }
 
 /* four U and four V samples from the 2x2 block means of three channels: a[ch] holds 8 samples of the even row, b[ch] of the row below */
-DEV void ing_rgbp_matrix(const uint32_t a[3][2], const uint32_t b[3][2], uint32_t &ou, uint32_t &ov)
+DEV void ing_rgbp_matrix(const h264e_color_t &C, const uint32_t a[3][2], const uint32_t b[3][2], uint32_t &ou, uint32_t &ov)
 {
     ou = ov = 0;
+#pragma unroll
     for (int k = 0; k < 4; k++)
     {
         int m[3];
+#pragma unroll
         for (int ch = 0; ch < 3; ch++) m[ch] = (ing_byte(a[ch], 2*k) + ing_byte(a[ch], 2*k + 1) + ing_byte(b[ch], 2*k) + ing_byte(b[ch], 2*k + 1) + 2) >> 2;
-        ou |= ing_u(m[0], m[1], m[2]) << (8*k);
-        ov |= ing_v(m[0], m[1], m[2]) << (8*k);
+        ou |= ing_u(C, m[0], m[1], m[2]) << (8*k);
+        ov |= ing_v(C, m[0], m[1], m[2]) << (8*k);
     }
 }
 
@@ -124,9 +138,9 @@ DEV void ingest_luma(const h264e_ingest_src_t &S, GLOBAL_AS uint8_t *dst, int g,
     const int n = S.width - x0 < 4 ? S.width - x0 : 4;
     const gu8 *row = (const gu8 *)S.plane[0] + (size_t)y*(size_t)S.stride[0];
     uint32_t o;
-    if (S.format == H264E_INGEST_RGB) o = S.pixel_bytes == 4 ? ing_rgb_luma<4>(row + (size_t)x0*4, n) : ing_rgb_luma<3>(row + (size_t)x0*3, n);
+    if (S.format == H264E_INGEST_RGB) o = S.pixel_bytes == 4 ? ing_rgb_luma<4>(S.cm, row + (size_t)x0*4, n) : ing_rgb_luma<3>(S.cm, row + (size_t)x0*3, n);
     else if (S.format == H264E_INGEST_RGBP)
-        o = ing_rgbp_luma(row + x0, (const gu8 *)S.plane[1] + (size_t)y*(size_t)S.stride[1] + x0, (const gu8 *)S.plane[2] + (size_t)y*(size_t)S.stride[2] + x0, n);
+        o = ing_rgbp_luma(S.cm, row + x0, (const gu8 *)S.plane[1] + (size_t)y*(size_t)S.stride[1] + x0, (const gu8 *)S.plane[2] + (size_t)y*(size_t)S.stride[2] + x0, n);
     else ing_fetch<4>(row + x0, n, &o);
     ing_store(dst + (size_t)y*(size_t)S.width + x0, n, o);
 }
@@ -141,17 +155,18 @@ DEV void ingest_chroma(const h264e_ingest_src_t &S, GLOBAL_AS uint8_t *dst, int 
     if (S.format == H264E_INGEST_RGB)
     {
         const gu8 *p0 = (const gu8 *)S.plane[0] + (size_t)(2*y)*(size_t)S.stride[0] + (size_t)(2*x0)*(size_t)S.pixel_bytes, *p1 = p0 + S.stride[0];
-        if (S.pixel_bytes == 4) ing_rgb_chroma<4>(p0, p1, n, ou, ov); else ing_rgb_chroma<3>(p0, p1, n, ou, ov);
+        if (S.pixel_bytes == 4) ing_rgb_chroma<4>(S.cm, p0, p1, n, ou, ov); else ing_rgb_chroma<3>(S.cm, p0, p1, n, ou, ov);
     } else if (S.format == H264E_INGEST_RGBP)
     {
         uint32_t a[3][2], b[3][2];
+#pragma unroll
         for (int c = 0; c < 3; c++)
         {
             const gu8 *p0 = (const gu8 *)S.plane[c] + (size_t)(2*y)*(size_t)S.stride[c] + 2*x0;
             ing_fetch<8>(p0, 2*n, a[c]);
             ing_fetch<8>(p0 + S.stride[c], 2*n, b[c]);
         }
-        ing_rgbp_matrix(a, b, ou, ov);
+        ing_rgbp_matrix(S.cm, a, b, ou, ov);
     } else if (S.format == H264E_INGEST_NV12)
     {
         uint32_t v[2];

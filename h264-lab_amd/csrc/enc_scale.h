@@ -50,6 +50,7 @@ typedef struct
     h264e_scale_comp_t c[3];            /* Y, U, V */
     int sw, sh, dw, dh;                 /* luma window and picture, all even; the chroma planes have half of each */
     int th;                             /* destination rows per tile */
+    h264e_color_t cm;                   /* planar RGB only (enc_scale_rgb.h) */
 } h264e_scale_src_t;
 
 typedef struct

@@ -5,7 +5,7 @@
  *
  *     1. each of R, G, B: the window Sw x Sh at (cx, cy) -> Dw x Dh by enc_scale.h's exact area filter, rounded to 8 bits -- all three at
  *        luma geometry;
- *     2. that Dw x Dh RGB picture -> I420 by enc_ingest.h's matrix: Y per pixel, U and V from the rounded 2x2 mean of each (already
+ *     2. that Dw x Dh RGB picture -> I420 by enc_ingest.h's matrix (the launch's h264e_color_t, as there): Y per pixel, U and V from the rounded 2x2 mean of each (already
  *        rounded) channel.  The double rounding of chroma is part of the definition: it is what scaling first and converting afterwards
  *        in two steps gives.
  *
@@ -41,19 +41,19 @@ DEV void scale_rgb_vpass(LDS_AS ScaleRgbLds *L, const ScaleTile &T, int ch, int 
 }
 
 /* luma, item = row*16 + g: samples 4g .. 4g + 3 of one row of the tile into the slot at dst */
-DEV void scale_rgb_luma(const LDS_AS ScaleRgbLds *L, const ScaleTile &T, GLOBAL_AS uint8_t *dst, int item)
+DEV void scale_rgb_luma(const h264e_color_t &C, const LDS_AS ScaleRgbLds *L, const ScaleTile &T, GLOBAL_AS uint8_t *dst, int item)
 {
     const int jj = item >> 4, g = item & 15, x0 = 4*g;
     if (jj >= T.nrows || x0 >= T.ncols) return;
     const int n = T.ncols - x0 < 4 ? T.ncols - x0 : 4;
     const uint32_t r = L->rgb[0][jj][g], gr = L->rgb[1][jj][g], b = L->rgb[2][jj][g];
     uint32_t o = 0;
-    for (int k = 0; k < 4; k++) o |= ing_y(ing_byte(&r, k), ing_byte(&gr, k), ing_byte(&b, k)) << (8*k);
+    for (int k = 0; k < 4; k++) o |= ing_y(C, ing_byte(&r, k), ing_byte(&gr, k), ing_byte(&b, k)) << (8*k);
     ing_store((gu8 *)dst + (size_t)(T.j0 + jj)*(size_t)T.dw + T.i0 + x0, n, o);
 }
 
 /* chroma, item = chroma row*8 + g: samples 4g .. 4g + 3 of one chroma row of the tile, U and V, from rows 2*row and 2*row + 1 of the LDS tile */
-DEV void scale_rgb_chroma(const LDS_AS ScaleRgbLds *L, const ScaleTile &T, GLOBAL_AS uint8_t *dst, int item)
+DEV void scale_rgb_chroma(const h264e_color_t &C, const LDS_AS ScaleRgbLds *L, const ScaleTile &T, GLOBAL_AS uint8_t *dst, int item)
 {
     const int jc = item >> 3, g = item & 7, x0 = 4*g, ccols = T.ncols >> 1, cw = T.dw >> 1, ch = T.dh >> 1;
     if (2*jc >= T.nrows || x0 >= ccols) return;
@@ -61,7 +61,7 @@ DEV void scale_rgb_chroma(const LDS_AS ScaleRgbLds *L, const ScaleTile &T, GLOBA
     uint32_t a[3][2], b[3][2], ou, ov;
     for (int c = 0; c < 3; c++)
         for (int i = 0; i < 2; i++) { a[c][i] = L->rgb[c][2*jc][2*g + i]; b[c][i] = L->rgb[c][2*jc + 1][2*g + i]; }
-    ing_rgbp_matrix(a, b, ou, ov);
+    ing_rgbp_matrix(C, a, b, ou, ov);
     gu8 *du = (gu8 *)dst + (size_t)T.dw*(size_t)T.dh + (size_t)((T.j0 >> 1) + jc)*(size_t)cw + (T.i0 >> 1) + x0;
     ing_store(du, n, ou);
     ing_store(du + (size_t)cw*(size_t)ch, n, ov);
@@ -69,10 +69,10 @@ DEV void scale_rgb_chroma(const LDS_AS ScaleRgbLds *L, const ScaleTile &T, GLOBA
 
 /* the conversion's work items of a tile: nrows*16 luma groups, then (nrows/2)*8 chroma groups */
 DEV int scale_rgb_items(const ScaleTile &T) { return T.nrows*16 + (T.nrows >> 1)*8; }
-DEV void scale_rgb_convert(const LDS_AS ScaleRgbLds *L, const ScaleTile &T, GLOBAL_AS uint8_t *dst, int item)
+DEV void scale_rgb_convert(const h264e_color_t &C, const LDS_AS ScaleRgbLds *L, const ScaleTile &T, GLOBAL_AS uint8_t *dst, int item)
 {
-    if (item < T.nrows*16) scale_rgb_luma(L, T, dst, item);
-    else scale_rgb_chroma(L, T, dst, item - T.nrows*16);
+    if (item < T.nrows*16) scale_rgb_luma(C, L, T, dst, item);
+    else scale_rgb_chroma(C, L, T, dst, item - T.nrows*16);
 }
 
 #endif

@@ -22,6 +22,9 @@
  * --scenecut N switches the scene-cut detector on with threshold N (H264E_clip_set_scenecut; a value that is not a positive number, as in
  * `--scenecut x`, selects H264E_SCENECUT_DEFAULT) and adds ONE stdout line, "scene cuts: f1 f2 ..." or "scene cuts: none".  Both belong
  * to the clip path: with --clip 0, with --gpus stream sharding or on an input that is not seekable they end the run (error line, exit 1).
+ * --colour bt709|bt601|bt709-full|bt601-full and --fps N[/D] say in every SPS what the file's samples are and how fast they play
+ * (H264E_set_color / H264E_set_frame_rate and their clip forms): the input is YUV, so nothing is converted.  They work on both paths and
+ * with --gpus; a value that is not understood ends the run.
  */
 #define _FILE_OFFSET_BITS 64
 #include <math.h>
@@ -36,6 +39,7 @@ static struct
     int have_input, have_output;
     int gop, qp, kbps, max_frames, speed, stats, psnr, device, clip, chains, threads, gpus;
     int scenecut, nkey, key_frames[1024];   /* --scenecut threshold (0 = off), --keyframes list */
+    int matrix, full_range, fps_num, fps_den;   /* --colour, --fps (all 0: nothing is signalled) */
     int unsupported;                    /* a reference option this encoder refuses was given: no stream is written, exit 1 */
 } cmd;
 
@@ -69,6 +73,28 @@ static void parse_long(const char *p, const char *val)
             cmd.key_frames[cmd.nkey++] = (int)f;
             q = *end ? end + 1 : end;
         }
+    }
+    else if (starts("colour", p) || starts("color", p))
+    {
+        static const struct { const char *name; int matrix, full; } names[] = {
+            { "bt709", H264E_MATRIX_BT709, 0 }, { "bt601", H264E_MATRIX_BT601, 0 }, { "bt709-full", H264E_MATRIX_BT709, 1 }, { "bt601-full", H264E_MATRIX_BT601, 1 } };
+        unsigned k;
+        for (k = 0; k < sizeof(names)/sizeof(names[0]) && strcmp(names[k].name, v); k++) {}
+        if (k == sizeof(names)/sizeof(names[0]))
+        {
+            printf("ERROR: --colour takes bt709, bt601, bt709-full or bt601-full, got %s\n", v);
+            cmd.unsupported = 1;
+        } else { cmd.matrix = names[k].matrix; cmd.full_range = names[k].full; }
+    }
+    else if (starts("fps", p))
+    {
+        char *end;
+        const long num = strtol(v, &end, 10), den = *end == '/' ? strtol(end + 1, &end, 10) : 1;
+        if (end == v || *end || num <= 0 || num > (1L << 30) || den <= 0 || den > 0x7fffffffL)
+        {
+            printf("ERROR: --fps takes N or N/D (N up to 2^30), got %s\n", v);
+            cmd.unsupported = 1;
+        } else { cmd.fps_num = (int)num; cmd.fps_den = (int)den; }
     }
     else if (starts("scenecut", p)) cmd.scenecut = atoi(v) > 0 ? atoi(v) : H264E_SCENECUT_DEFAULT;
     else if (starts("gop", p)) cmd.gop = atoi(v);
@@ -122,7 +148,8 @@ static int read_cmdline(int argc, char **argv)
                "Options (every --option takes a value):\n"
                "    --input,  -i <f>  --output, -o <f>  --gop <n>  --qp <n>  --kbps <n>  --maxframes <n>\n"
                "    --speed <n>  --threads <n>  --stats x  --psnr x  --device <n>  --clip 0|1  --chains <n>  --gpus <n>\n"
-               "    --keyframes f1,f2,...  --scenecut <threshold|x>   (clip path only)\n");
+               "    --keyframes f1,f2,...  --scenecut <threshold|x>   (clip path only)\n"
+               "    --colour bt709|bt601|bt709-full|bt601-full  --fps <n[/d]>   (signalled in the SPS; the samples are not touched)\n");
         return 0;
     }
     return 1;
@@ -451,6 +478,8 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
         if (shard_open(s)) goto out;
         if (cmd.nkey && H264E_clip_set_key_frames(s->clip, cmd.key_frames, cmd.nkey)) { printf("ERROR: --keyframes: %s\n", H264E_last_error()); goto out; }
         if (cmd.scenecut && H264E_clip_set_scenecut(s->clip, cmd.scenecut)) { printf("ERROR: --scenecut: %s\n", H264E_last_error()); goto out; }
+        if (cmd.matrix && H264E_clip_set_color(s->clip, cmd.matrix, cmd.full_range)) { printf("ERROR: --colour: %s\n", H264E_last_error()); goto out; }
+        if (cmd.fps_num && H264E_clip_set_frame_rate(s->clip, cmd.fps_num, cmd.fps_den)) { printf("ERROR: --fps: %s\n", H264E_last_error()); goto out; }
         g0 = g1;
     }
     if (nsh == 1) sh[0].rc = shard_encode_from(sh, 0);
@@ -590,6 +619,8 @@ int main(int argc, char **argv)
     error = H264E_init(enc, &create_param);
     if (error) { printf("H264E_init error = %d (%s)\n", error, H264E_last_error()); return 1; }
     if (cmd.threads > 1 && H264E_set_slices(enc, cmd.threads)) { printf("ERROR: --threads %d not supported\n", cmd.threads); return 1; }
+    if (cmd.matrix && H264E_set_color(enc, cmd.matrix, cmd.full_range)) { printf("ERROR: --colour: %s\n", H264E_last_error()); return 1; }
+    if (cmd.fps_num && H264E_set_frame_rate(enc, cmd.fps_num, cmd.fps_den)) { printf("ERROR: --fps: %s\n", H264E_last_error()); return 1; }
 
     for (i = 0; cmd.max_frames; i++)
     {

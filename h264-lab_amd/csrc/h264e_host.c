@@ -160,6 +160,8 @@ typedef struct
 {
     int width, height, nmbx, nmby, nmb, w, h, cropping;
     int vbv_size_bytes, sps_id;
+    /* what the SPS says about the samples (H264E_set_color / _set_frame_rate): all zero = no VUI at all.  seq_init leaves them alone */
+    int matrix, full_range, fps_num, fps_den;
 } seq_t;
 
 static void seq_init(seq_t *s, int width, int height, int vbv, int sps_id)
@@ -183,10 +185,11 @@ static size_t write_sps_pps(const seq_t *s, int pic_init_qp, uint8_t *d, nalu_cb
         { 13, 396, 2000/5, 2376 }, { 20, 396, 2000/5, 2376 }, { 21, 792, 4000/5, 4752 }, { 22, 1620, 4000/5, 8100 },
         { 30, 1620, 10000/5, 8100 }, { 31, 3600, 14000/5, 18000 }, { 32, 5120, 20000/5, 20480 }, { 40, 8192, 25000/5, 32768 },
         { 41, 8192, 62500/5, 32768 }, { 42, 8704, 62500/5, 34816 }, { 50, 22080, 135000/5, 110400 }, { 51, 36864, 240000/5, 184320 } };
-    uint8_t tmp[64];
+    uint8_t tmp[64];                                /* the SPS: at most 13 bytes + 13 of VUI */
     hbits_t b;
     size_t n = 0;
     int k = 0;
+    const int vui = s->matrix || s->fps_num;
     while (lim[k].level < 51 && (s->nmb > lim[k].max_fs || s->vbv_size_bytes > lim[k].max_vbvdiv5*(5*1000/8) ||
                                  (unsigned)s->nmb > lim[k].max_dpb)) k++;
     memset(&b, 0, sizeof(b)); b.buf = tmp;
@@ -204,7 +207,27 @@ static size_t write_sps_pps(const seq_t *s, int pic_init_qp, uint8_t *d, nalu_cb
         hb_ue(&b, 0); hb_ue(&b, (uint32_t)((s->w - s->width) >> 1));
         hb_ue(&b, 0); hb_ue(&b, (uint32_t)((s->h - s->height) >> 1));
     }
-    hb_put(&b, 1, 0);
+    hb_put(&b, 1, (uint32_t)vui);                   /* vui_parameters_present_flag */
+    if (vui)
+    {
+        /* E.1.1 in order: no aspect ratio, no overscan, the signal type with a colour description, no chroma location, the timing
+         * (a frame is two ticks: time_scale = 2 fps), no HRD, no pic_struct, no bitstream restriction */
+        hb_put(&b, 2, 0);
+        hb_put(&b, 1, (uint32_t)(s->matrix != 0));
+        if (s->matrix)
+        {
+            hb_put(&b, 3, 5); hb_put(&b, 1, (uint32_t)s->full_range); hb_put(&b, 1, 1);
+            hb_put(&b, 8, (uint32_t)s->matrix); hb_put(&b, 8, (uint32_t)s->matrix); hb_put(&b, 8, (uint32_t)s->matrix);
+        }
+        hb_put(&b, 1, 0);
+        hb_put(&b, 1, (uint32_t)(s->fps_num != 0));
+        if (s->fps_num)
+        {
+            hb_put(&b, 32, (uint32_t)s->fps_den); hb_put(&b, 32, 2u*(uint32_t)s->fps_num);
+            hb_put(&b, 1, 1);
+        }
+        hb_put(&b, 4, 0);
+    }
     hb_put(&b, 1, 1);
     if (b.n) hb_put(&b, 8 - b.n, 0);
     n += nal_emit(d + n, tmp, b.pos);
@@ -668,6 +691,56 @@ int H264E_set_denoise(H264E_persist_t *p, int on)
     if (on && h264e_hip_denoise_reset(mm.pool)) return H264E_STATUS_BAD_ARGUMENT;
     e->denoise = !!on;
     e->den_started = 0;
+    return H264E_STATUS_SUCCESS;
+}
+
+/* what both encoders refuse of a colour / a frame rate: the offending value goes into the error text, nothing is changed */
+static int color_refused(const char *who, int matrix, int full_range)
+{
+    if (matrix != H264E_MATRIX_UNSPECIFIED && matrix != H264E_MATRIX_BT709 && matrix != H264E_MATRIX_BT601)
+        snprintf(g_host_err, sizeof(g_host_err), "%s: matrix %d (0 = unspecified, 1 = BT.709, 6 = BT.601)", who, matrix);
+    else if (full_range != 0 && full_range != 1) snprintf(g_host_err, sizeof(g_host_err), "%s: full_range %d (0 or 1)", who, full_range);
+    else if (!matrix && full_range) snprintf(g_host_err, sizeof(g_host_err), "%s: full_range %d needs a matrix (1 or 6), not matrix 0", who, full_range);
+    else return 0;
+    return 1;
+}
+static int fps_refused(const char *who, int num, int den)
+{
+    if (!num && !den) return 0;
+    if (num <= 0 || num > (1 << 30)) snprintf(g_host_err, sizeof(g_host_err), "%s: numerator %d (1..2^30, or 0/0 for none)", who, num);
+    else if (den <= 0) snprintf(g_host_err, sizeof(g_host_err), "%s: denominator %d (1..2^31 - 1, or 0/0 for none)", who, den);
+    else return 0;
+    return 1;
+}
+static int color_apply(seq_t *s, h264e_hip_pool_t *pool, int matrix, int full_range)
+{
+    if (h264e_hip_set_color(pool, matrix == H264E_MATRIX_BT709, full_range)) return -1;
+    s->matrix = matrix; s->full_range = full_range;
+    return 0;
+}
+
+/* Colour of the stream: how RGB / RGBP device input is converted from now on, and what every SPS says.  Like
+ * H264E_set_denoise only between H264E_init and the first frame: the SPS is repeated at every key frame and must not change. */
+int H264E_set_color(H264E_persist_t *p, int matrix, int full_range)
+{
+    henc_t *e = (henc_t *)p;
+    impl_t mm;
+    g_host_err[0] = 0;
+    if (!impl_of(e, &mm)) return H264E_STATUS_BAD_PARAMETER;
+    if (e->frames_in) { snprintf(g_host_err, sizeof(g_host_err), "set_color: only before the first frame (%d encoded)", e->frames_in); return H264E_STATUS_BAD_PARAMETER; }
+    if (color_refused("set_color", matrix, full_range)) return H264E_STATUS_BAD_PARAMETER;
+    return color_apply(&e->seq, mm.pool, matrix, full_range) ? H264E_STATUS_BAD_ARGUMENT : H264E_STATUS_SUCCESS;
+}
+
+int H264E_set_frame_rate(H264E_persist_t *p, int num, int den)
+{
+    henc_t *e = (henc_t *)p;
+    impl_t mm;
+    g_host_err[0] = 0;
+    if (!impl_of(e, &mm)) return H264E_STATUS_BAD_PARAMETER;
+    if (e->frames_in) { snprintf(g_host_err, sizeof(g_host_err), "set_frame_rate: only before the first frame (%d encoded)", e->frames_in); return H264E_STATUS_BAD_PARAMETER; }
+    if (fps_refused("set_frame_rate", num, den)) return H264E_STATUS_BAD_PARAMETER;
+    e->seq.fps_num = num; e->seq.fps_den = den;
     return H264E_STATUS_SUCCESS;
 }
 
@@ -1338,6 +1411,27 @@ int H264E_clip_set_denoise(H264E_clip_t *c, int on)
     return 0;
 }
 
+/* Colour and frame rate of the clip's stream (see H264E_set_color): while the clip stands at frame 0; kept across a rewind.  Frames
+ * uploaded before the call keep the bytes they were converted to. */
+int H264E_clip_set_color(H264E_clip_t *c, int matrix, int full_range)
+{
+    g_host_err[0] = 0;
+    if (!c) return -1;
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "clip_set_color: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
+    if (color_refused("clip_set_color", matrix, full_range)) return -1;
+    return color_apply(&c->seq, c->pool, matrix, full_range);
+}
+
+int H264E_clip_set_frame_rate(H264E_clip_t *c, int num, int den)
+{
+    g_host_err[0] = 0;
+    if (!c) return -1;
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "clip_set_frame_rate: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
+    if (fps_refused("clip_set_frame_rate", num, den)) return -1;
+    c->seq.fps_num = num; c->seq.fps_den = den;
+    return 0;
+}
+
 /* The key-frame schedule of the clip: frames[0..n) become key frames in addition to the periodic ones, exactly as
  * H264E_FRAME_TYPE_KEY on those frames does in H264E_encode.  While the clip stands at frame 0; kept across a rewind; n = 0 clears
  * the list.  Refused with keep_records: GOP shards (H264E_clip_revalidate / _restart) assume fixed GOP blocks. */
@@ -1644,7 +1738,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
             {
                 /* the frame as the kernel exported it: complete NALs (start codes and emulation prevention done on the device) */
                 const uint8_t *nals = h264e_hip_stream_rbsp(c->pool, slot);
-                size_t start = pos, w = 0, need = (key ? 64 : 0) + r1.nbytes;
+                size_t start = pos, w = 0, need = (key ? 64 : 0) + r1.nbytes;       /* 64: the parameter sets stay below it with a VUI too (write_sps_pps) */
                 if (r1.in_device)
                 {
                     /* larger than the host-mapped mirror (sized for ordinary frames): copy it from the slot's device NAL arena */

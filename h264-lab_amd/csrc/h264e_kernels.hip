@@ -738,7 +738,7 @@ __global__ void __launch_bounds__(256) h264e_scale_rgb_kernel(h264e_scale_src_t 
         for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_rgb_vpass(L, T, ch, it);
         __syncthreads();
     }
-    for (int it = (int)threadIdx.x; it < scale_rgb_items(T); it += 256) scale_rgb_convert(L, T, (GLOBAL_AS uint8_t *)dst, it);
+    for (int it = (int)threadIdx.x; it < scale_rgb_items(T); it += 256) scale_rgb_convert(S.cm, L, T, (GLOBAL_AS uint8_t *)dst, it);
 }
 
 /* the luma histogram of one resident input frame (enc_scenecut.h): the plane's dwords are dealt to the workgroups in chunks of 256 lanes x

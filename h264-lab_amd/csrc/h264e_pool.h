@@ -17,6 +17,16 @@
 #include "enc_scale_rgb.h"
 #include "enc_scenecut.h"
 
+/* The matrix rows (tests/color_model.py): Kr / Kb scaled by 219/255 and 224/255 (limited) or 1 (full), times 256,
+ * rounded; one coefficient per row moved by 1 so that luma sums to 220 or 256 and chroma to 0 -- grey stays neutral.  Full-range chroma:
+ * the 0.5 weight is 127, not 128 (128 gives 256 for a saturated blue or red), and the nearer of the other two takes the 1, so that no
+ * result leaves 8 bits for any input (tests/test_color_model.py, all 2^24).  Index 2*bt709 + full_range; [0] is the matrix the project had. */
+static const h264e_color_t k_color_rows[4] = {
+    { { 66, 129, 25 }, { -38, -74, 112 }, { 112, -94, -18 }, 16 },
+    { { 77, 150, 29 }, { -43, -84, 127 }, { 127, -107, -20 }, 0 },
+    { { 47, 157, 16 }, { -26, -86, 112 }, { 112, -102, -10 }, 16 },
+    { { 54, 183, 19 }, { -29, -98, 127 }, { 127, -116, -11 }, 0 } };
+
 static thread_local char g_err[256];       /* per calling thread */
 #define FAIL(...) do { snprintf(g_err, sizeof(g_err), __VA_ARGS__); return -1; } while (0)
 extern "C" const char *h264e_hip_last_error(void) { return g_err; }
@@ -159,6 +169,7 @@ struct h264e_hip_pool
     hipEvent_t ev_copy;                  /* the copy stream's uploads, waited for by a denoise / scene-cut launch */
     hipEvent_t ev_sc[2];                 /* around the scene-cut launches of one call (their HIP-event time) */
     int *sc_rec;                         /* device [frames_resident][64]: luma histogram records of the scene-cut detector; NULL until it is switched on */
+    h264e_color_t cm;                    /* the RGB -> YCbCr matrix of the RGB / RGBP ingest and scale launches (h264e_hip_set_color) */
     hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
     hipEvent_t ev_in[2];                 /* h264e_hip_copy_timer_*: around a caller's launches on the copy stream */
     h264e_chain_dev_t *chains_host;      /* host mirror of the device descriptors */
@@ -399,6 +410,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
         if (process_guard_acquire(device)) { free(p); return -1; }
         p->guarded = !share;
     }
+    p->cm = k_color_rows[0];
     if (hipStreamCreate(&p->stream) != hipSuccess || hipStreamCreate(&p->copy_stream) != hipSuccess || hipStreamCreate(&p->abort_stream) != hipSuccess) { if (p->guarded) process_guard_release(device); free(p); FAIL("hipStreamCreate failed"); }
     for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventCreate(&p->ev[i][k]);
     (void)hipEventCreate(&p->ev_t0); (void)hipEventCreate(&p->ev_t1); (void)hipEventCreate(&p->ev_prep); (void)hipEventCreate(&p->ev_copy);
@@ -739,7 +751,7 @@ static void bk_launch_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst, hipStr
                 for (int it = 0; it < items; it++) scale_hpass(&L->s, S.c[ch], T, it);
                 for (int it = 0; it < T.nrows*16; it++) scale_rgb_vpass(L, T, ch, it);
             }
-            for (int it = 0; it < scale_rgb_items(T); it++) scale_rgb_convert(L, T, dst, it);
+            for (int it = 0; it < scale_rgb_items(T); it++) scale_rgb_convert(S.cm, L, T, dst, it);
         }
     free(L);
 }
@@ -760,6 +772,13 @@ static int ingest_is_device_memory(const h264e_hip_pool_t *p, const void *q, siz
 }
 #endif
 
+extern "C" int h264e_hip_set_color(h264e_hip_pool_t *p, int bt709, int full_range)
+{
+    if (!p || (unsigned)bt709 > 1 || (unsigned)full_range > 1) FAIL("set_color: bad argument");
+    p->cm = k_color_rows[2*bt709 + full_range];
+    return 0;
+}
+
 /* everything that is refused, without a launch; fills the kernel's view of the source */
 static int ingest_check(const h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, h264e_ingest_src_t *S)
 {
@@ -770,6 +789,7 @@ static int ingest_check(const h264e_hip_pool_t *p, int slot, int format, const v
     memset(S, 0, sizeof(*S));
     S->format = format; S->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1;
     S->width = p->G.width; S->height = p->G.height;
+    S->cm = p->cm;
     const int nplanes = format == H264E_INGEST_I420 || format == H264E_INGEST_RGBP ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
     for (int k = 0; k < nplanes; k++)
     {
@@ -866,6 +886,7 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int format, const vo
     if (sh > SCL_MAX_RATIO*dh) FAIL("scale_device: window height %d is more than %d times the picture's %d", sh, SCL_MAX_RATIO, dh);
     memset(S, 0, sizeof(*S));
     S->sw = sw; S->sh = sh; S->dw = dw; S->dh = dh;
+    S->cm = p->cm;
     S->th = (int)((long long)(SCL_ROWS - 2)*dh/sh);            /* th*sh/dh + 2 source rows at most: <= SCL_ROWS */
     if (S->th > SCL_TH_MAX) S->th = SCL_TH_MAX;
     const int rgbp = format == H264E_INGEST_RGBP;

@@ -122,6 +122,9 @@ int  h264e_hip_upload_planes(h264e_hip_pool_t *pool, int index, const uint8_t *c
 int  h264e_hip_ingest_check(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes);
 int  h264e_hip_ingest_device(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
 int  h264e_hip_ingest_device_async(h264e_hip_pool_t *pool, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
+/* The matrix that later RGB / RGBP ingest and scale launches of this pool convert with: bt709 0 = BT.601, 1 = BT.709; full_range 0 =
+ * limited (16..235 / 16..240), 1 = full (0..255).  A new pool has (0, 0).  Slots already written keep their bytes. */
+int  h264e_hip_set_color(h264e_hip_pool_t *pool, int bt709, int full_range);
 /* Device-resident input of another size (enc_scale.h): a window of an I420 or NV12 source frame is reduced to the pool's picture by an
  * exact area filter, by ONE kernel launch on the copy stream, ordered and completed like h264e_hip_ingest_device.  Planar RGB (format 3,
  * enc_scale_rgb.h): each channel is reduced by that filter at luma geometry, the result converted as the ingest does.  win = six ints:

@@ -115,6 +115,36 @@ int  H264E_set_slices(H264E_persist_t *enc, int nslices);
  * device and the denoised picture is encoded (the reconstruction still goes back to the caller's planes with const_input_flag = 0);
  * frames with encode_speed >= 2 are encoded raw and leave the state alone.  H264E_STATUS_BAD_PARAMETER after the first frame. */
 int  H264E_set_denoise(H264E_persist_t *enc, int on);
+/* Colour and frame rate of the stream, signalled in the VUI of every SPS (H.264 Annex E); with nothing set the SPS has no VUI and is
+ * byte for byte the reference's.
+ *   matrix: an H.264 matrix_coefficients code (Table E-5).  1 or 6 (a) selects how RGB and RGBP device input is converted from now on, at
+ *   the picture's size and through a window alike, and (b) is written into every SPS as video_signal_type: video_format 5,
+ *   video_full_range_flag = full_range, and a colour description with colour_primaries = transfer_characteristics = matrix_coefficients
+ *   = matrix.  For I420, NV12 and host input the call only says what the caller's samples are: they are not touched.  (0, 0) returns to
+ *   the default -- BT.601 limited conversion, nothing signalled; (0, 1) and every other matrix value are refused.
+ *   The conversion keeps the form above, Y = ((yr R + yg G + yb B + 128) >> 8) + yo, U and V from the rounded 2x2 means + 128:
+ *       matrix 6 limited (= 0)   66 129  25, 16    -38  -74 112    112  -94 -18
+ *       matrix 1 limited         47 157  16, 16    -26  -86 112    112 -102 -10
+ *       matrix 6 full            77 150  29,  0    -43  -84 127    127 -107 -20
+ *       matrix 1 full            54 183  19,  0    -29  -98 127    127 -116 -11
+ *   (Kr / Kb scaled by 219/255 and 224/255, or by 1, times 256, rounded; one coefficient per row moved by 1 so that luma sums to 220 or
+ *   256 and chroma to 0; in full-range chroma the 0.5 weight is 127, since 128 would give 256 for a saturated blue or red, and the
+ *   nearer neighbour takes the 1.  Grey stays neutral and no result leaves 16..235 / 16..240, or 0..255 -- there is no clamp;
+ *   tests/color_model.py restates it and proves the ranges over all 2^24 inputs).  With a window: scale each channel, round to 8 bits,
+ *   then this matrix.
+ *   frame rate num/den, 0 < num <= 2^30, 0 < den < 2^31: timing_info with num_units_in_tick = den, time_scale = 2 num,
+ *   fixed_frame_rate_flag = 1; 0/0 clears it.
+ * The SPS is repeated at every key frame and must not change inside a stream: the per-frame calls are accepted after H264E_init and
+ * before the first H264E_encode* only (H264E_STATUS_BAD_PARAMETER afterwards, as H264E_set_denoise), the clip calls only while the
+ * clip stands at frame 0 (after open or rewind; a rewind keeps the setting; 0 = done, -1 = refused).  Frames already uploaded were
+ * converted with the setting that held at their upload: change the colour BEFORE uploading.  A refusal changes nothing and names the
+ * offending value in H264E_last_error.  With rate control the parameter sets count in the frame's bytes as in the reference, so a
+ * signalled stream may differ from an unsignalled one behind the first key frame. */
+#define H264E_MATRIX_UNSPECIFIED 0
+#define H264E_MATRIX_BT709       1
+#define H264E_MATRIX_BT601       6
+int  H264E_set_color(H264E_persist_t *enc, int matrix, int full_range);
+int  H264E_set_frame_rate(H264E_persist_t *enc, int num, int den);
 /* Select the HIP device used by subsequent H264E_init calls of this process (default 0 / $H264E_DEVICE). */
 void H264E_set_device(int device);
 int  H264E_device_count(void);
@@ -165,7 +195,7 @@ typedef struct
  *   format I420: plane[0..2] = Y, U, V, each with its own stride (separately allocated, padded planes are fine);
  *          NV12: plane[0] = Y, plane[1] = interleaved U,V pairs;
  *          RGB:  plane[0] = interleaved 8-bit R,G,B of pixel_bytes 3 or 4 (a fourth byte is ignored), converted to BT.601 limited
- *                range in integers: Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16 per pixel; chroma from the rounded 2x2 mean of each
+ *                range in integers (another matrix or full range: H264E_set_color): Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16 per pixel; chroma from the rounded 2x2 mean of each
  *                channel, m = (a + b + c + d + 2) >> 2: U = ((-38 Rm - 74 Gm + 112 Bm + 128) >> 8) + 128,
  *                V = ((112 Rm - 94 Gm - 18 Bm + 128) >> 8) + 128 (arithmetic shifts).
  *          RGBP: plane[0..2] = the R, G and B planes, 8 bits per sample, each with its own pointer and stride (a CHW tensor, three
@@ -271,6 +301,9 @@ void H264E_clip_set_ssd_output(H264E_clip_t *clip, uint64_t *ssd);
  * made again from the first frame that is uploaded again.  The sums of squared differences compare the RAW input with the
  * reconstruction, as the reference's --psnr does.  Refused with keep_records (GOP shards).  0 = done, -1 = refused. */
 int  H264E_clip_set_denoise(H264E_clip_t *clip, int on);
+/* H264E_set_color / H264E_set_frame_rate for the clip encoder (see there) */
+int  H264E_clip_set_color(H264E_clip_t *clip, int matrix, int full_range);
+int  H264E_clip_set_frame_rate(H264E_clip_t *clip, int num, int den);
 /* Key frames where the caller wants them (a receiver asked for one, a splice point, a chapter mark): frames[0..n) (ascending, inside
  * the clip) are coded as key frames in addition to the periodic ones.  The stream is exactly what H264E_encode writes for the same
  * pictures with frame_type = H264E_FRAME_TYPE_KEY on the listed frames and H264E_FRAME_TYPE_DEFAULT on all others (h264-lab.h:6725-6775,

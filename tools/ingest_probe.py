@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What device-resident input costs and saves at 1080p (synth_v1, QP 26, GOP 30).  Per format (I420, NV12, RGB 3 and 4 bytes per pixel,
-planar RGB from a CHW tensor, and "rgbp_via_permute": the same CHW tensor turned into HWC by torch's permute().contiguous() and handed
+planar RGB from a CHW tensor with the default matrix and with BT.709 full range ("rgbp_bt709_full", H264E_clip_set_color), and "rgbp_via_permute": the same CHW tensor turned into HWC by torch's permute().contiguous() and handed
 over as interleaved RGB, the two steps the planar format replaces):
 the time per frame of H264E_clip_upload_device over `--frames` frames handed over in one call (one ingest kernel launch per frame, one
 wait at the end: launch + kernel, host wall clock around a call that ends in a device synchronise), next to H264E_clip_upload of the
@@ -21,6 +21,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import color_model as CM  # noqa: E402
 import ingest_model as M  # noqa: E402
 import pkg  # noqa: E402
 
@@ -45,8 +46,8 @@ def sources(torch, c, fmt):
         return [(torch.from_numpy(y).cuda(), torch.from_numpy(uv).cuda()) for y, uv in pairs], "nv12", c
     pb = 4 if fmt == "rgb4" else 3
     rgb = M.rgb_clip(W, H, 2, pb)
-    model = np.stack([M.rgb_to_i420(rgb[i % 2]) for i in range(len(c))])
-    if fmt in ("rgbp", "rgbp_via_permute"):
+    model = np.stack([CM.rgb_to_i420(rgb[i % 2], *((1, 1) if fmt == "rgbp_bt709_full" else (0, 0))) for i in range(len(c))])
+    if fmt in ("rgbp", "rgbp_bt709_full", "rgbp_via_permute"):
         ts = [torch.from_numpy(np.ascontiguousarray(rgb[i].transpose(2, 0, 1))).cuda() for i in range(2)]
         return [ts[i % 2] for i in range(len(c))], "rgbp", model
     ts = [torch.from_numpy(rgb[i]).cuda() for i in range(2)]
@@ -63,10 +64,10 @@ def main():
     P = pkg.load_pkg()
     c = host_frames(P, max(a.frames, a.perframe))
     line = {"clip": "1080p synth_v1, QP %d, GOP %d" % (QP, GOP), "frames": a.frames, "reps": a.reps, "formats": {}}
-    for fmt in ("i420", "nv12", "rgb3", "rgb4", "rgbp", "rgbp_via_permute"):
+    for fmt in ("i420", "nv12", "rgb3", "rgb4", "rgbp", "rgbp_bt709_full", "rgbp_via_permute"):
         src, name, model = sources(torch, c[: a.frames], fmt)
         torch.cuda.synchronize()
-        ce = P.ClipEncoder(W, H, a.frames, gop=GOP, qp=QP)
+        ce = P.ClipEncoder(W, H, a.frames, gop=GOP, qp=QP, color="bt709-full" if fmt == "rgbp_bt709_full" else None)
         dev_ms, host_ms = [], []
         for _ in range(a.reps + 1):                     # the first repetition warms up (code object, page tables)
             t0 = time.perf_counter()

@@ -22,8 +22,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import color_model as CM  # noqa: E402
 import pkg  # noqa: E402
-import rgbp_model as R  # noqa: E402
 import scale_model as M  # noqa: E402
 
 # name, format, source size, picture size, crop
@@ -37,6 +37,10 @@ CASES = [
     ("rgbp_crop_1920x1080_of_3840x2160", "rgbp", (3840, 2160), (1920, 1080), (960, 540, 1920, 1080)),
     ("rgbp_ingest_1920x1080", "rgbp", (1920, 1080), (1920, 1080), None),
     ("rgb3_ingest_1920x1080", "rgb", (1920, 1080), (1920, 1080), None),
+    # the same launches with a matrix that is not the default (H264E_clip_set_color): the coefficients are launch arguments either way
+    ("rgbp_scale_3840x2160_to_1920x1080_bt709_full", "rgbp", (3840, 2160), (1920, 1080), None),
+    ("rgbp_ingest_1920x1080_bt709_full", "rgbp", (1920, 1080), (1920, 1080), None),
+    ("rgb3_ingest_1920x1080_bt709_full", "rgb", (1920, 1080), (1920, 1080), None),
 ]
 
 
@@ -52,12 +56,12 @@ def make_sources(torch, rng, fmt, size, batch):
     return host, [torch.from_numpy(x).cuda() for x in host]
 
 
-def model(fmt, host, size, dw, dh, crop, plain):
+def model(fmt, host, size, dw, dh, crop, plain, color=(0, 0)):
     if fmt == "i420":
         return host.ravel() if plain else M.scale_frame(host, size[0], size[1], dw, dh, crop)
     if fmt == "rgb":
-        return R.to_i420(host.transpose(2, 0, 1))
-    return R.to_i420(host) if plain else R.scale_to_i420(host, dw, dh, crop)
+        return CM.to_i420(np.ascontiguousarray(host.transpose(2, 0, 1)), *color)
+    return CM.to_i420(host, *color) if plain else CM.scale_to_i420(host, dw, dh, crop, *color)
 
 
 def main():
@@ -76,11 +80,12 @@ def main():
     torch.cuda.synchronize()
     for name, fmt, size, (dw, dh), crop in CASES:
         host, dev = sources[fmt, size]
-        ce = P.ClipEncoder(dw, dh, a.batch, gop=30, qp=26)
+        color = (1, 1) if name.endswith("_bt709_full") else (0, 0)
+        ce = P.ClipEncoder(dw, dh, a.batch, gop=30, qp=26, color=color)
         plain = "ingest" in name
         kw = {} if plain else dict(src_size=size, crop=crop)
         ce.upload_device(dev, fmt, **kw)
-        assert np.array_equal(ce.download(0, 1)[0], model(fmt, host[0], size, dw, dh, crop, plain)), name + ": the slot differs from the model"
+        assert np.array_equal(ce.download(0, 1)[0], model(fmt, host[0], size, dw, dh, crop, plain, color)), name + ": the slot differs from the model"
         ce.input_time(True)
         runs.append((name, fmt, ce, dev, kw, []))
     chw = sources["rgbp", (1920, 1080)][1]
