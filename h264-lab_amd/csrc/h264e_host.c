@@ -294,6 +294,15 @@ static size_t emit_slices(uint8_t *d, size_t cap, const uint8_t *nals, const h26
     return pos;
 }
 
+/* where a finished frame's NALs are: in the slot's host-mapped mirror, or -- larger than the mirror, which is sized for ordinary
+ * frames -- copied from the slot's device NAL arena into buf.  NULL when buf cannot hold them or the copy fails */
+static const uint8_t *frame_nals(h264e_hip_pool_t *pool, int slot, const h264e_hip_result_t *r, uint8_t *buf, size_t buf_cap)
+{
+    if (!r->in_device) return h264e_hip_stream_rbsp(pool, slot);
+    if (!buf || r->nbytes > buf_cap || h264e_hip_stream_fetch_nals(pool, slot, buf, r->nbytes)) return NULL;
+    return buf;
+}
+
 /* ------------------------------------------------------------------ mv_clusters validation */
 
 static int mvx(int32_t v) { return (int16_t)(v & 0xffff); }
@@ -870,13 +879,9 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
     if (!den && put_frame(m->pool, in, dev, win)) return H264E_STATUS_BAD_ARGUMENT;
     if (frame_exact(m->pool, &task, e->seq.nmbx, e->seq.nmby, e->clusters) || h264e_hip_stream_done(m->pool, 0, &res) != 1) return H264E_STATUS_BAD_ARGUMENT;
     {
-        const uint8_t *nals = h264e_hip_stream_rbsp(m->pool, 0);
+        const uint8_t *nals = frame_nals(m->pool, 0, &res, m->rbsp, m->rbsp_cap);
         size_t w;
-        if (res.in_device)
-        {
-            if (res.nbytes > m->rbsp_cap || h264e_hip_stream_fetch_nals(m->pool, 0, m->rbsp, res.nbytes)) return H264E_STATUS_BAD_ARGUMENT;
-            nals = m->rbsp;
-        }
+        if (!nals) return H264E_STATUS_BAD_ARGUMENT;
         w = emit_slices(out + out_pos, cap - out_pos, nals, &res, opt->nalu_callback, opt->nalu_callback_token);
         if (!w)
         {
@@ -1511,13 +1516,15 @@ int H264E_clip_scenecut_time(H264E_clip_t *c, double *kernel_ms, long long *fram
     return 0;
 }
 
-/* the detector's pre-pass: the histograms of the frames uploaded so far and not yet analysed, read back, D(f) from consecutive
- * records, and the schedule with the cuts among them -- all before the tasks of the launch that first encodes them are built */
-static int clip_scenecut_analyse(H264E_clip_t *c, int limit)
+/* the pre-pass in front of the tasks, the detector: the histograms of the frames uploaded so far and not yet analysed, read back, D(f)
+ * from consecutive records, and the schedule with the cuts among them -- all before the tasks of the launch that first encodes them
+ * are built */
+static int clip_prepass_scenecut(H264E_clip_t *c, int limit)
 {
     const int a = c->sc_done;
     float ms = 0;
     int f, b;
+    if (!c->scenecut || a >= limit) return 0;
     if (limit - a > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "scenecut: frames %d..%d do not fit the input ring", a, limit - 1); return -1; }
     if (h264e_hip_scenecut_frames(c->pool, a % c->resident, limit - a, c->sc_hist + (size_t)a*64, &ms)) return -1;
     for (f = a; f < limit; f++)
@@ -1535,343 +1542,427 @@ static int clip_scenecut_analyse(H264E_clip_t *c, int limit)
 
 int H264E_clip_stamps(H264E_clip_t *c, unsigned long long *dst) { return c ? h264e_hip_stamps_read(c->pool, dst, 1) : -1; }
 
-int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_bytes, int *frame_bytes, int profile, H264E_clip_stats_t *st)
+/* ---- H264E_clip_encode: launches until the uploaded frames are encoded or the caller's buffer is full; every launch is
+ * plan -> pre-pass -> submit -> consume -> settle -> adapt */
+
+#define CLIP_RC_DEPTH_MAX 8     /* rate control: frames per launch, at most (H264E_RC_DEPTH) */
+#define CLIP_HEDGE_MAX 32       /* ... and hedge leaves */
+
+/* what a consumed frame means for its launch; the stops in the words of the H264E_DEBUG line */
+typedef enum
 {
-    const int nmb = c->seq.nmb, K = c->ring, no_deblock = (c->par.speed == 8 || c->par.speed == 10);
-    const int nslices = c->par.slices > 1 ? imin(imin(c->par.slices, H264E_HIP_MAX_SLICES), c->seq.nmby) : 1;
+    CLIP_GO_ON,                 /* accepted: on to the chain's next frame, if there is one */
+    CLIP_TAKE_LEAF,             /* accepted, and the frame behind it got another QP than the exact one: the leaf that has it comes next */
+    CLIP_STOP_LEAF_LOST, CLIP_STOP_MISSPEC, CLIP_STOP_QP_MISS, CLIP_STOP_QP_LEAF, CLIP_STOP_FULL,
+    CLIP_RELAUNCH,              /* a bounded wait expired on the device: the frames accepted so far stand, the others are launched again */
+    CLIP_ERROR
+} clip_step_t;
+static const char *const k_clip_ended_by[CLIP_ERROR] = {
+    [CLIP_GO_ON] = "all frames delivered",
+    [CLIP_STOP_LEAF_LOST] = "the hedge leaf with the exact QP did not complete (its own mv_clusters validation, or stopped)",
+    [CLIP_STOP_MISSPEC] = "mv_clusters mis-speculation",
+    [CLIP_STOP_QP_MISS] = "QP miss, no hedge leaf with the exact QP",
+    [CLIP_STOP_QP_LEAF] = "QP miss covered by a hedge leaf (nothing behind a leaf)",
+    [CLIP_STOP_FULL] = "output buffer full",
+    [CLIP_RELAUNCH] = "all frames delivered" };     /* (the line has always said so: the expired wait is in the error text and in spin_relaunches) */
+
+/* one H264E_clip_encode call: what it was given, the constants it derives from the clip's parameters, what it keeps from launch to launch */
+typedef struct
+{
+    uint8_t *out; size_t cap, pos;
+    int *frame_bytes;                       /* [frame - first], or NULL */
+    int first;                              /* the call's first frame */
+    int nslices, no_deblock, idr_state;
     /* frame-level rate control (encode_app --kbps, minih264e_test.c:596-600: desired_frame_bytes = kbps*1000/8/30, QP 10..50):
      * a frame's QP is a function of the byte count of the frame before it (h264-lab.h:5924-6141) and moves almost every
-     * frame: the frames behind the first one of a launch run on a speculated QP (see the launch loop), the controller on the host */
-    const int rc_on = c->rc_on, desired_frame_bytes = c->par.kbps > 0 ? c->par.kbps*1000/8/30 : 0;
-    const int qp_min = rc_on ? 10 : c->par.qp, qp_max = c->par.kbps > 0 ? 50 : rc_on ? 51 : c->par.qp;     /* qp 0: 10..51, h264-lab.h:6707-6715 */
-    const int pic_init_qp = imax(imin(30, qp_max), qp_min);     /* h264-lab.h:6768-6770 */
-    const int idr_state = c->par.first_idr_pic_id_state & 1;
-    const int first = c->next;
+     * frame: the frames behind the first one of a launch run on a speculated QP (clip_plan_launch), the controller on the host */
+    int desired_frame_bytes, qp_min, qp_max, pic_init_qp;
+    uint16_t qdat_i[2][42], qdat_p[2][42];  /* constant QP: the quantizer tables of every I / P frame */
+    int spin_retries;                       /* launches in a row that a bounded wait ended before a single frame got through */
+    long long far_reads;                    /* of the last launch that delivered its first frame */
+    H264E_clip_stats_t stats;
+} clip_call_t;
+
+/* one launch: the plan -- frames n .. n + F - 1 are tasks 0 .. F - 1 (the chain), task F + k is hedge leaf k -- and how it went */
+typedef struct
+{
+    int n, limit;                           /* first frame; frames [n, limit) were uploaded when the launch was planned */
+    int F, nh;                              /* frames in the chain, hedge leaves */
+    int qp_task[CLIP_RC_DEPTH_MAX];         /* rate control: the QP the chain's frames were given */
+    int hedge_level[CLIP_HEDGE_MAX], hedge_qp[CLIP_HEDGE_MAX];      /* the chain index of the frame a leaf encodes, and its QP */
+    int after_stop;                         /* follows a launch that was stopped (mis-speculation, rate-control miss): its first frame pays the refill */
+    double t_submit, t_first, t_last;       /* submit; first and last frame consumed */
+    int nvalid;                             /* frames accepted */
+    int leaf;                               /* CLIP_TAKE_LEAF: the task to take */
+    int moved_from, moved_to;               /* an accepted leaf's slot, and the slot its frame number owns */
+    clip_step_t step;                       /* of the last frame consumed: what ended the launch */
+} clip_launch_t;
+
+/* a failure between submit and sync gives the device's launch lock back; the statistics so far go out either way */
+static int clip_end(H264E_clip_t *c, const clip_call_t *x, H264E_clip_stats_t *st, int rc)
+{
+    if (rc) h264e_hip_release(c->pool);
+    if (st) *st = x->stats;
+    return rc;
+}
+
+/* stop the running launch and wait until it is gone, whatever either call answers: the failure has been reported */
+static clip_step_t clip_abort_launch(H264E_clip_t *c)
+{
+    (void)h264e_hip_stream_abort(c->pool);
+    (void)h264e_hip_sync(c->pool);
+    return CLIP_ERROR;
+}
+
+/* a task's QP: quantizer tables and slice header.  frame_num restarts at every key frame; idr_pic_id toggles with every key frame
+ * (h264-lab.h:6774-6775) */
+static void clip_task_set_qp(const H264E_clip_t *c, const clip_call_t *x, h264e_hip_task_t *t, int f, int qp)
+{
+    const struct clip_sched *s = c->sched + f;
+    t->qp = qp;
+    if (c->rc_on) build_qdat(t->qdat, qp, !s->key);
+    else memcpy(t->qdat, s->key ? x->qdat_i : x->qdat_p, sizeof(t->qdat));
+    slice_header_bits(&c->seq, s->key, s->frame_num, x->idr_state ^ s->idr, qp, x->pic_init_qp, x->no_deblock, x->nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
+}
+
+/* the launch that starts at frame l->n: how many frames, and their tasks */
+static void clip_plan_launch(H264E_clip_t *c, const clip_call_t *x, clip_launch_t *l)
+{
+    const struct clip_sched *sched = c->sched;
+    const int nmb = c->seq.nmb, K = c->ring, n = l->n, rc_on = c->rc_on;
+    /* rate control: frame n+1's QP is a function of frame n's size (h264-lab.h:5924-6141), so the frames behind the first one of
+     * a launch run on a SPECULATED QP: the controller is run ahead on predicted sizes (the last frame of the same kind); when a
+     * frame's real size is in, the exact QP of the next one is computed and compared with what it was given -- a mismatch stops
+     * the launch there (measured hit rates of the one-ahead guess: 15-66 %) */
+    const int rc_depth = imax(1, imin(CLIP_RC_DEPTH_MAX, getenv("H264E_RC_DEPTH") ? atoi(getenv("H264E_RC_DEPTH")) : (nmb >= 60000 ? 3 : 6)));     /* measured optima: 8K 3, below 6 */
+    const int F = rc_on ? imax(1, imin(imin(K - 1, rc_depth), l->limit - n)) : imin(imin(K - 1, c->launch_frames), l->limit - n);
     h264e_hip_task_t *tasks = c->tasks;
     int32_t (*used)[2] = c->used;
-    long long far_reads = 0;
-    uint16_t qdat_i[2][42], qdat_p[2][42];
-    size_t pos = 0;
-    int rc = -1, i, full = 0, qp = c->rc_qp, spin_retries = 0;
-    H264E_clip_stats_t stats;
-    double t0;
-    memset(&stats, 0, sizeof(stats));
-    g_host_err[0] = 0;
-    build_qdat(qdat_i, qp, 0);
-    build_qdat(qdat_p, qp, 1);
-    h264e_hip_profile(c->pool, profile);
-    stats.chains = K - 1;
-    stats.first_frame = first;
-
-    while (c->next < c->avail && !full)
+    rc_t rc_ahead;
+    int i, qp = c->rc_qp;
+    memset(tasks, 0, sizeof(*tasks)*(size_t)K);
+    if (rc_on && c->rc_frame != n)
     {
-        const int n = c->next, limit = c->avail;       /* frames uploaded from the idle hook during this launch join the next one */
-        /* with --psnr style statistics every frame's picture must still be in its slot when the launch has drained */
-        /* rate control: frame n+1's QP is a function of frame n's size (h264-lab.h:5924-6141), so the frames behind the first one of
-         * a launch run on a SPECULATED QP: the controller is run ahead on predicted sizes (the last frame of the same kind); when a
-         * frame's real size is in, the exact QP of the next one is computed and compared with what it was given -- a mismatch stops
-         * the launch there (measured hit rates of the one-ahead guess: 15-66 %) */
-        const int rc_depth = imax(1, imin(8, getenv("H264E_RC_DEPTH") ? atoi(getenv("H264E_RC_DEPTH")) : (nmb >= 60000 ? 3 : 6)));     /* measured optima: 8K 3, below 6 */
-        const int F = rc_on ? imax(1, imin(imin(K - 1, rc_depth), limit - n)) : imin(imin(K - 1, c->launch_frames), limit - n);
-        int qp_task[8];
-        rc_t rc_ahead;
-        int nvalid = 0;
-        const struct clip_sched *sched = c->sched;
-        t0 = now_ms();
-        /* scene cuts among the frames this launch may hold are in the schedule before its tasks are built */
-        if (c->scenecut && c->sc_done < limit && clip_scenecut_analyse(c, limit)) goto done;
-        memset(tasks, 0, sizeof(*tasks)*(size_t)K);
-        if (rc_on) qp = c->rc_qp;               /* (the task loop of the previous launch left a speculated value here) */
-        if (rc_on && c->rc_frame != n)
+        qp = c->rc_qp = rc_frame_start(&c->rcs, c->par.gop, nmb, c->par.vbv_size_bytes, x->desired_frame_bytes, x->qp_min, x->qp_max, sched[n].key);
+        c->rc_frame = n;
+    }
+    rc_ahead = c->rcs;
+    for (i = 0; i < F; i++)
+    {
+        h264e_hip_task_t *t = tasks + i;
+        const int f = n + i, key = sched[f].key;
+        if (rc_on)
         {
-            const int key = sched[n].key;
-            qp = c->rc_qp = rc_frame_start(&c->rcs, c->par.gop, nmb, c->par.vbv_size_bytes, desired_frame_bytes, qp_min, qp_max, key);
-            build_qdat(key ? qdat_i : qdat_p, qp, !key);
-            c->rc_frame = n;
-        } else if (rc_on)
-            build_qdat(sched[n].key ? qdat_i : qdat_p, qp, !sched[n].key);
-        rc_ahead = c->rcs;
-        for (i = 0; i < F; i++)
-        {
-            h264e_hip_task_t *t = tasks + i;
-            const int f = n + i, key = sched[f].key;
-            if (rc_on && i > 0)
+            if (i > 0)
             {
                 /* the controller, run ahead: the frame in front is predicted to weigh what the last frame of its kind did */
-                const int pkey = sched[f - 1].key, pred = c->rc_last_bytes[pkey] > 0 ? c->rc_last_bytes[pkey] : desired_frame_bytes;
-                rc_frame_end(&rc_ahead, nmb, c->par.vbv_size_bytes, desired_frame_bytes, pred, pkey, 0);
-                qp = rc_frame_start(&rc_ahead, c->par.gop, nmb, c->par.vbv_size_bytes, desired_frame_bytes, qp_min, qp_max, key);
-                build_qdat(key ? qdat_i : qdat_p, qp, !key);
+                const int pkey = sched[f - 1].key, pred = c->rc_last_bytes[pkey] > 0 ? c->rc_last_bytes[pkey] : x->desired_frame_bytes;
+                rc_frame_end(&rc_ahead, nmb, c->par.vbv_size_bytes, x->desired_frame_bytes, pred, pkey, 0);
+                qp = rc_frame_start(&rc_ahead, c->par.gop, nmb, c->par.vbv_size_bytes, x->desired_frame_bytes, x->qp_min, x->qp_max, key);
             }
-            qp_task[i & 7] = qp;
-            t->active = 1; t->frame_index = f % c->resident;
-            t->slice_type = key ? SLICE_I : SLICE_P;
-            t->qp = qp; t->speed = c->par.speed;
-            /* frame_num restarts at every key frame; idr_pic_id toggles with every key frame (h264-lab.h:6774-6775) */
-            t->nslices = nslices;
-            slice_header_bits(&c->seq, key, sched[f].frame_num, idr_state ^ sched[f].idr, qp, pic_init_qp, no_deblock, nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
-            memcpy(t->qdat, key ? qdat_i : qdat_p, sizeof(t->qdat));
-            t->stream_mode = 1; t->slot = f % K;
-            t->ref_slot = key ? -1 : (f - 1) % K;
-            t->ref_in_flight = !key && i > 0;
-            /* frame 0 of the launch gets the exact state; the frames behind it the best prediction of what it leaves */
-            t->mv_clusters[0] = used[i][0] = (i && c->have_after) ? c->after[0] : c->state[0];
-            t->mv_clusters[1] = used[i][1] = (i && c->have_after) ? c->after[1] : c->state[1];
-            /* validation on the device: the frame's finalizer walks its records exactly (task 0 from the exact state, the others from
-             * the verdict in front of them) and stops the launch itself when a macroblock consumed the wrong candidates */
-            t->walk_on_device = 1;
-            t->exact_state[0] = c->state[0]; t->exact_state[1] = c->state[1];
-            t->mv_clusters_per_mb = NULL;
-            t->traj_from_device = (i == 0) && c->first_dev;
-            t->first_row = (i == 0 && c->first_dev) ? c->first_row : 0;
-            t->narrow_window = c->narrow;
-            t->denoised = c->denoise && c->par.speed < 2;
+            l->qp_task[i] = qp;
         }
-        /* Hedges (rate control): the speculated QP of a frame is usually off by one or two when it is off, so every frame behind the
-         * first one is ALSO encoded with the neighbouring QPs, as leaves in spare slots (same reference, same mv_clusters
-         * speculation; the chip is nearly empty in this mode).  When the chain breaks at a frame, the leaf with the exact QP -- if
-         * there is one -- is the frame; its picture then moves to the slot the frame number owns and the launch ends there. */
-        int nh = 0, hedge_level[32], hedge_qp[32];
-        if (rc_on && F > 1)
-        {
-            static const int dq[4] = { -1, 1, -2, 2 };
-            const int rc_hedge = imax(0, imin(4, getenv("H264E_RC_HEDGE") ? atoi(getenv("H264E_RC_HEDGE")) : (nmb >= 60000 ? 0 : nmb >= 20000 ? 2 : 4)));      /* measured: 8K is bound by the resident workgroups, leaves only cost there */
-            int k, a;
-            for (k = 1; k < F; k++)
-                for (a = 0; a < rc_hedge; a++)
-                {
-                    const int q = qp_task[k & 7] + dq[a], f = n + k, key = sched[f].key, j = F + nh;
-                    h264e_hip_task_t *t = tasks + j;
-                    uint16_t qd[2][42];
-                    if (q < qp_min || q > qp_max || nh >= 32 || j + 2 >= K) continue;
-                    *t = tasks[k];
-                    build_qdat(qd, q, !key);
-                    t->qp = q;
-                    memcpy(t->qdat, qd, sizeof(t->qdat));
-                    slice_header_bits(&c->seq, key, sched[f].frame_num, idr_state ^ sched[f].idr, q, pic_init_qp, no_deblock, nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
-                    t->slot = (n + j) % K;              /* a slot no frame of this launch owns */
-                    t->walk_parent = k;                 /* = index of the chain's frame in front of it, + 1 */
-                    t->walk_quiet = 1;                  /* its own validation failing stops nobody else */
-                    used[j][0] = used[k][0]; used[j][1] = used[k][1];
-                    hedge_level[nh] = k; hedge_qp[nh] = q; nh++;
-                }
-        }
-        if (nh) c->recon_floor = n;             /* the leaves' slots held the pictures of frames n - K + F .. : gone now */
-        stats.rounds++;
-        const int after_stop = c->stopped_before;   /* this launch follows one that was stopped (mis-speculation, rate-control miss): its first frame pays the refill */
-        c->have_after = 0;
-        const double t_submit = now_ms();
-        double t_first = 0, t_last = 0;
-        int rc_miss = 0, take = -1, moved_from = -1, moved_to = -1, relaunch = 0;
-        const char *why = "all frames delivered";       /* what ended the launch (H264E_DEBUG) */
-        /* the denoiser: every frame uploaded so far and not yet denoised, in stream order, before the launch that reads them */
-        if (c->denoise && c->par.speed < 2 && c->den_done < limit)
-        {
-            if (limit - c->den_done > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "denoise: frames %d..%d do not fit the input ring", c->den_done, limit - 1); goto done; }
-            if (h264e_hip_denoise_frames(c->pool, c->den_done % c->resident, limit - c->den_done, c->den_done == 0)) goto done;
-            c->den_done = limit;
-        }
-        if (h264e_hip_submit(c->pool, tasks)) goto done;
+        t->active = 1; t->frame_index = f % c->resident;
+        t->slice_type = key ? SLICE_I : SLICE_P;
+        t->speed = c->par.speed;
+        t->nslices = x->nslices;
+        clip_task_set_qp(c, x, t, f, qp);
+        t->stream_mode = 1; t->slot = f % K;
+        t->ref_slot = key ? -1 : (f - 1) % K;
+        t->ref_in_flight = !key && i > 0;
+        /* frame 0 of the launch gets the exact state; the frames behind it the best prediction of what it leaves */
+        t->mv_clusters[0] = used[i][0] = (i && c->have_after) ? c->after[0] : c->state[0];
+        t->mv_clusters[1] = used[i][1] = (i && c->have_after) ? c->after[1] : c->state[1];
+        /* validation on the device: the frame's finalizer walks its records exactly (task 0 from the exact state, the others from
+         * the verdict in front of them) and stops the launch itself when a macroblock consumed the wrong candidates */
+        t->walk_on_device = 1;
+        t->exact_state[0] = c->state[0]; t->exact_state[1] = c->state[1];
+        t->mv_clusters_per_mb = NULL;
+        t->traj_from_device = (i == 0) && c->first_dev;
+        t->first_row = (i == 0 && c->first_dev) ? c->first_row : 0;
+        t->narrow_window = c->narrow;
+        t->denoised = c->denoise && c->par.speed < 2;
+    }
+    /* Hedges (rate control): the speculated QP of a frame is usually off by one or two when it is off, so every frame behind the
+     * first one is ALSO encoded with the neighbouring QPs, as leaves in spare slots (same reference, same mv_clusters
+     * speculation; the chip is nearly empty in this mode).  When the chain breaks at a frame, the leaf with the exact QP -- if
+     * there is one -- is the frame; its picture then moves to the slot the frame number owns and the launch ends there. */
+    l->nh = 0;
+    if (rc_on && F > 1)
+    {
+        static const int dq[4] = { -1, 1, -2, 2 };
+        const int rc_hedge = imax(0, imin(4, getenv("H264E_RC_HEDGE") ? atoi(getenv("H264E_RC_HEDGE")) : (nmb >= 60000 ? 0 : nmb >= 20000 ? 2 : 4)));      /* measured: 8K is bound by the resident workgroups, leaves only cost there */
+        int k, a;
+        for (k = 1; k < F; k++)
+            for (a = 0; a < rc_hedge; a++)
+            {
+                const int q = l->qp_task[k] + dq[a], j = F + l->nh;
+                h264e_hip_task_t *t = tasks + j;
+                if (q < x->qp_min || q > x->qp_max || l->nh >= CLIP_HEDGE_MAX || j + 2 >= K) continue;
+                *t = tasks[k];
+                clip_task_set_qp(c, x, t, n + k, q);
+                t->slot = (n + j) % K;              /* a slot no frame of this launch owns */
+                t->walk_parent = k;                 /* = index of the chain's frame in front of it, + 1 */
+                t->walk_quiet = 1;                  /* its own validation failing stops nobody else */
+                used[j][0] = used[k][0]; used[j][1] = used[k][1];
+                l->hedge_level[l->nh] = k; l->hedge_qp[l->nh] = q; l->nh++;
+            }
+    }
+    if (l->nh) c->recon_floor = n;              /* the leaves' slots held the pictures of frames n - K + F .. : gone now */
+    l->F = F;
+    l->after_stop = c->stopped_before;
+    c->have_after = 0;
+    l->t_first = l->t_last = 0;
+    l->nvalid = 0; l->leaf = l->moved_from = l->moved_to = -1;
+    l->step = CLIP_GO_ON;
+}
 
+/* the pre-pass in front of the submit, the denoiser: every frame uploaded so far and not yet denoised, in stream order, before the launch
+ * that reads them */
+static int clip_prepass_denoise(H264E_clip_t *c, int limit)
+{
+    if (!c->denoise || c->par.speed >= 2 || c->den_done >= limit) return 0;
+    if (limit - c->den_done > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "denoise: frames %d..%d do not fit the input ring", c->den_done, limit - 1); return -1; }
+    if (h264e_hip_denoise_frames(c->pool, c->den_done % c->resident, limit - c->den_done, c->den_done == 0)) return -1;
+    c->den_done = limit;
+    return 0;
+}
+
+/* wait for a job of the running launch, as h264e_hip_stream_done: 1 finished (r filled), 2 aborted, < 0 failed; 0: the launch ended
+ * without finishing it */
+static int clip_wait_frame(H264E_clip_t *c, int slot, h264e_hip_result_t *r)
+{
+    int dn, idle = 0;
+    memset(r, 0, sizeof(*r));
+    while ((dn = h264e_hip_stream_done(c->pool, slot, r)) == 0)
+    {
+        if (!h264e_hip_busy(c->pool) && ++idle > 2) break;      /* the launch ended without finishing this job */
+        if (c->idle_hook) c->idle_hook(c->idle_token);
+        sched_yield();
+    }
+    return dn ? dn : h264e_hip_stream_done(c->pool, slot, r);
+}
+
+/* task ti did not finish (dn != 1): why, and what becomes of the launch */
+static clip_step_t clip_frame_stopped(H264E_clip_t *c, clip_call_t *x, const clip_launch_t *l, int ti, int dn, const h264e_hip_result_t *r)
+{
+    if (dn < 0) return CLIP_ERROR;
+    /* a leaf did not make it (its own mv_clusters validation failed, or the launch was stopped): the frame is simply encoded in the
+     * next launch */
+    if (ti >= l->F) return h264e_hip_stream_abort(c->pool) ? CLIP_ERROR : CLIP_STOP_LEAF_LOST;
+    if (dn == 2 && r->walk_status == 2)
+    {
+        /* the device's exact walk found a macroblock of this frame that consumed other rounded candidates than the exact
+         * ones and stopped the launch.  Every macroblock before first_bad consumed the right ones: its row and
+         * the rows above are bit-identical in the next encode and are kept; the frame goes again from that row with the
+         * walked per-macroblock trajectory (it stays on the device), the frames behind it with the walk's end state */
+        c->first_row = r->first_bad/c->seq.nmbx;
+        c->first_dev = 1;
+        c->after[0] = r->state_out[0]; c->after[1] = r->state_out[1]; c->have_after = 1;
+        x->stats.reencoded_gops++;          /* counts relaunches */
+        return CLIP_STOP_MISSPEC;
+    }
+    /* The frame did not complete and nobody asked it to stop.  When the kernel reports that a bounded wait expired -- workgroups
+     * starved of wave slots, e.g. by another process' launch on the same device -- nothing wrong was returned: every frame
+     * accepted so far stands, and the unfinished ones are simply launched again (a fresh launch in this process).  Anything
+     * else, and a wait that keeps expiring without a single frame getting through, is an error. */
+    if (h264e_hip_sync(c->pool) && strstr(h264e_hip_last_error(), "bounded spin expired") && x->spin_retries < 3)
+    {
+        x->spin_retries++;
+        x->stats.spin_relaunches++;
+        return CLIP_RELAUNCH;
+    }
+    if (!g_host_err[0] && !h264e_hip_last_error()[0]) snprintf(g_host_err, sizeof(g_host_err), "frame %d did not complete", l->n + ti);
+    return CLIP_ERROR;
+}
+
+/* task ti finished: its NALs into the caller's buffer, the exact rate controller, the records, the stream state behind the frame */
+static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_t *l, int ti, const h264e_hip_result_t *r)
+{
+    const int nmb = c->seq.nmb, F = l->F, is_hedge = ti >= F;
+    const int f = l->n + (is_hedge ? l->hedge_level[ti - F] : ti), key = c->sched[f].key, slot = c->tasks[ti].slot, per_mb = (ti == 0 && c->first_dev);
+    const size_t start = x->pos, need = (key ? 64 : 0) + r->nbytes;       /* 64: the parameter sets stay below it with a VUI too (write_sps_pps) */
+    const uint8_t *nals;
+    const double t0 = now_ms();
+    size_t w;
+    int rc_miss = 0;
+    l->leaf = -1;
+    l->t_last = t0;
+    if (ti == 0) { l->t_first = t0; x->far_reads = 0; }
+    x->far_reads += r->far_reads;
+    if (r->overflow) { snprintf(g_host_err, sizeof(g_host_err), "bit buffer overflow (frame %d)", f); return clip_abort_launch(c); }
+    /* the frame as the kernel exported it: complete NALs (start codes and emulation prevention done on the device) */
+    if (r->in_device && c->big_cap < r->nbytes) { free(c->big); c->big_cap = (size_t)r->nbytes*2; c->big = (uint8_t *)malloc(c->big_cap); }
+    nals = frame_nals(c->pool, slot, r, c->big, c->big_cap);
+    if (!nals) { c->big_cap = 0; return clip_abort_launch(c); }
+    /* the caller's buffer is full: stop here, the stream continues with this frame in the next call */
+    if (x->pos + need > x->cap) return h264e_hip_stream_abort(c->pool) ? CLIP_ERROR : CLIP_STOP_FULL;
+    if (key) x->pos += write_sps_pps(&c->seq, x->pic_init_qp, x->out + x->pos, NULL, NULL);
+    w = emit_slices(x->out + x->pos, x->cap - x->pos, nals, r, NULL, NULL);
+    if (!w) { snprintf(g_host_err, sizeof(g_host_err), "malformed frame export"); return clip_abort_launch(c); }
+    x->pos += w;
+    if (x->frame_bytes) x->frame_bytes[f - x->first] = (int)(x->pos - start);
+    if (c->rc_on)
+    {
+        rc_frame_end(&c->rcs, nmb, c->par.vbv_size_bytes, x->desired_frame_bytes, (int)(x->pos - start), key, r->all_skipped);
+        c->rc_last_bytes[key] = (int)(x->pos - start);
+        /* (scene-cut detection: a frame that has not been analysed has no kind yet -- the launch that analyses it runs its
+         * rc_frame_start, on the same controller state) */
+        if (f + 1 < c->nframes && (!c->scenecut || f + 1 < c->sc_done))
+        {
+            /* the exact QP of the next frame; a frame of this launch that was given another one is stopped */
+            const int qp = c->rc_qp = rc_frame_start(&c->rcs, c->par.gop, nmb, c->par.vbv_size_bytes, x->desired_frame_bytes, x->qp_min, x->qp_max, c->sched[f + 1].key);
+            c->rc_frame = f + 1;
+            if (is_hedge) rc_miss = 1;                  /* a leaf has nothing behind it */
+            else if (ti + 1 < F && l->qp_task[ti + 1] != qp)
+            {
+                int hh;
+                rc_miss = 1;
+                for (hh = 0; hh < l->nh; hh++) if (l->hedge_level[hh] == ti + 1 && l->hedge_qp[hh] == qp) { l->leaf = F + hh; rc_miss = 0; }
+            }
+        } else if (is_hedge) rc_miss = 1;
+    }
+    if (c->rec_store)
+    {
+        /* what this accepted frame consumed: records + the candidates it was given (H264E_clip_revalidate) */
+        const size_t rb = sizeof(h264e_hip_mbrec_t)*(size_t)nmb;
+        if (!c->rec_store[f]) c->rec_store[f] = (h264e_hip_mbrec_t *)malloc(rb);
+        if (!c->rec_store[f]) return CLIP_ERROR;
+        memcpy(c->rec_store[f], h264e_hip_stream_mbrec(c->pool, slot), rb);
+        c->used_store[f][0] = c->used[ti][0]; c->used_store[f][1] = c->used[ti][1];
+        free(c->permb_store[f]); c->permb_store[f] = NULL;
+        if (per_mb)
+        {
+            c->permb_store[f] = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)nmb);
+            if (!c->permb_store[f] || h264e_hip_stream_fetch_traj(c->pool, slot, 1, c->permb_store[f])) return CLIP_ERROR;
+        }
+    }
+    c->state[0] = r->state_out[0]; c->state[1] = r->state_out[1];      /* exact state behind this frame (device walk), committed now that the frame is accepted */
+    if (ti == 0) c->first_dev = 0;
+    x->stats.assemble_ms += now_ms() - t0;
+    l->nvalid++;
+    if (is_hedge) { l->moved_from = slot; l->moved_to = f % c->ring; }
+    if (rc_miss)
+    {
+        if (h264e_hip_stream_abort(c->pool)) return CLIP_ERROR;
+        x->stats.reencoded_gops++;
+        return is_hedge ? CLIP_STOP_QP_LEAF : CLIP_STOP_QP_MISS;
+    }
+    return l->leaf >= 0 ? CLIP_TAKE_LEAF : CLIP_GO_ON;
+}
+
+/* the launch is over: drained, an accepted leaf's picture in the slot its frame owns, the stream position behind the accepted frames */
+static int clip_settle(H264E_clip_t *c, clip_call_t *x, const clip_launch_t *l)
+{
+    const int K = c->ring, n = l->n, nvalid = l->nvalid;
+    if (l->step == CLIP_RELAUNCH) (void)clip_abort_launch(c);       /* (the failure was reported by the sync that found it; the launch is over) */
+    else if (h264e_hip_sync(c->pool)) return -1;    /* the launch has drained (immediately after an abort) */
+    if (nvalid) x->spin_retries = 0;
+    if (l->moved_from >= 0 && h264e_hip_stream_copy_picture(c->pool, l->moved_from, l->moved_to)) return -1;
+    x->stats.encode_ms += now_ms() - l->t_submit;
+    /* device-side sums of squared differences of the frames just validated: their pictures are still in their slots */
+    if (c->ssd_out && nvalid && h264e_hip_ssd_frames(c->pool, nvalid, n % c->resident, c->resident, n % K, K, c->ssd_out + 3*(size_t)(n - x->first))) return -1;
+    c->next = n + nvalid;
+    if (l->after_stop && nvalid) { x->stats.relaunches_timed++; x->stats.first_frame_ms_after_relaunch += l->t_first - l->t_submit; }
+    c->stopped_before = nvalid < l->F && l->step != CLIP_STOP_FULL;
+    return 0;
+}
+
+/* what the launch teaches the next one: frames per launch, window geometry */
+static void clip_adapt(H264E_clip_t *c, const clip_call_t *x, const clip_launch_t *l)
+{
+    const int K = c->ring, nvalid = l->nvalid;
+    /* frames per launch: back to the pipeline depth after a mis-speculation, twice as many after a clean launch */
+    /* (after an event: twice the frames the stopped launch got through, an estimate of the spacing of the events) */
+    if (nvalid < l->F && l->step != CLIP_STOP_FULL) c->launch_frames = imin(imax(c->launch_base, 2*nvalid), K - 1);
+    else if (nvalid == l->F) c->launch_frames = imin(2*c->launch_frames, K - 1);
+    /* Window geometry for the next launch.  More than one macroblock in eight leaving the narrow window over at least 8 frames:
+     * the wide one pays -- for a while: such motion is often a transient (a scene cut, an object wrapping around), so the narrow
+     * geometry is tried again after wide_hold frames, a spell that doubles every time it fails again. */
+    if (c->narrow)
+    {
+        c->far_acc += x->far_reads; c->far_frames += nvalid;
+        if (c->far_frames >= 8)
+        {
+            if (c->far_acc > (long long)c->far_frames*c->seq.nmb/8)
+            {
+                c->narrow = 0;
+                c->wide_until = c->next + c->wide_hold;
+                c->wide_hold = imin(c->wide_hold*2, 960);
+            } else if (c->far_frames >= 64) c->wide_hold = 30;
+            c->far_acc = 0; c->far_frames = 0;
+        }
+    } else if (c->narrow_ok && c->next >= c->wide_until) { c->narrow = 1; c->far_acc = 0; c->far_frames = 0; }
+}
+
+/* H264E_DEBUG: one line per launch */
+static void clip_debug_line(const H264E_clip_t *c, const clip_call_t *x, const clip_launch_t *l)
+{
+    const double t_end = now_ms();
+    const int nvalid = l->nvalid;
+    const double t_first = nvalid ? l->t_first : t_end, t_last = nvalid ? l->t_last : t_end;     /* no frame of it was delivered: "first frame after" = when its verdict was in */
+    fprintf(stderr, "clip launch %d (first row %d, %s window, %lld far reads): %d frames in flight, %d valid, next %d; first frame after %.2f ms, then %.3f ms/frame, drained %.2f ms after the last; ended by: %s%s\n",
+            x->stats.rounds, c->tasks[0].first_row, c->tasks[0].narrow_window ? "narrow" : "wide", x->far_reads, l->F, nvalid, c->next, t_first - l->t_submit, nvalid > 1 ? (t_last - t_first)/(nvalid - 1 + (nvalid < l->F)) : 0.0, t_end - t_last,
+            k_clip_ended_by[l->step], l->nh ? " (+ hedge leaves)" : "");
+}
+
+int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_bytes, int *frame_bytes, int profile, H264E_clip_stats_t *st)
+{
+    clip_call_t x;
+    clip_launch_t l;
+    memset(&x, 0, sizeof(x));
+    g_host_err[0] = 0;
+    x.out = out; x.cap = cap; x.frame_bytes = frame_bytes; x.first = c->next;
+    x.nslices = c->par.slices > 1 ? imin(imin(c->par.slices, H264E_HIP_MAX_SLICES), c->seq.nmby) : 1;
+    x.no_deblock = (c->par.speed == 8 || c->par.speed == 10);
+    x.idr_state = c->par.first_idr_pic_id_state & 1;
+    x.desired_frame_bytes = c->par.kbps > 0 ? c->par.kbps*1000/8/30 : 0;
+    x.qp_min = c->rc_on ? 10 : c->par.qp; x.qp_max = c->par.kbps > 0 ? 50 : c->rc_on ? 51 : c->par.qp;     /* qp 0: 10..51, h264-lab.h:6707-6715 */
+    x.pic_init_qp = imax(imin(30, x.qp_max), x.qp_min);     /* h264-lab.h:6768-6770 */
+    build_qdat(x.qdat_i, c->rc_qp, 0);
+    build_qdat(x.qdat_p, c->rc_qp, 1);
+    h264e_hip_profile(c->pool, profile);
+    x.stats.chains = c->ring - 1;
+    x.stats.first_frame = x.first;
+    l.step = CLIP_GO_ON;
+
+    while (c->next < c->avail && l.step != CLIP_STOP_FULL)
+    {
+        int ti = 0;
+        l.n = c->next; l.limit = c->avail;          /* frames uploaded from the idle hook during this launch join the next one */
+        if (clip_prepass_scenecut(c, l.limit)) return clip_end(c, &x, st, -1);
+        clip_plan_launch(c, &x, &l);
+        x.stats.rounds++;
+        l.t_submit = now_ms();
+        if (clip_prepass_denoise(c, l.limit) || h264e_hip_submit(c->pool, c->tasks)) return clip_end(c, &x, st, -1);
         /* consume the frames in stream order while the launch is still running */
-        for (i = 0; i < F || take >= 0; i++)
+        do
         {
-            const int is_hedge = take >= 0, ti = is_hedge ? take : i;
-            const int f = is_hedge ? n + hedge_level[take - F] : n + i, key = sched[f].key, slot = tasks[ti].slot, per_mb = (ti == 0 && c->first_dev);
-            h264e_hip_result_t r1;
-            int dn, idle = 0;
-            int32_t cc[2];
-            memset(&r1, 0, sizeof(r1));
-            while ((dn = h264e_hip_stream_done(c->pool, slot, &r1)) == 0)
-            {
-                if (!h264e_hip_busy(c->pool) && ++idle > 2) break;      /* the launch ended without finishing this job */
-                if (c->idle_hook) c->idle_hook(c->idle_token);
-                sched_yield();
-            }
-            take = -1;
-            if (dn == 0) dn = h264e_hip_stream_done(c->pool, slot, &r1);
-            if (is_hedge && dn != 1)
-            {
-                /* the leaf did not make it (its own mv_clusters validation failed, or the launch was stopped): the frame is simply
-                 * encoded in the next launch */
-                if (dn < 0) goto done;
-                if (h264e_hip_stream_abort(c->pool)) goto done;
-                why = "the hedge leaf with the exact QP did not complete (its own mv_clusters validation, or stopped)";
-                break;
-            }
-            if (dn == 2 && r1.walk_status == 2)
-            {
-                /* the device's exact walk found a macroblock of this frame that consumed other rounded candidates than the exact
-                 * ones and stopped the launch.  Every macroblock before first_bad consumed the right ones: its row and
-                 * the rows above are bit-identical in the next encode and are kept; the frame goes again from that row with the
-                 * walked per-macroblock trajectory (it stays on the device), the frames behind it with the walk's end state */
-                c->first_row = r1.first_bad/c->seq.nmbx;
-                c->first_dev = 1;
-                c->after[0] = r1.state_out[0]; c->after[1] = r1.state_out[1]; c->have_after = 1;
-                stats.reencoded_gops++;             /* counts relaunches */
-                why = "mv_clusters mis-speculation";
-                break;
-            }
-            if (dn != 1)
-            {
-                if (dn < 0) goto done;
-                /* The frame did not complete and nobody asked it to stop.  When the kernel reports that a bounded wait expired -- workgroups
-                 * starved of wave slots, e.g. by another process' launch on the same device -- nothing wrong was returned: every frame
-                 * accepted so far stands, and the unfinished ones are simply launched again (a fresh launch in this process).  Anything
-                 * else, and a wait that keeps expiring without a single frame getting through, is an error. */
-                if (h264e_hip_sync(c->pool) && strstr(h264e_hip_last_error(), "bounded spin expired") && spin_retries < 3)
-                {
-                    spin_retries++;
-                    stats.spin_relaunches++;
-                    relaunch = 1;
-                    break;
-                }
-                if (!g_host_err[0] && !h264e_hip_last_error()[0]) snprintf(g_host_err, sizeof(g_host_err), "frame %d did not complete", f);
-                goto done;
-            }
-            t_last = now_ms();
-            if (i == 0) { t_first = t_last; far_reads = 0; }
-            far_reads += r1.far_reads;
-            if (r1.overflow) { snprintf(g_host_err, sizeof(g_host_err), "bit buffer overflow (frame %d)", f); (void)h264e_hip_stream_abort(c->pool); (void)h264e_hip_sync(c->pool); goto done; }
-            cc[0] = r1.state_out[0]; cc[1] = r1.state_out[1];      /* exact state behind this frame (device walk), committed once the frame is accepted */
-            t0 = now_ms();
-            {
-                /* the frame as the kernel exported it: complete NALs (start codes and emulation prevention done on the device) */
-                const uint8_t *nals = h264e_hip_stream_rbsp(c->pool, slot);
-                size_t start = pos, w = 0, need = (key ? 64 : 0) + r1.nbytes;       /* 64: the parameter sets stay below it with a VUI too (write_sps_pps) */
-                if (r1.in_device)
-                {
-                    /* larger than the host-mapped mirror (sized for ordinary frames): copy it from the slot's device NAL arena */
-                    if (c->big_cap < r1.nbytes) { free(c->big); c->big_cap = (size_t)r1.nbytes*2; c->big = (uint8_t *)malloc(c->big_cap); }
-                    if (!c->big || h264e_hip_stream_fetch_nals(c->pool, slot, c->big, r1.nbytes)) { c->big_cap = 0; (void)h264e_hip_stream_abort(c->pool); (void)h264e_hip_sync(c->pool); goto done; }
-                    nals = c->big;
-                }
-                if (pos + need > cap)
-                {
-                    /* the caller's buffer is full: stop here, the stream continues with this frame in the next call */
-                    if (h264e_hip_stream_abort(c->pool)) goto done;
-                    full = 1;
-                    break;
-                }
-                if (key) pos += write_sps_pps(&c->seq, pic_init_qp, out + pos, NULL, NULL);
-                w = emit_slices(out + pos, cap - pos, nals, &r1, NULL, NULL);
-                if (!w) { snprintf(g_host_err, sizeof(g_host_err), "malformed frame export"); (void)h264e_hip_stream_abort(c->pool); (void)h264e_hip_sync(c->pool); goto done; }
-                pos += w;
-                if (frame_bytes) frame_bytes[f - first] = (int)(pos - start);
-                if (rc_on)
-                {
-                    rc_frame_end(&c->rcs, nmb, c->par.vbv_size_bytes, desired_frame_bytes, (int)(pos - start), key, r1.all_skipped);
-                    c->rc_last_bytes[key] = (int)(pos - start);
-                    /* (scene-cut detection: a frame that has not been analysed has no kind yet -- the launch that analyses it runs its
-                     * rc_frame_start, on the same controller state) */
-                    if (f + 1 < c->nframes && (!c->scenecut || f + 1 < c->sc_done))
-                    {
-                        /* the exact QP of the next frame; a frame of this launch that was given another one is stopped */
-                        const int nkey = sched[f + 1].key;
-                        qp = c->rc_qp = rc_frame_start(&c->rcs, c->par.gop, nmb, c->par.vbv_size_bytes, desired_frame_bytes, qp_min, qp_max, nkey);
-                        c->rc_frame = f + 1;
-                        if (is_hedge) rc_miss = 1;                  /* a leaf has nothing behind it */
-                        else if (i + 1 < F && qp_task[(i + 1) & 7] != qp)
-                        {
-                            int hh;
-                            rc_miss = 1;
-                            for (hh = 0; hh < nh; hh++) if (hedge_level[hh] == i + 1 && hedge_qp[hh] == qp) { take = F + hh; rc_miss = 0; }
-                        }
-                    } else if (is_hedge) rc_miss = 1;
-                }
-            }
-            if (c->rec_store)
-            {
-                /* what this accepted frame consumed: records + the candidates it was given (H264E_clip_revalidate) */
-                const size_t rb = sizeof(h264e_hip_mbrec_t)*(size_t)nmb;
-                if (!c->rec_store[f]) c->rec_store[f] = (h264e_hip_mbrec_t *)malloc(rb);
-                if (!c->rec_store[f]) goto done;
-                memcpy(c->rec_store[f], h264e_hip_stream_mbrec(c->pool, slot), rb);
-                c->used_store[f][0] = used[ti][0]; c->used_store[f][1] = used[ti][1];
-                free(c->permb_store[f]); c->permb_store[f] = NULL;
-                if (per_mb)
-                {
-                    c->permb_store[f] = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)nmb);
-                    if (!c->permb_store[f] || h264e_hip_stream_fetch_traj(c->pool, slot, 1, c->permb_store[f])) goto done;
-                }
-            }
-            c->state[0] = cc[0]; c->state[1] = cc[1];
-            if (ti == 0) c->first_dev = 0;
-            stats.assemble_ms += now_ms() - t0;
-            nvalid++;
-            if (is_hedge) { moved_from = slot; moved_to = f % K; }
-            if (rc_miss)
-            {
-                if (h264e_hip_stream_abort(c->pool)) goto done;
-                stats.reencoded_gops++;
-                why = is_hedge ? "QP miss covered by a hedge leaf (nothing behind a leaf)" : "QP miss, no hedge leaf with the exact QP";
-                break;
-            }
-            if (take >= 0) i = F - 1;           /* the chain ends here: one more round, for the leaf */
-        }
-        if (relaunch) { (void)h264e_hip_stream_abort(c->pool); (void)h264e_hip_sync(c->pool); }       /* (the failure was reported above; the launch is over) */
-        else if (h264e_hip_sync(c->pool)) goto done;    /* the launch has drained (immediately after an abort) */
-        if (nvalid) spin_retries = 0;
-        if (moved_from >= 0 && h264e_hip_stream_copy_picture(c->pool, moved_from, moved_to)) goto done;
-        stats.encode_ms += now_ms() - t_submit;
-        if (c->ssd_out && nvalid)
-        {
-            /* device-side sums of squared differences of the frames just validated: their pictures are still in their slots */
-            if (h264e_hip_ssd_frames(c->pool, nvalid, n % c->resident, c->resident, n % K, K, c->ssd_out + 3*(size_t)(n - first))) goto done;
-        }
-        c->next = n + nvalid;
-        if (after_stop && nvalid) { stats.relaunches_timed++; stats.first_frame_ms_after_relaunch += t_first - t_submit; }
-        c->stopped_before = nvalid < F && !full;
-        /* frames per launch: back to the pipeline depth after a mis-speculation, twice as many after a clean launch */
-        /* (after an event: twice the frames the stopped launch got through, an estimate of the spacing of the events) */
-        if (nvalid < F && !full) c->launch_frames = imin(imax(c->launch_base, 2*nvalid), K - 1);
-        else if (nvalid == F) c->launch_frames = imin(2*c->launch_frames, K - 1);
-        /* Window geometry for the next launch.  More than one macroblock in eight leaving the narrow window over at least 8 frames:
-         * the wide one pays -- for a while: such motion is often a transient (a scene cut, an object wrapping around), so the narrow
-         * geometry is tried again after wide_hold frames, a spell that doubles every time it fails again. */
-        if (c->narrow)
-        {
-            c->far_acc += far_reads; c->far_frames += nvalid;
-            if (c->far_frames >= 8)
-            {
-                if (c->far_acc > (long long)c->far_frames*nmb/8)
-                {
-                    c->narrow = 0;
-                    c->wide_until = c->next + c->wide_hold;
-                    c->wide_hold = imin(c->wide_hold*2, 960);
-                } else if (c->far_frames >= 64) c->wide_hold = 30;
-                c->far_acc = 0; c->far_frames = 0;
-            }
-        } else if (c->narrow_ok && c->next >= c->wide_until) { c->narrow = 1; c->far_acc = 0; c->far_frames = 0; }
-        if (getenv("H264E_DEBUG"))
-        {
-            const double t_end = now_ms();
-            if (!nvalid) t_first = t_last = t_end;              /* no frame of it was delivered: "first frame after" = when its verdict was in */
-            fprintf(stderr, "clip launch %d (first row %d, %s window, %lld far reads): %d frames in flight, %d valid, next %d; first frame after %.2f ms, then %.3f ms/frame, drained %.2f ms after the last; ended by: %s%s\n",
-                    stats.rounds, tasks[0].first_row, tasks[0].narrow_window ? "narrow" : "wide", far_reads, F, nvalid, c->next, t_first - t_submit, nvalid > 1 ? (t_last - t_first)/(nvalid - 1 + (nvalid < F)) : 0.0, t_end - t_last,
-                    full ? "output buffer full" : why, nh ? " (+ hedge leaves)" : "");
-        }
-        if (full && c->next == first)
+            h264e_hip_result_t r;
+            const int dn = clip_wait_frame(c, c->tasks[ti].slot, &r);
+            l.step = dn == 1 ? clip_take_frame(c, &x, &l, ti, &r) : clip_frame_stopped(c, &x, &l, ti, dn, &r);
+            ti = l.step == CLIP_TAKE_LEAF ? l.leaf : ti + 1;        /* the chain ends here: one more round, for the leaf */
+        } while (l.step == CLIP_TAKE_LEAF || (l.step == CLIP_GO_ON && ti < l.F));
+        if (l.step == CLIP_ERROR || clip_settle(c, &x, &l)) return clip_end(c, &x, st, -1);
+        clip_adapt(c, &x, &l);
+        if (getenv("H264E_DEBUG")) clip_debug_line(c, &x, &l);
+        if (l.step == CLIP_STOP_FULL && c->next == x.first)
         {
             snprintf(g_host_err, sizeof(g_host_err), "output buffer too small for one frame");
-            goto done;
+            return clip_end(c, &x, st, -1);
         }
     }
-    stats.frames = c->next - first;
-    stats.delivered_mbs = (long long)stats.frames*nmb;
+    x.stats.frames = c->next - x.first;
+    x.stats.delivered_mbs = (long long)x.stats.frames*c->seq.nmb;
     {
         unsigned long long pm = 0;
-        if (!h264e_hip_mb_counter(c->pool, &pm, 1)) stats.processed_mbs = (long long)pm;
+        if (!h264e_hip_mb_counter(c->pool, &pm, 1)) x.stats.processed_mbs = (long long)pm;
     }
-    stats.mv_clusters_out[0] = c->state[0]; stats.mv_clusters_out[1] = c->state[1];
-    stats.next_idr_pic_id_state = c->next ? idr_state ^ c->sched[c->next - 1].idr : idr_state;
-    h264e_hip_profile_read(c->pool, &stats.mb_kernel_ms, &stats.splice_kernel_ms, &stats.kernel_launches);
-    if (out_bytes) *out_bytes = pos;
-    rc = 0;
-done:
-    if (rc) h264e_hip_release(c->pool);         /* a failure between submit and sync: give the device's launch lock back */
-    if (st) *st = stats;
-    return rc;
+    x.stats.mv_clusters_out[0] = c->state[0]; x.stats.mv_clusters_out[1] = c->state[1];
+    x.stats.next_idr_pic_id_state = c->next ? x.idr_state ^ c->sched[c->next - 1].idr : x.idr_state;
+    h264e_hip_profile_read(c->pool, &x.stats.mb_kernel_ms, &x.stats.splice_kernel_ms, &x.stats.kernel_launches);
+    if (out_bytes) *out_bytes = x.pos;
+    return clip_end(c, &x, st, 0);
 }
 
 

@@ -290,12 +290,13 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
  * consecutive frames of one stream (lag*job + 2*row: a counting sort); every workgroup still only waits for workgroups that precede it
  * in this order (far reads: a bounded distance ahead).  Built for the number of jobs a launch really has, so that a pool with many
  * slots does not dispatch thousands of empty workgroups with every short launch.
- * H264E_XCD_BANDS=N (experiment, profiles/r02_xcd_bands.txt): workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md:
- * blocks b and b+8 share one), so the order is additionally arranged so that a macroblock row lands on the XCD of its band of rows
- * (row*N/nmby mod 8): the rows whose reference windows overlap then share an L2. */
+ * bands = 8 (profiles/r02_xcd_bands.txt): workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md: blocks b and b+8
+ * share one), so the order is additionally arranged so that a macroblock row lands on the XCD of its band of rows (row*8/nmby): the
+ * rows whose reference windows overlap then share an L2.  bands = 0: none; -1: the default policy below, or what H264E_XCD_BANDS
+ * forces.  The per-XCD queues are sized for eight bands, so any other count is refused.  Fails with the error text set. */
 /* entries a launch of `jobs` jobs can take in the dispatch order (banded: eight equally long queues per job, padded) */
 static size_t order_capacity(const h264e_geom_t &G, int jobs) { return (size_t)jobs*(size_t)(8*((G.nmby + 7)/8 + 1)); }
-static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced)
+static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced, int bands)
 {
     const h264e_geom_t &G = p->G;
     const int rows = G.nmby + 1, total = jobs*rows, lag = narrow ? H264E_NARROW_FRAME_LAG : H264E_FRAME_LAG, maxkey = lag*(jobs - 1) + 2*(rows - 1);
@@ -305,11 +306,12 @@ static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced)
      * random), everything else loses 1-13 % (1080p -4 %, 720p -1 %, CIF -13 %, rate control -4 %; row-band slices -9 % at every size,
      * 4K and 8K included: a slice is a band, and an XCD cannot share its slice's load with the others).  So: on for single-slice
      * launches from 4K up, H264E_XCD_BANDS=8 / 0 forces */
-    const int bands = getenv("H264E_XCD_BANDS") ? atoi(getenv("H264E_XCD_BANDS")) : (G.nmb >= 30000 && !sliced ? 8 : 0);
+    if (bands < 0) bands = getenv("H264E_XCD_BANDS") ? atoi(getenv("H264E_XCD_BANDS")) : (G.nmb >= 30000 && !sliced ? 8 : 0);
+    if (bands != 0 && bands != 8) FAIL("dispatch order: %d XCD bands (H264E_XCD_BANDS): only 0 and 8 are supported", bands);
     uint32_t *ord = p->order_host;
     int *start = (int *)calloc((size_t)maxkey + 2, sizeof(int));
     uint32_t *tmp = bands ? (uint32_t *)malloc(sizeof(uint32_t)*(size_t)total) : ord;
-    if (!start || !tmp) { free(start); if (bands) free(tmp); return -1; }
+    if (!start || !tmp) { free(start); if (bands) free(tmp); FAIL("out of host memory"); }
     for (int job = 0; job < jobs; job++) for (int r = 0; r < rows; r++) start[lag*job + 2*r + 1]++;
     for (int k = 0; k <= maxkey; k++) start[k + 1] += start[k];
     for (int job = 0; job < jobs; job++) for (int r = 0; r < rows; r++) tmp[start[lag*job + 2*r]++] = ((uint32_t)job << 16) | (uint32_t)r;     /* ties: by job */
@@ -328,25 +330,16 @@ static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced)
         uint32_t *q = (uint32_t *)malloc(sizeof(uint32_t)*8*qlen);
         int *fill = (int *)calloc((size_t)8*jobs, sizeof(int));
         size_t cnt[8] = { 0 };
-        if (!q || !fill) { free(q); free(fill); free(tmp); return -1; }
+        if (!q || !fill) { free(q); free(fill); free(tmp); FAIL("out of host memory"); }
         for (size_t i = 0; i < 8*qlen; i++) q[i] = H264E_ORDER_PAD;
         /* queue x, job j owns the entries [j*per, (j+1)*per) ... in KEY order that would interleave the jobs; so: append in key order, and
          * when a job's last entry of a queue has gone in, append its padding right behind it */
         int *want = (int *)calloc((size_t)8*jobs, sizeof(int));
-        if (!want) { free(q); free(fill); free(tmp); return -1; }
+        if (!want) { free(q); free(fill); free(tmp); FAIL("out of host memory"); }
         for (int i = 0; i < total; i++)
         {
             const int row = (int)(tmp[i] & 0xffffu), x = (row >= G.nmby ? bands - 1 : imin_h(bands - 1, row*bands/G.nmby)) & 7;      /* band b -> XCD b % 8 */
             want[8*(tmp[i] >> 16) + x]++;
-        }
-        int empty = 0;
-        for (int i = 0; i < 8*jobs; i++) if (!want[i]) empty = 1;
-        if (empty && bands < 8)
-        {
-            /* fewer bands than XCDs (H264E_XCD_BANDS < 8): no banding */
-            memcpy(ord, tmp, sizeof(uint32_t)*(size_t)total);
-            free(q); free(fill); free(want); free(tmp);
-            return 0;
         }
         for (int i = 0; i < total; i++)
         {
@@ -1455,7 +1448,7 @@ extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tas
     /* the dispatch order for this launch's shape (jobs up to the last active one; window geometry) */
     if (njobs != p->order_jobs || any_narrow != p->order_narrow || (max_slices >= 2) != p->order_sliced)
     {
-        if (build_order(p, njobs, any_narrow, max_slices >= 2)) FAIL("out of host memory");
+        if (build_order(p, njobs, any_narrow, max_slices >= 2, -1)) return -1;
         HIPCHK(hipMemcpyAsync(p->order, p->order_host, sizeof(uint32_t)*p->order_count, hipMemcpyHostToDevice, p->stream));     /* pageable: staged before the call returns */
         p->order_jobs = njobs; p->order_narrow = any_narrow; p->order_sliced = max_slices >= 2;
     }
@@ -1587,14 +1580,9 @@ extern "C" int h264e_hip_rewind_frame(h264e_hip_pool_t *p, int chain)
 extern "C" long h264e_hip_selftest_order(h264e_hip_pool_t *p, int jobs, int narrow, int banded, uint32_t *out, size_t cap)
 {
     if (!p || jobs < 1 || jobs > p->nchains || !out) { snprintf(g_err, sizeof(g_err), "selftest_order: bad argument"); return -1; }
-    const char *old = getenv("H264E_XCD_BANDS");
-    char keep[32];
-    if (old) snprintf(keep, sizeof(keep), "%s", old);
-    setenv("H264E_XCD_BANDS", banded ? "8" : "0", 1);
-    const int rc = build_order(p, jobs, narrow, 0);
-    if (old) setenv("H264E_XCD_BANDS", keep, 1); else unsetenv("H264E_XCD_BANDS");
+    const int rc = build_order(p, jobs, narrow, 0, banded ? 8 : 0);
     p->order_jobs = -1;
-    if (rc) { snprintf(g_err, sizeof(g_err), "out of host memory"); return -1; }
+    if (rc) return -1;
     memcpy(out, p->order_host, sizeof(uint32_t)*(p->order_count < cap ? p->order_count : cap));
     return (long)p->order_count;
 }

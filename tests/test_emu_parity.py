@@ -137,6 +137,39 @@ def test_clip_encoder_rate_control(name, w, h, n, gop, kbps, slices):
     assert out == want and fs == sizes
 
 
+def _rate_controlled_clip_through_a_small_output_buffer(P, slices, **lib):
+    """rate control in several H264E_clip_encode calls whose output buffer fills in the middle of a launch: the "buffer full" exit
+    interleaves with the QP-miss / hedge-leaf exits.  96x80 (5 macroblock rows), 12 frames, GOP 5, a byte target low enough that
+    the QP moves on most frames; the capacity is one and a half times the largest frame.  Same bytes and sizes as one call with
+    ample capacity, and as the oracle."""
+    w, h, n, gop, kbps = 96, 80, 12, 5, 60
+    c = clips.make("synth", w, h, n)
+    want, sizes = oracle_lib.encode_clip(c, w, h, gop=gop, kbps=kbps, slices=slices)
+    ce = P.ClipEncoder(w, h, n, gop=gop, kbps=kbps, slices=slices, **lib)
+    ce.upload(c)
+    whole, whole_sizes, _ = ce.encode()
+    cap = max(whole_sizes) * 3 // 2
+    out, fs, calls, stops = b"", [], 0, 0
+    while len(fs) < n:
+        o, s, st = ce.encode(rewind=not calls, cap=cap)
+        assert st.frames > 0 and len(o) <= cap
+        out += o
+        fs += s
+        calls += 1
+        stops += st.reencoded_gops
+    ce.close()
+    assert calls > 2, "the output buffer never filled"
+    assert stops > 0, "no launch was stopped for a QP miss: the case no longer interleaves the two exits"
+    assert fs == whole_sizes == sizes
+    assert out == whole == want
+
+
+@pytest.mark.parametrize("slices", [0, 2])
+@pytest.mark.parametrize("lib", [pkg.EMU_LIB, pkg.EMU_REV_LIB], ids=["lanes_up", "lanes_down"])
+def test_rate_control_resumes_when_the_output_buffer_fills_mid_launch(lib, slices):
+    _rate_controlled_clip_through_a_small_output_buffer(pkg.load_pkg(), slices, lib=lib)
+
+
 def test_nal_escape_pass_on_adversarial_payloads():
     """the device's emulation-prevention pass (whole-wave copy of blocks without a 00 00 0x triple, byte automaton for the
     others) against the reference's automaton: zero runs, triples across block edges, zero-rich random data"""
@@ -396,6 +429,7 @@ def test_dispatch_order_with_xcd_bands_is_complete_padded_and_dependency_safe(w,
     L.h264e_hip_selftest_order.restype = C.c_long
     pool = C.c_void_p()
     assert L.h264e_hip_pool_create(C.byref(pool), 0, w, h, jobs, 1) == 0
+    env = dict(os.environ)
     try:
         nmby, lag = (h + 15) // 16, 4 if narrow else 7
         rows = nmby + 1
@@ -405,6 +439,7 @@ def test_dispatch_order_with_xcd_bands_is_complete_padded_and_dependency_safe(w,
         assert plain == jobs * rows
         assert sorted(buf[:plain]) == sorted((j << 16) | r for j in range(jobs) for r in range(rows))
         n = L.h264e_hip_selftest_order(pool, jobs, narrow, 1, buf, cap)
+        assert dict(os.environ) == env, "the order hook changed the process environment"
         assert 0 < n <= cap and n % 8 == 0
         order = list(buf[:n])
         real = [e for e in order if e != 0xffffffff]
@@ -424,3 +459,25 @@ def test_dispatch_order_with_xcd_bands_is_complete_padded_and_dependency_safe(w,
                     assert abs((e >> 16) - k // per) <= (2 * rows) // lag + 1
     finally:
         L.h264e_hip_pool_destroy(pool)
+
+
+def test_a_band_count_other_than_0_or_8_is_refused(monkeypatch):
+    """the per-XCD queues of build_order are sized for eight bands: H264E_XCD_BANDS=12 is refused with a message that names the value
+    (it used to write past them on the host heap), 0 and 8 still encode"""
+    P = pkg.load_pkg()
+    w, h, n = 64, 48, 2
+    c = clips.make("synth", w, h, n)
+    want, sizes = oracle_lib.encode_clip(c, w, h, gop=30, qp=30)
+    for bands in ("12", "0", "8"):
+        monkeypatch.setenv("H264E_XCD_BANDS", bands)
+        ce = P.ClipEncoder(w, h, n, gop=30, qp=30, lib=pkg.EMU_LIB)
+        ce.upload(c)
+        try:
+            if bands == "12":
+                with pytest.raises(P.H264EError, match="12 XCD bands"):
+                    ce.encode()
+            else:
+                out, fs, _ = ce.encode()
+                assert out == want and fs == sizes
+        finally:
+            ce.close()

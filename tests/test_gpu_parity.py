@@ -303,6 +303,38 @@ def test_clip_encoder_resumes_across_calls_and_reads_recon(P):
     ce.close()
 
 
+def _rate_controlled_clip_through_a_small_output_buffer(P, slices, **lib):
+    """rate control in several H264E_clip_encode calls whose output buffer fills in the middle of a launch: the "buffer full" exit
+    interleaves with the QP-miss / hedge-leaf exits.  96x80 (5 macroblock rows), 12 frames, GOP 5, a byte target low enough that
+    the QP moves on most frames; the capacity is one and a half times the largest frame.  Same bytes and sizes as one call with
+    ample capacity, and as the oracle."""
+    w, h, n, gop, kbps = 96, 80, 12, 5, 60
+    c = clips.make("synth", w, h, n)
+    want, sizes = oracle_lib.encode_clip(c, w, h, gop=gop, kbps=kbps, slices=slices)
+    ce = P.ClipEncoder(w, h, n, gop=gop, kbps=kbps, slices=slices, **lib)
+    ce.upload(c)
+    whole, whole_sizes, _ = ce.encode()
+    cap = max(whole_sizes) * 3 // 2
+    out, fs, calls, stops = b"", [], 0, 0
+    while len(fs) < n:
+        o, s, st = ce.encode(rewind=not calls, cap=cap)
+        assert st.frames > 0 and len(o) <= cap
+        out += o
+        fs += s
+        calls += 1
+        stops += st.reencoded_gops
+    ce.close()
+    assert calls > 2, "the output buffer never filled"
+    assert stops > 0, "no launch was stopped for a QP miss: the case no longer interleaves the two exits"
+    assert fs == whole_sizes == sizes
+    assert out == whole == want
+
+
+@pytest.mark.parametrize("slices", [0, 2])
+def test_rate_control_resumes_when_the_output_buffer_fills_mid_launch(P, slices):
+    _rate_controlled_clip_through_a_small_output_buffer(P, slices)
+
+
 def test_frames_larger_than_the_host_mirror_are_fetched(P, monkeypatch):
     """a frame that does not fit the slot's host-mapped mirror (sized for ordinary frames) is fetched from the device NAL arena:
     forced with a 4000-byte mirror; QP 10 noise also exceeds the default mirror's 160 bytes per macroblock"""
