@@ -177,7 +177,10 @@ DEV uint32_t lds32u(const lu8 *p)
  */
 #define WIN_M 24
 #define WIN_W 64
-#define WIN_STRIDE 68       /* 17 dwords: consecutive rows start on different LDS banks */
+/* The window buffer is MIRRORED so that it can slide (wave_slide_window): picture column c lives at position c mod 64 of its row and,
+ * for positions below WIN_STRIDE - 64, again 64 bytes further on.  The window whose first column is wx0 is then the 64 contiguous
+ * bytes from win_org(wx0) on, wherever the row loop stands: readers see a linear window (rv_ptr) and never test for a wrap. */
+#define WIN_STRIDE 120      /* 30 dwords: the last origin (56) + 64 columns; rows spread over the 32 ds_read_b32 banks two apart, as 17 dwords did */
 struct RefView
 {
     Plane P; const lu8 *win; int has_win, wx0, wy0;
@@ -197,6 +200,15 @@ DEV bool rv_inside(const RefView &V, int x0, int y0, int x1, int y1)
     return V.has_win && x0 >= V.wx0 && y0 >= V.wy0 && x1 < V.wx0 + V.vw && y1 < V.wy0 + V.vh;
 }
 DEV const lu8 *rv_ptr(const RefView &V, int x, int y) { return V.win + (y - V.wy0)*WIN_STRIDE + (x - V.wx0); }
+/* where the window whose first column is wx0 starts in a row of the mirrored buffer (dword aligned; the row loop's wx0 are multiples of 8) */
+DEV int win_org(int wx0) { return wx0 & 60; }
+/* one dword of a window row at position pos (taken mod 64), and at its mirror position where the row has one */
+DEV void win_store4(uint8_t *row, int pos, uint32_t v)
+{
+    pos &= 63;
+    lds32_store(row + pos, v);
+    if (pos < WIN_STRIDE - 64) lds32_store(row + pos + 64, v);
+}
 
 /*
  * Temporal wavefront: the reference picture may still be under construction by an earlier job of the same launch.
@@ -282,6 +294,7 @@ DEV void wave_load_window(uint8_t *win, const Plane &P, int wx0, int wy0, int na
     /* narrow geometry (h264e_dev.h): only 53 columns x 52 rows of the window are ever read */
     const int rows = narrow ? H264E_NARROW_VH : WIN_W;
     const bool interior = wx0 >= 0 && wx0 + WIN_W <= P.w;
+    const int org = win_org(wx0);
     if (interior)
     {
         u32x4 v[4];
@@ -304,8 +317,9 @@ DEV void wave_load_window(uint8_t *win, const Plane &P, int wx0, int wy0, int na
                 const int r = (l >> 2) + 16*k;
                 if (r < rows)
                 {
-                    uint8_t *d = win + r*WIN_STRIDE + 16*seg;
-                    lds32_store(d, v[k].x); lds32_store(d + 4, v[k].y); lds32_store(d + 8, v[k].z); lds32_store(d + 12, v[k].w);
+                    uint8_t *d = win + r*WIN_STRIDE;
+                    const int pos = org + 16*seg;
+                    win_store4(d, pos, v[k].x); win_store4(d, pos + 4, v[k].y); win_store4(d, pos + 8, v[k].z); win_store4(d, pos + 12, v[k].w);
                 }
             }
         }
@@ -317,8 +331,38 @@ DEV void wave_load_window(uint8_t *win, const Plane &P, int wx0, int wy0, int na
             if (l < rows)
             {
                 const int y = imin(imax(wy0 + l, 0), P.h - 1);
-                for (int g = 0; g < 2*nq; g++) lds32_store(win + l*WIN_STRIDE + 4*g, ref_load4(P, wx0 + 4*g, y));
+                for (int g = 0; g < 2*nq; g++) win_store4(win + l*WIN_STRIDE, org + 4*g, ref_load4(P, wx0 + 4*g, y));
             }
+        }
+    }
+    wave_sync();
+}
+
+/* One macroblock step to the right: the window that started at wx0 - 16 is in LDS, and only the strip that becomes valid with wx0 is
+ * loaded -- one lane per window row, 16 bytes (narrow: 16 + 4).  The strip STARTS AT THE DWORD THAT HOLDS THE FIRST NEWLY VALID COLUMN,
+ * never where the previous load ended: whatever an earlier load brought beyond its valid width (the tail of a strip's last dword, the
+ * right part of a whole load) was not final in the frame being referenced then, and is loaded again here, behind the counter that now
+ * covers it.  wide: columns wx0+48 .. wx0+63; narrow (valid width 53): wx0+37 .. wx0+52, in the dwords wx0+36 .. wx0+55.  Everything
+ * left of the strip was valid -- final -- when it was loaded, in all rows (the row range of a window does not move along the row).
+ * Only for windows that, like their predecessor, lie inside the picture's columns (the caller's test). */
+template <bool NARROW> DEV void wave_slide_window(uint8_t *win, const Plane &P, int wx0, int wy0)
+{
+    constexpr int rows = NARROW ? H264E_NARROW_VH : WIN_W;
+    constexpr int rel = NARROW ? (H264E_NARROW_VW - 16) & ~3 : WIN_W - 16;       /* first dword of the strip, relative to wx0 */
+    static_assert(!NARROW || rel + 20 >= H264E_NARROW_VW, "the narrow strip is five dwords");
+    const int pos = win_org(wx0) + rel;
+    WAVE_FOR(l)
+    {
+        if (l < rows)
+        {
+            const int y = imin(imax(wy0 + l, 0), P.h - 1);
+            const gu8 *s = P.p + (size_t)y*P.stride + wx0 + rel;
+            const u32x4 v = cload128(s);
+            uint32_t t = 0;
+            if (NARROW) t = cload32(s + 16);
+            uint8_t *d = win + l*WIN_STRIDE;
+            win_store4(d, pos, v.x); win_store4(d, pos + 4, v.y); win_store4(d, pos + 8, v.z); win_store4(d, pos + 12, v.w);
+            if (NARROW) win_store4(d, pos + 16, t);
         }
     }
     wave_sync();

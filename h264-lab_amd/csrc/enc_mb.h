@@ -65,8 +65,12 @@ struct RowLds
     /* ---- both sides */
     int far_reads[3];                               /* reference accesses of this row that left the valid window (search / reconstruction side / 8x8 search helper) */
     int far_fail[3];                                /* a dynamic wait behind such an access gave up (enc_kernels.h rv_wait_rect): -1 expired, -2 producer aborted */
+    int win_x;                                      /* search side: macroblock column whose window this workgroup loaded last (enc_row.h row_prefetch), -2 = none yet
+                                                       (set by row_begin in every variant: not among the search-side buffers at the end) */
     int16_t slice_row[H264E_MAX_SLICES + 2];       /* this frame's slice start rows (copy of the task's) */
-    unsigned long long prof[4][32], prof_last[4], prof_c0, prof_w0;     /* -DH264E_STAMPS diagnostic build only */
+#ifdef H264E_STAMPS
+    unsigned long long prof[4][32], prof_last[4], prof_c0, prof_w0;     /* diagnostic build only: the mirrored window needs the room */
+#endif
     /* hand-off words of the two-wave pipeline (h264e_kernels.hip): monotonic counters "macroblocks done" per stage, and a stop code */
     int f_noskip, f_bound, f_inter, f_decided, f_wdone, f_stop;
     int early_bound;                                /* an upper bound of the inter cost, known right after the candidate evaluation (f_bound) */
@@ -105,7 +109,7 @@ struct RowLds
     mv32 part_mv[4][4], part_mvd[4][4];
     GCtx gctx[4];                                   /* the motion search's predictor context, one copy per partition type (lane group) */
     int gcost[4], gnum[4];                          /* cost and number of partitions of every partition type searched */
-    alignas(16) uint8_t win[WIN_W*WIN_STRIDE + 16];  /* reference luma window around the current macroblock */
+    alignas(16) uint8_t win[WIN_W*WIN_STRIDE + 16];  /* reference luma window around the current macroblock, mirrored (enc_kernels.h WIN_STRIDE) */
     alignas(16) uint8_t skip_pred[256];
     alignas(16) uint8_t skip_pred_c[128];           /* chroma of the early-skip test (the reconstruction side predicts chroma again for itself) */
     alignas(16) uint8_t gtest[4][256];              /* prediction of every partition type searched */

@@ -73,8 +73,11 @@ DEV void row_begin(RowLds &L, const h264e_geom_t &G, const ChainG &C, const h264
     df_tab_load(L.dftab);
     L.qconst[0] = k_lambda_mv_q4[T.qp]; L.qconst[1] = k_lambda_q4[T.qp]; L.qconst[2] = k_skip_thr_inter[T.qp];
     L.qconst[3] = k_skip_thr_i4x4[T.qp]; L.qconst[4] = k_lambda_i4_q4[T.qp]; L.qconst[5] = k_lambda_i16_q4[T.qp];
+    L.win_x = -2;
+#ifdef H264E_STAMPS
     for (int i = 0; i < 32; i++) L.prof[0][i] = L.prof[1][i] = L.prof[2][i] = L.prof[3][i] = 0;
     L.prof_last[0] = L.prof_last[1] = 0;
+#endif
     PROF_ROW_BEGIN(L);
     wave_sync();
     PROF_ROW_SYNC(L);
@@ -166,7 +169,11 @@ DEV void load_input(MbBuf &B, const h264e_geom_t &G, const RowTask &T, int mbx, 
 
 /* What macroblock (x, row) needs that does not depend on the row above: its input samples and, for P slices, the
  * reference window (the caller has waited for the temporal dependency).  Issued BEFORE the wait for the row above, so
- * the HBM latency of these loads overlaps with that wait. */
+ * the HBM latency of these loads overlaps with that wait.
+ * The window SLIDES (enc_kernels.h wave_slide_window: one strip of 16 new columns instead of the whole window) when the window of
+ * x - 1 is what this workgroup loaded last (L.win_x: never for the first macroblock a workgroup encodes, wherever its row starts) and
+ * both windows lie inside the picture's columns; otherwise -- at the left and right border with their clamped loads, in pictures
+ * narrower than the window -- it is loaded whole. */
 template <int GEOM> DEV void row_prefetch(RowLds &L, const h264e_geom_t &G, const RowTask &T, int row, int x)
 {
     load_input(L.mb[x & 1], G, T, x, row);
@@ -174,7 +181,10 @@ template <int GEOM> DEV void row_prefetch(RowLds &L, const h264e_geom_t &G, cons
     {
         Plane P;
         P.p = (const gu8 *)T.ref[0]; P.w = G.W; P.h = G.H; P.stride = G.W;
-        wave_load_window(L.win, P, x*16 - WIN_M, row*16 - WIN_M, T.narrow);
+        const int wx0 = x*16 - WIN_M;
+        if (uni(L.win_x) == x - 1 && wx0 - 16 >= 0 && wx0 + WIN_W <= P.w) wave_slide_window<GEOM == GEOM_NARROW>(L.win, P, wx0, row*16 - WIN_M);
+        else wave_load_window(L.win, P, wx0, row*16 - WIN_M, T.narrow);
+        L.win_x = x;
     }
 }
 
@@ -214,7 +224,7 @@ template <int GEOM> DEV void mb_ctx_init(MbCtx &m, RowLds &L, const h264e_geom_t
     m.lambda_mv = uni(L.qconst[0]); m.lambda_q4 = uni(L.qconst[1]); m.skip_thr = uni(L.qconst[2]);
     m.skip_thr_i4 = uni(L.qconst[3]); m.lambda_i4 = uni(L.qconst[4]); m.lambda_i16 = uni(L.qconst[5]);
     m.rv.dep = (const GLOBAL_AS int *)T.dep_progress; m.rv.nmbx = G.nmbx; m.rv.nmby = G.nmby;
-    m.rv.P = m.ref[0]; m.rv.win = (const lu8 *)L.win; m.rv.has_win = GEOM != GEOM_INTRA && T.slice_type == 0; m.rv.wx0 = x*16 - WIN_M; m.rv.wy0 = row*16 - WIN_M;
+    m.rv.P = m.ref[0]; m.rv.win = (const lu8 *)L.win + win_org(x*16 - WIN_M); m.rv.has_win = GEOM != GEOM_INTRA && T.slice_type == 0; m.rv.wx0 = x*16 - WIN_M; m.rv.wy0 = row*16 - WIN_M;
     m.rv.vw = GEOM == GEOM_NARROW ? H264E_NARROW_VW : WIN_W; m.rv.vh = GEOM == GEOM_NARROW ? H264E_NARROW_VH : WIN_W; m.rv.far = &L.far_reads[side]; m.rv.fail = &L.far_fail[side]; m.rv.slice_row = L.slice_row; m.rv.nslices = T.nslices; m.rv.spin_limit = G.spin_limit;
 }
 

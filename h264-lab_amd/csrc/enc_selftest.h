@@ -50,7 +50,7 @@ DEV void stage_selftest(StageLds &S, RowLds &L, int stage, const GLOBAL_AS uint8
     if (stage == 1 || stage == 2)
     {
         const int x = a[0], y = a[1], window = stage == 1 ? a[2] : a[6];
-        if (window) { R.has_win = 1; R.wx0 = x - WIN_M; R.wy0 = y - WIN_M; wave_load_window(S.win, P, R.wx0, R.wy0, 0); wave_sync(); }
+        if (window) { R.has_win = 1; R.wx0 = x - WIN_M; R.wy0 = y - WIN_M; R.win = (const lu8 *)S.win + win_org(R.wx0); wave_load_window(S.win, P, R.wx0, R.wy0, 0); wave_sync(); }
         if (stage == 1)
         {
             int s4[4];
@@ -164,7 +164,7 @@ DEV void stage_selftest(StageLds &S, RowLds &L, int stage, const GLOBAL_AS uint8
         m.G = &Gs; m.speed = a[10]; m.slice_type = 0; m.x = 2; m.y = 2; m.num = 14; m.qp = a[9];
         m.lambda_mv = k_lambda_mv_q4[a[9]];
         m.rv = R; m.rv.P = P8; m.rv.nmbx = 6; m.rv.nmby = 6;
-        if (a[19]) { m.rv.has_win = 1; m.rv.win = (const lu8 *)L.win; m.rv.wx0 = 32 - WIN_M; m.rv.wy0 = 32 - WIN_M; wave_load_window(L.win, P8, m.rv.wx0, m.rv.wy0, 0); }
+        if (a[19]) { m.rv.has_win = 1; m.rv.wx0 = 32 - WIN_M; m.rv.win = (const lu8 *)L.win + win_org(m.rv.wx0); m.rv.wy0 = 32 - WIN_M; wave_load_window(L.win, P8, m.rv.wx0, m.rv.wy0, 0); }
         WAVE_FOR(l) { lds32_store(L.mb[0].inp + 4*l, gload32((const gu8 *)in + 96*96 + 4*l)); lds32_store(L.gtest[0] + 4*l, 0u); }
         wave_sync();
         const rect_t range = { a[11], a[12], a[13], a[14] };
