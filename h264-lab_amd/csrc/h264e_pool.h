@@ -55,6 +55,7 @@ static int imin_h(int a, int b) { return a < b ? a : b; }
  * behind the other's (measured: "bounded spin expired" with 3-4 concurrent clip encoders, tools/multi_clip_probe.py).  A pool takes
  * its device's token with its first submit and gives it back when its launches have drained (h264e_hip_sync / release / destroy). */
 #include <pthread.h>
+#include <stdarg.h>
 #define H264E_MAX_DEVICES 64
 /* a token, not a mutex: a launch group takes it on the thread that launches the merged grid and gives it back on whichever member
  * thread sees the launch drained -- a pthread mutex may only be unlocked by the thread that locked it */
@@ -175,6 +176,7 @@ struct h264e_hip_pool
     h264e_chain_dev_t *chains_host;      /* host mirror of the device descriptors */
     h264e_chain_dev_t *chains_dev;
     h264e_frame_task_t *tasks_dev;       /* ring of TASK_RING task arrays */
+    h264e_frame_task_t *tasks_host;      /* [nchains] the task array of the submit being built (fill_task) */
     int *progress_all;
     int *errflag;
     unsigned long long *mb_counter;      /* device: macroblocks reconstructed by this pool's rows, delivered or not (h264e_hip_mb_counter) */
@@ -217,15 +219,27 @@ struct h264e_hip_pool
     int ev_pending;
 };
 
+/* One description of a launch, computed in ONE place from the host tasks (submit_check): what pick_variant, the dispatch order and a
+ * launch group's merge need to know about it.  A group member hands its shape to the group, which merges them (shape_merge). */
+typedef struct
+{
+    int jobs, narrow;                    /* jobs up to the last active one; their window geometry (every job of a launch has the same) */
+    int forced, all_intra;               /* kernel variant forced by H264E_WAVES (0: chosen per launch); no job has anything to search */
+    int sliced, parallel, tree;          /* a job has two or more row-band slices (the band policy of build_order); see pick_variant */
+} launch_shape_t;
+
 /* launch groups (see h264e_hip_group_create below) */
 #define H264E_GROUP_MAX 8
 struct h264e_hip_group
 {
     int device, nmembers, arrived, round, failed;
-    h264e_hip_pool_t *member[H264E_GROUP_MAX];
-    /* what each member wants launched this round */
-    h264e_frame_task_t *pend_tasks[H264E_GROUP_MAX];
-    int pend_jobs[H264E_GROUP_MAX], pend_narrow[H264E_GROUP_MAX], pend_waves[H264E_GROUP_MAX], pend[H264E_GROUP_MAX];
+    struct
+    {
+        h264e_hip_pool_t *pool;
+        h264e_frame_task_t *tasks;       /* what the member wants launched this round: shape.jobs device jobs (owned) */
+        launch_shape_t shape;
+        int pending;
+    } member[H264E_GROUP_MAX];
     pthread_mutex_t mu;
     pthread_cond_t cv;
     hipStream_t stream;
@@ -234,7 +248,6 @@ struct h264e_hip_group
     h264e_frame_task_t *tasks_dev; size_t tasks_cap;
     uint32_t *order_dev; size_t order_cap;
     int holds_device;                    /* the group's merged launch owns the device's launch token (taken at the launch, given back when it has drained) */
-    int last_variant[2];                 /* kernel variant of the last round's launches, per window geometry (-1: none): for tests and logs */
     char err[256];                       /* why the last round failed: every member reports it, not only the thread that launched */
 };
 
@@ -267,7 +280,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     if (p->abort_stream) (void)hipStreamSynchronize(p->abort_stream);
     device_release(p);
     host_free(p->hheap);
-    free(p->host_rbsp); free(p->host_mbrec); free(p->slot_launch); free(p->order_host);
+    free(p->host_rbsp); free(p->host_mbrec); free(p->slot_launch); free(p->order_host); free(p->tasks_host);
     dev_free(p->heap);
     dev_free(p->den);
     dev_free(p->sc_rec);
@@ -286,21 +299,81 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     free(p);
 }
 
-/* Dispatch order of a launch of `jobs` jobs: (job, row) sorted by the step at which the row can start when consecutive jobs are
- * consecutive frames of one stream (lag*job + 2*row: a counting sort); every workgroup still only waits for workgroups that precede it
- * in this order (far reads: a bounded distance ahead).  Built for the number of jobs a launch really has, so that a pool with many
- * slots does not dispatch thousands of empty workgroups with every short launch.
- * bands = 8 (profiles/r02_xcd_bands.txt): workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md: blocks b and b+8
- * share one), so the order is additionally arranged so that a macroblock row lands on the XCD of its band of rows (row*8/nmby): the
- * rows whose reference windows overlap then share an L2.  bands = 0: none; -1: the default policy below, or what H264E_XCD_BANDS
- * forces.  The per-XCD queues are sized for eight bands, so any other count is refused.  Fails with the error text set. */
+/* Dispatch order of a launch: the jobs of `nmembers` streams, member after member (member i's job j is launch job base_i + j), as
+ * (job << 16) | row words sorted by the step at which the row can start when consecutive jobs of a member are consecutive frames of one
+ * stream (lag*j + 2*row: a counting sort); ties go by j, then member, then row, so several streams are interleaved frame by frame.
+ * Every workgroup still only waits for workgroups that precede it in this order (far reads: a bounded distance ahead).  Built for the
+ * number of jobs a launch really has, so that a pool with many slots does not dispatch thousands of empty workgroups with every short
+ * launch.  Pure: no pool, no runtime call, no environment.  `out` takes rows * (all jobs) words; -1 = out of host memory. */
+#define H264E_ORDER_MAX_JOBS 65536     /* a job has 16 bits of the order word */
+static int order_by_start_step(uint32_t *out, int rows, int lag, const int *member_jobs, int nmembers)
+{
+    int maxjobs = 0;
+    for (int i = 0; i < nmembers; i++) if (member_jobs[i] > maxjobs) maxjobs = member_jobs[i];
+    if (maxjobs < 1) return 0;
+    const int maxkey = lag*(maxjobs - 1) + 2*(rows - 1);
+    int *start = (int *)calloc((size_t)maxkey + 2, sizeof(int));
+    if (!start) return -1;
+    for (int i = 0; i < nmembers; i++) for (int j = 0; j < member_jobs[i]; j++) for (int r = 0; r < rows; r++) start[lag*j + 2*r + 1]++;
+    for (int k = 0; k <= maxkey; k++) start[k + 1] += start[k];
+    for (int j = 0; j < maxjobs; j++)
+        for (int i = 0, base = 0; i < nmembers; base += member_jobs[i], i++)
+            if (j < member_jobs[i])
+                for (int r = 0; r < rows; r++) out[start[lag*j + 2*r]++] = ((uint32_t)(base + j) << 16) | (uint32_t)r;
+    free(start);
+    return 0;
+}
+
 /* entries a launch of `jobs` jobs can take in the dispatch order (banded: eight equally long queues per job, padded) */
 static size_t order_capacity(const h264e_geom_t &G, int jobs) { return (size_t)jobs*(size_t)(8*((G.nmby + 7)/8 + 1)); }
+
+/* The second step on top of that order: 8 XCD bands (profiles/r02_xcd_bands.txt).  Workgroups are dealt round-robin over the 8 XCDs
+ * (MI355X_MICROARCH.md: blocks b and b+8 share one), so the `total` words of `in` are arranged so that a macroblock row lands on the XCD
+ * of its band of rows (row*8/nmby): the rows whose reference windows overlap then share an L2.  Returns the entries written to `out`
+ * (order_capacity of them), 0 = out of host memory.
+ * Eight queues in key order, one per XCD; slot i takes entry i / 8 of queue i % 8.  The queues are EQUALLY LONG, job by job: a band that
+ * has fewer rows than the tallest one (nmby is rarely a multiple of 8; one band also carries the finalizer) is padded with entries that
+ * are nobody's.  Without that the queues drift apart by a row or two per job, and because workgroups are dispatched strictly in index
+ * order, an XCD whose resident workgroups all wait for rows of a queue that lags behind blocks the dispatch of exactly those rows:
+ * measured as 2-4 % at 1080p with fixed bands, and as a dead launch ("bounded spin expired") once a launch is long enough -- 600 jobs
+ * of 720p, CIF, or 1080p with 8 slices. */
+static size_t order_into_bands(const h264e_geom_t &G, int jobs, const uint32_t *in, int total, uint32_t *out)
+{
+    const int bands = 8, per = (G.nmby + 7)/8 + 1;
+    const size_t qlen = (size_t)per*jobs;
+    uint32_t *q = (uint32_t *)malloc(sizeof(uint32_t)*8*qlen);
+    int *fill = (int *)calloc((size_t)8*jobs, sizeof(int)), *want = (int *)calloc((size_t)8*jobs, sizeof(int));
+    size_t cnt[8] = { 0 }, n = 0;
+    if (!q || !fill || !want) { free(q); free(fill); free(want); return 0; }
+    for (size_t i = 0; i < 8*qlen; i++) q[i] = H264E_ORDER_PAD;
+    /* queue x, job j owns the entries [j*per, (j+1)*per) ... in KEY order that would interleave the jobs; so: append in key order, and
+     * when a job's last entry of a queue has gone in, append its padding right behind it */
+    for (int i = 0; i < total; i++)
+    {
+        const int row = (int)(in[i] & 0xffffu), x = (row >= G.nmby ? bands - 1 : imin_h(bands - 1, row*bands/G.nmby)) & 7;      /* band b -> XCD b % 8 */
+        want[8*(in[i] >> 16) + x]++;
+    }
+    for (int i = 0; i < total; i++)
+    {
+        const int row = (int)(in[i] & 0xffffu), jb = (int)(in[i] >> 16), x = (row >= G.nmby ? bands - 1 : imin_h(bands - 1, row*bands/G.nmby)) & 7;
+        /* a picture of fewer than 8 rows leaves queues without a row of this job: they get the job's padding with its first entry */
+        if (row == 0) for (int y = 0; y < 8; y++) if (!want[8*jb + y]) cnt[y] += (size_t)per;
+        q[(size_t)x*qlen + cnt[x]++] = in[i];
+        if (++fill[8*jb + x] == want[8*jb + x]) cnt[x] += (size_t)(per - want[8*jb + x]);        /* the padding stays H264E_ORDER_PAD */
+    }
+    for (size_t k = 0; k < qlen; k++) for (int x = 0; x < 8; x++) out[n++] = q[(size_t)x*qlen + k];
+    free(q); free(fill); free(want);
+    return n;
+}
+
+/* The order of a pool's own launch of `jobs` jobs into p->order_host / order_count: the one-member case of order_by_start_step, then the
+ * bands.  bands = 0: none; 8: banded; -1: the default policy below, or what H264E_XCD_BANDS forces.  The per-XCD queues are sized for
+ * eight bands, so any other count is refused.  Fails with the error text set. */
 static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced, int bands)
 {
     const h264e_geom_t &G = p->G;
-    const int rows = G.nmby + 1, total = jobs*rows, lag = narrow ? H264E_NARROW_FRAME_LAG : H264E_FRAME_LAG, maxkey = lag*(jobs - 1) + 2*(rows - 1);
-    /* measured (gpurun_out/bands_pad, one MI355X, padded queues): 8 bands nearly halve FETCH_SIZE everywhere (1080p: 1521 -> 830 MB per
+    const int rows = G.nmby + 1, total = jobs*rows, lag = narrow ? H264E_NARROW_FRAME_LAG : H264E_FRAME_LAG;
+    /* measured (profiles/r04_xcd_bands.txt, one MI355X, padded queues): 8 bands nearly halve FETCH_SIZE everywhere (1080p: 1521 -> 830 MB per
      * launch, WRITE_SIZE 765 -> 603) -- HBM traffic nobody waits for at 2 % of the bandwidth -- and what they do to the SPEED depends on
      * what a launch is short of: single-slice streams of big pictures gain (4K +5 %, 8K +14 %: a frame's rows no longer fit the L2s at
      * random), everything else loses 1-13 % (1080p -4 %, 720p -1 %, CIF -13 %, rate control -4 %; row-band slices -9 % at every size,
@@ -308,52 +381,12 @@ static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced, in
      * launches from 4K up, H264E_XCD_BANDS=8 / 0 forces */
     if (bands < 0) bands = getenv("H264E_XCD_BANDS") ? atoi(getenv("H264E_XCD_BANDS")) : (G.nmb >= 30000 && !sliced ? 8 : 0);
     if (bands != 0 && bands != 8) FAIL("dispatch order: %d XCD bands (H264E_XCD_BANDS): only 0 and 8 are supported", bands);
-    uint32_t *ord = p->order_host;
-    int *start = (int *)calloc((size_t)maxkey + 2, sizeof(int));
-    uint32_t *tmp = bands ? (uint32_t *)malloc(sizeof(uint32_t)*(size_t)total) : ord;
-    if (!start || !tmp) { free(start); if (bands) free(tmp); FAIL("out of host memory"); }
-    for (int job = 0; job < jobs; job++) for (int r = 0; r < rows; r++) start[lag*job + 2*r + 1]++;
-    for (int k = 0; k <= maxkey; k++) start[k + 1] += start[k];
-    for (int job = 0; job < jobs; job++) for (int r = 0; r < rows; r++) tmp[start[lag*job + 2*r]++] = ((uint32_t)job << 16) | (uint32_t)r;     /* ties: by job */
-    free(start);
+    uint32_t *tmp = bands ? (uint32_t *)malloc(sizeof(uint32_t)*(size_t)total) : p->order_host;
+    int rc = tmp ? order_by_start_step(tmp, rows, lag, &jobs, 1) : -1;
     p->order_count = (size_t)total;
-    if (bands)
-    {
-        /* Eight queues in key order, one per XCD; slot i takes entry i / 8 of queue i % 8.  The queues are EQUALLY LONG, job by job:
-         * a band that has fewer rows than the tallest one (nmby is rarely a multiple of 8; one band also carries the finalizer) is
-         * padded with entries that are nobody's.  Without that the queues drift apart by a row or two per job, and because workgroups
-         * are dispatched strictly in index order, an XCD whose resident workgroups all wait for rows of a queue that lags behind
-         * blocks the dispatch of exactly those rows: measured as 2-4 % at 1080p with fixed bands, and as a dead launch ("bounded spin
-         * expired") once a launch is long enough -- 600 jobs of 720p, CIF, or 1080p with 8 slices. */
-        const int per = (G.nmby + 7)/8 + 1;
-        const size_t qlen = (size_t)per*jobs;
-        uint32_t *q = (uint32_t *)malloc(sizeof(uint32_t)*8*qlen);
-        int *fill = (int *)calloc((size_t)8*jobs, sizeof(int));
-        size_t cnt[8] = { 0 };
-        if (!q || !fill) { free(q); free(fill); free(tmp); FAIL("out of host memory"); }
-        for (size_t i = 0; i < 8*qlen; i++) q[i] = H264E_ORDER_PAD;
-        /* queue x, job j owns the entries [j*per, (j+1)*per) ... in KEY order that would interleave the jobs; so: append in key order, and
-         * when a job's last entry of a queue has gone in, append its padding right behind it */
-        int *want = (int *)calloc((size_t)8*jobs, sizeof(int));
-        if (!want) { free(q); free(fill); free(tmp); FAIL("out of host memory"); }
-        for (int i = 0; i < total; i++)
-        {
-            const int row = (int)(tmp[i] & 0xffffu), x = (row >= G.nmby ? bands - 1 : imin_h(bands - 1, row*bands/G.nmby)) & 7;      /* band b -> XCD b % 8 */
-            want[8*(tmp[i] >> 16) + x]++;
-        }
-        for (int i = 0; i < total; i++)
-        {
-            const int row = (int)(tmp[i] & 0xffffu), jb = (int)(tmp[i] >> 16), x = (row >= G.nmby ? bands - 1 : imin_h(bands - 1, row*bands/G.nmby)) & 7;
-            /* a picture of fewer than 8 rows leaves queues without a row of this job: they get the job's padding with its first entry */
-            if (row == 0) for (int y = 0; y < 8; y++) if (!want[8*jb + y]) cnt[y] += (size_t)per;
-            q[(size_t)x*qlen + cnt[x]++] = tmp[i];
-            if (++fill[8*jb + x] == want[8*jb + x]) cnt[x] += (size_t)(per - want[8*jb + x]);        /* the padding stays H264E_ORDER_PAD */
-        }
-        size_t n = 0;
-        for (size_t k = 0; k < qlen; k++) for (int x = 0; x < 8; x++) ord[n++] = q[(size_t)x*qlen + k];
-        p->order_count = n;
-        free(q); free(fill); free(want); free(tmp);
-    }
+    if (!rc && bands && !(p->order_count = order_into_bands(G, jobs, tmp, total, p->order_host))) rc = -1;
+    if (bands) free(tmp);
+    if (rc) FAIL("out of host memory");
     return 0;
 }
 
@@ -417,6 +450,12 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     p->slot_launch = (int *)calloc((size_t)nchains, sizeof(int));
     p->host_rbsp = (uint8_t **)calloc((size_t)nchains, sizeof(uint8_t *));
     p->host_mbrec = (h264e_hip_mbrec_t **)calloc((size_t)nchains, sizeof(h264e_hip_mbrec_t *));
+    p->tasks_host = (h264e_frame_task_t *)calloc((size_t)nchains, sizeof(h264e_frame_task_t));
+    if (!p->chains_host || !p->clu_dev || !p->ref_sel || !p->traj_dev || !p->traj_cur || !p->slot_launch || !p->host_rbsp || !p->host_mbrec || !p->tasks_host)
+    {
+        h264e_hip_pool_destroy(p);
+        FAIL("out of host memory");
+    }
     int bad = 0;
     const size_t plane = (size_t)G.W*G.H*3/2;
     const uint32_t arena_cap = (uint32_t)((size_t)G.nmb*640 + 1024);
@@ -1000,7 +1039,7 @@ extern "C" int h264e_hip_sync(h264e_hip_pool_t *p)
         if (g->holds_device && !g->arrived) { g->holds_device = 0; device_token_give(g->device); }
         pthread_mutex_unlock(&g->mu);
         if (eg != hipSuccess) FAIL("group launch: %s", hipGetErrorString(eg));
-        if (p->profile && g->nmembers && g->member[0] == p)
+        if (p->profile && g->nmembers && g->member[0].pool == p)
             for (int k = 0; k < 2; k++)
             {
                 float a = 0;
@@ -1062,137 +1101,140 @@ extern "C" int h264e_hip_group_create(h264e_hip_group_t **out, int device)
     pthread_mutex_init(&g->mu, 0); pthread_cond_init(&g->cv, 0);
     if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&g->stream) != hipSuccess) { free(g); FAIL("group_create: no stream on device %d", device); }
     (void)hipEventCreate(&g->ev_done);
-    for (int k = 0; k < 2; k++) { (void)hipEventCreate(&g->ev_t0[k]); (void)hipEventCreate(&g->ev_t1[k]); g->last_variant[k] = -1; }
+    for (int k = 0; k < 2; k++) { (void)hipEventCreate(&g->ev_t0[k]); (void)hipEventCreate(&g->ev_t1[k]); }
     *out = g;
     return 0;
 }
 
-/* Kernel variant of a launch that offers `rows` macroblock rows in `wgs` workgroups (bk_launch_mb): 0 intra frames only; 4 two waves per
- * row at 4 per SIMD (2048 resident workgroups) where the rows fill the chip; 3 the four-wave latency variant (192 VGPRs: 512 resident
- * workgroups) ONLY where the whole grid is resident anyway -- its far reads may wait for any workgroup of the grid; 2 in between. */
+/* Kernel variant of a launch of `jobs` jobs of `nmby` macroblock rows each (bk_launch_mb); `jobs` is the shape's own or, in a launch group,
+ * the MERGED count: a member's own few rows say nothing about how full the chip will be.  Two wavefronts per macroblock row (search |
+ * reconstruction pipeline) halve the macroblock latency for twice the wave slots: the better trade wherever a launch is latency bound
+ * (single-slice streams: mis-speculation events; rate control and the frame-at-a-time API: a few frames per launch) and still level for
+ * multi-slice streams -- variant 2.  Around it:
+ * 0, the intra-only variant of the one-wave kernel: an all-intra launch has nothing to search and no events -- no inter code, half the
+ *    registers, twice the rows in flight (22.4 vs 18.3 M MB/s at 1080p);
+ * 4, the two-wave kernel allocated for 4 waves per SIMD (2048 resident workgroups), where the rows fill the chip and the launch is
+ *    `parallel`: it has more independent work than one single-slice stream's temporal wavefront -- several slices per frame, pictures of
+ *    200+ macroblock rows (8K class), several streams merged.  Only there do the extra resident rows buy more than the 128-register
+ *    allocation costs (spills in the search; round-4 sweep profiles/r04_variant_sweep.txt: 1080p 2 / 4 / 8 slices +5 %, 8K single slice +34 %, two
+ *    slices +20 %; a single-slice 1080p / 4K / 720p stream -6 % / -5 % / -3 % -- its passes are bound by the mis-speculation refills,
+ *    i.e. by the macroblock latency).  Not with a `tree`: a launch that carries hedge leaves (rate control) ever uses a few frames of it,
+ *    pure latency (1080p 4 Mbit/s: 245 vs 213 fps, 8 slices 413 vs 381);
+ * 3, the latency variant -- four waves per row, the 8x8 partition search and the deblocking + stores on waves of their own (192 VGPRs:
+ *    512 resident workgroups): launches of one or a few frames, where the chip is empty and only the macroblock latency counts -- ONLY
+ *    where the whole grid is resident anyway, because its far reads may wait for any workgroup of the grid. */
 #define H264E_RESIDENT_WG_V2 1536
 #define H264E_RESIDENT_WG_V3 512
-/* `parallel`: the launch has more independent work than one single-slice stream's temporal wavefront -- several slices per frame,
- * pictures of 200+ macroblock rows (8K class), several streams merged: only there do the extra resident rows of the 4-per-SIMD kernel
- * buy more than its 128-register allocation costs (spills in the search; r4 sweep gpurun_out/var_sweep*: 1080p 2 / 4 / 8 slices +5 %,
- * 8K single slice +34 %, two slices +20 %; a single-slice 1080p / 4K / 720p stream -6 % / -5 % / -3 % -- its passes are bound by the
- * mis-speculation refills, i.e. by the macroblock latency).  `tree`: the launch carries hedge leaves (rate control): a few frames of
- * it are ever used, pure latency (1080p 4 Mbit/s: 245 vs 213 fps, 8 slices 413 vs 381). */
-static int pick_variant(int forced, int all_intra, int rows, int wgs, int parallel, int tree)
+static int pick_variant(const launch_shape_t &s, int jobs, int nmby)
 {
-    if (forced) return forced;
-    if (all_intra) return 0;
-    if (rows >= H264E_RESIDENT_WG_V2 && parallel && !tree) return 4;
-    if (wgs <= H264E_RESIDENT_WG_V3) return 3;
+    if (s.forced) return s.forced;
+    if (s.all_intra) return 0;
+    if (jobs*nmby >= H264E_RESIDENT_WG_V2 && s.parallel && !s.tree) return 4;
+    if (jobs*(nmby + 1) <= H264E_RESIDENT_WG_V3) return 3;
     return 2;
 }
 
-/* all members that are still in the group have submitted: merge and launch (g->mu held).  ONE launch per window geometry (narrow /
- * wide: different kernels), its variant chosen from the MERGED grid: a member's own few rows say nothing about how full the chip will
- * be, and the four-wave latency variant (512 resident workgroups) must never carry a grid that does not fit the chip. */
+/* the macroblock kernel on `stream`, between two events when they are given; what the launch itself reports */
+static hipError_t launch_mb(const h264e_geom_t &G, int narrow, int variant, int jobs, size_t nblocks, const h264e_frame_task_t *tasks, const uint32_t *order,
+                            hipEvent_t before, hipEvent_t after, hipStream_t stream)
+{
+    hipError_t e = before ? hipEventRecord(before, stream) : hipSuccess;
+    if (e != hipSuccess) return e;
+    bk_launch_mb(G, narrow, variant, jobs, (unsigned)nblocks, tasks, order, stream);
+    e = after ? hipEventRecord(after, stream) : hipSuccess;
+    const hipError_t le = hipGetLastError();
+    return le != hipSuccess ? le : e;
+}
+
+/* why a round failed: every member reports the text, not only the thread that launched */
+static int group_fail(h264e_hip_group_t *g, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g->err, sizeof(g->err), fmt, ap);
+    va_end(ap);
+    return -1;
+}
+
+/* room in one of the group's device buffers.  Both are sized for a whole round BEFORE its first launch: growing them between two launches
+ * of a round would free memory the first one is still reading */
+static int group_grow(h264e_hip_group_t *g, void **buf, size_t *cap, size_t need, size_t slack, size_t elem)
+{
+    if (need <= *cap) return 0;
+    if (*buf) (void)hipFree(*buf);           /* (synchronises with the previous round's launch, which every member has waited for anyway) */
+    *cap = need + slack;
+    if (hipMalloc(buf, elem**cap) == hipSuccess) return 0;
+    *buf = 0; *cap = 0;
+    return group_fail(g, "group launch: device allocation failed");
+}
+
+/* ONE launch for the pending members of one window geometry (narrow / wide: different kernels), into td / od: the jobs member after
+ * member, the shapes merged -- two or more streams in the grid are parallel work like slices are (a group of one: what solo_launch
+ * would decide) --, the dispatch orders interleaved (order_by_start_step).  The four-wave latency variant (512 resident workgroups)
+ * must never carry a grid that does not fit the chip: pick_variant sees the merged job count.  Returns the jobs launched, -1 on failure. */
+static int group_launch_geometry(h264e_hip_group_t *g, int narrow, h264e_frame_task_t *td, uint32_t *od)
+{
+    launch_shape_t m = { 0, narrow, 0, 1, 0, 0, 0 };
+    int idx[H264E_GROUP_MAX], jobs[H264E_GROUP_MAX], n = 0, rc = 0;
+    for (int k = 0; k < g->nmembers; k++)
+        if (g->member[k].pending && g->member[k].shape.narrow == narrow)
+        {
+            const launch_shape_t &s = g->member[k].shape;
+            idx[n] = k; jobs[n++] = s.jobs; m.jobs += s.jobs;
+            if (s.forced) m.forced = s.forced;                          /* H264E_WAVES: the same for every pool of the process */
+            m.all_intra &= s.all_intra; m.parallel |= s.parallel; m.tree |= s.tree;
+        }
+    if (!n) return 0;
+    m.parallel |= n >= 2;
+    const h264e_geom_t &G = g->member[idx[0]].pool->G;
+    const size_t total = (size_t)m.jobs*(size_t)(G.nmby + 1);
+    if (m.jobs >= H264E_ORDER_MAX_JOBS) return group_fail(g, "group launch: too many jobs");
+    h264e_frame_task_t *th = (h264e_frame_task_t *)malloc(sizeof(h264e_frame_task_t)*(size_t)m.jobs);
+    uint32_t *oh = (uint32_t *)malloc(sizeof(uint32_t)*total);
+    if (!th || !oh || order_by_start_step(oh, G.nmby + 1, narrow ? H264E_NARROW_FRAME_LAG : H264E_FRAME_LAG, jobs, n)) rc = group_fail(g, "out of host memory");
+    /* the members prepared their slots (progress counters, ...) on their own streams: the launch waits for all of that */
+    for (int i = 0, b = 0; i < n && !rc; b += jobs[i++])
+    {
+        h264e_hip_pool_t *p = g->member[idx[i]].pool;
+        memcpy(th + b, g->member[idx[i]].tasks, sizeof(h264e_frame_task_t)*(size_t)jobs[i]);
+        if (hipEventRecord(p->ev_prep, p->stream) != hipSuccess || hipStreamWaitEvent(g->stream, p->ev_prep, 0) != hipSuccess) rc = group_fail(g, "group launch: cannot order the launch behind a member's stream");
+    }
+    if (!rc && (hipMemcpyAsync(td, th, sizeof(h264e_frame_task_t)*(size_t)m.jobs, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+                hipMemcpyAsync(od, oh, sizeof(uint32_t)*total, hipMemcpyHostToDevice, g->stream) != hipSuccess)) rc = group_fail(g, "group launch: task upload failed");
+    free(th); free(oh);            /* pageable sources: staged before the calls return */
+    if (!rc)
+    {
+        const hipError_t le = launch_mb(G, narrow, pick_variant(m, m.jobs, G.nmby), m.jobs, total, td, od, g->ev_t0[narrow], g->ev_t1[narrow], g->stream);
+        if (le != hipSuccess) rc = group_fail(g, "group launch: %s", hipGetErrorString(le));
+        else g->timed[narrow] = 1;
+    }
+    return rc ? rc : m.jobs;
+}
+
+/* all members that are still in the group have submitted: merge and launch (g->mu held), one launch per window geometry */
 static int group_launch_locked(h264e_hip_group_t *g)
 {
+    const size_t rows = (size_t)g->member[0].pool->G.nmby + 1;         /* one picture size per group (h264e_hip_group_join) */
+    size_t need_tasks = 0, off = 0;
     int rc = 0;
-    size_t need_tasks = 0, need_order = 0, task_off = 0, order_off = 0;
     g->err[0] = 0;
     g->timed[0] = g->timed[1] = 0;
-    g->last_variant[0] = g->last_variant[1] = -1;
-#define GFAIL(...) do { snprintf(g->err, sizeof(g->err), __VA_ARGS__); rc = -1; } while (0)
-    if (hipSetDevice(g->device) != hipSuccess) GFAIL("group launch: hipSetDevice(%d) failed", g->device);
-    /* buffers for the whole round, sized BEFORE the first launch: growing them between two launches of a round would free memory the first
-     * one is still reading */
-    for (int k = 0; k < g->nmembers; k++)
-        if (g->pend[k]) { need_tasks += (size_t)g->pend_jobs[k]; need_order += (size_t)g->pend_jobs[k]*(size_t)(g->member[k]->G.nmby + 1); }
-    if (!rc && need_tasks > g->tasks_cap)
-    {
-        if (g->tasks_dev) (void)hipFree(g->tasks_dev);           /* (synchronises with the previous round's launch, which every member has waited for anyway) */
-        g->tasks_cap = need_tasks + 64;
-        if (hipMalloc((void **)&g->tasks_dev, sizeof(h264e_frame_task_t)*g->tasks_cap) != hipSuccess) { g->tasks_dev = 0; g->tasks_cap = 0; GFAIL("group launch: device allocation failed"); }
-    }
-    if (!rc && need_order > g->order_cap)
-    {
-        if (g->order_dev) (void)hipFree(g->order_dev);
-        g->order_cap = need_order + 4096;
-        if (hipMalloc((void **)&g->order_dev, sizeof(uint32_t)*g->order_cap) != hipSuccess) { g->order_dev = 0; g->order_cap = 0; GFAIL("group launch: device allocation failed"); }
-    }
+    for (int k = 0; k < g->nmembers; k++) if (g->member[k].pending) need_tasks += (size_t)g->member[k].shape.jobs;
+    if (hipSetDevice(g->device) != hipSuccess) rc = group_fail(g, "group launch: hipSetDevice(%d) failed", g->device);
+    if (!rc) rc = group_grow(g, (void **)&g->tasks_dev, &g->tasks_cap, need_tasks, 64, sizeof(h264e_frame_task_t));
+    if (!rc) rc = group_grow(g, (void **)&g->order_dev, &g->order_cap, need_tasks*rows, 4096, sizeof(uint32_t));
     /* the merged launch owns the device like any other persistent launch (g_device_held): taken here, given back by the first member whose
      * h264e_hip_sync sees the launch drained, or when the group goes away */
     if (!rc && need_tasks && !g->holds_device) { device_token_take(g->device); g->holds_device = 1; }
     for (int narrow = 0; narrow < 2 && !rc; narrow++)
     {
-        int idx[H264E_GROUP_MAX], n = 0, jobs = 0, forced = 0, all_intra = 1;
-        for (int k = 0; k < g->nmembers; k++)
-            if (g->pend[k] && g->pend_narrow[k] == narrow)
-            {
-                idx[n++] = k; jobs += g->pend_jobs[k];
-                if (g->pend_waves[k] > 0) forced = g->pend_waves[k];     /* H264E_WAVES: the same for every pool of the process */
-                if (g->pend_waves[k] != 0) all_intra = 0;               /* 0 = a launch of intra frames only, -1 = to be chosen here */
-            }
-        if (!n) continue;
-        const h264e_geom_t &G = g->member[idx[0]]->G;
-        const int rows = G.nmby + 1, lag = narrow ? H264E_NARROW_FRAME_LAG : H264E_FRAME_LAG;
-        const size_t total = (size_t)jobs*rows;
-        /* two or more streams in the grid are parallel work like slices are (a group of one: what h264e_hip_submit would decide) */
-        int parallel = n >= 2 || G.nmby >= 200, tree = 0;
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < g->pend_jobs[idx[i]]; j++)
-            {
-                const h264e_frame_task_t &t = g->pend_tasks[idx[i]][j];
-                if (t.active && t.nslices >= 2) parallel = 1;
-                if (t.active && t.walk_quiet) tree = 1;
-            }
-        const int variant = pick_variant(forced, all_intra, jobs*G.nmby, (int)total, parallel, tree);
-        if (jobs >= 65536) { GFAIL("group launch: too many jobs"); break; }
-        h264e_frame_task_t *th = (h264e_frame_task_t *)malloc(sizeof(h264e_frame_task_t)*(size_t)jobs);
-        uint32_t *oh = (uint32_t *)malloc(sizeof(uint32_t)*total);
-        if (!th || !oh) { free(th); free(oh); GFAIL("out of host memory"); break; }
-        /* jobs member after member; dispatch order by start step lag*job + 2*row (a counting sort over all members: ties go member by
-         * member, so the streams are interleaved frame by frame) */
-        int base[H264E_GROUP_MAX], maxjobs = 0;
-        for (int i = 0, b = 0; i < n; i++)
-        {
-            base[i] = b;
-            memcpy(th + b, g->pend_tasks[idx[i]], sizeof(h264e_frame_task_t)*(size_t)g->pend_jobs[idx[i]]);
-            b += g->pend_jobs[idx[i]];
-            if (g->pend_jobs[idx[i]] > maxjobs) maxjobs = g->pend_jobs[idx[i]];
-        }
-        const int maxkey = lag*(maxjobs - 1) + 2*(rows - 1);
-        int *start = (int *)calloc((size_t)maxkey + 2, sizeof(int));
-        if (!start) { free(th); free(oh); GFAIL("out of host memory"); break; }
-        for (int i = 0; i < n; i++) for (int j = 0; j < g->pend_jobs[idx[i]]; j++) for (int r = 0; r < rows; r++) start[lag*j + 2*r + 1]++;
-        for (int k = 0; k <= maxkey; k++) start[k + 1] += start[k];
-        for (int j = 0; j < maxjobs; j++)
-            for (int i = 0; i < n; i++)
-                if (j < g->pend_jobs[idx[i]])
-                    for (int r = 0; r < rows; r++) oh[start[lag*j + 2*r]++] = ((uint32_t)(base[i] + j) << 16) | (uint32_t)r;
-        free(start);
-        /* the members prepared their slots (progress counters, ...) on their own streams: the launch waits for all of that */
-        for (int i = 0; i < n && !rc; i++)
-        {
-            h264e_hip_pool_t *p = g->member[idx[i]];
-            if (hipEventRecord(p->ev_prep, p->stream) != hipSuccess || hipStreamWaitEvent(g->stream, p->ev_prep, 0) != hipSuccess) GFAIL("group launch: cannot order the launch behind a member's stream");
-        }
-        h264e_frame_task_t *td = g->tasks_dev + task_off;
-        uint32_t *od = g->order_dev + order_off;
-        if (!rc && (hipMemcpyAsync(td, th, sizeof(h264e_frame_task_t)*(size_t)jobs, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
-                    hipMemcpyAsync(od, oh, sizeof(uint32_t)*total, hipMemcpyHostToDevice, g->stream) != hipSuccess)) GFAIL("group launch: task upload failed");
-        free(th); free(oh);            /* pageable sources: staged before the calls return */
-        if (!rc)
-        {
-            (void)hipEventRecord(g->ev_t0[narrow], g->stream);
-            bk_launch_mb(G, narrow, variant, jobs, (unsigned)total, td, od, g->stream);
-            (void)hipEventRecord(g->ev_t1[narrow], g->stream);
-            const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) GFAIL("group launch: %s", hipGetErrorString(le));
-            else { g->timed[narrow] = 1; g->last_variant[narrow] = variant; }
-        }
-        task_off += (size_t)jobs; order_off += total;
+        const int jobs = group_launch_geometry(g, narrow, g->tasks_dev + off, g->order_dev + off*rows);
+        if (jobs < 0) rc = -1; else off += (size_t)jobs;
     }
-#undef GFAIL
-    if (hipEventRecord(g->ev_done, g->stream) != hipSuccess && !rc) { snprintf(g->err, sizeof(g->err), "group launch: hipEventRecord failed"); rc = -1; }
-    if (rc && !g->err[0]) snprintf(g->err, sizeof(g->err), "group launch failed");
+    if (hipEventRecord(g->ev_done, g->stream) != hipSuccess && !rc) rc = group_fail(g, "group launch: hipEventRecord failed");
+    if (rc && !g->err[0]) (void)group_fail(g, "group launch failed");
     if (rc) snprintf(g_err, sizeof(g_err), "%s", g->err);
-    for (int k = 0; k < g->nmembers; k++) { free(g->pend_tasks[k]); g->pend_tasks[k] = 0; g->pend[k] = 0; }
+    for (int k = 0; k < g->nmembers; k++) { free(g->member[k].tasks); g->member[k].tasks = 0; g->member[k].pending = 0; }
     g->arrived = 0;
     g->failed = rc;
     g->round++;
@@ -1200,18 +1242,18 @@ static int group_launch_locked(h264e_hip_group_t *g)
     return rc;
 }
 
-/* a member's launch: hand it to the group and wait until the merged launch is on its way */
-static int group_submit(h264e_hip_pool_t *p, const h264e_frame_task_t *host, int njobs, int narrow, int waves)
+/* a member's launch: hand its jobs and its shape to the group and wait until the merged launch is on its way */
+static int group_submit(h264e_hip_pool_t *p, const h264e_frame_task_t *host, const launch_shape_t &s)
 {
     h264e_hip_group_t *g = p->group;
     int rc = 0, k;
     pthread_mutex_lock(&g->mu);
-    for (k = 0; k < g->nmembers && g->member[k] != p; k++) ;
+    for (k = 0; k < g->nmembers && g->member[k].pool != p; k++) ;
     if (k == g->nmembers) { pthread_mutex_unlock(&g->mu); FAIL("group_submit: not a member"); }
-    g->pend_tasks[k] = (h264e_frame_task_t *)malloc(sizeof(h264e_frame_task_t)*(size_t)njobs);
-    if (!g->pend_tasks[k]) { pthread_mutex_unlock(&g->mu); FAIL("out of host memory"); }
-    memcpy(g->pend_tasks[k], host, sizeof(h264e_frame_task_t)*(size_t)njobs);
-    g->pend_jobs[k] = njobs; g->pend_narrow[k] = narrow; g->pend_waves[k] = waves; g->pend[k] = 1;
+    g->member[k].tasks = (h264e_frame_task_t *)malloc(sizeof(h264e_frame_task_t)*(size_t)s.jobs);
+    if (!g->member[k].tasks) { pthread_mutex_unlock(&g->mu); FAIL("out of host memory"); }
+    memcpy(g->member[k].tasks, host, sizeof(h264e_frame_task_t)*(size_t)s.jobs);
+    g->member[k].shape = s; g->member[k].pending = 1;
     p->group_round = g->round;
     g->arrived++;
     if (g->arrived == g->nmembers) rc = group_launch_locked(g);
@@ -1238,10 +1280,10 @@ extern "C" int h264e_hip_group_join(h264e_hip_group_t *g, h264e_hip_pool_t *p)
     int bad = g->nmembers >= H264E_GROUP_MAX || (g->nmembers >= 1 && g->nmembers >= room) || p->device != g->device || g->arrived;
     if (!bad && g->nmembers)
     {
-        const h264e_geom_t &A = g->member[0]->G, &B = p->G;
+        const h264e_geom_t &A = g->member[0].pool->G, &B = p->G;
         bad = A.width != B.width || A.height != B.height || A.row_words != B.row_words || A.spin_limit != B.spin_limit;
     }
-    if (!bad) { g->member[g->nmembers++] = p; p->group = g; }
+    if (!bad) { memset(&g->member[g->nmembers], 0, sizeof(g->member[0])); g->member[g->nmembers++].pool = p; p->group = g; }
     pthread_mutex_unlock(&g->mu);
     if (bad) FAIL("group_join: the group is full (at most %d streams of this picture size share a launch), busy, on another device or holds another picture size", room < H264E_GROUP_MAX ? room : H264E_GROUP_MAX);
     return 0;
@@ -1252,17 +1294,12 @@ extern "C" void h264e_hip_group_leave(h264e_hip_group_t *g, h264e_hip_pool_t *p)
     if (!g || !p || p->group != g) return;
     pthread_mutex_lock(&g->mu);
     int k;
-    for (k = 0; k < g->nmembers && g->member[k] != p; k++) ;
+    for (k = 0; k < g->nmembers && g->member[k].pool != p; k++) ;
     if (k < g->nmembers)
     {
-        if (g->pend[k]) { free(g->pend_tasks[k]); g->arrived--; }
-        for (; k + 1 < g->nmembers; k++)
-        {
-            g->member[k] = g->member[k + 1]; g->pend_tasks[k] = g->pend_tasks[k + 1]; g->pend_jobs[k] = g->pend_jobs[k + 1];
-            g->pend_narrow[k] = g->pend_narrow[k + 1]; g->pend_waves[k] = g->pend_waves[k + 1]; g->pend[k] = g->pend[k + 1];
-        }
+        if (g->member[k].pending) { free(g->member[k].tasks); g->arrived--; }
+        memmove(&g->member[k], &g->member[k + 1], sizeof(g->member[0])*(size_t)(g->nmembers - 1 - k));
         g->nmembers--;
-        g->pend_tasks[g->nmembers] = 0; g->pend[g->nmembers] = 0;
         /* the others may have been waiting for this member only */
         if (g->nmembers && g->arrived == g->nmembers) (void)group_launch_locked(g);
         if (!g->nmembers && g->holds_device)
@@ -1282,7 +1319,7 @@ extern "C" void h264e_hip_group_destroy(h264e_hip_group_t *g)
     if (!g) return;
     (void)hipSetDevice(g->device);
     (void)hipStreamSynchronize(g->stream);
-    for (int k = 0; k < g->nmembers; k++) { g->member[k]->group = 0; free(g->pend_tasks[k]); }
+    for (int k = 0; k < g->nmembers; k++) { g->member[k].pool->group = 0; if (g->member[k].pending) free(g->member[k].tasks); }
     if (g->tasks_dev) (void)hipFree(g->tasks_dev);
     if (g->order_dev) (void)hipFree(g->order_dev);
     if (g->holds_device) { g->holds_device = 0; device_token_give(g->device); }
@@ -1293,176 +1330,200 @@ extern "C" void h264e_hip_group_destroy(h264e_hip_group_t *g)
     free(g);
 }
 
-extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tasks)
+/* ---- h264e_hip_submit: check, fill, token, upload, then launch or hand to the group */
+
+/* Every refusal of a submit, and the launch's shape.  The pool is const: a refused submit has changed nothing. */
+static int submit_check(const h264e_hip_pool_t *p, const h264e_hip_task_t *tasks, launch_shape_t *s)
 {
-    if (!p || !tasks) FAIL("submit: null argument");
     const h264e_geom_t &G = p->G;
-    if (p->pending >= TASK_RING - 1 && h264e_hip_sync(p)) return -1;
-    h264e_frame_task_t *host = (h264e_frame_task_t *)calloc((size_t)p->nchains, sizeof(h264e_frame_task_t));
-    if (!host) FAIL("out of host memory");
-    int any = 0, any_narrow = 0, any_wide = 0, njobs = 0, all_intra = 1, max_slices = 1, any_leaf = 0;
-    const int launch_id = ++p->launch_counter;
+    int any_narrow = 0, any_wide = 0, max_slices = 1;
+    memset(s, 0, sizeof(*s));
+    s->forced = p->waves; s->all_intra = 1;
     for (int c = 0; c < p->nchains; c++)
     {
         const h264e_hip_task_t &t = tasks[c];
-        h264e_frame_task_t &d = host[c];
-        d.active = t.active;
         if (!t.active) continue;
         if (t.frame_index < 0 || t.frame_index >= p->frames_resident ||
             t.qp < 10 || t.qp > 51 || t.hdr_nbits < 0 || t.hdr_nbits > 56 || t.nslices < 0 || t.nslices > H264E_MAX_SLICES || t.nslices > G.nmby)
-        {
-            free(host);
             FAIL("submit: bad task for chain %d", c);
-        }
-        any = 1; njobs = c + 1;
-        if (t.slice_type != 2) all_intra = 0;
+        if (t.denoised && !p->den) FAIL("submit: task %d asks for the denoised picture, but the denoiser is not on", c);
+        /* temporal wavefront: job c builds the picture of chain slot t.slot from the picture of slot t.ref_slot */
+        if (t.stream_mode && (t.slot < 0 || t.slot >= p->nchains || t.ref_slot >= p->nchains || (t.slice_type == 0 && t.ref_slot < 0) ||
+                              (t.ref_in_flight && t.ref_slot < 0)))
+            FAIL("submit: bad stream task %d", c);
+        s->jobs = c + 1;
+        if (t.slice_type != 2) s->all_intra = 0;
         if (t.nslices > max_slices) max_slices = t.nslices;
-        if (t.stream_mode && t.walk_quiet) any_leaf = 1;
-        if (t.denoised && !p->den) { free(host); FAIL("submit: task %d asks for the denoised picture, but the denoiser is not on", c); }
-        const uint8_t *f = t.denoised ? den_frame(p, den_index(p, t.frame_index)) : p->clip + p->frame_bytes*(size_t)t.frame_index;
-        d.in[0] = f; d.in[1] = f + (size_t)G.width*G.height; d.in[2] = d.in[1] + (size_t)(G.width/2)*(G.height/2);
-        d.in_stride[0] = G.width; d.in_stride[1] = d.in_stride[2] = G.width/2;
-        d.slice_type = t.slice_type; d.qp = t.qp; d.speed = t.speed;
-        d.no_deblock = (t.speed == 8 || t.speed == 10);                 /* h264-lab.h:6717 */
-        if (t.stream_mode)
-        {
-            /* temporal wavefront: job c builds the picture of chain slot t.slot from the picture of slot t.ref_slot */
-            if (t.slot < 0 || t.slot >= p->nchains || t.ref_slot >= p->nchains || (t.slice_type == 0 && t.ref_slot < 0) ||
-                (t.ref_in_flight && t.ref_slot < 0))
-            {
-                free(host);
-                FAIL("submit: bad stream task %d", c);
-            }
-            d.chain = t.slot;
-            d.abort_word = p->abort_dev;
-            if (t.walk_on_device)
-            {
-                const int par = t.walk_parent > 0 ? t.walk_parent - 1 : c - 1;
-                d.walk_on_device = 1;
-                d.walk_quiet = t.walk_quiet;
-                d.exact_state[0] = t.exact_state[0]; d.exact_state[1] = t.exact_state[1];
-                d.walk_out = p->walkrec + t.slot;
-                d.walk_prev = (par >= 0 && par < c && tasks[par].active && tasks[par].stream_mode && tasks[par].walk_on_device) ? p->walkrec + tasks[par].slot : 0;
-                d.traj_out = p->traj_dev[t.slot] + (size_t)(p->traj_cur[t.slot] ^ 1)*2*G.nmb;
-            }
-            for (int k = 0; k < 3; k++)
-            {
-                d.dec[k] = p->chains_host[t.slot].rec[0][k];
-                d.ref[k] = t.ref_slot >= 0 ? p->chains_host[t.ref_slot].rec[0][k] : p->chains_host[t.slot].rec[1][k];
-            }
-            d.dep_progress = t.ref_in_flight ? p->chains_host[t.ref_slot].progress : 0;
-        } else
-        {
-            const int rs = p->ref_sel[c];
-            d.chain = c;
-            for (int k = 0; k < 3; k++) { d.ref[k] = p->chains_host[c].rec[rs][k]; d.dec[k] = p->chains_host[c].rec[rs ^ 1][k]; }
-            d.dep_progress = 0;
-            p->ref_sel[c] ^= 1;
-        }
-        /* the finalizer exports the slot's result to host-mapped memory: the host reads NALs, flags and records without a
-         * device-to-host copy */
-        d.arena_reset = 1;
-        d.stepflags = p->stepflags + 2*c;
-        d.host_done = p->host_done + d.chain;
-        d.host_rbsp = p->host_rbsp[d.chain]; d.host_rbsp_cap = p->host_rbsp_cap;
-        d.host_mbrec = (h264e_mbrec_t *)p->host_mbrec[d.chain];
-        p->host_done[d.chain].done = 0;
-        p->slot_launch[d.chain] = launch_id;
-        d.chain_desc = p->chains_dev + d.chain;
-        d.errflag = p->errflag;
-        d.mb_counter = p->mb_counter;
-        d.first_row = (t.stream_mode && t.first_row > 0 && t.first_row < G.nmby) ? t.first_row : 0;
-        d.narrow = t.stream_mode && t.narrow_window;
-        any_narrow |= d.narrow;
-        any_wide |= !d.narrow;
-        d.hdr_nal = t.hdr_nal; d.hdr_nbits = t.hdr_nbits; d.hdr_bits = t.hdr_bits;
-        {
-            /* row bands exactly as the reference splits them (h264-lab.h:6530): mby += (nmby - mby)/(nthreads - ithr) */
-            int mby = 0;
-            d.nslices = t.nslices > 1 ? t.nslices : 1;
-            for (int k = 0; k < d.nslices; k++) { d.slice_row[k] = (int16_t)mby; mby += (G.nmby - mby)/(d.nslices - k); }
-            d.slice_row[d.nslices] = (int16_t)G.nmby;
-        }
-        d.clusters[0] = t.mv_clusters[0]; d.clusters[1] = t.mv_clusters[1];
-        d.clusters_per_mb = 0;
-        if (t.stream_mode && t.traj_from_device)
-            d.clusters_per_mb = p->traj_dev[t.slot] + (size_t)p->traj_cur[t.slot]*2*G.nmb;     /* the latest device walk of this slot */
-        else if (t.mv_clusters_per_mb)
-        {
-            const size_t n = sizeof(int32_t)*2*(size_t)G.nmb;
-            const int cs = t.stream_mode ? t.slot : c;
-            /* the re-encode path is rare and synchronous: a blocking copy keeps the host array's lifetime simple */
-            if (hipStreamSynchronize(p->stream) != hipSuccess || hipMemcpy(p->clu_dev[cs], t.mv_clusters_per_mb, n, hipMemcpyHostToDevice) != hipSuccess)
-            {
-                free(host);
-                FAIL("mv_clusters upload failed");
-            }
-            d.clusters_per_mb = p->clu_dev[cs];
-        }
-        memcpy(d.qdat, t.qdat, sizeof(d.qdat));
-        d.launch_id = launch_id;
-        if (d.walk_on_device) p->traj_cur[t.slot] ^= 1;         /* this launch's walk writes the other buffer: it is the latest from now on */
+        /* hedge leaves.  (The device job's walk_quiet, which is only set under walk_on_device, would say the same: the clip encoder
+         * only ever sets walk_quiet on copies of tasks that have both -- h264e_host.c clip_plan_launch.) */
+        if (t.stream_mode && t.walk_quiet) s->tree = 1;
+        if (t.stream_mode && t.narrow_window) any_narrow = 1; else any_wide = 1;
     }
-    if (!any) { free(host); return 0; }
-    if (!p->group) device_acquire(p);   /* one launch at a time per device (see g_device_held); a launch group takes the token for its merged launch (group_launch_locked) */
-    if (any_narrow && any_wide) { free(host); FAIL("submit: the jobs of one launch must agree on narrow_window"); }
-    h264e_frame_task_t *slot = p->tasks_dev + (size_t)p->ring_pos*p->nchains;
-    p->ring_pos = (p->ring_pos + 1) % TASK_RING;
-    p->pending++;
-    HIPCHK(hipSetDevice(p->device));
-    /* pageable source: the runtime stages the copy before returning, so `host` can be freed right away */
-    hipError_t e = hipMemcpyAsync(slot, host, sizeof(h264e_frame_task_t)*(size_t)p->nchains, hipMemcpyHostToDevice, p->stream);
-    if (e != hipSuccess) { free(host); FAIL("task upload: %s", hipGetErrorString(e)); }
-    e = hipMemsetAsync(p->progress_all, 0, sizeof(int)*2*(size_t)p->nchains*G.nmby, p->stream);
-    /* rows kept from the previous encode of a frame count as complete */
+    if (any_narrow && any_wide) FAIL("submit: the jobs of one launch must agree on narrow_window");
+    if (s->jobs >= H264E_ORDER_MAX_JOBS) FAIL("submit: too many jobs");
+    s->narrow = any_narrow;
+    s->sliced = max_slices >= 2;
+    s->parallel = s->sliced || G.nmby >= 200;
+    return 0;
+}
+
+/* reference and decoded picture of job c: a stream task names its slots (and may walk on the device), a frame-at-a-time task
+ * ping-pongs the two pictures of its chain */
+static void fill_pictures(h264e_hip_pool_t *p, const h264e_hip_task_t *tasks, int c, h264e_frame_task_t &d)
+{
+    const h264e_hip_task_t &t = tasks[c];
+    if (!t.stream_mode)
+    {
+        const int rs = p->ref_sel[c];
+        d.chain = c;
+        for (int k = 0; k < 3; k++) { d.ref[k] = p->chains_host[c].rec[rs][k]; d.dec[k] = p->chains_host[c].rec[rs ^ 1][k]; }
+        p->ref_sel[c] ^= 1;
+        return;
+    }
+    d.chain = t.slot;
+    d.abort_word = p->abort_dev;
+    if (t.walk_on_device)
+    {
+        const int par = t.walk_parent > 0 ? t.walk_parent - 1 : c - 1;
+        d.walk_on_device = 1;
+        d.walk_quiet = t.walk_quiet;
+        d.exact_state[0] = t.exact_state[0]; d.exact_state[1] = t.exact_state[1];
+        d.walk_out = p->walkrec + t.slot;
+        d.walk_prev = (par >= 0 && par < c && tasks[par].active && tasks[par].stream_mode && tasks[par].walk_on_device) ? p->walkrec + tasks[par].slot : 0;
+        d.traj_out = p->traj_dev[t.slot] + (size_t)(p->traj_cur[t.slot] ^ 1)*2*p->G.nmb;
+    }
+    for (int k = 0; k < 3; k++)
+    {
+        d.dec[k] = p->chains_host[t.slot].rec[0][k];
+        d.ref[k] = t.ref_slot >= 0 ? p->chains_host[t.ref_slot].rec[0][k] : p->chains_host[t.slot].rec[1][k];
+    }
+    d.dep_progress = t.ref_in_flight ? p->chains_host[t.ref_slot].progress : 0;
+}
+
+/* row bands exactly as the reference splits them (h264-lab.h:6530): mby += (nmby - mby)/(nthreads - ithr) */
+static void fill_slice_rows(const h264e_geom_t &G, int nslices, h264e_frame_task_t &d)
+{
+    int mby = 0;
+    d.nslices = nslices > 1 ? nslices : 1;
+    for (int k = 0; k < d.nslices; k++) { d.slice_row[k] = (int16_t)mby; mby += (G.nmby - mby)/(d.nslices - k); }
+    d.slice_row[d.nslices] = (int16_t)G.nmby;
+}
+
+/* where the job's per-macroblock mv_clusters come from: the latest device walk of its slot, a host array (the re-encode path, rare
+ * and synchronous: a blocking copy keeps the host array's lifetime simple), or nowhere */
+static int fill_clusters(h264e_hip_pool_t *p, const h264e_hip_task_t &t, int c, h264e_frame_task_t &d)
+{
+    const size_t n = sizeof(int32_t)*2*(size_t)p->G.nmb;
+    const int cs = t.stream_mode ? t.slot : c;
+    d.clusters[0] = t.mv_clusters[0]; d.clusters[1] = t.mv_clusters[1];
+    if (t.stream_mode && t.traj_from_device) d.clusters_per_mb = p->traj_dev[t.slot] + (size_t)p->traj_cur[t.slot]*2*p->G.nmb;
+    else if (t.mv_clusters_per_mb)
+    {
+        if (hipStreamSynchronize(p->stream) != hipSuccess || hipMemcpy(p->clu_dev[cs], t.mv_clusters_per_mb, n, hipMemcpyHostToDevice) != hipSuccess) FAIL("mv_clusters upload failed");
+        d.clusters_per_mb = p->clu_dev[cs];
+    }
+    return 0;
+}
+
+/* the device job of the checked, active task c (d is zeroed), and what the pool remembers about it */
+static int fill_task(h264e_hip_pool_t *p, const h264e_hip_task_t *tasks, int c, int launch_id, h264e_frame_task_t &d)
+{
+    const h264e_geom_t &G = p->G;
+    const h264e_hip_task_t &t = tasks[c];
+    const uint8_t *f = t.denoised ? den_frame(p, den_index(p, t.frame_index)) : p->clip + p->frame_bytes*(size_t)t.frame_index;
+    d.active = t.active;
+    d.in[0] = f; d.in[1] = f + (size_t)G.width*G.height; d.in[2] = d.in[1] + (size_t)(G.width/2)*(G.height/2);
+    d.in_stride[0] = G.width; d.in_stride[1] = d.in_stride[2] = G.width/2;
+    d.slice_type = t.slice_type; d.qp = t.qp; d.speed = t.speed;
+    d.no_deblock = (t.speed == 8 || t.speed == 10);                 /* h264-lab.h:6717 */
+    fill_pictures(p, tasks, c, d);
+    /* the finalizer exports the slot's result to host-mapped memory: the host reads NALs, flags and records without a
+     * device-to-host copy */
+    d.arena_reset = 1;
+    d.stepflags = p->stepflags + 2*c;
+    d.host_done = p->host_done + d.chain;
+    d.host_rbsp = p->host_rbsp[d.chain]; d.host_rbsp_cap = p->host_rbsp_cap;
+    d.host_mbrec = (h264e_mbrec_t *)p->host_mbrec[d.chain];
+    d.chain_desc = p->chains_dev + d.chain;
+    d.errflag = p->errflag;
+    d.mb_counter = p->mb_counter;
+    d.first_row = (t.stream_mode && t.first_row > 0 && t.first_row < G.nmby) ? t.first_row : 0;
+    d.narrow = t.stream_mode && t.narrow_window;
+    d.hdr_nal = t.hdr_nal; d.hdr_nbits = t.hdr_nbits; d.hdr_bits = t.hdr_bits;
+    fill_slice_rows(G, t.nslices, d);
+    if (fill_clusters(p, t, c, d)) return -1;
+    memcpy(d.qdat, t.qdat, sizeof(d.qdat));
+    d.launch_id = launch_id;
+    p->host_done[d.chain].done = 0;
+    p->slot_launch[d.chain] = launch_id;
+    if (d.walk_on_device) p->traj_cur[t.slot] ^= 1;         /* this launch's walk writes the other buffer: it is the latest from now on */
+    return 0;
+}
+
+/* every row and `decided` counter to zero; rows kept from the previous encode of a frame (first_row) count as complete */
+static int reset_progress(h264e_hip_pool_t *p, const h264e_frame_task_t *host)
+{
+    const h264e_geom_t &G = p->G;
+    hipError_t e = hipMemsetAsync(p->progress_all, 0, sizeof(int)*2*(size_t)p->nchains*G.nmby, p->stream);
     for (int c = 0; c < p->nchains && e == hipSuccess; c++)
         if (host[c].active && host[c].first_row > 0)
         {
-            int *done = (int *)malloc(sizeof(int)*(size_t)host[c].first_row);
+            int *done = (int *)malloc(sizeof(int)*(size_t)host[c].first_row), *progress = p->chains_host[host[c].chain].progress;
             if (!done) { e = hipErrorOutOfMemory; break; }
             for (int r = 0; r < host[c].first_row; r++) done[r] = G.nmbx + 1;
-            e = hipMemcpyAsync(p->chains_host[host[c].chain].progress, done, sizeof(int)*(size_t)host[c].first_row, hipMemcpyHostToDevice, p->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(p->chains_host[host[c].chain].progress + G.nmby, done, sizeof(int)*(size_t)host[c].first_row, hipMemcpyHostToDevice, p->stream);
+            e = hipMemcpyAsync(progress, done, sizeof(int)*(size_t)host[c].first_row, hipMemcpyHostToDevice, p->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(progress + G.nmby, done, sizeof(int)*(size_t)host[c].first_row, hipMemcpyHostToDevice, p->stream);
             free(done);         /* pageable source: staged before the call returns */
         }
-    if (e != hipSuccess) { free(host); FAIL("progress reset: %s", hipGetErrorString(e)); }
-    /* wavefronts per macroblock row: two (search | reconstruction pipeline) halve the macroblock latency for twice the wave slots --
-     * the better trade wherever a launch is latency bound (single-slice streams: mis-speculation events; rate control and the
-     * frame-at-a-time API: a few frames per launch) and still level for multi-slice streams; an all-intra launch has nothing to
-     * search and no events: one wave per row, twice the rows in flight (22.4 vs 18.3 M MB/s at 1080p) */
-    /* (waves = 0 selects the intra-only variant of the one-wave kernel: no inter code, half the registers, twice the rows in flight) */
-    /* (... and 4 the two-wave kernel allocated for 4 waves per SIMD: launches bound by the rows in flight -- 8K-class pictures, many slices) */
-    /* which launches that is: pick_variant above (re-measured in round 4 with the slimmer macroblock step) */
-    /* (... and 3 the latency variant -- four waves per row: the 8x8 partition search and the deblocking + stores on waves of their own:
-     * launches of one or a few frames, where the chip is empty and only the macroblock latency counts: the frame-at-a-time API) */
-    const int waves = pick_variant(p->waves, all_intra, njobs*G.nmby, njobs*(G.nmby + 1), max_slices >= 2 || G.nmby >= 200, any_leaf);
-    if (p->group)
-    {
-        /* member of a launch group: the launch is merged with the other members' and the variant is chosen from the MERGED grid
-         * (group_launch_locked): this member only says what it cannot decide there -- forced by H264E_WAVES, intra frames only (0), or open (-1) */
-        const int grc = group_submit(p, host, njobs, any_narrow, p->waves ? p->waves : all_intra ? 0 : -1);
-        free(host);
-        return grc;
-    }
-    free(host);
-    /* the dispatch order for this launch's shape (jobs up to the last active one; window geometry) */
-    if (njobs != p->order_jobs || any_narrow != p->order_narrow || (max_slices >= 2) != p->order_sliced)
-    {
-        if (build_order(p, njobs, any_narrow, max_slices >= 2, -1)) return -1;
-        HIPCHK(hipMemcpyAsync(p->order, p->order_host, sizeof(uint32_t)*p->order_count, hipMemcpyHostToDevice, p->stream));     /* pageable: staged before the call returns */
-        p->order_jobs = njobs; p->order_narrow = any_narrow; p->order_sliced = max_slices >= 2;
-    }
+    if (e != hipSuccess) FAIL("progress reset: %s", hipGetErrorString(e));
+    return 0;
+}
+
+/* a pool's own launch of the uploaded jobs `slot`: the dispatch order is cached for the launch's shape (jobs up to the last active
+ * one; window geometry; sliced or not), the launch is timed when the pool is profiled */
+static int solo_launch(h264e_hip_pool_t *p, const h264e_frame_task_t *slot, const launch_shape_t &s)
+{
     const int pe = p->ev_pending;
-    if (p->profile) HIPCHK(hipEventRecord(p->ev[pe][0], p->stream));
-    bk_launch_mb(G, any_narrow, waves, njobs, (unsigned)p->order_count, slot, p->order, p->stream);
-    if (p->profile) HIPCHK(hipEventRecord(p->ev[pe][1], p->stream));
-    HIPCHK(hipGetLastError());
+    if (s.jobs != p->order_jobs || s.narrow != p->order_narrow || s.sliced != p->order_sliced)
+    {
+        if (build_order(p, s.jobs, s.narrow, s.sliced, -1)) return -1;
+        HIPCHK(hipMemcpyAsync(p->order, p->order_host, sizeof(uint32_t)*p->order_count, hipMemcpyHostToDevice, p->stream));     /* pageable: staged before the call returns */
+        p->order_jobs = s.jobs; p->order_narrow = s.narrow; p->order_sliced = s.sliced;
+    }
+    const hipError_t e = launch_mb(p->G, s.narrow, pick_variant(s, s.jobs, p->G.nmby), s.jobs, p->order_count, slot, p->order,
+                                   p->profile ? p->ev[pe][0] : 0, p->profile ? p->ev[pe][1] : 0, p->stream);
+    if (e != hipSuccess) FAIL("macroblock kernel launch: %s", hipGetErrorString(e));
     if (p->profile)
     {
         HIPCHK(hipEventRecord(p->ev[pe][2], p->stream));
         p->ev_pending++;
     }
     return 0;
+}
+
+extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tasks)
+{
+    launch_shape_t s;
+    if (!p || !tasks) FAIL("submit: null argument");
+    HIPCHK(hipSetDevice(p->device));
+    if (submit_check(p, tasks, &s)) return -1;
+    if (!s.jobs) return 0;
+    if (p->pending >= TASK_RING - 1 && h264e_hip_sync(p)) return -1;
+    h264e_frame_task_t *host = p->tasks_host;
+    const int launch_id = ++p->launch_counter;
+    memset(host, 0, sizeof(h264e_frame_task_t)*(size_t)p->nchains);
+    for (int c = 0; c < p->nchains; c++)
+        if (tasks[c].active && fill_task(p, tasks, c, launch_id, host[c])) return -1;
+    if (!p->group) device_acquire(p);   /* one launch at a time per device (see g_device_held); a launch group takes the token for its merged launch (group_launch_locked) */
+    h264e_frame_task_t *slot = p->tasks_dev + (size_t)p->ring_pos*p->nchains;
+    p->ring_pos = (p->ring_pos + 1) % TASK_RING;
+    p->pending++;
+    /* pageable source: the runtime stages the copy before returning, so the next submit may overwrite `host` */
+    const hipError_t e = hipMemcpyAsync(slot, host, sizeof(h264e_frame_task_t)*(size_t)p->nchains, hipMemcpyHostToDevice, p->stream);
+    if (e != hipSuccess) FAIL("task upload: %s", hipGetErrorString(e));
+    if (reset_progress(p, host)) return -1;
+    /* member of a launch group: the launch is merged with the other members' and the variant is chosen from the MERGED grid */
+    return p->group ? group_submit(p, host, s) : solo_launch(p, slot, s);
 }
 
 /* ---- results: every job's finalizer exports them to the host-mapped mirrors of its chain slot */
@@ -1585,6 +1646,21 @@ extern "C" long h264e_hip_selftest_order(h264e_hip_pool_t *p, int jobs, int narr
     if (rc) return -1;
     memcpy(out, p->order_host, sizeof(uint32_t)*(p->order_count < cap ? p->order_count : cap));
     return (long)p->order_count;
+}
+
+/* test hook: order_by_start_step itself, for a launch that merges `nmembers` streams of member_jobs[i] jobs each; returns the number of
+ * entries (out gets at most cap of them), -1 on failure */
+extern "C" long h264e_hip_selftest_merged_order(int rows, int lag, const int *member_jobs, int nmembers, uint32_t *out, size_t cap)
+{
+    size_t jobs = 0;
+    for (int i = 0; member_jobs && i < nmembers; i++) jobs += member_jobs[i] > 0 ? (size_t)member_jobs[i] : H264E_ORDER_MAX_JOBS;
+    if (rows < 1 || rows > 65536 || lag < 1 || !member_jobs || nmembers < 1 || !out || jobs >= H264E_ORDER_MAX_JOBS) { snprintf(g_err, sizeof(g_err), "selftest_merged_order: bad argument"); return -1; }
+    uint32_t *ord = (uint32_t *)malloc(sizeof(uint32_t)*jobs*(size_t)rows);
+    const int rc = ord ? order_by_start_step(ord, rows, lag, member_jobs, nmembers) : -1;
+    if (!rc) memcpy(out, ord, sizeof(uint32_t)*(jobs*(size_t)rows < cap ? jobs*(size_t)rows : cap));
+    free(ord);
+    if (rc) { snprintf(g_err, sizeof(g_err), "out of host memory"); return -1; }
+    return (long)(jobs*(size_t)rows);
 }
 
 extern "C" int h264e_hip_selftest_nal_escape(h264e_hip_pool_t *p, const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap, uint32_t *out_n)

@@ -215,6 +215,9 @@ int  h264e_hip_timer_stop(h264e_hip_pool_t *pool, double *ms);
 /* test hook: the dispatch order of a launch of `jobs` jobs as (job << 16 | row) entries, 0xffffffff = padding (banded orders: eight
  * equally long per-XCD queues, h264e_pool.h build_order); returns the number of entries, -1 on failure */
 long h264e_hip_selftest_order(h264e_hip_pool_t *pool, int jobs, int narrow, int banded, uint32_t *out, size_t cap);
+/* test hook: the unbanded order of a launch that merges several streams (a launch group): member i contributes member_jobs[i] jobs of
+ * `rows` workgroups, numbered member after member; entries sorted by lag*j + 2*row, ties by j, then member, then row */
+long h264e_hip_selftest_merged_order(int rows, int lag, const int *member_jobs, int nmembers, uint32_t *out, size_t cap);
 int  h264e_hip_selftest_nal_escape(h264e_hip_pool_t *pool, const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap, uint32_t *out_n);
 /* test hook: one wave-level stage of the macroblock pipeline on caller-supplied operands (h264e_kernels.hip stage_selftest lists
  * the stages and their operand layouts; tests/test_stages.py compares them with the reference's own functions) */

@@ -47,10 +47,26 @@ extern "C" void emu_check_global(const void *p, size_t n, const char *file, int 
 #include "../../h264-lab_amd/csrc/enc_selftest.h"
 #include "../../include/h264e_hip.h"
 
+/* H264E_EMU_LAUNCH_LOG=path: every launch appends one line with what the host layer decided for it -- the decisions that never change a
+ * byte of the emulated stream (tests/test_emu_launch_plan.py).  The order words are hashed with 32-bit FNV-1a, low byte first. */
+static void log_launch(int narrow, int variant, int njobs, unsigned nblocks, const h264e_frame_task_t *tasks, const uint32_t *order)
+{
+    const char *path = getenv("H264E_EMU_LAUNCH_LOG");
+    if (!path || !path[0]) return;
+    uint32_t hash = 2166136261u;
+    int active = 0;
+    for (unsigned i = 0; i < nblocks; i++) for (int b = 0; b < 4; b++) hash = (hash ^ ((order[i] >> (8*b)) & 0xffu))*16777619u;
+    for (int job = 0; job < njobs; job++) active += !!tasks[job].active;
+    FILE *f = fopen(path, "a");
+    if (!f) return;
+    fprintf(f, "narrow=%d variant=%d njobs=%d nblocks=%u order=%08x active=%d\n", narrow, variant, njobs, nblocks, (unsigned)hash, active);     /* one write: lines of two threads do not mix */
+    fclose(f);
+}
+
 /* variant 0 = a launch of intra frames only (the kernel variant without inter code), like h264e_kernels.hip bk_launch_mb */
 static void bk_launch_mb(const h264e_geom_t &G, int narrow, int variant, int njobs, unsigned nblocks, const h264e_frame_task_t *tasks, const uint32_t *order, hipStream_t)
 {
-    (void)order; (void)nblocks;
+    log_launch(narrow, variant, njobs, nblocks, tasks, order);
     for (int job = 0; job < njobs; job++)
     {
         const h264e_frame_task_t &T = tasks[job];

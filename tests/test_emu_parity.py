@@ -461,6 +461,52 @@ def test_dispatch_order_with_xcd_bands_is_complete_padded_and_dependency_safe(w,
         L.h264e_hip_pool_destroy(pool)
 
 
+def _merged_order(L, rows, lag, member_jobs):
+    import ctypes as C
+    L.h264e_hip_selftest_merged_order.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_uint32), C.c_size_t]
+    L.h264e_hip_selftest_merged_order.restype = C.c_long
+    cap = rows * sum(member_jobs) + 8
+    buf = (C.c_uint32 * cap)()
+    n = L.h264e_hip_selftest_merged_order(rows, lag, (C.c_int * len(member_jobs))(*member_jobs), len(member_jobs), buf, cap)
+    assert n == rows * sum(member_jobs)
+    return list(buf[:n])
+
+
+@pytest.mark.parametrize("rows", [4, 2], ids=["64x48", "2x2"])
+@pytest.mark.parametrize("lag", [4, 7])
+def test_merged_dispatch_order_of_a_launch_group(rows, lag):
+    """h264e_pool.h order_by_start_step, the one order builder of solo and merged launches: members with 3, 1 and 2 jobs, numbered member
+    after member.  Every (job, row) is there exactly once, in the order of Python's sorted by (lag*j + 2*r, j, member, r) -- j the job's
+    number within its member's stream, so the streams advance frame by frame, side by side"""
+    L = pkg.load_pkg().load(pkg.EMU_LIB)
+    jobs = (3, 1, 2)
+    base = [sum(jobs[:m]) for m in range(len(jobs))]
+    got = _merged_order(L, rows, lag, jobs)
+    assert sorted(got) == [(j << 16) | r for j in range(sum(jobs)) for r in range(rows)]
+    want = sorted((lag * j + 2 * r, j, m, r) for m in range(len(jobs)) for j in range(jobs[m]) for r in range(rows))
+    assert got == [((base[m] + j) << 16) | r for _, j, m, r in want]
+
+
+@pytest.mark.parametrize("w,h,narrow", [(64, 48, 1), (64, 48, 0), (2, 2, 1)])
+def test_one_member_order_is_the_pools_own_order(w, h, narrow):
+    """one member of 5 jobs == h264e_hip_selftest_order(..., banded=0) of a pool of that picture size, word for word"""
+    import ctypes as C
+    L = pkg.load_pkg().load(pkg.EMU_LIB)
+    L.h264e_hip_pool_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.h264e_hip_pool_destroy.argtypes = [C.c_void_p]
+    L.h264e_hip_selftest_order.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t]
+    L.h264e_hip_selftest_order.restype = C.c_long
+    rows, jobs = (h + 15) // 16 + 1, 5
+    pool = C.c_void_p()
+    assert L.h264e_hip_pool_create(C.byref(pool), 0, w, h, jobs, 1) == 0
+    try:
+        buf = (C.c_uint32 * (jobs * rows))()
+        assert L.h264e_hip_selftest_order(pool, jobs, narrow, 0, buf, jobs * rows) == jobs * rows
+        assert _merged_order(L, rows, 4 if narrow else 7, (jobs,)) == list(buf)
+    finally:
+        L.h264e_hip_pool_destroy(pool)
+
+
 def test_a_band_count_other_than_0_or_8_is_refused(monkeypatch):
     """the per-XCD queues of build_order are sized for eight bands: H264E_XCD_BANDS=12 is refused with a message that names the value
     (it used to write past them on the host heap), 0 and 8 still encode"""
