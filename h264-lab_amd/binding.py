@@ -195,6 +195,21 @@ def dev_frame(frame, fmt, w, h, stream=None):
     return d, frame
 
 
+def recon_out(fmt, w, h, device=0):
+    """a fresh torch uint8 destination on GPU `device` for the reconstruction of a w x h picture: "i420" one packed (h*3/2, w) tensor,
+    "nv12" (y of (h, w), uv of (h/2, w)), "rgb" (h, w, 3), "rgbp" (3, h, w)"""
+    f = _DEV_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else int(fmt)
+    shapes = {DEV_FORMAT_I420: [(h * 3 // 2, w)], DEV_FORMAT_NV12: [(h, w), (h // 2, w)], DEV_FORMAT_RGB: [(h, w, 3)], DEV_FORMAT_RGBP: [(3, h, w)]}
+    if f not in shapes:
+        raise H264EError("read_recon_device: unknown format %r" % (fmt,))
+    try:
+        import torch
+    except ImportError:
+        raise H264EError("read_recon_device: out=None returns a torch tensor and torch cannot be imported -- pass the destination as out=")
+    made = [torch.empty(s, dtype=torch.uint8, device=torch.device("cuda", device)) for s in shapes[f]]
+    return made[0] if len(made) == 1 else tuple(made)
+
+
 MATRIX_UNSPECIFIED, MATRIX_BT709, MATRIX_BT601 = 0, 1, 6       # include/h264e_mi355x.h (H.264 Table E-5)
 _COLORS = {"bt709": (MATRIX_BT709, 0), "bt601": (MATRIX_BT601, 0), "bt709-full": (MATRIX_BT709, 1), "bt601-full": (MATRIX_BT601, 1)}
 
@@ -323,6 +338,9 @@ def load(path=None):
     L.H264E_clip_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(DevFrame)]
     L.H264E_encode_device_scaled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RunParam), C.POINTER(DevFrame), C.POINTER(DevWindow), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.H264E_clip_upload_device_scaled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(DevFrame), C.POINTER(DevWindow)]
+    L.H264E_read_recon_device.argtypes = [C.c_void_p, C.POINTER(DevFrame)]
+    L.H264E_clip_read_recon_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(DevFrame)]
+    L.H264E_clip_output_time.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.H264E_clip_input_time.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.H264E_clip_download.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.H264E_dev_malloc.argtypes = [C.c_int, C.c_size_t]
@@ -414,6 +432,20 @@ class Encoder:
         if st:
             raise _err(self.L, "H264E_encode_device%s status %d" % ("_scaled" if win is not None else "", st))
         return C.string_at(data, n.value)
+
+    def read_recon_device(self, fmt="rgbp", out=None, stream=None):
+        """H264E_read_recon_device: the reconstruction of the last encoded frame -- what a decoder shows for it -- into GPU memory as
+        fmt "i420", "nv12", "rgb" or "rgbp" (converted by the inverse of the encoder's colour matrix).  out: the destination, described
+        like an input frame (see dev_frame: tensors, CHW views, tuples of planes, (pointer, stride) pairs); only the rows' bytes are
+        written.  out=None: a fresh torch tensor on device $H264E_DEVICE (default 0) -- (h*3/2, w) packed, (y, uv), (h, w, 3) or
+        (3, h, w).  stream: the hipStream_t whose queued work may still use `out`; by default torch's current stream.  Returns out."""
+        if out is None:
+            out = recon_out(fmt, self.w, self.h, int(os.environ.get("H264E_DEVICE", "0")))
+        d, _keep = dev_frame(out, fmt, self.w, self.h, stream)
+        st = self.L.H264E_read_recon_device(self.persist, C.byref(d))
+        if st:
+            raise _err(self.L, "H264E_read_recon_device status %d" % st)
+        return out
 
     def set_color(self, color):
         """H264E_set_color: how RGB / RGBP device input is converted and what every SPS signals ("bt709", "bt601", "bt709-full",
@@ -620,6 +652,23 @@ class ClipEncoder:
         if self.L.H264E_clip_read_recon(self.c, frame, buf.ctypes.data):
             raise _err(self.L, "H264E_clip_read_recon")
         return buf
+
+    def read_recon_device(self, frame, fmt="rgbp", out=None, stream=None):
+        """H264E_clip_read_recon_device: the reconstruction of `frame` (one of the last frames encoded, as read_recon), cropped to the
+        picture, into GPU memory; fmt, out and stream as Encoder.read_recon_device (out=None: a fresh torch tensor on the clip's device)"""
+        if out is None:
+            out = recon_out(fmt, self.w, self.h, self.par.device)
+        d, _keep = dev_frame(out, fmt, self.w, self.h, stream)
+        if self.L.H264E_clip_read_recon_device(self.c, frame, C.byref(d)):
+            raise _err(self.L, "H264E_clip_read_recon_device")
+        return out
+
+    def output_time(self, enable=True):
+        """(HIP-event milliseconds inside the launches of the read_recon_device calls timed so far, their number); switches the timing
+        of later calls on or off"""
+        ms, n = C.c_double(), C.c_longlong()
+        self.L.H264E_clip_output_time(self.c, int(bool(enable)), C.byref(ms), C.byref(n))
+        return ms.value, n.value
 
     def close(self):
         if self.c:

@@ -505,6 +505,7 @@ typedef struct
     int frames_in;                          /* frames H264E_encode has taken since H264E_init */
     int denoise, den_started;               /* temporal denoiser on (H264E_set_denoise); its state has left zero */
     int parent_all_skipped;                 /* row bands: what the reference's parent encoder holds in mb.skip_run == nmb (encode_frame) */
+    int have_recon;                         /* a frame has been encoded: the pool holds its reconstruction (H264E_read_recon_device) */
 } henc_t;
 
 /* The reference API has no destructor and callers simply free() the blob, so nothing that needs
@@ -912,6 +913,7 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
         }
     }
     if (++e->frame_num >= e->param.gop && e->param.gop && e->run_param.frame_type == H264E_FRAME_TYPE_DEFAULT) e->frame_num = 0;
+    e->have_recon = 1;
     *coded_data = out;
     *sizeof_coded_data = (int)out_pos;
     return H264E_STATUS_SUCCESS;
@@ -940,6 +942,24 @@ int H264E_encode_device_scaled(H264E_persist_t *p, H264E_scratch_t *scratch, con
         return H264E_STATUS_BAD_ARGUMENT;
     }
     return encode_frame(p, scratch, opt, NULL, frame, win, coded_data, sizeof_coded_data);
+}
+
+/* The reconstruction of the last frame -- the picture const_input_flag = 0 writes back for host input -- into device memory, by the egress
+ * kernel (enc_egress.h).  A transparent VBV-overflow frame left the pool's pictures alone: the last reconstruction is what it shows. */
+int H264E_read_recon_device(H264E_persist_t *p, const H264E_dev_frame_t *dst)
+{
+    henc_t *e = (henc_t *)p;
+    impl_t mm;
+    g_host_err[0] = 0;
+    if (!impl_of(e, &mm)) return H264E_STATUS_BAD_ARGUMENT;
+    if (!dst) { snprintf(g_host_err, sizeof(g_host_err), "H264E_read_recon_device: null destination"); return H264E_STATUS_BAD_ARGUMENT; }
+    if (!e->have_recon)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "H264E_read_recon_device: no frame has been encoded yet");
+        return H264E_STATUS_BAD_ARGUMENT;
+    }
+    return h264e_hip_egress_last(mm.pool, 0, dst->format, (void *const *)dst->plane, dst->stride, dst->pixel_bytes, dst->producer_stream) ? H264E_STATUS_BAD_ARGUMENT
+                                                                                                                                     : H264E_STATUS_SUCCESS;
 }
 
 void *H264E_dev_malloc(int device, size_t bytes) { g_host_err[0] = 0; return h264e_hip_dev_malloc(device, bytes); }
@@ -1323,6 +1343,39 @@ int H264E_clip_read_recon(H264E_clip_t *c, int frame, uint8_t *dst)
      * the pictures of older frames -- only the frames accepted since the last launch's first frame are guaranteed to be intact */
     if (c->rc_on && frame < c->recon_floor) return -1;
     return h264e_hip_read_recon_slot(c->pool, frame % c->ring, dst);
+}
+
+/* the same picture, cropped to the clip's width x height, into device memory by the egress kernel (enc_egress.h): the window of
+ * H264E_clip_read_recon, every refusal with its reason */
+int H264E_clip_read_recon_device(H264E_clip_t *c, int frame, const H264E_dev_frame_t *dst)
+{
+    g_host_err[0] = 0;
+    if (!c || !dst) { snprintf(g_host_err, sizeof(g_host_err), "clip_read_recon_device: null %s", c ? "destination" : "clip"); return -1; }
+    if (frame < 0 || frame >= c->next)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "clip_read_recon_device: frame %d has not been encoded (%d frames have)", frame, c->next);
+        return -1;
+    }
+    if (frame < c->next - (c->ring - 1))
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "clip_read_recon_device: the picture of frame %d has been overwritten (the last %d frames are kept: %d..%d)", frame, c->ring - 1,
+                 imax(c->next - (c->ring - 1), 0), c->next - 1);
+        return -1;
+    }
+    if (c->rc_on && frame < c->recon_floor)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "clip_read_recon_device: the picture of frame %d may have been overwritten by the rate control's alternative encodes (frames %d..%d are intact)",
+                 frame, c->recon_floor, c->next - 1);
+        return -1;
+    }
+    return h264e_hip_egress_slot(c->pool, frame % c->ring, dst->format, (void *const *)dst->plane, dst->stride, dst->pixel_bytes, dst->producer_stream);
+}
+
+/* diagnostic: HIP-event time of the egress launches made while `enable` was set (tools/egress_probe.py) */
+int H264E_clip_output_time(H264E_clip_t *c, int enable, double *kernel_ms, long long *frames)
+{
+    if (!c) return -1;
+    return h264e_hip_egress_time(c->pool, enable, kernel_ms, frames);
 }
 
 /* [3] sums of squared differences (Y, U, V; input vs reconstruction) per frame encoded by the following H264E_clip_encode calls,

@@ -13,7 +13,8 @@
  *   h264e_denoise_kernel the temporal denoiser (enc_denoise.h) over one frame: raw input + previous denoised picture -> new
  *                        denoised picture, out of place, one launch per frame in stream order.
  *   h264e_ingest_kernel  device-resident input (enc_ingest.h): one I420 / NV12 / RGB frame in HBM -> the packed I420 input slot.
- *   h264e_scale_kernel   the same for a source of another size (enc_scale.h): a window of an I420 / NV12 frame, box-filtered down to the slot.
+ *   h264e_egress_kernel  device-resident output (enc_egress.h): a reconstructed picture -> I420 / NV12 / RGB / planar RGB in the caller's HBM.
+ *   h264e_scale_kernel   the same as the ingest for a source of another size (enc_scale.h): a window of an I420 / NV12 frame, box-filtered down to the slot.
  *   h264e_scale_rgb_kernel  ... of a planar RGB frame (enc_scale_rgb.h): the three channels box-filtered into LDS, converted to I420 from there.
  *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
  *
@@ -27,6 +28,7 @@
 #include "enc_selftest.h"
 #include "enc_denoise.h"
 #include "enc_ingest.h"
+#include "enc_egress.h"
 #include "enc_scale.h"
 #include "enc_scale_rgb.h"
 #include "enc_scenecut.h"
@@ -701,6 +703,14 @@ __global__ void __launch_bounds__(256) h264e_ingest_kernel(h264e_ingest_src_t S,
     else ingest_chroma(S, (GLOBAL_AS uint8_t *)dst, g, y);
 }
 
+/* device-resident output over one picture (enc_egress.h): grid.z = 0 luma / 1 both chroma planes for I420 and NV12, grid.y = row; the RGB
+ * formats have grid.z = 0 alone and grid.y = a PAIR of rows (one chroma row); grid.x * 256 lanes x 4 samples along the row.  Every workgroup
+ * reads its own bytes of the picture and writes its own bytes of the destination (no inter-workgroup traffic, no LDS). */
+__global__ void __launch_bounds__(256) h264e_egress_kernel(h264e_egress_dst_t D, const uint8_t *src)
+{
+    egress_group(D, (const GLOBAL_AS uint8_t *)src, (int)(blockIdx.x*blockDim.x + threadIdx.x), (int)blockIdx.y, (int)blockIdx.z);
+}
+
 /* device-resident input of another size (enc_scale.h): grid.z = plane, grid.x / grid.y = the tile of 64 x S.th destination samples.  Column
  * and row taps once per tile, then the horizontal sums of the tile's source rows into LDS, then the vertical pass from LDS.  Every
  * workgroup reads its own source bytes and writes its own bytes of the slot (no inter-workgroup traffic). */
@@ -823,6 +833,12 @@ static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStrea
 {
     const unsigned gx = (unsigned)((((S.width + 3) >> 2) + 255) >> 8);
     hipLaunchKernelGGL(h264e_ingest_kernel, dim3(gx, (unsigned)S.height, 2), dim3(256), 0, st, S, dst);
+}
+static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hipStream_t st)
+{
+    const unsigned gx = (unsigned)((((D.width + 3) >> 2) + 255) >> 8);
+    const int rgb = D.format == H264E_INGEST_RGB || D.format == H264E_INGEST_RGBP;
+    hipLaunchKernelGGL(h264e_egress_kernel, dim3(gx, (unsigned)(rgb ? D.height >> 1 : D.height), rgb ? 1 : 2), dim3(256), 0, st, D, src);
 }
 static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t st)
 {

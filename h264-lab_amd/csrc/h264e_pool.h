@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_scale, bk_launch_scale_rgb and bk_launch_scenecut; the emulation's versions of those five are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb and bk_launch_scenecut; the emulation's versions of those six are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -13,6 +13,7 @@
 #define H264E_POOL_H
 #include "enc_denoise.h"
 #include "enc_ingest.h"
+#include "enc_egress.h"
 #include "enc_scale.h"
 #include "enc_scale_rgb.h"
 #include "enc_scenecut.h"
@@ -26,6 +27,14 @@ static const h264e_color_t k_color_rows[4] = {
     { { 77, 150, 29 }, { -43, -84, 127 }, { 127, -107, -20 }, 0 },
     { { 47, 157, 16 }, { -26, -86, 112 }, { 112, -102, -10 }, 16 },
     { { 54, 183, 19 }, { -29, -98, 127 }, { 127, -116, -11 }, 0 } };
+
+/* ... and their inverses for the way out (enc_egress.h, DESIGN.md 4.5g, tests/egress_model.py): ky = 256 or 256*255/219; rv = 2(1 - Kr),
+ * gu = -2 Kb (1 - Kb)/Kg, gv = -2 Kr (1 - Kr)/Kg, bu = 2(1 - Kb), times 256, or 256*255/224 for limited range; rounded.  Same index. */
+static const h264e_icolor_t k_icolor_rows[4] = {
+    { 298, 16, 409, -100, -208, 516 },
+    { 256, 0, 359, -88, -183, 454 },
+    { 298, 16, 459, -55, -136, 541 },
+    { 256, 0, 403, -48, -120, 475 } };
 
 static thread_local char g_err[256];       /* per calling thread */
 #define FAIL(...) do { snprintf(g_err, sizeof(g_err), __VA_ARGS__); return -1; } while (0)
@@ -173,6 +182,9 @@ struct h264e_hip_pool
     h264e_color_t cm;                    /* the RGB -> YCbCr matrix of the RGB / RGBP ingest and scale launches (h264e_hip_set_color) */
     hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
     hipEvent_t ev_in[2];                 /* h264e_hip_copy_timer_*: around a caller's launches on the copy stream */
+    h264e_icolor_t icm;                  /* the YCbCr -> RGB matrix of the RGB / RGBP egress launches: the inverse of cm (h264e_hip_set_color) */
+    hipEvent_t ev_out[2];                /* h264e_hip_egress_time: around each egress launch while the timing is on */
+    int out_timed; double out_ms; long long out_calls;
     h264e_chain_dev_t *chains_host;      /* host mirror of the device descriptors */
     h264e_chain_dev_t *chains_dev;
     h264e_frame_task_t *tasks_dev;       /* ring of TASK_RING task arrays */
@@ -289,6 +301,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
         for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventDestroy(p->ev[i][k]);
         (void)hipEventDestroy(p->ev_t0); (void)hipEventDestroy(p->ev_t1); (void)hipEventDestroy(p->ev_prep); (void)hipEventDestroy(p->ev_copy);
         (void)hipEventDestroy(p->ev_ingest[0]); (void)hipEventDestroy(p->ev_ingest[1]); (void)hipEventDestroy(p->ev_in[0]); (void)hipEventDestroy(p->ev_in[1]);
+        (void)hipEventDestroy(p->ev_out[0]); (void)hipEventDestroy(p->ev_out[1]);
         (void)hipEventDestroy(p->ev_sc[0]); (void)hipEventDestroy(p->ev_sc[1]);
         (void)hipStreamDestroy(p->stream);
         if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
@@ -436,11 +449,12 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
         if (process_guard_acquire(device)) { free(p); return -1; }
         p->guarded = !share;
     }
-    p->cm = k_color_rows[0];
+    p->cm = k_color_rows[0]; p->icm = k_icolor_rows[0];
     if (hipStreamCreate(&p->stream) != hipSuccess || hipStreamCreate(&p->copy_stream) != hipSuccess || hipStreamCreate(&p->abort_stream) != hipSuccess) { if (p->guarded) process_guard_release(device); free(p); FAIL("hipStreamCreate failed"); }
     for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventCreate(&p->ev[i][k]);
     (void)hipEventCreate(&p->ev_t0); (void)hipEventCreate(&p->ev_t1); (void)hipEventCreate(&p->ev_prep); (void)hipEventCreate(&p->ev_copy);
     (void)hipEventCreate(&p->ev_ingest[0]); (void)hipEventCreate(&p->ev_ingest[1]); (void)hipEventCreate(&p->ev_in[0]); (void)hipEventCreate(&p->ev_in[1]);
+    (void)hipEventCreate(&p->ev_out[0]); (void)hipEventCreate(&p->ev_out[1]);
     (void)hipEventCreate(&p->ev_sc[0]); (void)hipEventCreate(&p->ev_sc[1]);
     p->chains_host = (h264e_chain_dev_t *)calloc((size_t)nchains, sizeof(h264e_chain_dev_t));
     p->clu_dev = (int32_t **)calloc((size_t)nchains, sizeof(int32_t *));
@@ -746,6 +760,14 @@ static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStrea
     for (int y = 0; y < S.height; y++)
         for (int g = 0; g < (S.width + 3)/4; g++) { ingest_luma(S, dst, g, y); ingest_chroma(S, dst, g, y); }
 }
+/* ... and the egress's (enc_egress.h): the same, per part */
+static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hipStream_t)
+{
+    const int rgb = D.format == H264E_INGEST_RGB || D.format == H264E_INGEST_RGBP;
+    for (int part = 0; part < (rgb ? 1 : 2); part++)
+        for (int y = 0; y < (rgb ? D.height >> 1 : D.height); y++)
+            for (int g = 0; g < (D.width + 3)/4; g++) egress_group(D, src, g, y, part);
+}
 /* ... and the scaler's (enc_scale.h): tile by tile, each of the kernel's three steps as a lane loop over the tile's LDS */
 static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t)
 {
@@ -808,6 +830,7 @@ extern "C" int h264e_hip_set_color(h264e_hip_pool_t *p, int bt709, int full_rang
 {
     if (!p || (unsigned)bt709 > 1 || (unsigned)full_range > 1) FAIL("set_color: bad argument");
     p->cm = k_color_rows[2*bt709 + full_range];
+    p->icm = k_icolor_rows[2*bt709 + full_range];
     return 0;
 }
 
@@ -971,6 +994,96 @@ extern "C" int h264e_hip_scale_device(h264e_hip_pool_t *p, int slot, int format,
 {
     if (h264e_hip_scale_device_async(p, slot, format, planes, strides, win, producer_stream)) return -1;
     HIPCHK(hipStreamSynchronize(p->copy_stream));
+    return 0;
+}
+
+/* ---- device-resident output (enc_egress.h): one h264e_egress_kernel launch per picture on the pool's copy stream */
+
+/* everything that is refused, without a launch; fills the kernel's view of the destination */
+static int egress_check(const h264e_hip_pool_t *p, int slot, int format, void *const planes[3], const int strides[3], int pixel_bytes, h264e_egress_dst_t *D)
+{
+    if (!p || !planes || !strides) FAIL("egress: null argument");
+    if (slot < 0 || slot >= p->nchains) FAIL("egress: picture slot %d outside the pool's %d", slot, p->nchains);
+    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12 && format != H264E_INGEST_RGB && format != H264E_INGEST_RGBP) FAIL("egress: unknown format %d", format);
+    if (format == H264E_INGEST_RGB && pixel_bytes != 3 && pixel_bytes != 4) FAIL("egress: RGB pixels of %d bytes (3 or 4)", pixel_bytes);
+    memset(D, 0, sizeof(*D));
+    D->format = format; D->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1;
+    D->width = p->G.width; D->height = p->G.height; D->W = p->G.W; D->H = p->G.H;
+    D->cm = p->icm;
+    const int nplanes = format == H264E_INGEST_I420 || format == H264E_INGEST_RGBP ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
+    for (int k = 0; k < nplanes; k++)
+    {
+        /* bytes and rows of destination plane k, as the ingest counts them for a source */
+        const int row_bytes = format == H264E_INGEST_RGB ? D->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP) ? D->width : D->width/2;
+        if (!planes[k]) FAIL("egress: plane %d is NULL", k);
+        if (strides[k] < row_bytes) FAIL("egress: stride %d of plane %d is below its %d row bytes", strides[k], k, row_bytes);
+#ifndef H264E_EMU
+        /* what will be written: from the first byte of the first row to the last byte of the last */
+        const int rows = k == 0 || format == H264E_INGEST_RGBP ? D->height : D->height/2;
+        if (!ingest_is_device_memory(p, planes[k], (size_t)(rows - 1)*(size_t)strides[k] + (size_t)row_bytes))
+            FAIL("egress: plane %d (%p, %d rows %d bytes apart) is not memory of device %d, or not inside one allocation", k, planes[k], rows, strides[k], p->device);
+#endif
+        D->plane[k] = (uint8_t *)planes[k]; D->stride[k] = strides[k];
+    }
+    return 0;
+}
+
+extern "C" int h264e_hip_egress_check(h264e_hip_pool_t *p, int slot, int format, void *const planes[3], const int strides[3], int pixel_bytes)
+{
+    h264e_egress_dst_t D;
+    if (p) (void)hipSetDevice(p->device);
+    return egress_check(p, slot, format, planes, strides, pixel_bytes, &D);
+}
+
+/* the checks, then the launch on the copy stream behind (a) everything queued on the producer's stream so far -- the caller's earlier work
+ * may still read the destination -- and (b) the pool's encode stream (and its launch group's merged launch), which writes the picture;
+ * returns when the destination has been written */
+static int egress_run(h264e_hip_pool_t *p, int slot, int sel, int format, void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream)
+{
+    h264e_egress_dst_t D;
+    if (p) HIPCHK(hipSetDevice(p->device));
+    if (egress_check(p, slot, format, planes, strides, pixel_bytes, &D)) return -1;
+    if (producer_stream)
+    {
+        HIPCHK(hipEventRecord(p->ev_ingest[0], (hipStream_t)producer_stream));
+        HIPCHK(hipStreamWaitEvent(p->copy_stream, p->ev_ingest[0], 0));
+    }
+    HIPCHK(hipEventRecord(p->ev_ingest[1], p->stream));
+    HIPCHK(hipStreamWaitEvent(p->copy_stream, p->ev_ingest[1], 0));
+    if (p->group) HIPCHK(hipStreamWaitEvent(p->copy_stream, p->group->ev_done, 0));
+    if (p->out_timed) HIPCHK(hipEventRecord(p->ev_out[0], p->copy_stream));
+    bk_launch_egress(D, p->chains_host[slot].rec[sel][0], p->copy_stream);
+    HIPCHK(hipGetLastError());
+    if (p->out_timed) HIPCHK(hipEventRecord(p->ev_out[1], p->copy_stream));
+    HIPCHK(hipStreamSynchronize(p->copy_stream));
+    if (p->out_timed)
+    {
+        float f = 0;
+        HIPCHK(hipEventElapsedTime(&f, p->ev_out[0], p->ev_out[1]));
+        p->out_ms += f; p->out_calls++;
+    }
+    return 0;
+}
+
+/* stream pools: the picture h264e_hip_read_recon_slot reads */
+extern "C" int h264e_hip_egress_slot(h264e_hip_pool_t *p, int slot, int format, void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream)
+{
+    return egress_run(p, slot, 0, format, planes, strides, pixel_bytes, producer_stream);
+}
+
+/* frame at a time: the picture h264e_hip_read_recon reads (after the swap: the chain's last reconstruction) */
+extern "C" int h264e_hip_egress_last(h264e_hip_pool_t *p, int chain, int format, void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream)
+{
+    return egress_run(p, chain, p && chain >= 0 && chain < p->nchains ? p->ref_sel[chain] : 0, format, planes, strides, pixel_bytes, producer_stream);
+}
+
+/* HIP-event time of the egress launches made while `enable` was set: the totals since the pool was created (the probe) */
+extern "C" int h264e_hip_egress_time(h264e_hip_pool_t *p, int enable, double *ms, long long *calls)
+{
+    if (!p) FAIL("egress_time: null pool");
+    p->out_timed = enable != 0;
+    if (ms) *ms = p->out_ms;
+    if (calls) *calls = p->out_calls;
     return 0;
 }
 

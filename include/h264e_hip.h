@@ -193,6 +193,22 @@ int  h264e_hip_busy(h264e_hip_pool_t *pool);
 int  h264e_hip_read_recon(h264e_hip_pool_t *pool, int chain, uint8_t *dst);
 /* stream pools: the picture of chain slot `slot` (coded size, packed I420) */
 int  h264e_hip_read_recon_slot(h264e_hip_pool_t *pool, int slot, uint8_t *dst);
+/* Device-resident output (enc_egress.h), the way back of h264e_hip_ingest_device: a reconstructed picture, cropped to the pool's width x
+ * height, into device memory of the pool's device in one of the ingest's four formats (RGB / RGBP: converted by the inverse of the matrix
+ * h264e_hip_set_color selected, chroma replicated over its 2x2 block, a fourth byte of an RGB pixel written as 255), by ONE kernel launch
+ * on the pool's copy stream.  planes / strides: a pointer and a row stride in bytes (>= the row's bytes) per destination plane, counted
+ * as for a source; only the rows' bytes are written, never the padding between them.  _slot: the picture h264e_hip_read_recon_slot
+ * reads; _last: the one h264e_hip_read_recon reads.  producer_stream: the hipStream_t whose queued work may still use the destination
+ * (the launch waits for everything queued there so far), or NULL; the launch also waits for the pool's encode stream.  Returns when the
+ * destination has been written.  Refused without a launch (h264e_hip_last_error names the value): null arguments, a slot out of range,
+ * an unknown format / pixel_bytes, a NULL plane, a short stride, and a plane that the runtime does not report as memory of the pool's
+ * device inside one allocation from the first byte written to the last.
+ * _check: the refusals alone (0 = this destination would be accepted), nothing is launched.
+ * _time: enable != 0 times the later launches with HIP events; ms / calls: the totals since the pool was created (tools/egress_probe.py). */
+int  h264e_hip_egress_check(h264e_hip_pool_t *pool, int slot_or_chain, int format, void *const planes[3], const int strides[3], int pixel_bytes);
+int  h264e_hip_egress_slot(h264e_hip_pool_t *pool, int slot, int format, void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
+int  h264e_hip_egress_last(h264e_hip_pool_t *pool, int chain, int format, void *const planes[3], const int strides[3], int pixel_bytes, void *producer_stream);
+int  h264e_hip_egress_time(h264e_hip_pool_t *pool, int enable, double *ms, long long *calls);
 /* sums of squared differences between resident input frames and stream pictures, one small kernel per call: frame i uses input
  * slot (in0 + i) % in_mod and picture slot (pic0 + i) % pic_mod; out = host [n][3] (Y, U, V), picture size width x height */
 int  h264e_hip_ssd_frames(h264e_hip_pool_t *pool, int n, int in0, int in_mod, int pic0, int pic_mod, uint64_t *out);

@@ -241,6 +241,36 @@ int  H264E_encode_device(H264E_persist_t *enc, H264E_scratch_t *scratch, const H
 typedef struct { int src_width, src_height, crop_x, crop_y, crop_width, crop_height; } H264E_dev_window_t;   /* crop_width = 0: the whole source */
 int  H264E_encode_device_scaled(H264E_persist_t *enc, H264E_scratch_t *scratch, const H264E_run_param_t *run_param,
                                 const H264E_dev_frame_t *frame, const H264E_dev_window_t *win, unsigned char **coded_data, int *sizeof_coded_data);
+/* Device-resident output, the way back: the reconstruction of an encoded frame -- the picture a decoder shows for it, which lies in the
+ * GPU's memory as the next frame's reference -- is cropped to width x height and written into device memory the caller owns by one small
+ * kernel, without a trip through host memory (quality metrics against the source tensor, codec-in-the-loop training, a preview, choosing
+ * the rung of a ladder).  dst describes the destination exactly as H264E_dev_frame_t describes a source: format, pixel_bytes, a pointer
+ * and a row stride (bytes, at least the row's bytes; no alignment is asked of either) per plane; the plane pointers are written through.
+ * Only the bytes of the rows are written: padding between rows and everything around the planes keeps what it held.
+ *   I420: plane[0..2] = Y, U, V;   NV12: plane[0] = Y, plane[1] = interleaved U,V pairs: copies of the coded samples.
+ *   RGB:  plane[0] = interleaved R,G,B of pixel_bytes 3 or 4 (the fourth byte is written as 255);   RGBP: plane[0..2] = R, G, B planes.
+ * The conversion for RGB and RGBP -- the reference has none, this integer definition is the definition (tests/egress_model.py restates it):
+ * every chroma sample serves the 2x2 luma block it belongs to (sample replication, the counterpart of the ingest's 2x2 mean; no
+ * interpolation), and per pixel, with C = Y - yo, D = U - 128, E = V - 128 and arithmetic shifts,
+ *     R = clamp((ky C + rv E + 128) >> 8),   G = clamp((ky C + gu D + gv E + 128) >> 8),   B = clamp((ky C + bu D + 128) >> 8),
+ * clamped to 0..255 (a coded picture can hold any Y, U, V triple).  The coefficients are the inverse, in 1/256, of the matrix that
+ * H264E_set_color / H264E_clip_set_color selected (nothing set: BT.601 limited):
+ *                                 ky  yo   rv    gu    gv   bu
+ *       matrix 6 limited (= 0)   298  16  409  -100  -208  516
+ *       matrix 1 limited         298  16  459   -55  -136  541
+ *       matrix 6 full            256   0  359   -88  -183  454
+ *       matrix 1 full            256   0  403   -48  -120  475
+ *   (rv = 2(1 - Kr), bu = 2(1 - Kb), gu = -2 Kb (1 - Kb)/Kg, gv = -2 Kr (1 - Kr)/Kg, times 255/224 for limited range; ky = 255/219 or 1;
+ *   times 256, rounded.  Grey (U = V = 128) stays grey, black and white give 0 and 255.)
+ * producer_stream: the hipStream_t whose queued work may still read or write the destination -- the kernel waits for everything queued
+ * there so far -- or NULL when the caller has synchronised.  The calls return when the destination has been written.  Refused, with the
+ * value named in H264E_last_error and the destination untouched: an unknown format, pixel_bytes other than 3 or 4 for RGB, a NULL plane,
+ * a stride below the row's bytes, and a plane that is not device memory of the encoder's GPU inside one allocation from the first byte
+ * written to the last.  Nothing is scaled on the way out.
+ * H264E_read_recon_device: the picture the last successful H264E_encode / H264E_encode_device / H264E_encode_device_scaled left -- what
+ * const_input_flag = 0 writes back into host planes; it works with either value of that flag (H264E_encode_device still needs 1) and
+ * leaves the stream alone.  H264E_STATUS_BAD_ARGUMENT before the first frame and for a refused destination. */
+int  H264E_read_recon_device(H264E_persist_t *enc, const H264E_dev_frame_t *dst);
 /* device memory and blocking copies for callers without a HIP toolchain (to_device: 1 = host to device, 0 = device to host) */
 void *H264E_dev_malloc(int device, size_t bytes);
 void  H264E_dev_free(void *p);
@@ -294,6 +324,14 @@ int  H264E_clip_download(H264E_clip_t *clip, int first, int nframes, uint8_t *i4
  * ring - 1 frames in constant-QP mode; with rate control only the frames accepted since the last launch began -- the launches' hedge
  * leaves are encoded over the pictures of older frames).  -1 outside that window. */
 int  H264E_clip_read_recon(H264E_clip_t *clip, int frame, uint8_t *dst);
+/* the same picture, cropped to the clip's width x height, into device memory in the layout dst describes (see H264E_read_recon_device
+ * for formats, conversion, ordering and what is refused).  The same window of frames as H264E_clip_read_recon: the last ring - 1 frames,
+ * with rate control only those accepted since the last launch began.  0 = done, -1 = refused: outside that window (a frame not yet
+ * encoded, one whose picture slot has been reused) H264E_last_error names the frame and the frames that can be read. */
+int  H264E_clip_read_recon_device(H264E_clip_t *clip, int frame, const H264E_dev_frame_t *dst);
+/* diagnostic: enable != 0 times the kernel launches of later H264E_clip_read_recon_device calls with HIP events; kernel_ms / frames: the
+ * totals since open (tools/egress_probe.py) */
+int  H264E_clip_output_time(H264E_clip_t *clip, int enable, double *kernel_ms, long long *frames);
 /* per encoded frame [3] sums of squared differences input vs reconstruction (Y, U, V), computed on the device: encode_app --psnr */
 void H264E_clip_set_ssd_output(H264E_clip_t *clip, uint64_t *ssd);
 /* The temporal denoiser for the clip encoder (see H264E_set_denoise; the clip's speed < 2 selects it for every frame): only while the
