@@ -6,18 +6,26 @@
 #define H264E_ENC_SELFTEST_H
 #include "enc_row.h"
 
-/* ------------------------------------------------------------------ per-stage test hook (tests/test_stages.py)
+/* ------------------------------------------------------------------ per-stage test hook (tests/test_stages.py, tests/test_stage_edges.py)
  * Runs ONE of the macroblock pipeline's wave-level stages on caller-supplied operands, so that each can be compared with the
- * reference's own function of the same stage (tests/golden/stages.json, made by oracle/stage_harness.c):
+ * reference's own function of the same stage (tests/golden/stages.json and stage_edges.json, made by oracle/stage_harness.c):
  *   1 SAD quadrants (wave_sad_ref_q)           in: picture 64x64 | block 16x16         args: x, y, window      out: int32 sad4[4], sum
  *   2 luma quarter-sample (wave_interp_luma)   in: picture 64x64                       args: x, y, w, h, dx, dy, window   out: 16x16 (stride 16)
  *   3 chroma bilinear (wave_interp_chroma)     in: picture 64x64 (used as U and V)     args: x, y, w, h, dx, dy           out: 16x16: U cols 0-7, V cols 8-15
  *   4 transform/quant/dequant/recon            in: inp 256 | pred 256 | qdat 42 x u16  args: mode              out: int32 nz, dcflag | qblk_t q[16] | i16 dc[16] | i16 lev[16] | recon 256
- *   5 CAVLC block (cavlc_block)                in: int16 coef[16]                      args: first, maxn, nctx out: int32 nnz, nbits | bytes
+ *   5 CAVLC block (cavlc_block)                in: int16 coef[16]                      args: first, maxn, nctx, bits already in the buffer (ones)   out: int32 nnz, nbits | bytes
  *   8 motion search of one partition (diamond)  in: picture 96x96 | macroblock 16x16      args: px, py, w, h, mv x/y, pred x/y, min_sad, qp, speed, range[4], limit[4], window
  *                                                out: int32 cost, mv x, mv y | prediction 16x16 (stride 16)
  *   7 deblock one macroblock (wave_deblock)     in: luma tile 20x24 | U tile 10x12 | V tile 10x12 | bs 32   args: qp, qp_left, qp_top   out: the three tiles
  *   6 intra 4x4 mode choice (wave_i4_choose)   in: edge 13 (L3..L0, UL, U0..U7) | block 4x4 stride 16   args: avail, mpred, penalty   out: int32 mode, cost | prediction 4x4 stride 16
+ *   9 intra 16x16 (intra16_cost, wave_pred16)  in: block 16x16 | left 16 | top 16      args: avail, qp         out: int32 mode, cost | prediction 16x16
+ *  10 chroma prediction (wave_pred_chroma)     in: left 8 U, 8 V | top 8 U, 8 V        args: avail, mode (luma numbering)   out: 8 rows of U cols 0-7, V cols 8-15
+ *  11 vector predictor (mvp_get_arr / _put_arr) in: int32 mv_left[4], mv_tl[4], mv_top[8] | n x (x, y, w, h, mv) in 4x4-block units   args: avail, n
+ *                                               out: int32 predictor[16] | the context after the last put, as given
+ *  12 boundary strengths (df_strength)         in: int32 df_mv[25]                     args: df_nzflag, left_type, top_type, type, x, slice_top   out: bs 32
+ *  13 partition_hints                          in: n x int32 sad[4]                    args: n <= 64           out: n x int32 mode[4]
+ *  14 mv_cost                                  in: n x int32 (mv x, y, pred x, y, qp)  args: n <= 256          out: n x int32 cost
+ *  15 bit writer (bw_put, bw_ue, bw_se)        in: n x int32 (kind 0/1/2, value, length)   args: n <= 64       out: int32 nbits, overflow | bytes
  * `window` = 1 reads the reference samples through the LDS window like the macroblock loop, 0 through the HBM path.
  */
 struct StageLds
@@ -113,6 +121,7 @@ DEV void stage_selftest(StageLds &S, RowLds &L, int stage, const GLOBAL_AS uint8
         wave_sync();
         BitW b;
         b.acc = 0; b.nacc = 0; b.pos = 0; b.cap = 60; b.overflow = 0; b.buf = (GLOBAL_AS uint32_t *)(out + 8);
+        if (a[3] > 0) bw_put(b, imin(a[3], 31), (1u << imin(a[3], 31)) - 1u);          /* bits already in the buffer: ones, so that a lost or smeared bit shows */
         const int nnz = cavlc_block(b, S.ct, S.coef, a[0], a[1], a[2]);
         const uint32_t nbits = bw_bits(b);
         if (b.nacc) bw_put(b, 32 - b.nacc, 0);
@@ -181,6 +190,111 @@ DEV void stage_selftest(StageLds &S, RowLds &L, int stage, const GLOBAL_AS uint8
         wave_sync();
         WAVE_FOR(l) { gstore32((gu8 *)out + 16 + 4*l, lds32(L.gtest[0] + 4*l)); }
         if (wave_lane() == 0) { oi[0] = L.gcost[0]; oi[1] = L.gcost[1]; oi[2] = L.gcost[2]; }
+    } else if (stage == 9 || stage == 10)
+    {
+        /* the macroblock's input and its neighbours' reconstructed edge lines where row_step keeps them: L.pix_left / B.pix_top, 16 Y | 8 U | 8 V */
+        MbBuf &B = L.mb[0];
+        WAVE_FOR(l)
+        {
+            if (stage == 9)
+            {
+                lds32_store(B.inp + 4*l, gload32((const gu8 *)in + 4*l));
+                if (l < 4) { lds32_store(L.pix_left + 4*l, gload32((const gu8 *)in + 256 + 4*l)); lds32_store(B.pix_top + 4*l, gload32((const gu8 *)in + 272 + 4*l)); }
+            } else if (l < 4) { lds32_store(L.pix_left + 16 + 4*l, gload32((const gu8 *)in + 4*l)); lds32_store(B.pix_top + 16 + 4*l, gload32((const gu8 *)in + 16 + 4*l)); }
+        }
+        wave_sync();
+        if (stage == 9)
+        {
+            MbCtx m;
+            m.avail = a[0]; m.qp = imin(imax(a[1], 0), 51); m.i16_mode = -1;
+            m.lambda_q4 = k_lambda_q4[m.qp]; m.lambda_i16 = k_lambda_i16_q4[m.qp];
+            const int cost = intra16_cost(L, B, m);
+            wave_sync();
+            WAVE_FOR(l) { gstore32((gu8 *)out + 8 + 4*l, lds32(L.i16pred + 4*l)); }
+            if (wave_lane() == 0) { oi[0] = m.i16_mode; oi[1] = cost; }
+        } else
+        {
+            WAVE_FOR(l) { if (l < 32) lds32_store(L.pred_c + 4*l, 0u); }
+            wave_sync();
+            wave_pred_chroma(L.pred_c, L.pix_left + 16, B.pix_top + 16, a[0], a[1]);
+            WAVE_FOR(l) { if (l < 32) gstore32((gu8 *)out + 4*l, lds32(L.pred_c + 4*l)); }
+        }
+    } else if (stage == 11)
+    {
+        /* one macroblock's partitions in coding order: every partition reads its predictor, then puts its vector (mb_write's sequence) */
+        MbBuf &B = L.mb[0];
+        const GLOBAL_AS int32_t *ii = (const GLOBAL_AS int32_t *)in;
+        const int n = imin(imax(a[1], 0), 16);
+        WAVE_FOR(l)
+        {
+            if (l < 4) { L.mv_left[l] = ii[l]; L.mv_tl[l] = ii[4 + l]; }
+            if (l < 8) B.mv_top[l] = ii[8 + l];
+        }
+        wave_sync();
+        for (int k = 0; k < n; k++)
+        {
+            const int x = uni(ii[16 + 5*k]) & 3, y = uni(ii[17 + 5*k]) & 3, w = imin(uni(ii[18 + 5*k]), 4 - x), h = imin(uni(ii[19 + 5*k]), 4 - y);
+            const mv32 pred = (mv32)uni(mvp_get_arr(L.mv_left, L.mv_tl, B.mv_top, a[0], x, y, w, h));
+            if (wave_lane() == 0) oi[k] = pred;
+            wave_sync();
+            mvp_put_arr(L.mv_left, L.mv_tl, B.mv_top, x, y, w, h, (mv32)uni(ii[20 + 5*k]));
+            wave_sync();
+        }
+        WAVE_FOR(l)
+        {
+            if (l < 4) { oi[16 + l] = L.mv_left[l]; oi[20 + l] = L.mv_tl[l]; }
+            if (l < 8) oi[24 + l] = B.mv_top[l];
+        }
+    } else if (stage == 12)
+    {
+        const GLOBAL_AS int32_t *ii = (const GLOBAL_AS int32_t *)in;
+        MbCtx m;
+        WAVE_FOR(l) { if (l < 25) L.df_mv[l] = ii[l]; if (l < 8) lds32_store(L.bs + 4*l, 0xeeeeeeeeu); }
+        if (wave_lane() == 0) { L.df_nzflag = (uint32_t)a[0]; L.left_type = a[1]; }
+        wave_sync();
+        m.type = a[3]; m.x = a[4]; m.slice_top = a[5];
+        df_strength(L, m, a[2]);
+        WAVE_FOR(l) { if (l < 8) gstore32((gu8 *)out + 4*l, lds32(L.bs + 4*l)); }
+    } else if (stage == 13 || stage == 14)
+    {
+        /* scalars of the decision, a[0] records per launch, one lane each: 13 partition_hints (4 SADs -> 4 flags), 14 mv_cost (vector, predictor, QP) */
+        const GLOBAL_AS int32_t *ii = (const GLOBAL_AS int32_t *)in;
+        const int n = imin(imax(a[0], 0), stage == 13 ? 64 : 256);
+        WAVE_FOR(l)
+        {
+            for (int k = l; k < n; k += 64)
+            {
+                if (stage == 13)
+                {
+                    const int sad[4] = { ii[4*k], ii[4*k + 1], ii[4*k + 2], ii[4*k + 3] };
+                    int mode[4] = { 0, 0, 0, 0 };
+                    partition_hints(sad, mode);
+                    for (int j = 0; j < 4; j++) oi[4*k + j] = mode[j];
+                } else
+                {
+                    MbCtx m;
+                    m.lambda_mv = k_lambda_mv_q4[imin(imax(ii[5*k + 4], 0), 51)];
+                    oi[k] = mv_cost(m, mvmk(ii[5*k], ii[5*k + 1]), mvmk(ii[5*k + 2], ii[5*k + 3]));
+                }
+            }
+        }
+    } else if (stage == 15)
+    {
+        /* a list of puts: (kind, value, length) with kind 0 bw_put, 1 bw_ue, 2 bw_se */
+        const GLOBAL_AS int32_t *ii = (const GLOBAL_AS int32_t *)in;
+        const int n = imin(imax(a[0], 0), 64);
+        BitW b;
+        b.acc = 0; b.nacc = 0; b.pos = 0; b.cap = 60; b.overflow = 0; b.buf = (GLOBAL_AS uint32_t *)(out + 8);
+        for (int k = 0; k < n; k++)
+        {
+            const int kind = uni(ii[3*k]), v = uni(ii[3*k + 1]), len = uni(ii[3*k + 2]);
+            if (kind == 0) bw_put(b, imin(imax(len, 0), 32), (uint32_t)v);
+            else if (kind == 1) bw_ue(b, (uint32_t)v);
+            else bw_se(b, v);
+        }
+        const uint32_t nbits = bw_bits(b);
+        if (b.nacc) bw_put(b, 32 - b.nacc, 0);
+        if (wave_lane() == 0) { oi[0] = (int32_t)nbits; oi[1] = b.overflow; }
     }
 }
 

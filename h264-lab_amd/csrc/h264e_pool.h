@@ -1801,7 +1801,7 @@ extern "C" int h264e_hip_selftest_nal_escape(h264e_hip_pool_t *p, const uint8_t 
 
 extern "C" int h264e_hip_selftest_stage(h264e_hip_pool_t *p, int stage, const uint8_t *in, uint32_t nin, const int *args /* [24] */, uint8_t *out, uint32_t nout)
 {
-    if (!p || !in || !args || !out || stage < 1 || stage > 8 || nin > STAGE_IN_MAX || nout > STAGE_OUT_MAX) FAIL("selftest_stage: bad argument");
+    if (!p || !in || !args || !out || stage < 1 || stage > 15 || nin > STAGE_IN_MAX || nout > STAGE_OUT_MAX) FAIL("selftest_stage: bad argument");
     uint8_t *buf = 0;
     HIPCHK(hipSetDevice(p->device));
     if (hipMalloc((void **)&buf, STAGE_IN_MAX + STAGE_OUT_MAX + 256) != hipSuccess) FAIL("selftest_stage: device allocation failed");

@@ -236,7 +236,7 @@ long h264e_hip_selftest_order(h264e_hip_pool_t *pool, int jobs, int narrow, int 
 long h264e_hip_selftest_merged_order(int rows, int lag, const int *member_jobs, int nmembers, uint32_t *out, size_t cap);
 int  h264e_hip_selftest_nal_escape(h264e_hip_pool_t *pool, const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap, uint32_t *out_n);
 /* test hook: one wave-level stage of the macroblock pipeline on caller-supplied operands (h264e_kernels.hip stage_selftest lists
- * the stages and their operand layouts; tests/test_stages.py compares them with the reference's own functions) */
+ * the stages and their operand layouts; tests/test_stages.py and tests/test_stage_edges.py compare them with the reference's own functions) */
 int  h264e_hip_selftest_stage(h264e_hip_pool_t *pool, int stage, const uint8_t *in, uint32_t nin, const int *args /* [24] */, uint8_t *out, uint32_t nout);
 const char *h264e_hip_last_error(void);
 

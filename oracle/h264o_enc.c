@@ -800,12 +800,11 @@ static void mb_write(h264o_enc_t *e, mb_t *m)
 /* ------------------------------------------------------------------ deblock control */
 
 /* H:5535-5637 df_strength + the edge masking of H:5653-5661 */
-static void mb_deblock(h264o_enc_t *e, const mb_t *m)
+static void df_strengths(h264o_enc_t *e, const mb_t *m, uint8_t bs[32])
 {
-    uint8_t bs[32];
     uint32_t flag = e->df_nzflag;
-    int x, y, qp_top, qp_left, qp = e->prev_qp;
-    memset(bs, 0, sizeof(bs));
+    int x, y;
+    memset(bs, 0, 32);
     e->df_nz_top[m->x] = (uint8_t)(flag >> 20);
     if (m->type < 5)
     {
@@ -828,6 +827,13 @@ static void mb_deblock(h264o_enc_t *e, const mb_t *m)
     e->df_type[m->x] = (int8_t)m->type;
     if (!m->x) memset(bs, 0, 4);
     if (m->y == e->slice_start_row) memset(bs + 16, 0, 4);          /* picture top, or H:5799-5803: no filtering across a slice border */
+}
+
+static void mb_deblock(h264o_enc_t *e, const mb_t *m)
+{
+    uint8_t bs[32];
+    int qp_top, qp_left, qp = e->prev_qp;
+    df_strengths(e, m, bs);
     qp_top = e->df_qp[m->x];
     qp_left = m->x ? e->df_qp[m->x - 1] : qp;
     e->df_qp[m->x] = (uint8_t)qp;
@@ -1314,4 +1320,67 @@ long h264o_encode_clip(const h264o_param_t *par, const uint8_t *clip, int nframe
     }
     h264o_close(e);
     return (long)pos;
+}
+
+/* ------------------------------------------------------------------ entry points for the per-stage tests (tests/test_stage_edges.py):
+ * the decision functions above that are static, on a state built from the arguments */
+
+/* ctx: mv_left[4], mv_tl[4], mv_top[5] (the macroblock's four + the first of the one above-right); parts: n x (x, y, w, h) in 4x4-block
+ * units, in coding order: every partition reads its predictor, then puts its vector; ctx is updated in place */
+void h264o_test_mvp(int32_t *ctx, int avail, int n, const int *parts, const int32_t *mvs, int32_t *preds)
+{
+    static h264o_enc_t e;
+    mb_t m;
+    mv32 top[8];
+    int i;
+    memset(&e, 0, sizeof(e)); memset(&m, 0, sizeof(m)); memset(top, 0, sizeof(top));
+    for (i = 0; i < 4; i++) { e.mv_left[i] = ctx[i]; e.mv_tl[i] = ctx[4 + i]; }
+    for (i = 0; i < 5; i++) top[i] = ctx[8 + i];
+    e.mv_top = top; m.x = 0; m.avail = avail;
+    for (i = 0; i < n; i++)
+    {
+        const int *r = parts + 4*i;
+        preds[i] = mvp_get(&e, &m, r[0], r[1], r[2], r[3]);
+        mvp_put(&e, &m, r[0], r[1], r[2], r[3], mvs[i]);
+    }
+    for (i = 0; i < 4; i++) { ctx[i] = e.mv_left[i]; ctx[4 + i] = e.mv_tl[i]; }
+    for (i = 0; i < 5; i++) ctx[8 + i] = top[i];
+}
+
+void h264o_test_strengths(uint32_t nzflag, const int32_t *df_mv /* [25] */, int type, int left_type, int top_type, int x, int slice_top, uint8_t *bs /* [32] */)
+{
+    static h264o_enc_t e;
+    mb_t m;
+    int8_t types[2];
+    uint8_t nz_top[2];
+    memset(&e, 0, sizeof(e)); memset(&m, 0, sizeof(m));
+    e.df_nzflag = nzflag; memcpy(e.df_mv, df_mv, sizeof(e.df_mv));
+    x = x ? 1 : 0;
+    types[0] = (int8_t)(x ? left_type : top_type); types[1] = (int8_t)top_type;
+    e.df_type = types; e.df_nz_top = nz_top;
+    m.type = type; m.x = x; m.y = slice_top ? 0 : 1; e.slice_start_row = 0;
+    df_strengths(&e, &m, bs);
+}
+
+void h264o_test_partition_hints(const int *sad, int *mode) { partition_hints(sad, mode); }
+
+int h264o_test_mv_cost(int vx, int vy, int px, int py, int qp)
+{
+    static h264o_enc_t e;
+    e.qp = qp;
+    return mv_cost(&e, mvmk(vx, vy), mvmk(px, py));
+}
+
+/* left / top: 16 samples each, NULL = not available; returns the mode, *cost its cost, pred the 16x16 prediction */
+int h264o_test_intra16(const uint8_t *inp, const uint8_t *left, const uint8_t *top, int avail, int qp, uint8_t *pred, int *cost)
+{
+    static h264o_enc_t e;
+    static mb_t m;
+    memset(&m, 0, sizeof(m));
+    e.qp = qp; m.avail = avail; m.cost = 0x7FFFFFFF; m.type = 0;
+    memcpy(m.inp, inp, 256);
+    intra16_choose(&e, &m, left, top);
+    memcpy(pred, m.pred, 256);
+    *cost = m.cost;
+    return m.i16_mode;
 }
