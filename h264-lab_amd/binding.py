@@ -62,7 +62,12 @@ class DevWindow(C.Structure):  # H264E_dev_window_t: the source's size and the w
 
 DEV_FORMAT_I420, DEV_FORMAT_NV12, DEV_FORMAT_RGB, DEV_FORMAT_RGBP = 0, 1, 2, 3
 H264E_SCENECUT_DEFAULT = 128        # include/h264e_mi355x.h
-_DEV_FORMATS = {"i420": DEV_FORMAT_I420, "nv12": DEV_FORMAT_NV12, "rgb": DEV_FORMAT_RGB, "rgbp": DEV_FORMAT_RGBP}
+DEV_SAMPLE_U8, DEV_SAMPLE_F16, DEV_SAMPLE_BF16, DEV_SAMPLE_F32 = 0x00, 0x10, 0x20, 0x30       # bits 4-5 of the format: planar RGB only
+DEV_FORMAT_RGBP_F16, DEV_FORMAT_RGBP_BF16, DEV_FORMAT_RGBP_F32 = DEV_FORMAT_RGBP | DEV_SAMPLE_F16, DEV_FORMAT_RGBP | DEV_SAMPLE_BF16, DEV_FORMAT_RGBP | DEV_SAMPLE_F32
+_DEV_FORMATS = {"i420": DEV_FORMAT_I420, "nv12": DEV_FORMAT_NV12, "rgb": DEV_FORMAT_RGB, "rgbp": DEV_FORMAT_RGBP,
+                "rgbp_f16": DEV_FORMAT_RGBP_F16, "rgbp_bf16": DEV_FORMAT_RGBP_BF16, "rgbp_f32": DEV_FORMAT_RGBP_F32}
+# float planar RGB: format code -> (bytes per sample, the torch dtype's name, the __cuda_array_interface__ typestr or None)
+_FLOAT_SAMPLES = {DEV_FORMAT_RGBP_F16: (2, "float16", "<f2"), DEV_FORMAT_RGBP_BF16: (2, "bfloat16", None), DEV_FORMAT_RGBP_F32: (4, "float32", "<f4")}
 
 
 def hip_runtimes():
@@ -81,28 +86,49 @@ def _one_runtime():
                          "library that owns the frames BEFORE this one (and do not set H264E_SYSTEM_HIP=1 next to torch), so that one runtime serves both" % ", ".join(r))
 
 
-def _dev_array(a):
+def _float_format_of(a):
+    """the float planar RGB format code of one array by its sample type, or (None, the type's name)"""
+    if hasattr(a, "data_ptr") and hasattr(a, "stride"):
+        name = str(getattr(a, "dtype", "?"))
+        for f, (_, dtype, _) in _FLOAT_SAMPLES.items():
+            if name == "torch." + dtype:
+                return f, name
+        return None, name
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is not None:
+        for f, (_, _, typestr) in _FLOAT_SAMPLES.items():
+            if typestr is not None and cai["typestr"] == typestr:
+                return f, typestr
+        return None, cai["typestr"]
+    return None, "a (pointer, stride) pair"
+
+
+def _dev_array(a, f=None):
     """(pointer, shape, strides in bytes, producer stream or None) of one device array: an object with data_ptr() / stride() / shape
     (a torch tensor), one with __cuda_array_interface__, or an explicit (pointer, row stride in bytes) pair -- whose shape is not
-    known, so nothing about it is checked here."""
+    known, so nothing about it is checked here.  f: one of the float planar RGB formats -- the array must hold that sample type;
+    otherwise 8-bit samples."""
     if isinstance(a, (tuple, list)) and len(a) == 2 and all(isinstance(x, int) for x in a):
         return int(a[0]), None, (int(a[1]),), None
+    if f is not None and _float_format_of(a)[0] != f:
+        raise H264EError("device input: format %r takes %s samples, not %s" % ([k for k, v in _DEV_FORMATS.items() if v == f][0], _FLOAT_SAMPLES[f][1], _float_format_of(a)[1]))
+    item = _FLOAT_SAMPLES[f][0] if f is not None else 1
     if hasattr(a, "data_ptr") and hasattr(a, "stride"):
-        if a.element_size() != 1:
+        if f is None and a.element_size() != 1:
             raise H264EError("device input must be 8-bit samples, not %s" % (getattr(a, "dtype", "?"),))
         stream = None
         torch = sys.modules.get("torch")            # never imported here: a tensor in hand means the caller has
         if torch is not None and getattr(a, "is_cuda", False):
             stream = torch.cuda.current_stream(a.device)
-        return int(a.data_ptr()), tuple(a.shape), tuple(int(x) for x in a.stride()), stream
+        return int(a.data_ptr()), tuple(a.shape), tuple(int(x) * item for x in a.stride()), stream
     cai = getattr(a, "__cuda_array_interface__", None)
     if cai is not None:
-        if cai["typestr"] not in ("|u1", "<u1", ">u1", "|i1"):
+        if f is None and cai["typestr"] not in ("|u1", "<u1", ">u1", "|i1"):
             raise H264EError("device input must be 8-bit samples, not %s" % cai["typestr"])
         shape = tuple(cai["shape"])
         strides = cai.get("strides")
         if strides is None:
-            strides, acc = [], 1
+            strides, acc = [], item
             for d in reversed(shape):
                 strides.insert(0, acc)
                 acc *= d
@@ -137,13 +163,35 @@ def _dev_plane(a, rows, row_bytes, what):
     return ptr, strides[0], stream
 
 
+def _float_plane(a, f, rows, w, what):
+    """one (rows, w) plane of float samples, last axis contiguous: (pointer, row stride in bytes, stream)"""
+    ptr, shape, strides, stream = _dev_array(a, f)
+    if shape is not None and (tuple(shape) != (rows, w) or strides[1] != _FLOAT_SAMPLES[f][0]):
+        raise H264EError("device input: %s must be a (%d, %d) array whose last axis is contiguous, got shape %r strides %r (bytes)" % (what, rows, w, shape, strides))
+    return ptr, strides[0], stream
+
+
+def dev_format(fmt, frame=None):
+    """the H264E_DEV_FORMAT_* code of a format name or number; "rgbpf" is float planar RGB with the sample type of `frame` (a float16,
+    bfloat16 or float32 array, or three such planes)"""
+    if fmt != "rgbpf":
+        return _DEV_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+    arrays = list(frame) if isinstance(frame, (tuple, list)) and len(frame) == 3 else [frame]
+    found = [_float_format_of(a) for a in arrays]
+    for f, name in found:
+        if f is None or f != found[0][0]:
+            raise H264EError("device input: format 'rgbpf' takes float16, bfloat16 or float32 samples (one type for all planes), not %s" % (name,))
+    return found[0][0]
+
+
 def dev_frame(frame, fmt, w, h, stream=None):
     """H264E_dev_frame_t for one frame of a w x h picture.  fmt "i420": three 2-D planes (y, u, v) or one packed (h*3/2, w) array;
     "nv12": (y of (h, w), uv of (h/2, w)); "rgb": one (h, w, 3 | 4) array; "rgbp": one uint8 (3, h, w) array (CHW: any channel and row
-    strides, so views work without a copy) or three 2-D planes (r, g, b).  Arrays: torch tensors, anything with
-    __cuda_array_interface__, or (pointer, row stride in bytes) pairs.  stream: the hipStream_t (an int) that writes the frame; by
-    default torch's current stream for torch tensors.  Returns (DevFrame, the objects that must stay alive during the call)."""
-    f = _DEV_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+    strides, so views work without a copy) or three 2-D planes (r, g, b); "rgbp_f16", "rgbp_bf16", "rgbp_f32": the same of float
+    samples in [0, 1], and "rgbpf" whichever of the three the array's dtype says.  Arrays: torch tensors, anything with
+    __cuda_array_interface__ (no bfloat16 there), or (pointer, row stride in bytes) pairs.  stream: the hipStream_t (an int) that writes
+    the frame; by default torch's current stream for torch tensors.  Returns (DevFrame, the objects that must stay alive during the call)."""
+    f = dev_format(fmt, frame)
     pb, planes = 0, []
     _one_runtime()
     if f == DEV_FORMAT_I420:
@@ -178,6 +226,15 @@ def dev_frame(frame, fmt, w, h, stream=None):
                 raise H264EError("device input: planar RGB must be a (3, %d, %d) array whose last axis is contiguous (any channel and row strides), "
                                  "or three (%d, %d) planes, got shape %r strides %r" % (h, w, h, w, shape, strides))
             planes = [(ptr + c * strides[0], strides[1], st) for c in range(3)]
+    elif f in _FLOAT_SAMPLES:
+        if isinstance(frame, (tuple, list)) and len(frame) == 3:
+            planes = [_float_plane(a, f, h, w, what) for a, what in zip(frame, "RGB")]
+        else:
+            ptr, shape, strides, st = _dev_array(frame, f)
+            if shape is None or tuple(shape) != (3, h, w) or strides[2] != _FLOAT_SAMPLES[f][0]:
+                raise H264EError("device input: float planar RGB must be a (3, %d, %d) array whose last axis is contiguous (any channel and row strides), "
+                                 "or three (%d, %d) planes, got shape %r strides %r (bytes)" % (h, w, h, w, shape, strides))
+            planes = [(ptr + c * strides[0], strides[1], st) for c in range(3)]
     else:
         raise H264EError("device input: unknown format %r" % (fmt,))
     d = DevFrame(format=f, pixel_bytes=pb)
@@ -197,16 +254,19 @@ def dev_frame(frame, fmt, w, h, stream=None):
 
 def recon_out(fmt, w, h, device=0):
     """a fresh torch uint8 destination on GPU `device` for the reconstruction of a w x h picture: "i420" one packed (h*3/2, w) tensor,
-    "nv12" (y of (h, w), uv of (h/2, w)), "rgb" (h, w, 3), "rgbp" (3, h, w)"""
-    f = _DEV_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else int(fmt)
+    "nv12" (y of (h, w), uv of (h/2, w)), "rgb" (h, w, 3), "rgbp" (3, h, w); "rgbp_f16" / "rgbp_bf16" / "rgbp_f32" a (3, h, w) tensor of
+    that float type, "rgbpf" float32"""
+    f = DEV_FORMAT_RGBP_F32 if fmt == "rgbpf" else _DEV_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else int(fmt)
     shapes = {DEV_FORMAT_I420: [(h * 3 // 2, w)], DEV_FORMAT_NV12: [(h, w), (h // 2, w)], DEV_FORMAT_RGB: [(h, w, 3)], DEV_FORMAT_RGBP: [(3, h, w)]}
+    shapes.update({k: [(3, h, w)] for k in _FLOAT_SAMPLES})
     if f not in shapes:
         raise H264EError("read_recon_device: unknown format %r" % (fmt,))
     try:
         import torch
     except ImportError:
         raise H264EError("read_recon_device: out=None returns a torch tensor and torch cannot be imported -- pass the destination as out=")
-    made = [torch.empty(s, dtype=torch.uint8, device=torch.device("cuda", device)) for s in shapes[f]]
+    dtype = getattr(torch, _FLOAT_SAMPLES[f][1]) if f in _FLOAT_SAMPLES else torch.uint8
+    made = [torch.empty(s, dtype=dtype, device=torch.device("cuda", device)) for s in shapes[f]]
     return made[0] if len(made) == 1 else tuple(made)
 
 
@@ -418,7 +478,7 @@ class Encoder:
         return C.string_at(data, n.value)
 
     def encode_device(self, frame, fmt, frame_type=FRAME_TYPE_DEFAULT, stream=None, src_size=None, crop=None):
-        """H264E_encode_device: the frame is taken from GPU memory (see dev_frame for what `frame` may be: fmt "i420", "nv12", "rgb" or "rgbp");
+        """H264E_encode_device: the frame is taken from GPU memory (see dev_frame for what `frame` may be: fmt "i420", "nv12", "rgb", "rgbp" or float "rgbp_f16" / "rgbp_bf16" / "rgbp_f32" / "rgbpf");
         needs const_input=1.  The frame's memory may be reused as soon as this returns.  src_size=(w, h): the frame has that size and is
         reduced to the encoder's picture (H264E_encode_device_scaled), crop=(x, y, w, h): only that window of it."""
         win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)
@@ -435,7 +495,8 @@ class Encoder:
 
     def read_recon_device(self, fmt="rgbp", out=None, stream=None):
         """H264E_read_recon_device: the reconstruction of the last encoded frame -- what a decoder shows for it -- into GPU memory as
-        fmt "i420", "nv12", "rgb" or "rgbp" (converted by the inverse of the encoder's colour matrix).  out: the destination, described
+        fmt "i420", "nv12", "rgb" or "rgbp" (converted by the inverse of the encoder's colour matrix), or float planar RGB in [0, 1]:
+        "rgbp_f16", "rgbp_bf16", "rgbp_f32", "rgbpf" (the type of `out`; float32 for out=None).  out: the destination, described
         like an input frame (see dev_frame: tensors, CHW views, tuples of planes, (pointer, stride) pairs); only the rows' bytes are
         written.  out=None: a fresh torch tensor on device $H264E_DEVICE (default 0) -- (h*3/2, w) packed, (y, uv), (h, w, 3) or
         (3, h, w).  stream: the hipStream_t whose queued work may still use `out`; by default torch's current stream.  Returns out."""
@@ -553,7 +614,7 @@ class ClipEncoder:
             raise _err(self.L, "H264E_clip_upload")
 
     def upload_device(self, frames, fmt, first=0, stream=None, src_size=None, crop=None):
-        """H264E_clip_upload_device: `frames` is a sequence of frames in GPU memory (see dev_frame: fmt "i420", "nv12", "rgb" or "rgbp"), frame
+        """H264E_clip_upload_device: `frames` is a sequence of frames in GPU memory (see dev_frame: fmt "i420", "nv12", "rgb", "rgbp" or float "rgbp_f16" / "rgbp_bf16" / "rgbp_f32" / "rgbpf"), frame
         first + i from frames[i].  Their memory may be reused as soon as this returns.  src_size=(w, h): the frames have that size and are
         reduced to the clip's picture (H264E_clip_upload_device_scaled), crop=(x, y, w, h): only that window of them."""
         win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)

@@ -6,7 +6,9 @@
  *   - I420: three planes, each with its own pointer and stride: a cropping strided copy;
  *   - NV12: the luma plane as above, U and V interleaved into plane[1];
  *   - RGB:  interleaved 8-bit R,G,B of pixel_bytes 3 or 4 (the fourth byte is written as 255);
- *   - RGBP: three planes R, G, B (a CHW tensor, or three allocations), any channel and row strides.
+ *   - RGBP: three planes R, G, B (a CHW tensor, or three allocations), any channel and row strides -- 8-bit samples, or the same 8-bit
+ *     values v as float32 v / 255 (ONE correctly rounded division), or as that float32 rounded to nearest even to float16 / bfloat16:
+ *     (u8.float() / 255).to(dtype), bit for bit (tests/float_model.py).
  *
  * RGB and RGBP convert -- the reference has no such conversion, this integer definition IS the definition (tests/egress_model.py restates
  * it): every chroma sample serves its 2x2 block by replication (the counterpart of the ingest's 2x2 mean, no interpolation), and per pixel,
@@ -40,6 +42,7 @@ typedef struct
     int width, height;                  /* the picture: luma samples, both even */
     int W, H;                           /* the coded size of the source: multiples of 16 */
     h264e_icolor_t cm;                  /* RGB / RGBP only */
+    int sample;                         /* H264E_SAMPLE_*: RGBP only, the launch picks the kernel by it (strides stay in bytes) */
 } h264e_egress_dst_t;
 
 /* the aligned dword at byte offset 4*i of a source row */
@@ -111,9 +114,46 @@ DEV void egress_chroma(const h264e_egress_dst_t &D, const GLOBAL_AS uint8_t *src
     ing_store((gu8 *)D.plane[2] + (size_t)y*(size_t)D.stride[2] + x0, n, v);
 }
 
-/* pixels 4g .. min(4g + 3, width - 1) of rows 2y and 2y + 1, interleaved (PB = bytes per pixel) or planar (PB = 0): n is 2 or 4, the two
- * rows share chroma row y, whose samples 2g and 2g + 1 are one half of an aligned dword */
-template <int PB> DEV void egress_rgb(const h264e_egress_dst_t &D, const GLOBAL_AS uint8_t *src, int g, int y)
+/* the 8-bit value v as a float sample of type ST, in the low bits: float32 v / 255 -- a true division, correctly rounded, NOT v * (1 / 255.f), which differs
+ * for 126 of the 256 values -- then narrowed.  "/" is that division in the emulation's compiler and, by default, in hipcc; the product's
+ * Makefile names the option (-fhip-fp32-correctly-rounded-divide-sqrt) so that no other flag takes it away unnoticed, and
+ * tests/test_gpu_float_io.py compares every one of the 256 quotients on the device */
+template <int ST> DEV uint32_t egr_float_sample(uint32_t v)
+{
+    const float f = (float)(int)v/255.0f;
+    return ST == H264E_SAMPLE_F32 ? fs_to_bits(f) : ST == H264E_SAMPLE_F16 ? fs_float_to_half(f) : fs_float_to_bf16(f);
+}
+
+/* n (2 or 4) samples c[] of a row as float samples to d: one store of 8 or 16 bytes where the group is whole -- d is a multiple of the
+ * sample size, which is all such a store to global memory asks -- else sample by sample; never a byte beyond d + n samples */
+template <int ST> DEV void egr_store_float(gu8 *d, int n, const uint32_t c[4])
+{
+    constexpr int SB = fs_bytes<ST>();
+    EMU_GLOBAL(d, (size_t)(n*SB));
+    uint32_t s[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) s[k] = egr_float_sample<ST>(c[k]);
+    if (n == 4)
+    {
+#ifdef H264E_EMU
+        if (SB == 4) memcpy(d, s, 16);
+        else { const uint32_t t[2] = { s[0] | (s[1] << 16), s[2] | (s[3] << 16) }; memcpy(d, t, 8); }
+#else
+        if (SB == 4) { u32x4 t; t.x = s[0]; t.y = s[1]; t.z = s[2]; t.w = s[3]; *(GLOBAL_AS u32x4 *)d = t; }
+        else { fs_u32x2 t; t.x = s[0] | (s[1] << 16); t.y = s[2] | (s[3] << 16); *(GLOBAL_AS fs_u32x2 *)d = t; }
+#endif
+        return;
+    }
+    for (int k = 0; k < 4; k++)
+        if (k < n)
+        {
+            if (SB == 4) *(GLOBAL_AS uint32_t *)(d + 4*k) = s[k]; else *(GLOBAL_AS uint16_t *)(d + 2*k) = (uint16_t)s[k];
+        }
+}
+
+/* pixels 4g .. min(4g + 3, width - 1) of rows 2y and 2y + 1, interleaved (PB = bytes per pixel) or planar (PB = 0, samples of type ST): n is
+ * 2 or 4, the two rows share chroma row y, whose samples 2g and 2g + 1 are one half of an aligned dword */
+template <int PB, int ST = H264E_SAMPLE_U8> DEV void egress_rgb(const h264e_egress_dst_t &D, const GLOBAL_AS uint8_t *src, int g, int y)
 {
     const int x0 = 4*g;
     if (x0 >= D.width || 2*y >= D.height) return;
@@ -139,7 +179,11 @@ template <int PB> DEV void egress_rgb(const h264e_egress_dst_t &D, const GLOBAL_
         {
 #pragma unroll
             for (int ch = 0; ch < 3; ch++)
-                ing_store((gu8 *)D.plane[ch] + (size_t)row*(size_t)D.stride[ch] + x0, n, c[ch][0] | (c[ch][1] << 8) | (c[ch][2] << 16) | (c[ch][3] << 24));
+            {
+                gu8 *d = (gu8 *)D.plane[ch] + (size_t)row*(size_t)D.stride[ch];
+                if (ST == H264E_SAMPLE_U8) ing_store(d + x0, n, c[ch][0] | (c[ch][1] << 8) | (c[ch][2] << 16) | (c[ch][3] << 24));
+                else egr_store_float<ST>(d + (size_t)x0*fs_bytes<ST>(), n, c[ch]);
+            }
         } else
         {
             constexpr int NB = PB ? 4*PB : 4;

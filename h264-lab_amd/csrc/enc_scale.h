@@ -51,6 +51,7 @@ typedef struct
     int sw, sh, dw, dh;                 /* luma window and picture, all even; the chroma planes have half of each */
     int th;                             /* destination rows per tile */
     h264e_color_t cm;                   /* planar RGB only (enc_scale_rgb.h) */
+    int sample;                         /* H264E_SAMPLE_*: planar RGB only; float planes have step = the sample's bytes */
 } h264e_scale_src_t;
 
 typedef struct

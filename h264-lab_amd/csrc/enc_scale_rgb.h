@@ -9,6 +9,9 @@
  *        rounded) channel.  The double rounding of chroma is part of the definition: it is what scaling first and converting afterwards
  *        in two steps gives.
  *
+ * Float planes (H264E_SAMPLE_F16 / _BF16 / _F32) are quantised by enc_ingest.h's fq_quant as the horizontal pass loads them
+ * (scale_hpass_float): the filter works on the QUANTISED samples, so the slot is exactly that of the quantised 8-bit planes.
+ *
  * So S == D is the plain planar ingest of the cropped region, and a constant colour stays that colour's Y, U, V at every ratio.  Limits
  * as for I420 (enc_scale.h).
  *
@@ -30,6 +33,26 @@ typedef struct
     ScaleLds s;                                     /* the taps and one channel's horizontal sums at a time */
     uint32_t rgb[3][SCL_TH_MAX][SCL_TW/4];          /* the scaled tile: four 8-bit samples of a row per dword */
 } ScaleRgbLds;
+
+/* scale_hpass for float planes, item = r*64 + column: the same sum over the row's taps, every tap one sample-aligned load, quantised.
+ * C.step is the sample's size; no byte outside the taps is read */
+template <int ST> DEV void scale_hpass_float(LDS_AS ScaleLds *L, const h264e_scale_comp_t &C, const ScaleTile &T, int item)
+{
+    constexpr int SB = fs_bytes<ST>();
+    const int r = item >> 6, t = item & (SCL_TW - 1);
+    if (t >= T.ncols || r >= scale_src_rows(L, T)) return;
+    const int k0 = L->ck0[t], k1 = L->ck1[t];
+    const uint32_t dw = (uint32_t)T.dw, a0 = (uint32_t)(T.i0 + t)*(uint32_t)T.sw;
+    const gu8 *row = (const gu8 *)C.base + (size_t)(L->rl0[0] + r)*(size_t)C.stride;
+    uint32_t sum = 0, first = 0, last = 0;
+    for (int k = k0; k <= k1; k++)
+    {
+        last = fq_quant(fs_load<ST>(row + (size_t)k*SB));
+        if (k == k0) first = last;
+        sum += last;
+    }
+    L->hsum[r][t] = dw*sum - (a0 - (uint32_t)k0*dw)*first - (((uint32_t)k1 + 1u)*dw - (a0 + (uint32_t)T.sw))*last;
+}
 
 /* the vertical pass of channel ch, item = row*16 + g: samples 4g .. 4g + 3 of one row of the tile into the LDS tile (whole dwords: what
  * lies beyond the tile's last column is never used) */

@@ -16,6 +16,8 @@
  *   h264e_egress_kernel  device-resident output (enc_egress.h): a reconstructed picture -> I420 / NV12 / RGB / planar RGB in the caller's HBM.
  *   h264e_scale_kernel   the same as the ingest for a source of another size (enc_scale.h): a window of an I420 / NV12 frame, box-filtered down to the slot.
  *   h264e_scale_rgb_kernel  ... of a planar RGB frame (enc_scale_rgb.h): the three channels box-filtered into LDS, converted to I420 from there.
+ *   h264e_ingest_float_kernel<ST>, h264e_scale_rgb_float_kernel<ST>, h264e_egress_float_kernel<ST>  the planar RGB paths for float16 /
+ *                        bfloat16 / float32 samples in [0, 1], quantised on the way in and divided by 255 on the way out.
  *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
  *
  * HIP only (hipcc --offload-arch=gfx950).  The host side of the boundary is h264e_pool.h, included at the end; the test-only
@@ -703,12 +705,26 @@ __global__ void __launch_bounds__(256) h264e_ingest_kernel(h264e_ingest_src_t S,
     else ingest_chroma(S, (GLOBAL_AS uint8_t *)dst, g, y);
 }
 
+/* ... of float planar RGB (ST = H264E_SAMPLE_F16 / _BF16 / _F32): kernels of their own, so that the 8-bit kernel has no branch per sample */
+template <int ST> __global__ void __launch_bounds__(256) h264e_ingest_float_kernel(h264e_ingest_src_t S, uint8_t *dst)
+{
+    const int g = (int)(blockIdx.x*blockDim.x + threadIdx.x), y = (int)blockIdx.y;
+    if (blockIdx.z == 0) ingest_float_luma<ST>(S, (GLOBAL_AS uint8_t *)dst, g, y);
+    else ingest_float_chroma<ST>(S, (GLOBAL_AS uint8_t *)dst, g, y);
+}
+
 /* device-resident output over one picture (enc_egress.h): grid.z = 0 luma / 1 both chroma planes for I420 and NV12, grid.y = row; the RGB
  * formats have grid.z = 0 alone and grid.y = a PAIR of rows (one chroma row); grid.x * 256 lanes x 4 samples along the row.  Every workgroup
  * reads its own bytes of the picture and writes its own bytes of the destination (no inter-workgroup traffic, no LDS). */
 __global__ void __launch_bounds__(256) h264e_egress_kernel(h264e_egress_dst_t D, const uint8_t *src)
 {
     egress_group(D, (const GLOBAL_AS uint8_t *)src, (int)(blockIdx.x*blockDim.x + threadIdx.x), (int)blockIdx.y, (int)blockIdx.z);
+}
+
+/* ... to float planar RGB: grid.y = a pair of rows, as for the 8-bit RGB formats */
+template <int ST> __global__ void __launch_bounds__(256) h264e_egress_float_kernel(h264e_egress_dst_t D, const uint8_t *src)
+{
+    egress_rgb<0, ST>(D, (const GLOBAL_AS uint8_t *)src, (int)(blockIdx.x*blockDim.x + threadIdx.x), (int)blockIdx.y);
 }
 
 /* device-resident input of another size (enc_scale.h): grid.z = plane, grid.x / grid.y = the tile of 64 x S.th destination samples.  Column
@@ -744,6 +760,27 @@ __global__ void __launch_bounds__(256) h264e_scale_rgb_kernel(h264e_scale_src_t 
     for (int ch = 0; ch < 3; ch++)
     {
         for (int it = (int)threadIdx.x; it < items; it += 256) scale_hpass(&L->s, S.c[ch], T, it);
+        __syncthreads();
+        for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_rgb_vpass(L, T, ch, it);
+        __syncthreads();
+    }
+    for (int it = (int)threadIdx.x; it < scale_rgb_items(T); it += 256) scale_rgb_convert(S.cm, L, T, (GLOBAL_AS uint8_t *)dst, it);
+}
+
+/* ... of float planes: the same steps, the horizontal pass quantises as it loads (scale_hpass_float).  A kernel of its own, so that the
+ * 8-bit kernel above stays the code it was */
+template <int ST> __global__ void __launch_bounds__(256) h264e_scale_rgb_float_kernel(h264e_scale_src_t S, uint8_t *dst)
+{
+    __shared__ __attribute__((aligned(16))) ScaleRgbLds lds;
+    LDS_AS ScaleRgbLds *L = (LDS_AS ScaleRgbLds *)&lds;
+    ScaleTile T;
+    if (!scale_tile(S, 0, (int)blockIdx.x, (int)blockIdx.y, T)) return;
+    scale_tables(&L->s, T, (int)threadIdx.x);
+    __syncthreads();
+    const int items = scale_src_rows(&L->s, T) << 6;
+    for (int ch = 0; ch < 3; ch++)
+    {
+        for (int it = (int)threadIdx.x; it < items; it += 256) scale_hpass_float<ST>(&L->s, S.c[ch], T, it);
         __syncthreads();
         for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_rgb_vpass(L, T, ch, it);
         __syncthreads();
@@ -829,16 +866,22 @@ static void bk_launch_denoise(const uint8_t *in, const uint8_t *prev, uint8_t *o
     const unsigned gx = (unsigned)((((width + 3) >> 2) + 255) >> 8);
     hipLaunchKernelGGL(h264e_denoise_kernel, dim3(gx, (unsigned)height, 3), dim3(256), 0, st, in, prev, out, width, height);
 }
+/* planar RGB by sample type: the 8-bit kernel K8, or the float kernel KF<H264E_SAMPLE_*>, 256 lanes per workgroup */
+#define LAUNCH_BY_SAMPLE(sample, K8, KF, grid, st, ...) do { \
+    if ((sample) == H264E_SAMPLE_F16) hipLaunchKernelGGL(KF<H264E_SAMPLE_F16>, grid, dim3(256), 0, st, __VA_ARGS__); \
+    else if ((sample) == H264E_SAMPLE_BF16) hipLaunchKernelGGL(KF<H264E_SAMPLE_BF16>, grid, dim3(256), 0, st, __VA_ARGS__); \
+    else if ((sample) == H264E_SAMPLE_F32) hipLaunchKernelGGL(KF<H264E_SAMPLE_F32>, grid, dim3(256), 0, st, __VA_ARGS__); \
+    else hipLaunchKernelGGL(K8, grid, dim3(256), 0, st, __VA_ARGS__); } while (0)
 static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t st)
 {
     const unsigned gx = (unsigned)((((S.width + 3) >> 2) + 255) >> 8);
-    hipLaunchKernelGGL(h264e_ingest_kernel, dim3(gx, (unsigned)S.height, 2), dim3(256), 0, st, S, dst);
+    LAUNCH_BY_SAMPLE(S.sample, h264e_ingest_kernel, h264e_ingest_float_kernel, dim3(gx, (unsigned)S.height, 2), st, S, dst);
 }
 static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hipStream_t st)
 {
     const unsigned gx = (unsigned)((((D.width + 3) >> 2) + 255) >> 8);
     const int rgb = D.format == H264E_INGEST_RGB || D.format == H264E_INGEST_RGBP;
-    hipLaunchKernelGGL(h264e_egress_kernel, dim3(gx, (unsigned)(rgb ? D.height >> 1 : D.height), rgb ? 1 : 2), dim3(256), 0, st, D, src);
+    LAUNCH_BY_SAMPLE(D.sample, h264e_egress_kernel, h264e_egress_float_kernel, dim3(gx, (unsigned)(rgb ? D.height >> 1 : D.height), rgb ? 1 : 2), st, D, src);
 }
 static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t st)
 {
@@ -846,7 +889,7 @@ static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_
 }
 static void bk_launch_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t st)
 {
-    hipLaunchKernelGGL(h264e_scale_rgb_kernel, dim3((unsigned)((S.dw + SCL_TW - 1)/SCL_TW), (unsigned)((S.dh + S.th - 1)/S.th), 1), dim3(256), 0, st, S, dst);
+    LAUNCH_BY_SAMPLE(S.sample, h264e_scale_rgb_kernel, h264e_scale_rgb_float_kernel, dim3((unsigned)((S.dw + SCL_TW - 1)/SCL_TW), (unsigned)((S.dh + S.th - 1)/S.th), 1), st, S, dst);
 }
 /* one workgroup per chunk, at most 256 (one per CU): at most 256 adders per record word, 254 at 1080p */
 static void bk_launch_scenecut(const uint8_t *luma, uint32_t nbytes, int *record, hipStream_t st)

@@ -755,19 +755,32 @@ extern "C" int h264e_hip_upload_planes(h264e_hip_pool_t *p, int index, const uin
 
 #ifdef H264E_EMU
 /* the emulation's launch: the kernel's per-group code as a lane loop, row by row */
-static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t)
+/* ST = H264E_SAMPLE_*: the 8-bit code, or the float kernels' (one dispatch per launch: EMU_BY_SAMPLE) */
+#define EMU_BY_SAMPLE(sample, F, ...) do { \
+    if ((sample) == H264E_SAMPLE_F16) F<H264E_SAMPLE_F16>(__VA_ARGS__); else if ((sample) == H264E_SAMPLE_BF16) F<H264E_SAMPLE_BF16>(__VA_ARGS__); \
+    else if ((sample) == H264E_SAMPLE_F32) F<H264E_SAMPLE_F32>(__VA_ARGS__); else F<H264E_SAMPLE_U8>(__VA_ARGS__); } while (0)
+template <int ST> static void emu_ingest(const h264e_ingest_src_t &S, uint8_t *dst)
 {
     for (int y = 0; y < S.height; y++)
-        for (int g = 0; g < (S.width + 3)/4; g++) { ingest_luma(S, dst, g, y); ingest_chroma(S, dst, g, y); }
+        for (int g = 0; g < (S.width + 3)/4; g++)
+        {
+            if constexpr (ST == H264E_SAMPLE_U8) { ingest_luma(S, dst, g, y); ingest_chroma(S, dst, g, y); }
+            else { ingest_float_luma<ST>(S, dst, g, y); ingest_float_chroma<ST>(S, dst, g, y); }
+        }
 }
+static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t) { EMU_BY_SAMPLE(S.sample, emu_ingest, S, dst); }
 /* ... and the egress's (enc_egress.h): the same, per part */
-static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hipStream_t)
+template <int ST> static void emu_egress(const h264e_egress_dst_t &D, const uint8_t *src)
 {
     const int rgb = D.format == H264E_INGEST_RGB || D.format == H264E_INGEST_RGBP;
     for (int part = 0; part < (rgb ? 1 : 2); part++)
         for (int y = 0; y < (rgb ? D.height >> 1 : D.height); y++)
-            for (int g = 0; g < (D.width + 3)/4; g++) egress_group(D, src, g, y, part);
+            for (int g = 0; g < (D.width + 3)/4; g++)
+            {
+                if constexpr (ST == H264E_SAMPLE_U8) egress_group(D, src, g, y, part); else egress_rgb<0, ST>(D, src, g, y);
+            }
 }
+static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hipStream_t) { EMU_BY_SAMPLE(D.sample, emu_egress, D, src); }
 /* ... and the scaler's (enc_scale.h): tile by tile, each of the kernel's three steps as a lane loop over the tile's LDS */
 static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t)
 {
@@ -788,7 +801,7 @@ static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_
     free(L);
 }
 /* ... and the planar RGB scaler's (enc_scale_rgb.h): per tile the taps, per channel the two passes into the LDS tile, then the conversion */
-static void bk_launch_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t)
+template <int ST> static void emu_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst)
 {
     ScaleRgbLds *L = (ScaleRgbLds *)malloc(sizeof(ScaleRgbLds));
     if (!L) return;
@@ -802,13 +815,17 @@ static void bk_launch_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst, hipStr
             const int items = scale_src_rows(&L->s, T) << 6;
             for (int ch = 0; ch < 3; ch++)
             {
-                for (int it = 0; it < items; it++) scale_hpass(&L->s, S.c[ch], T, it);
+                for (int it = 0; it < items; it++)
+                {
+                    if constexpr (ST == H264E_SAMPLE_U8) scale_hpass(&L->s, S.c[ch], T, it); else scale_hpass_float<ST>(&L->s, S.c[ch], T, it);
+                }
                 for (int it = 0; it < T.nrows*16; it++) scale_rgb_vpass(L, T, ch, it);
             }
             for (int it = 0; it < scale_rgb_items(T); it++) scale_rgb_convert(S.cm, L, T, dst, it);
         }
     free(L);
 }
+static void bk_launch_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t) { EMU_BY_SAMPLE(S.sample, emu_scale_rgb, S, dst); }
 #else
 /* the product refuses what the runtime does not know as device memory of this pool's device, and a plane that does not lie inside ONE
  * allocation from its first to its last byte: a host address or a read beyond the allocation is a memory fault in the kernel, not an
@@ -826,6 +843,26 @@ static int ingest_is_device_memory(const h264e_hip_pool_t *p, const void *q, siz
 }
 #endif
 
+/* H264E_dev_frame_t.format: the layout in bits 0-1, the sample type in bits 4-5 (planar RGB only), nothing else; *sb = a sample's bytes */
+static const char *const k_format_names[4] = { "I420", "NV12", "RGB", "RGBP" }, *const k_sample_names[4] = { "u8", "f16", "bf16", "f32" };
+static int dev_format_split(const char *who, int format, int *base, int *sample, int *sb)
+{
+    if (format & ~0x33) FAIL("%s: unknown format %d", who, format);
+    *base = format & 3; *sample = (format >> 4) & 3;
+    *sb = *sample == H264E_SAMPLE_F32 ? 4 : *sample ? 2 : 1;
+    if (*sample && *base != H264E_INGEST_RGBP)
+        FAIL("%s: format %d asks for %s samples (0x%x) of %s (format %d): float samples are planar RGB (format %d) only", who, format, k_sample_names[*sample], *sample << 4,
+             k_format_names[*base], *base, H264E_INGEST_RGBP);
+    return 0;
+}
+/* float planes: every pointer and stride a multiple of the sample's bytes (what the kernels' loads and stores rest on) */
+static int dev_sample_aligned(const char *who, int k, const void *plane, int stride, int sb, int sample)
+{
+    if ((uintptr_t)plane % (unsigned)sb) FAIL("%s: plane %d (%p) is not a multiple of the %d bytes of a %s sample", who, k, plane, sb, k_sample_names[sample]);
+    if (stride % sb) FAIL("%s: stride %d of plane %d is not a multiple of the %d bytes of a %s sample", who, stride, k, sb, k_sample_names[sample]);
+    return 0;
+}
+
 extern "C" int h264e_hip_set_color(h264e_hip_pool_t *p, int bt709, int full_range)
 {
     if (!p || (unsigned)bt709 > 1 || (unsigned)full_range > 1) FAIL("set_color: bad argument");
@@ -835,22 +872,24 @@ extern "C" int h264e_hip_set_color(h264e_hip_pool_t *p, int bt709, int full_rang
 }
 
 /* everything that is refused, without a launch; fills the kernel's view of the source */
-static int ingest_check(const h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], int pixel_bytes, h264e_ingest_src_t *S)
+static int ingest_check(const h264e_hip_pool_t *p, int slot, int dev_format, const void *const planes[3], const int strides[3], int pixel_bytes, h264e_ingest_src_t *S)
 {
+    int format, sample, sb;
     if (!p || !planes || !strides) FAIL("ingest_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("ingest_device: slot %d outside the %d resident frames", slot, p->frames_resident);
-    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12 && format != H264E_INGEST_RGB && format != H264E_INGEST_RGBP) FAIL("ingest_device: unknown format %d", format);
+    if (dev_format_split("ingest_device", dev_format, &format, &sample, &sb)) return -1;
     if (format == H264E_INGEST_RGB && pixel_bytes != 3 && pixel_bytes != 4) FAIL("ingest_device: RGB pixels of %d bytes (3 or 4)", pixel_bytes);
     memset(S, 0, sizeof(*S));
-    S->format = format; S->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1;
+    S->format = format; S->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1; S->sample = sample;
     S->width = p->G.width; S->height = p->G.height;
     S->cm = p->cm;
     const int nplanes = format == H264E_INGEST_I420 || format == H264E_INGEST_RGBP ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
     for (int k = 0; k < nplanes; k++)
     {
-        /* bytes and rows of source plane k: RGB pixels; full-size luma and R, G, B planes; half-size chroma (NV12: U,V pairs, so `width` bytes again) */
-        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP) ? S->width : S->width/2;
+        /* bytes and rows of source plane k: RGB pixels; full-size luma and R, G, B planes (sb bytes per sample); half-size chroma (NV12: U,V pairs, so `width` bytes again) */
+        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP) ? S->width*sb : S->width/2;
         if (!planes[k]) FAIL("ingest_device: plane %d is NULL", k);
+        if (dev_sample_aligned("ingest_device", k, planes[k], strides[k], sb, sample)) return -1;
         if (strides[k] < row_bytes) FAIL("ingest_device: stride %d of plane %d is below its %d row bytes", strides[k], k, row_bytes);
 #ifndef H264E_EMU
         const int rows = k == 0 || format == H264E_INGEST_RGBP ? S->height : S->height/2;
@@ -918,12 +957,13 @@ extern "C" int h264e_hip_ingest_device(h264e_hip_pool_t *p, int slot, int format
 /* everything that is refused, without a launch; fills the kernel's view of the source.  win = {src_width, src_height, crop_x, crop_y,
  * crop_width, crop_height}, crop_width 0 = the whole source.  Plane extents come from the SOURCE size and the window: what must be
  * device memory inside one allocation is [the window's first byte, the last byte of its last row] of every plane. */
-static int scale_check(const h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], const int *win, h264e_scale_src_t *S)
+static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, const void *const planes[3], const int strides[3], const int *win, h264e_scale_src_t *S)
 {
+    int format, sample, sb;
     if (!p || !planes || !strides || !win) FAIL("scale_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("scale_device: slot %d outside the %d resident frames", slot, p->frames_resident);
+    if (dev_format_split("scale_device", dev_format, &format, &sample, &sb)) return -1;
     if (format == H264E_INGEST_RGB) FAIL("scale_device: interleaved RGB (format %d) cannot be combined with a window: convert at the picture's size, or hand over planar RGB (format %d), I420 or NV12", format, H264E_INGEST_RGBP);
-    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12 && format != H264E_INGEST_RGBP) FAIL("scale_device: unknown format %d", format);
     const int srcw = win[0], srch = win[1], dw = p->G.width, dh = p->G.height;
     if (srcw <= 0 || srch <= 0) FAIL("scale_device: source of %d x %d samples", srcw, srch);
     const int cx = win[4] ? win[2] : 0, cy = win[4] ? win[3] : 0, sw = win[4] ? win[4] : srcw, sh = win[4] ? win[5] : srch;
@@ -941,7 +981,7 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int format, const vo
     if (sh > SCL_MAX_RATIO*dh) FAIL("scale_device: window height %d is more than %d times the picture's %d", sh, SCL_MAX_RATIO, dh);
     memset(S, 0, sizeof(*S));
     S->sw = sw; S->sh = sh; S->dw = dw; S->dh = dh;
-    S->cm = p->cm;
+    S->cm = p->cm; S->sample = sample;
     S->th = (int)((long long)(SCL_ROWS - 2)*dh/sh);            /* th*sh/dh + 2 source rows at most: <= SCL_ROWS */
     if (S->th > SCL_TH_MAX) S->th = SCL_TH_MAX;
     const int rgbp = format == H264E_INGEST_RGBP;
@@ -949,11 +989,12 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int format, const vo
     const int nplanes = format == H264E_INGEST_NV12 ? 2 : 3, cw = (srcw + 1)/2;
     for (int k = 0; k < nplanes; k++)
     {
-        /* bytes of a source row, and the window in this plane: x0 bytes into row y0, wbytes x rows (planar RGB: every plane as luma) */
+        /* bytes of a source row, and the window in this plane: x0 bytes into row y0, wbytes x rows (planar RGB: every plane as luma, sb bytes per sample) */
         const int nv = k && format == H264E_INGEST_NV12, full = k == 0 || rgbp;
-        const int row_bytes = full ? srcw : nv ? 2*cw : cw;
-        const int x0 = full ? cx : nv ? cx : cx/2, y0 = full ? cy : cy/2, wbytes = full ? sw : nv ? sw : sw/2, rows = full ? sh : sh/2;
+        const int row_bytes = full ? srcw*sb : nv ? 2*cw : cw;
+        const int x0 = full ? cx*sb : nv ? cx : cx/2, y0 = full ? cy : cy/2, wbytes = full ? sw*sb : nv ? sw : sw/2, rows = full ? sh : sh/2;
         if (!planes[k]) FAIL("scale_device: plane %d is NULL", k);
+        if (dev_sample_aligned("scale_device", k, planes[k], strides[k], sb, sample)) return -1;
         if (strides[k] < row_bytes) FAIL("scale_device: stride %d of plane %d is below the %d bytes of a source row", strides[k], k, row_bytes);
         const uint8_t *lo = (const uint8_t *)planes[k] + (size_t)y0*(size_t)strides[k] + (size_t)x0;
         const size_t nbytes = (size_t)(rows - 1)*(size_t)strides[k] + (size_t)wbytes;
@@ -965,7 +1006,7 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int format, const vo
         for (int c = k; c < (nv ? 3 : k + 1); c++)
         {
             S->c[c].base = lo + (nv && c == 2 ? 1 : 0); S->c[c].lo = lo; S->c[c].hi = lo + nbytes;
-            S->c[c].stride = strides[k]; S->c[c].step = nv ? 2 : 1;
+            S->c[c].stride = strides[k]; S->c[c].step = nv ? 2 : sb;
         }
     }
     return 0;
@@ -984,7 +1025,7 @@ extern "C" int h264e_hip_scale_device_async(h264e_hip_pool_t *p, int slot, int f
     if (p) HIPCHK(hipSetDevice(p->device));
     if (scale_check(p, slot, format, planes, strides, win, &S)) return -1;
     if (ingest_order(p, producer_stream)) return -1;
-    if (format == H264E_INGEST_RGBP) bk_launch_scale_rgb(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
+    if ((format & 3) == H264E_INGEST_RGBP) bk_launch_scale_rgb(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
     else bk_launch_scale(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1000,22 +1041,24 @@ extern "C" int h264e_hip_scale_device(h264e_hip_pool_t *p, int slot, int format,
 /* ---- device-resident output (enc_egress.h): one h264e_egress_kernel launch per picture on the pool's copy stream */
 
 /* everything that is refused, without a launch; fills the kernel's view of the destination */
-static int egress_check(const h264e_hip_pool_t *p, int slot, int format, void *const planes[3], const int strides[3], int pixel_bytes, h264e_egress_dst_t *D)
+static int egress_check(const h264e_hip_pool_t *p, int slot, int dev_format, void *const planes[3], const int strides[3], int pixel_bytes, h264e_egress_dst_t *D)
 {
+    int format, sample, sb;
     if (!p || !planes || !strides) FAIL("egress: null argument");
     if (slot < 0 || slot >= p->nchains) FAIL("egress: picture slot %d outside the pool's %d", slot, p->nchains);
-    if (format != H264E_INGEST_I420 && format != H264E_INGEST_NV12 && format != H264E_INGEST_RGB && format != H264E_INGEST_RGBP) FAIL("egress: unknown format %d", format);
+    if (dev_format_split("egress", dev_format, &format, &sample, &sb)) return -1;
     if (format == H264E_INGEST_RGB && pixel_bytes != 3 && pixel_bytes != 4) FAIL("egress: RGB pixels of %d bytes (3 or 4)", pixel_bytes);
     memset(D, 0, sizeof(*D));
-    D->format = format; D->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1;
+    D->format = format; D->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1; D->sample = sample;
     D->width = p->G.width; D->height = p->G.height; D->W = p->G.W; D->H = p->G.H;
     D->cm = p->icm;
     const int nplanes = format == H264E_INGEST_I420 || format == H264E_INGEST_RGBP ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
     for (int k = 0; k < nplanes; k++)
     {
         /* bytes and rows of destination plane k, as the ingest counts them for a source */
-        const int row_bytes = format == H264E_INGEST_RGB ? D->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP) ? D->width : D->width/2;
+        const int row_bytes = format == H264E_INGEST_RGB ? D->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP) ? D->width*sb : D->width/2;
         if (!planes[k]) FAIL("egress: plane %d is NULL", k);
+        if (dev_sample_aligned("egress", k, planes[k], strides[k], sb, sample)) return -1;
         if (strides[k] < row_bytes) FAIL("egress: stride %d of plane %d is below its %d row bytes", strides[k], k, row_bytes);
 #ifndef H264E_EMU
         /* what will be written: from the first byte of the first row to the last byte of the last */

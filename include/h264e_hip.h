@@ -110,7 +110,9 @@ void h264e_hip_host_free(void *p);
 int  h264e_hip_upload_planes(h264e_hip_pool_t *pool, int index, const uint8_t *const yuv[3], const int stride[3]);
 /* Device-resident input (enc_ingest.h): one frame that already lies in this pool's device memory -- format 0 = I420 (three planes),
  * 1 = NV12 (Y, interleaved UV), 2 = interleaved RGB of pixel_bytes 3 or 4 (BT.601 limited range, integer), 3 = planar RGB (three planes
- * R, G, B, the same arithmetic) -- into resident slot `slot`,
+ * R, G, B, the same arithmetic); 3 | 0x10 / 0x20 / 0x30 = planar RGB of float16 / bfloat16 / float32 samples in [0, 1], quantised to
+ * 8 bits as they are loaded (enc_ingest.h fq_quant; pointers and strides multiples of the sample's size; a sample type on another
+ * format is refused) -- into resident slot `slot`,
  * by ONE kernel launch on the pool's copy stream.  planes / strides: a pointer and a row stride in bytes (>= the row's bytes) per
  * source plane; unused entries are ignored.  producer_stream: the hipStream_t whose queued work writes the source (the launch waits
  * for everything queued there so far), or NULL when the caller has synchronised.  Returns when the slot has been written: the source
@@ -195,7 +197,8 @@ int  h264e_hip_read_recon(h264e_hip_pool_t *pool, int chain, uint8_t *dst);
 int  h264e_hip_read_recon_slot(h264e_hip_pool_t *pool, int slot, uint8_t *dst);
 /* Device-resident output (enc_egress.h), the way back of h264e_hip_ingest_device: a reconstructed picture, cropped to the pool's width x
  * height, into device memory of the pool's device in one of the ingest's four formats (RGB / RGBP: converted by the inverse of the matrix
- * h264e_hip_set_color selected, chroma replicated over its 2x2 block, a fourth byte of an RGB pixel written as 255), by ONE kernel launch
+ * h264e_hip_set_color selected, chroma replicated over its 2x2 block, a fourth byte of an RGB pixel written as 255; 3 | 0x10 / 0x20 /
+ * 0x30: the planar RGB values v as float16 / bfloat16 / float32 v / 255, enc_egress.h egr_float_sample), by ONE kernel launch
  * on the pool's copy stream.  planes / strides: a pointer and a row stride in bytes (>= the row's bytes) per destination plane, counted
  * as for a source; only the rows' bytes are written, never the padding between them.  _slot: the picture h264e_hip_read_recon_slot
  * reads; _last: the one h264e_hip_read_recon reads.  producer_stream: the hipStream_t whose queued work may still use the destination

@@ -201,7 +201,14 @@ typedef struct
  *          RGBP: plane[0..2] = the R, G and B planes, 8 bits per sample, each with its own pointer and stride (a CHW tensor, three
  *                allocations, padded or odd strides and addresses); pixel_bytes is ignored.  The same arithmetic: byte for byte what
  *                RGB gives for the same image.
- * stride: bytes from row to row, at least the row's bytes; no alignment is asked of pointers or strides.  producer_stream: the
+ *          RGBP | H264E_DEV_SAMPLE_F16 / _BF16 / _F32 (bits 4-5 of format; on any other layout they are refused): the same three
+ *                planes of float16, bfloat16 or float32 samples in [0, 1], as vision models and renderers hold them.  Every sample x
+ *                is widened to float32 (exact) and quantised, q = clamp(rint(x * 255), 0, 255): ONE float32 multiply, round to nearest
+ *                even; NaN, negative values and -0.0 give 0, values above 1 give 255 -- torch's nan_to_num((x.float() * 255).round()
+ *                .clamp(0, 255), nan=0).to(uint8).  From q on the frame IS the 8-bit RGBP frame: the stream and the input slot are
+ *                exactly those of the quantised planes (tests/float_model.py restates it).  Strides stay in bytes; plane pointers and
+ *                strides must be multiples of the sample's size.
+ * stride: bytes from row to row, at least the row's bytes; no alignment is asked of pointers or strides of 8-bit samples.  producer_stream: the
  * hipStream_t on which the work that writes the frame was queued -- the encoder waits for everything queued there so far -- or NULL
  * when the caller has synchronised.  Every call that takes such frames returns when they have been read: the memory may be reused
  * at once.  The pointers must be device memory of the encoder's GPU; anything else is refused (H264E_last_error says why). */
@@ -209,9 +216,13 @@ typedef struct
 #define H264E_DEV_FORMAT_NV12 1
 #define H264E_DEV_FORMAT_RGB  2
 #define H264E_DEV_FORMAT_RGBP 3
+#define H264E_DEV_SAMPLE_U8    0x00         /* the sample type, OR-ed into format: RGBP only */
+#define H264E_DEV_SAMPLE_F16   0x10
+#define H264E_DEV_SAMPLE_BF16  0x20
+#define H264E_DEV_SAMPLE_F32   0x30
 typedef struct
 {
-    int format;                             /* H264E_DEV_FORMAT_* */
+    int format;                             /* H264E_DEV_FORMAT_*, for RGBP | H264E_DEV_SAMPLE_* */
     int pixel_bytes;                        /* RGB: 3 or 4; ignored otherwise (RGBP included) */
     const void *plane[3];
     int stride[3];
@@ -234,7 +245,8 @@ int  H264E_encode_device(H264E_persist_t *enc, H264E_scratch_t *scratch, const H
  * from the window to Dw x Dh (rounded to 8 bits, all three at luma geometry), and the conversion above is applied to that RGB picture --
  * the order a caller scaling and converting in two steps would use; chroma is the matrix of the rounded 2x2 mean of already rounded
  * samples (tests/rgbp_model.py restates it).  A pure crop equals the plain ingest of the cropped region, a constant colour stays the
- * same at every ratio.  Refused (H264E_last_error names the value): interleaved RGB
+ * same at every ratio.  Float RGBP: the window filters the QUANTISED samples, so the slot is that of the quantised 8-bit planes.
+ * Refused (H264E_last_error names the value): interleaved RGB
  * with a window, odd or negative crop values, a window that leaves the source, is smaller than the picture in an axis (no upscaling),
  * larger than 4096 samples or more than 16 times the picture in an axis, a stride below the source row's bytes, and planes that are
  * not device memory of the encoder's GPU from the window's first byte to its last. */
@@ -249,6 +261,9 @@ int  H264E_encode_device_scaled(H264E_persist_t *enc, H264E_scratch_t *scratch, 
  * Only the bytes of the rows are written: padding between rows and everything around the planes keeps what it held.
  *   I420: plane[0..2] = Y, U, V;   NV12: plane[0] = Y, plane[1] = interleaved U,V pairs: copies of the coded samples.
  *   RGB:  plane[0] = interleaved R,G,B of pixel_bytes 3 or 4 (the fourth byte is written as 255);   RGBP: plane[0..2] = R, G, B planes.
+ *   RGBP | H264E_DEV_SAMPLE_F16 / _BF16 / _F32: the 8-bit R, G, B values v of RGBP written as float32 v / 255 (ONE correctly rounded
+ *         division, not a multiplication by 1/255), for float16 and bfloat16 that float32 value rounded to nearest even: torch's
+ *         (u8.float() / 255).to(dtype) with IEEE division (torch on the CPU), bit for bit.  Pointers and strides: multiples of the sample's size.
  * The conversion for RGB and RGBP -- the reference has none, this integer definition is the definition (tests/egress_model.py restates it):
  * every chroma sample serves the 2x2 luma block it belongs to (sample replication, the counterpart of the ingest's 2x2 mean; no
  * interpolation), and per pixel, with C = Y - yo, D = U - 128, E = V - 128 and arithmetic shifts,
@@ -265,6 +280,7 @@ int  H264E_encode_device_scaled(H264E_persist_t *enc, H264E_scratch_t *scratch, 
  * producer_stream: the hipStream_t whose queued work may still read or write the destination -- the kernel waits for everything queued
  * there so far -- or NULL when the caller has synchronised.  The calls return when the destination has been written.  Refused, with the
  * value named in H264E_last_error and the destination untouched: an unknown format, pixel_bytes other than 3 or 4 for RGB, a NULL plane,
+ * a sample type on another layout than RGBP, a pointer or stride that is not a multiple of a float sample's size,
  * a stride below the row's bytes, and a plane that is not device memory of the encoder's GPU inside one allocation from the first byte
  * written to the last.  Nothing is scaled on the way out.
  * H264E_read_recon_device: the picture the last successful H264E_encode / H264E_encode_device / H264E_encode_device_scaled left -- what

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """What device-resident input costs and saves at 1080p (synth_v1, QP 26, GOP 30).  Per format (I420, NV12, RGB 3 and 4 bytes per pixel,
 planar RGB from a CHW tensor with the default matrix and with BT.709 full range ("rgbp_bt709_full", H264E_clip_set_color), and "rgbp_via_permute": the same CHW tensor turned into HWC by torch's permute().contiguous() and handed
-over as interleaved RGB, the two steps the planar format replaces):
+over as interleaved RGB, the two steps the planar format replaces; with --fmt also float planar RGB, "rgbp_f16" / "rgbp_bf16" / "rgbp_f32":
+the same picture as a float CHW tensor in [0, 1] through the float ingest, and "rgbp_f16_via_quantise" / ...: that tensor quantised by
+torch, (x * 255).round().clamp(0, 255).to(uint8), and handed over as "rgbp", the two steps the float formats replace):
 the time per frame of H264E_clip_upload_device over `--frames` frames handed over in one call (one ingest kernel launch per frame, one
 wait at the end: launch + kernel, host wall clock around a call that ends in a device synchronise), next to H264E_clip_upload of the
 same frames from host memory -- the copy it replaces.  Then the per-frame API: H264E_encode (host planes) against H264E_encode_device
 (torch tensor), alternating, `--reps` times.  Prints one JSON line.  The kernel's own time comes from a profiler run of this tool, e.g.
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/ingest_probe.py --frames 60 --reps 1
 
-    python tools/ingest_probe.py [--frames 60] [--perframe 60] [--reps 5]
+    python tools/ingest_probe.py [--frames 60] [--perframe 60] [--reps 5] [--fmt i420,rgbp,rgbp_f16,rgbp_f16_via_quantise,...]
 """
 import argparse
 import json
@@ -26,6 +28,8 @@ import ingest_model as M  # noqa: E402
 import pkg  # noqa: E402
 
 W, H, QP, GOP = 1920, 1080, 26, 30
+FORMATS = ("i420", "nv12", "rgb3", "rgb4", "rgbp", "rgbp_bt709_full", "rgbp_via_permute")
+FLOAT_FORMATS = tuple("rgbp_" + k + v for k in ("f16", "bf16", "f32") for v in ("", "_via_quantise"))
 
 
 def host_frames(P, n):
@@ -47,8 +51,12 @@ def sources(torch, c, fmt):
     pb = 4 if fmt == "rgb4" else 3
     rgb = M.rgb_clip(W, H, 2, pb)
     model = np.stack([CM.rgb_to_i420(rgb[i % 2], *((1, 1) if fmt == "rgbp_bt709_full" else (0, 0))) for i in range(len(c))])
-    if fmt in ("rgbp", "rgbp_bt709_full", "rgbp_via_permute"):
+    if fmt in ("rgbp", "rgbp_bt709_full", "rgbp_via_permute") or fmt in FLOAT_FORMATS:
         ts = [torch.from_numpy(np.ascontiguousarray(rgb[i].transpose(2, 0, 1))).cuda() for i in range(2)]
+        if fmt in FLOAT_FORMATS:            # v / 255 in the sample type: quantises back to v
+            dtype = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}[fmt.split("_")[1]]
+            ts = [(t.cpu().float() / 255).to(dtype).cuda() for t in ts]
+            return [ts[i % 2] for i in range(len(c))], "rgbpf", model
         return [ts[i % 2] for i in range(len(c))], "rgbp", model
     ts = [torch.from_numpy(rgb[i]).cuda() for i in range(2)]
     return [ts[i % 2] for i in range(len(c))], "rgb", model
@@ -59,12 +67,17 @@ def main():
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--perframe", type=int, default=60)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--fmt", default=",".join(FORMATS), help="comma-separated, of: %s" % ", ".join(FORMATS + FLOAT_FORMATS))
     a = ap.parse_args()
+    fmts = [f for f in a.fmt.split(",") if f]
+    for f in fmts:
+        if f not in FORMATS + FLOAT_FORMATS:
+            ap.error("--fmt %s: one of %s" % (f, ", ".join(FORMATS + FLOAT_FORMATS)))
     import torch
     P = pkg.load_pkg()
     c = host_frames(P, max(a.frames, a.perframe))
     line = {"clip": "1080p synth_v1, QP %d, GOP %d" % (QP, GOP), "frames": a.frames, "reps": a.reps, "formats": {}}
-    for fmt in ("i420", "nv12", "rgb3", "rgb4", "rgbp", "rgbp_bt709_full", "rgbp_via_permute"):
+    for fmt in fmts:
         src, name, model = sources(torch, c[: a.frames], fmt)
         torch.cuda.synchronize()
         ce = P.ClipEncoder(W, H, a.frames, gop=GOP, qp=QP, color="bt709-full" if fmt == "rgbp_bt709_full" else None)
@@ -73,6 +86,8 @@ def main():
             t0 = time.perf_counter()
             if fmt == "rgbp_via_permute":
                 ce.upload_device([t.permute(1, 2, 0).contiguous() for t in src], "rgb")
+            elif fmt.endswith("_via_quantise"):
+                ce.upload_device([(t * 255).round().clamp(0, 255).to(torch.uint8) for t in src], "rgbp")
             else:
                 ce.upload_device(src, name)
             t1 = time.perf_counter()
