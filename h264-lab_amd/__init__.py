@@ -6,6 +6,7 @@ the HIP library has not been built, and encoder creation fails when no HIP devic
 """
 from .binding import (  # noqa: F401
     CreateParam, RunParam, IoYuv, Encoder, ClipEncoder, ClipParam, ClipStats, load, lib_path, build, H264EError,
+    psnr_from_ssd, ssim_planes,
     DevFrame, DevWindow, dev_frame, dev_window, recon_out, encode_ladder, DEV_FORMAT_I420, DEV_FORMAT_NV12, DEV_FORMAT_RGB, DEV_FORMAT_RGBP, DEV_FORMAT_RGBP_F16, DEV_FORMAT_RGBP_BF16, DEV_FORMAT_RGBP_F32,
     DEV_SAMPLE_U8, DEV_SAMPLE_F16, DEV_SAMPLE_BF16, DEV_SAMPLE_F32, dev_format, H264E_SCENECUT_DEFAULT,
     MATRIX_UNSPECIFIED, MATRIX_BT709, MATRIX_BT601,

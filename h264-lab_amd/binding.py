@@ -379,6 +379,10 @@ def load(path=None):
     L.H264E_clip_read_recon.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.H264E_clip_set_ssd_output.argtypes = [C.c_void_p, C.c_void_p]
     L.H264E_clip_set_ssd_output.restype = None
+    L.H264E_clip_set_ssim_output.argtypes = [C.c_void_p, C.c_void_p]
+    L.H264E_clip_quality_time.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
+    L.H264E_read_quality.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.H264E_ssim_planes.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.H264E_clip_set_denoise.argtypes = [C.c_void_p, C.c_int]
     L.H264E_clip_set_key_frames.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
     L.H264E_clip_set_scenecut.argtypes = [C.c_void_p, C.c_int]
@@ -414,6 +418,35 @@ def load(path=None):
 
 def _err(L, what):
     return H264EError("%s: %s" % (what, (L.H264E_last_error() or b"").decode()))
+
+
+def psnr_from_ssd(ssd, w, h):
+    """dB per plane from sums of squared differences [..., 3] (Y, U, V) of a w x h picture: 10 log10(255^2 samples / ssd), inf for 0"""
+    ssd = np.asarray(ssd, np.float64)
+    samples = np.array([w * h, (w // 2) * (h // 2), (w // 2) * (h // 2)], np.float64)
+    with np.errstate(divide="ignore"):
+        return np.where(ssd > 0, 10.0 * np.log10(255.0 * 255.0 * samples / np.where(ssd > 0, ssd, 1.0)), np.inf)
+
+
+def ssim_planes(a, b, device=None, lib=None):
+    """H264E_ssim_planes: the SSIM (8x8 windows in steps of 4, as x264 and ffmpeg's filter) of two 2-D uint8 planes of one shape in GPU
+    memory -- torch tensors (views with any row stride are fine, the last axis contiguous), objects with __cuda_array_interface__ --
+    by the encoder's own kernel.  Work queued on the tensors' streams is waited for first.  Returns a float."""
+    L = load(lib)
+    pa, sha, sta, stream_a = _dev_array(a)
+    pb, shb, stb, stream_b = _dev_array(b)
+    if sha is None or shb is None or len(sha) != 2 or tuple(sha) != tuple(shb) or sta[1] != 1 or stb[1] != 1:
+        raise H264EError("ssim_planes: two 2-D uint8 arrays of one shape whose last axis is contiguous, got shapes %r, %r strides %r, %r" % (sha, shb, sta, stb))
+    for st in (stream_a, stream_b):
+        if st is not None and hasattr(st, "synchronize"):
+            st.synchronize()
+    if device is None:
+        dev = getattr(a, "device", None)
+        device = dev.index if getattr(dev, "index", None) is not None else -1
+    out = C.c_double()
+    if L.H264E_ssim_planes(int(device), pa, sta[0], pb, stb[0], sha[1], sha[0], C.byref(out)):
+        raise _err(L, "H264E_ssim_planes")
+    return out.value
 
 
 class Encoder:
@@ -508,6 +541,16 @@ class Encoder:
             raise _err(self.L, "H264E_read_recon_device status %d" % st)
         return out
 
+    def read_quality(self, ssd=True, ssim=True):
+        """H264E_read_quality: the last call's input, as it lies in the encoder's input slot, against the reconstruction it left:
+        (ssd uint64 [3], ssim float64 [3]) for Y, U, V; a metric that was not asked for is None"""
+        d = np.zeros(3, np.uint64) if ssd else None
+        s = np.zeros(3, np.float64) if ssim else None
+        st = self.L.H264E_read_quality(self.persist, d.ctypes.data if ssd else None, s.ctypes.data if ssim else None)
+        if st:
+            raise _err(self.L, "H264E_read_quality status %d" % st)
+        return d, s
+
     def set_color(self, color):
         """H264E_set_color: how RGB / RGBP device input is converted and what every SPS signals ("bt709", "bt601", "bt709-full",
         "bt601-full" or a (matrix, full_range) pair; (0, 0) = the default); only before the first frame."""
@@ -542,9 +585,11 @@ class ClipEncoder:
 
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
                  clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0,
-                 color=None, fps=None):
+                 color=None, fps=None, quality=None):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
+        self._ssd = self._ssim = None           # the registered metric arrays [nframes][3], owned here while registered
+        self._q_frames = 0
         self.par = ClipParam(width, height, gop, qp, speed, 100000 // 8, device, max_chains, idr_state, (C.c_int32 * 2)(*clusters_in), slices, kbps, resident, keep_records)
         self.c = C.c_void_p()
         if self.L.H264E_clip_open(C.byref(self.c), C.byref(self.par), nframes):
@@ -560,9 +605,36 @@ class ClipEncoder:
                 self.set_color(color)
             if fps is not None:
                 self.set_frame_rate(fps)
+            if quality:
+                self.set_quality(**(quality if isinstance(quality, dict) else {}))
         except H264EError:
             self.close()
             raise
+
+    def set_quality(self, ssd=True, ssim=True):
+        """Per-frame metrics of the following encodes, computed on the device (H264E_clip_set_ssd_output / _set_ssim_output): sums of
+        squared differences and / or SSIM, input against reconstruction.  read_quality() hands out the last call's."""
+        self._ssd = np.zeros((self.n, 3), np.uint64) if ssd else None
+        self._ssim = np.zeros((self.n, 3), np.float64) if ssim else None
+        self.L.H264E_clip_set_ssd_output(self.c, self._ssd.ctypes.data if ssd else None)
+        if self.L.H264E_clip_set_ssim_output(self.c, self._ssim.ctypes.data if ssim else None):
+            self.L.H264E_clip_set_ssd_output(self.c, None)
+            self._ssd = self._ssim = None
+            raise _err(self.L, "H264E_clip_set_ssim_output")
+        self._q_frames = 0
+
+    def read_quality(self):
+        """(ssd uint64 [frames, 3], ssim float64 [frames, 3]) of the frames of the last encode() / encode_multi, Y, U, V; a metric that is
+        off is None"""
+        n = self._q_frames
+        return (self._ssd[:n].copy() if self._ssd is not None else None), (self._ssim[:n].copy() if self._ssim is not None else None)
+
+    def quality_time(self, enable=True):
+        """(HIP-event milliseconds inside the SSD launches, inside the SSIM launches, frames they covered) timed so far; switches the
+        timing of later encodes on or off"""
+        a, b, n = C.c_double(), C.c_double(), C.c_longlong()
+        self.L.H264E_clip_quality_time(self.c, int(bool(enable)), C.byref(a), C.byref(b), C.byref(n))
+        return a.value, b.value, n.value
 
     def set_denoise(self, on):
         """The temporal denoiser (H264E_clip_set_denoise): only while the clip stands at frame 0."""
@@ -656,6 +728,7 @@ class ClipEncoder:
         st = ClipStats()
         if self.L.H264E_clip_encode(self.c, out.ctypes.data, cap, C.byref(nb), sizes, int(profile), C.byref(st)):
             raise _err(self.L, "H264E_clip_encode")
+        self._q_frames = st.frames
         return out[: nb.value].tobytes(), list(sizes)[: st.frames], st
 
     @staticmethod
@@ -680,6 +753,8 @@ class ClipEncoder:
         fb = (C.POINTER(C.c_int) * n)(*[C.cast(s, C.POINTER(C.c_int)) for s in sizes])
         if L.H264E_clip_encode_multi(clips, n, outp, capa, nb, fb, sts):
             raise _err(L, "H264E_clip_encode_multi")
+        for i, e in enumerate(encoders):
+            e._q_frames = sts[i].frames
         return [(outs[i][: nb[i]].tobytes(), list(sizes[i])[: sts[i].frames], sts[i]) for i in range(n)]
 
     def revalidate(self, exact_in):
@@ -733,6 +808,10 @@ class ClipEncoder:
 
     def close(self):
         if self.c:
+            if self._ssd is not None or self._ssim is not None:     # the library must not keep pointers into arrays that go away
+                self.L.H264E_clip_set_ssd_output(self.c, None)
+                self.L.H264E_clip_set_ssim_output(self.c, None)
+                self._ssd = self._ssim = None
             self.L.H264E_clip_close(self.c)
             self.c = C.c_void_p()
 

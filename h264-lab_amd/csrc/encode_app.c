@@ -9,6 +9,8 @@
  * file name, default 352x288 (T:256-329, T:483-485); defaults gop 20, qp 33 (T:10-17); --maxframes only matters
  * when 0 (T:576); --kbps K -> desired_frame_bytes = K*1000/8/30, qp 10..50 (T:596-600); vbv_size_bytes = 12500
  * (T:524); --psnr makes const_input_flag 0 and prints the reference's PSNR line (T:331-405, T:521);
+ * --ssim (ours: the reference has none) adds ONE stdout line behind it, "SSIM Y=%.6f U=%.6f V=%.6f All=%.6f (%.2f db)": the means over the
+ * frames of the per-plane SSIM taken on the device, All = (4 Y + U + V) / 6, db = -10 log10(1 - All); it works on both paths and with --gpus;
  * stdout carries "sizeof_persist = %d sizeof_scratch = %d" and, with --stats, "frame=%d, bytes=%d" (T:568, T:650).
  * --threads N (T:34-111, T:163) = N row-band slices per frame, the bitstream of the reference built with -DH264E_MAX_THREADS
  * (no host threads are involved here: the slices are wavefronts of the same kernel launch).
@@ -37,7 +39,7 @@ static struct
 {
     char input_file[1024], output_file[1024], recon_file[1024];
     int have_input, have_output;
-    int gop, qp, kbps, max_frames, speed, stats, psnr, device, clip, chains, threads, gpus;
+    int gop, qp, kbps, max_frames, speed, stats, psnr, ssim, device, clip, chains, threads, gpus;
     int scenecut, nkey, key_frames[1024];   /* --scenecut threshold (0 = off), --keyframes list */
     int matrix, full_range, fps_num, fps_den;   /* --colour, --fps (all 0: nothing is signalled) */
     int unsupported;                    /* a reference option this encoder refuses was given: no stream is written, exit 1 */
@@ -105,6 +107,7 @@ static void parse_long(const char *p, const char *val)
     else if (starts("threads", p)) cmd.threads = atoi(v);       /* T:163-166: N row-band slices per frame (the reference's H264E_MAX_THREADS build) */
     else if (starts("stats", p)) cmd.stats = 1;
     else if (starts("psnr", p)) cmd.psnr = 1;
+    else if (starts("ssim", p)) cmd.ssim = 1;
     else if (starts("output", p)) { snprintf(cmd.output_file, sizeof(cmd.output_file), "%s", v); cmd.have_output = 1; }
     else if (starts("input", p)) { snprintf(cmd.input_file, sizeof(cmd.input_file), "%s", v); cmd.have_input = 1; }
     else if (starts("recon", p)) snprintf(cmd.recon_file, sizeof(cmd.recon_file), "%s", v);
@@ -147,7 +150,7 @@ static int read_cmdline(int argc, char **argv)
                "    4sif cif sif pal ntsc d1 16cif 16sif 720p 4SVGA 4XGA 16VGA 16VGA\n"
                "Options (every --option takes a value):\n"
                "    --input,  -i <f>  --output, -o <f>  --gop <n>  --qp <n>  --kbps <n>  --maxframes <n>\n"
-               "    --speed <n>  --threads <n>  --stats x  --psnr x  --device <n>  --clip 0|1  --chains <n>  --gpus <n>\n"
+               "    --speed <n>  --threads <n>  --stats x  --psnr x  --ssim x  --device <n>  --clip 0|1  --chains <n>  --gpus <n>\n"
                "    --keyframes f1,f2,...  --scenecut <threshold|x>   (clip path only)\n"
                "    --colour bt709|bt601|bt709-full|bt601-full  --fps <n[/d]>   (signalled in the SPS; the samples are not touched)\n");
         return 0;
@@ -215,6 +218,23 @@ static void psnr_print(void)                                                    
     printf("  %6.2f db/rate ", 10*log10((double)g_psnr.count[0]*g_psnr.count[0]*3/2*255*255/(g_psnr.noise[0]*g_psnr.bytes)));
     printf("  %6.3f db/lgrate ", db/log10(kbps));
     printf("  \n");
+}
+
+/* --ssim: the means over the frames of the per-plane SSIM the device computes (H264E_clip_set_ssim_output / H264E_read_quality), added in
+ * file order on both paths, so that both print the same line; All as ffmpeg reports it for 4:2:0 */
+static struct { double sum[3]; int frames; } g_ssim;
+
+static void ssim_add(const double *v)
+{
+    int k;
+    for (k = 0; k < 3; k++) g_ssim.sum[k] += v[k];
+    g_ssim.frames++;
+}
+
+static void ssim_print(void)
+{
+    const double n = g_ssim.frames ? g_ssim.frames : 1, y = g_ssim.sum[0]/n, u = g_ssim.sum[1]/n, v = g_ssim.sum[2]/n, all = (4*y + u + v)/6;
+    printf("SSIM Y=%.6f U=%.6f V=%.6f All=%.6f (%.2f db)\n", y, u, v, all, -10*log10(1 - all));
 }
 
 /*
@@ -312,6 +332,7 @@ typedef struct
     size_t *foff;                       /* [nframes + 1] byte offset of every frame in the shard's stream */
     int *fsize;                         /* [nframes] */
     uint64_t *ssd;                      /* [nframes][3] or NULL */
+    double *ssim;                       /* [nframes][3] or NULL */
     H264E_clip_t *clip;
     H264E_clip_param_t par;
     uint8_t *stage[2], *out;
@@ -341,7 +362,8 @@ static int shard_open(shard_t *s)
     s->fsize = (int *)calloc((size_t)n, sizeof(int));
     s->foff = (size_t *)calloc((size_t)n + 1, sizeof(size_t));
     if (cmd.psnr) s->ssd = (uint64_t *)calloc(3*(size_t)n, sizeof(uint64_t));
-    if (!s->stage[0] || !s->stage[1] || !s->out || !s->fsize || !s->foff || (cmd.psnr && !s->ssd)) { printf("ERROR: not enough memory\n"); return 1; }
+    if (cmd.ssim) s->ssim = (double *)calloc(3*(size_t)n, sizeof(double));
+    if (!s->stage[0] || !s->stage[1] || !s->out || !s->fsize || !s->foff || (cmd.psnr && !s->ssd) || (cmd.ssim && !s->ssim)) { printf("ERROR: not enough memory\n"); return 1; }
     if (H264E_clip_open(&s->clip, &s->par, n)) { printf("ERROR: %s\n", H264E_last_error()); return 1; }
     return 0;
 }
@@ -350,7 +372,7 @@ static void shard_close(shard_t *s)
 {
     if (s->clip) { (void)H264E_clip_upload_wait(s->clip); H264E_clip_close(s->clip); }
     H264E_clip_host_free(s->stage[0]); H264E_clip_host_free(s->stage[1]);
-    free(s->out); free(s->fsize); free(s->foff); free(s->ssd); free(s->mem);
+    free(s->out); free(s->fsize); free(s->foff); free(s->ssd); free(s->ssim); free(s->mem);
 }
 
 /* (re)encode frames [from, nframes) of the shard: reader thread -> staging buffers -> HBM ring -> clip encoder -> output */
@@ -362,10 +384,11 @@ static int shard_encode_from(shard_t *s, int from)
     pthread_t th;
     H264E_clip_stats_t st;
     uint64_t *ssd_tmp = s->ssd ? (uint64_t *)malloc(sizeof(uint64_t)*3*(size_t)s->nframes) : NULL;
+    double *ssim_tmp = s->ssim ? (double *)malloc(sizeof(double)*3*(size_t)s->nframes) : NULL;
     int *sizes = (int *)malloc(sizeof(int)*(size_t)s->nframes);
     int done = from, rc = 1, i;
     FILE *fin = fopen(cmd.input_file, "rb");
-    if (!fin || !sizes || (s->ssd && !ssd_tmp)) { printf("ERROR: cant open input file %s\n", cmd.input_file); return 1; }
+    if (!fin || !sizes || (s->ssd && !ssd_tmp) || (s->ssim && !ssim_tmp)) { printf("ERROR: cant open input file %s\n", cmd.input_file); return 1; }
     fseeko(fin, (off_t)fsz*(off_t)(s->file_first + from), SEEK_SET);
     memset(&fd, 0, sizeof(fd));
     fd.fin = fin; fd.fsz = fsz; fd.nframes = s->nframes - from; fd.base = from; fd.chunk = s->chunk;
@@ -396,6 +419,7 @@ static int shard_encode_from(shard_t *s, int from)
             continue;
         }
         if (ssd_tmp) H264E_clip_set_ssd_output(s->clip, ssd_tmp);
+        if (ssim_tmp && H264E_clip_set_ssim_output(s->clip, ssim_tmp)) { printf("ERROR: --ssim: %s\n", H264E_last_error()); goto out; }
         if (H264E_clip_encode(s->clip, s->out, s->out_cap, &nb, sizes, 0, &st)) { printf("ERROR: %s\n", H264E_last_error()); goto out; }
         if (s->fout) { if (nb && !fwrite(s->out, nb, 1, s->fout)) { printf("ERROR writing output file\n"); goto out; } }
         else
@@ -417,6 +441,7 @@ static int shard_encode_from(shard_t *s, int from)
             pos += (size_t)sizes[i];
             s->foff[f + 1] = s->mem_len + pos;
             if (ssd_tmp) memcpy(s->ssd + 3*(size_t)f, ssd_tmp + 3*(size_t)i, 3*sizeof(uint64_t));
+            if (ssim_tmp) memcpy(s->ssim + 3*(size_t)f, ssim_tmp + 3*(size_t)i, 3*sizeof(double));
         }
         s->mem_len += nb;
         done += st.frames; s->rounds += st.rounds; s->relaunches += st.reencoded_gops; s->enc_ms += st.encode_ms; s->chains = st.chains;
@@ -431,7 +456,8 @@ out:
     (void)H264E_clip_upload_wait(s->clip);
     H264E_clip_set_idle_hook(s->clip, NULL, NULL);
     fclose(fin);
-    free(sizes); free(ssd_tmp);
+    (void)H264E_clip_set_ssim_output(s->clip, NULL);
+    free(sizes); free(ssd_tmp); free(ssim_tmp);
     return rc;
 }
 
@@ -524,9 +550,11 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
                 g_psnr.frames++;
                 g_psnr.bytes += sh[k].fsize[i];
             }
+            if (sh[k].ssim) ssim_add(sh[k].ssim + 3*(size_t)i);
         }
     }
     if (cmd.psnr) psnr_print();
+    if (cmd.ssim) ssim_print();
     if (cmd.scenecut)
     {
         uint8_t *cut = (uint8_t *)calloc((size_t)n, 1);
@@ -643,8 +671,15 @@ int main(int argc, char **argv)
         if (cmd.stats) printf("frame=%d, bytes=%d\n", frames++, sizeof_coded_data);
         if (!fwrite(coded_data, (size_t)sizeof_coded_data, 1, fout)) { printf("ERROR writing output file\n"); break; }
         if (cmd.psnr) psnr_add(buf_save, buf_in, w, h, sizeof_coded_data);
+        if (cmd.ssim)
+        {
+            double v[3];
+            if (H264E_read_quality(enc, NULL, v)) { printf("ERROR: --ssim: %s\n", H264E_last_error()); return 1; }
+            ssim_add(v);
+        }
     }
     if (cmd.psnr) psnr_print();
+    if (cmd.ssim) ssim_print();
     H264E_close(enc);
     free(enc); free(scratch); free(buf_in); free(buf_save);
     fclose(fin); fclose(fout);

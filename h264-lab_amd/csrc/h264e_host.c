@@ -875,6 +875,8 @@ static int encode_frame(H264E_persist_t *p, H264E_scratch_t *scratch, const H264
         if (opt->nalu_callback) opt->nalu_callback(out + out_pos + 4, (int)(w - 4), opt->nalu_callback_token);
         out_pos += w;
         res.all_skipped = 1;
+        /* nothing is encoded, but the call's input still goes into the slot: H264E_read_quality compares it with the unchanged picture */
+        if (!den && put_frame(m->pool, in, dev, win)) return H264E_STATUS_BAD_ARGUMENT;
     } else
     {
     if (!den && put_frame(m->pool, in, dev, win)) return H264E_STATUS_BAD_ARGUMENT;
@@ -962,6 +964,36 @@ int H264E_read_recon_device(H264E_persist_t *p, const H264E_dev_frame_t *dst)
                                                                                                                                      : H264E_STATUS_SUCCESS;
 }
 
+/* Quality of the last frame: the call's input as it lies in the pool's input slot against the picture H264E_read_recon_device reads */
+int H264E_read_quality(H264E_persist_t *p, uint64_t ssd[3], double ssim[3])
+{
+    henc_t *e = (henc_t *)p;
+    impl_t mm;
+    g_host_err[0] = 0;
+    if (!impl_of(e, &mm)) return H264E_STATUS_BAD_ARGUMENT;
+    if (!ssd && !ssim) { snprintf(g_host_err, sizeof(g_host_err), "H264E_read_quality: both outputs are NULL"); return H264E_STATUS_BAD_ARGUMENT; }
+    if (!e->have_recon)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "H264E_read_quality: no frame has been encoded yet");
+        return H264E_STATUS_BAD_ARGUMENT;
+    }
+    return h264e_hip_quality_last(mm.pool, 0, ssd, ssim) ? H264E_STATUS_BAD_ARGUMENT : H264E_STATUS_SUCCESS;
+}
+
+/* The same SSIM for any pair of 8-bit planes in device memory (h264e_hip_ssim_planes).  The launch needs a stream and the partials
+ * buffer of a pool: a one-slot 16 x 16 pool lives for the length of the call (nothing stays behind that would hold the device's process
+ * guard); an application with many pairs to compare pays that once per call. */
+int H264E_ssim_planes(int device, const void *a, int a_stride, const void *b, int b_stride, int width, int height, double *ssim)
+{
+    h264e_hip_pool_t *pool = NULL;
+    int rc;
+    g_host_err[0] = 0;
+    if (h264e_hip_pool_create(&pool, device < 0 ? pick_device() : device, 16, 16, 1, 1)) return -1;
+    rc = h264e_hip_ssim_planes(pool, a, a_stride, b, b_stride, width, height, ssim);
+    h264e_hip_pool_destroy(pool);
+    return rc;
+}
+
 void *H264E_dev_malloc(int device, size_t bytes) { g_host_err[0] = 0; return h264e_hip_dev_malloc(device, bytes); }
 void H264E_dev_free(void *p) { h264e_hip_dev_free(p); }
 int H264E_dev_memcpy(void *dst, const void *src, size_t bytes, int to_device) { g_host_err[0] = 0; return h264e_hip_dev_memcpy(dst, src, bytes, to_device); }
@@ -1013,6 +1045,7 @@ struct H264E_clip_tag
     int32_t (*used_store)[2];               /* [nframes] frame-constant candidates it was given ... */
     int32_t **permb_store;                  /* [nframes] ... or the per-macroblock trajectory it was given */
     uint64_t *ssd_out;                      /* optional: [3] sums of squared differences input vs reconstruction per encoded frame of a call */
+    double *ssim_out;                       /* optional: [3] SSIM values of the same pairs, indexed the same way (H264E_clip_set_ssim_output) */
     int recon_floor;                        /* rate control: frames below this one may have been overwritten by hedge leaves (H264E_clip_read_recon) */
     int32_t *traj;                          /* scratch: walked trajectory [nmb][2] */
     uint8_t *big; size_t big_cap;           /* scratch: NALs of a frame that did not fit the host mirror */
@@ -1381,6 +1414,27 @@ int H264E_clip_output_time(H264E_clip_t *c, int enable, double *kernel_ms, long 
 /* [3] sums of squared differences (Y, U, V; input vs reconstruction) per frame encoded by the following H264E_clip_encode calls,
  * computed on the device (encode_app --psnr); NULL switches it off */
 void H264E_clip_set_ssd_output(H264E_clip_t *c, uint64_t *ssd) { if (c) c->ssd_out = ssd; }
+
+/* ... and [3] SSIM values per frame (enc_ssim.h), filled next to the sums in clip_settle; NULL switches it off */
+int H264E_clip_set_ssim_output(H264E_clip_t *c, double *ssim)
+{
+    g_host_err[0] = 0;
+    if (!c) { snprintf(g_host_err, sizeof(g_host_err), "H264E_clip_set_ssim_output: null clip"); return -1; }
+    if (ssim && (c->seq.width < 16 || c->seq.height < 16))
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "H264E_clip_set_ssim_output: a %d x %d picture has a chroma plane without an 8 x 8 window: SSIM needs 16 x 16 at least", c->seq.width, c->seq.height);
+        return -1;
+    }
+    c->ssim_out = ssim;
+    return 0;
+}
+
+/* diagnostic: HIP-event time of the SSD and SSIM launches made while `enable` was set (tools/quality_probe.py) */
+int H264E_clip_quality_time(H264E_clip_t *c, int enable, double *ssd_ms, double *ssim_ms, long long *frames)
+{
+    if (!c) return -1;
+    return h264e_hip_quality_time(c->pool, enable, ssd_ms, ssim_ms, frames);
+}
 
 /*
  * GOP sharding of ONE stream: a shard that started from a SPECULATED mv_clusters state is checked once the
@@ -1915,6 +1969,7 @@ static int clip_settle(H264E_clip_t *c, clip_call_t *x, const clip_launch_t *l)
     x->stats.encode_ms += now_ms() - l->t_submit;
     /* device-side sums of squared differences of the frames just validated: their pictures are still in their slots */
     if (c->ssd_out && nvalid && h264e_hip_ssd_frames(c->pool, nvalid, n % c->resident, c->resident, n % K, K, c->ssd_out + 3*(size_t)(n - x->first))) return -1;
+    if (c->ssim_out && nvalid && h264e_hip_ssim_frames(c->pool, nvalid, n % c->resident, c->resident, n % K, K, c->ssim_out + 3*(size_t)(n - x->first))) return -1;
     c->next = n + nvalid;
     if (l->after_stop && nvalid) { x->stats.relaunches_timed++; x->stats.first_frame_ms_after_relaunch += l->t_first - l->t_submit; }
     c->stopped_before = nvalid < l->F && l->step != CLIP_STOP_FULL;

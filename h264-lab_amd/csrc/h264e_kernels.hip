@@ -34,6 +34,7 @@
 #include "enc_scale.h"
 #include "enc_scale_rgb.h"
 #include "enc_scenecut.h"
+#include "enc_ssim.h"
 #include "../../include/h264e_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -680,6 +681,40 @@ __global__ void h264e_ssd_kernel(const uint8_t *clip, size_t frame_bytes, int wi
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(out + 3*i + pl, s);
 }
 
+/* structural similarity (enc_ssim.h): grid.x = tile of SSIM_TW x SSIM_TW windows, grid.y = frame, grid.z = plane.  Block sums into LDS, one
+ * window per lane, the tile's values added by a tree over the lane index: one float64 partial per workgroup, no atomics.  PLANES = 3 (the
+ * frames of a clip, or the last frame of an encoder) or 1 (a plane pair).  Templates, like the float kernels: the compiler emits them behind
+ * every kernel the project had, whose places in the code object therefore stay what they were. */
+template <int PLANES> __global__ void __launch_bounds__(256) h264e_ssim_kernel(h264e_ssim_args_t A)
+{
+    __shared__ __attribute__((aligned(16))) SsimLds lds;
+    LDS_AS SsimLds *L = (LDS_AS SsimLds *)&lds;
+    const int t = (int)threadIdx.x, i = (int)blockIdx.y, pl = (int)blockIdx.z;
+    const ssim_plane_t P = ssim_plane(A, i, pl);
+    const int ntx = ssim_tiles(P.bw - 1), nty = ssim_tiles(P.bh - 1);
+    if ((int)blockIdx.x >= ntx*nty) return;                 /* chroma planes have fewer tiles (uniform per workgroup) */
+    const int ty = (int)blockIdx.x/ntx, tx = (int)blockIdx.x - ty*ntx;
+    ssim_block(L, P, tx, ty, t);
+    __syncthreads();
+    ssim_window(L, P, tx, ty, t);
+    __syncthreads();
+    for (int s = 128; s; s >>= 1) { ssim_reduce(L->red, t, s); __syncthreads(); }
+    if (t == 0) ssim_store((GLOBAL_AS double *)A.partial + ((size_t)i*PLANES + pl)*(size_t)A.max_tiles + blockIdx.x, L->red[0]);
+}
+
+/* ... its second launch: grid.x = frame, grid.y = plane; the partials in tile order (lane t: t, t + 256, ...), the same tree, the mean */
+template <int PLANES> __global__ void __launch_bounds__(256) h264e_ssim_mean_kernel(h264e_ssim_args_t A)
+{
+    __shared__ double red[256];
+    const int t = (int)threadIdx.x, i = (int)blockIdx.x, pl = (int)blockIdx.y;
+    const ssim_plane_t P = ssim_plane(A, i, pl);
+    const int ntiles = ssim_tiles(P.bw - 1)*ssim_tiles(P.bh - 1);
+    ssim_gather((LDS_AS double *)red, (const GLOBAL_AS double *)A.partial + ((size_t)i*PLANES + pl)*(size_t)A.max_tiles, ntiles, t);
+    __syncthreads();
+    for (int s = 128; s; s >>= 1) { ssim_reduce((LDS_AS double *)red, t, s); __syncthreads(); }
+    if (t == 0) ssim_store((GLOBAL_AS double *)A.out + (size_t)i*PLANES + pl, red[0]/((double)(P.bw - 1)*(double)(P.bh - 1)));
+}
+
 /* the temporal denoiser over one packed I420 frame (width x height): grid.z = plane, grid.y = row, grid.x * 256 lanes x 4 samples along
  * the row; the gain table is staged in LDS.  in / prev / out are separate frames (no inter-workgroup traffic). */
 __global__ void __launch_bounds__(256) h264e_denoise_kernel(const uint8_t *in, const uint8_t *prev, uint8_t *out, int width, int height)
@@ -902,6 +937,19 @@ static void bk_launch_scenecut(const uint8_t *luma, uint32_t nbytes, int *record
 static void bk_launch_stage_selftest(int stage, const uint8_t *in, const int *args, uint8_t *out, hipStream_t st)
 {
     hipLaunchKernelGGL(h264e_stage_selftest_kernel, dim3(1), dim3(64), 0, st, stage, in, args, out);
+}
+/* n frames x planes (3, or 1 for a plane pair) in one launch, then the means */
+static void bk_launch_ssim(const h264e_ssim_args_t &A, int n, int planes, hipStream_t st)
+{
+    if (planes == 3)
+    {
+        hipLaunchKernelGGL(h264e_ssim_kernel<3>, dim3((unsigned)A.max_tiles, (unsigned)n, 3), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(h264e_ssim_mean_kernel<3>, dim3((unsigned)n, 3), dim3(256), 0, st, A);
+    } else
+    {
+        hipLaunchKernelGGL(h264e_ssim_kernel<1>, dim3((unsigned)A.max_tiles, (unsigned)n, 1), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(h264e_ssim_mean_kernel<1>, dim3((unsigned)n, 1), dim3(256), 0, st, A);
+    }
 }
 
 #include "h264e_pool.h"

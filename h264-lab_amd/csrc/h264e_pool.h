@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb and bk_launch_scenecut; the emulation's versions of those six are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut and bk_launch_ssim; the emulation's versions of those seven are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -17,6 +17,7 @@
 #include "enc_scale.h"
 #include "enc_scale_rgb.h"
 #include "enc_scenecut.h"
+#include "enc_ssim.h"
 
 /* The matrix rows (tests/color_model.py): Kr / Kb scaled by 219/255 and 224/255 (limited) or 1 (full), times 256,
  * rounded; one coefficient per row moved by 1 so that luma sums to 220 or 256 and chroma to 0 -- grey stays neutral.  Full-range chroma:
@@ -185,6 +186,11 @@ struct h264e_hip_pool
     h264e_icolor_t icm;                  /* the YCbCr -> RGB matrix of the RGB / RGBP egress launches: the inverse of cm (h264e_hip_set_color) */
     hipEvent_t ev_out[2];                /* h264e_hip_egress_time: around each egress launch while the timing is on */
     int out_timed; double out_ms; long long out_calls;
+    /* quality metrics (h264e_hip_ssim_frames / _ssim_planes / _quality_last): one allocation that appears with the first use -- a one-entry
+     * picture descriptor (quality_last), then the SSIM results and tile partials, qual_doubles of them */
+    uint8_t *qual_dev; size_t qual_doubles;
+    hipEvent_t ev_q[2];                  /* h264e_hip_quality_time: around the SSD launch / the SSIM launches of a call while the timing is on */
+    int q_timed; double q_ssd_ms, q_ssim_ms; long long q_frames, q_ssd_frames;
     h264e_chain_dev_t *chains_host;      /* host mirror of the device descriptors */
     h264e_chain_dev_t *chains_dev;
     h264e_frame_task_t *tasks_dev;       /* ring of TASK_RING task arrays */
@@ -296,8 +302,10 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     dev_free(p->heap);
     dev_free(p->den);
     dev_free(p->sc_rec);
+    dev_free(p->qual_dev);
     if (p->stream)
     {
+        (void)hipEventDestroy(p->ev_q[0]); (void)hipEventDestroy(p->ev_q[1]);
         for (int i = 0; i < TASK_RING; i++) for (int k = 0; k < 3; k++) (void)hipEventDestroy(p->ev[i][k]);
         (void)hipEventDestroy(p->ev_t0); (void)hipEventDestroy(p->ev_t1); (void)hipEventDestroy(p->ev_prep); (void)hipEventDestroy(p->ev_copy);
         (void)hipEventDestroy(p->ev_ingest[0]); (void)hipEventDestroy(p->ev_ingest[1]); (void)hipEventDestroy(p->ev_in[0]); (void)hipEventDestroy(p->ev_in[1]);
@@ -456,6 +464,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     (void)hipEventCreate(&p->ev_ingest[0]); (void)hipEventCreate(&p->ev_ingest[1]); (void)hipEventCreate(&p->ev_in[0]); (void)hipEventCreate(&p->ev_in[1]);
     (void)hipEventCreate(&p->ev_out[0]); (void)hipEventCreate(&p->ev_out[1]);
     (void)hipEventCreate(&p->ev_sc[0]); (void)hipEventCreate(&p->ev_sc[1]);
+    (void)hipEventCreate(&p->ev_q[0]); (void)hipEventCreate(&p->ev_q[1]);
     p->chains_host = (h264e_chain_dev_t *)calloc((size_t)nchains, sizeof(h264e_chain_dev_t));
     p->clu_dev = (int32_t **)calloc((size_t)nchains, sizeof(int32_t *));
     p->ref_sel = (int *)calloc((size_t)nchains, sizeof(int));
@@ -602,17 +611,31 @@ extern "C" void h264e_hip_host_free(void *q)
 }
 
 
+/* the launch against the pictures `chains` describes (the pool's own, or h264e_hip_quality_last's one-entry descriptor) */
+static int ssd_run(h264e_hip_pool_t *p, int n, int in0, int in_mod, const h264e_chain_dev_t *chains, int pic0, int pic_mod, uint64_t *out)
+{
+    const h264e_geom_t &G = p->G;
+    HIPCHK(hipMemsetAsync(p->ssd_dev, 0, sizeof(unsigned long long)*3*(size_t)n, p->stream));
+    if (p->q_timed) HIPCHK(hipEventRecord(p->ev_q[0], p->stream));
+    bk_launch_ssd(n, (const uint8_t *)p->clip, p->frame_bytes, G.width, G.height, in0, in_mod, chains, pic0, pic_mod, G.W, p->ssd_dev, p->stream);
+    HIPCHK(hipGetLastError());
+    if (p->q_timed) HIPCHK(hipEventRecord(p->ev_q[1], p->stream));
+    HIPCHK(hipMemcpyAsync(out, p->ssd_dev, sizeof(unsigned long long)*3*(size_t)n, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (p->q_timed)
+    {
+        float f = 0;
+        HIPCHK(hipEventElapsedTime(&f, p->ev_q[0], p->ev_q[1]));
+        p->q_ssd_ms += f; p->q_ssd_frames += n;
+    }
+    return 0;
+}
+
 extern "C" int h264e_hip_ssd_frames(h264e_hip_pool_t *p, int n, int in0, int in_mod, int pic0, int pic_mod, uint64_t *out)
 {
     if (!p || !out || n <= 0 || n > p->nchains || in_mod <= 0 || in_mod > p->frames_resident || pic_mod <= 0 || pic_mod > p->nchains) FAIL("ssd_frames: bad argument");
-    const h264e_geom_t &G = p->G;
     HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemsetAsync(p->ssd_dev, 0, sizeof(unsigned long long)*3*(size_t)n, p->stream));
-    bk_launch_ssd(n, (const uint8_t *)p->clip, p->frame_bytes, G.width, G.height, in0, in_mod, (const h264e_chain_dev_t *)p->chains_dev, pic0, pic_mod, G.W, p->ssd_dev, p->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, p->ssd_dev, sizeof(unsigned long long)*3*(size_t)n, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    return 0;
+    return ssd_run(p, n, in0, in_mod, (const h264e_chain_dev_t *)p->chains_dev, pic0, pic_mod, out);
 }
 
 /* ---- temporal denoiser (enc_denoise.h): one h264e_denoise_kernel launch per frame on the pool's stream, in stream order */
@@ -1153,6 +1176,157 @@ extern "C" int h264e_hip_copy_timer_stop(h264e_hip_pool_t *p, double *ms)
 }
 
 /* plain device memory for callers without a HIP toolchain of their own (H264E_dev_malloc / _free / _memcpy) */
+/* ---- structural similarity (enc_ssim.h): h264e_ssim_kernel + h264e_ssim_mean_kernel on the pool's stream, all frames and planes of a call
+ * in one pair of launches */
+
+#ifdef H264E_EMU
+#ifdef H264E_EMU_REVERSE
+#define EMU_LANES256(t) for (int t = 255; t >= 0; --t)
+#else
+#define EMU_LANES256(t) for (int t = 0; t < 256; ++t)
+#endif
+/* the emulation's launch: tile by tile, each of the kernel's steps as a lane loop over the tile's LDS, then the second kernel's per plane */
+static void bk_launch_ssim(const h264e_ssim_args_t &A, int n, int planes, hipStream_t)
+{
+    SsimLds *L = (SsimLds *)malloc(sizeof(SsimLds));
+    if (!L) return;
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < n; i++)
+            for (int pl = 0; pl < planes; pl++)
+            {
+                const ssim_plane_t P = ssim_plane(A, i, pl);
+                const int ntx = ssim_tiles(P.bw - 1), nty = ssim_tiles(P.bh - 1);
+                double *partial = A.partial + ((size_t)i*planes + pl)*(size_t)A.max_tiles;
+                for (int k = 0; k < (pass ? 1 : ntx*nty); k++)
+                {
+                    memset(L, 0xEE, sizeof(*L));
+                    if (!pass)
+                    {
+                        EMU_LANES256(t) ssim_block(L, P, k % ntx, k/ntx, t);
+                        EMU_LANES256(t) ssim_window(L, P, k % ntx, k/ntx, t);
+                    } else EMU_LANES256(t) ssim_gather(L->red, partial, ntx*nty, t);
+                    for (int s = 128; s; s >>= 1) EMU_LANES256(t) ssim_reduce(L->red, t, s);
+                    if (!pass) ssim_store(partial + k, L->red[0]);
+                    else ssim_store(A.out + (size_t)i*planes + pl, L->red[0]/((double)(P.bw - 1)*(double)(P.bh - 1)));
+                }
+            }
+    free(L);
+}
+#endif
+
+#define QUAL_HEAD 512                   /* bytes in front of the doubles: h264e_hip_quality_last's picture descriptor */
+#define SSIM_MAX_DIM 32768
+static int qual_reserve(h264e_hip_pool_t *p, size_t doubles)
+{
+    static_assert(sizeof(h264e_chain_dev_t) <= QUAL_HEAD, "the descriptor fits the head of the quality buffer");
+    if (p->qual_dev && p->qual_doubles >= doubles) return 0;
+    HIPCHK(hipStreamSynchronize(p->stream));
+    dev_free(p->qual_dev);
+    p->qual_dev = 0; p->qual_doubles = 0;
+    if (dev_malloc((void **)&p->qual_dev, QUAL_HEAD + sizeof(double)*doubles)) { p->qual_dev = 0; FAIL("quality: device allocation failed (%zu bytes)", QUAL_HEAD + sizeof(double)*doubles); }
+    p->qual_doubles = doubles;
+    return 0;
+}
+static int ssim_max_tiles(int w, int h) { return ssim_tiles((w >> 2) - 1)*ssim_tiles((h >> 2) - 1); }
+
+/* both launches for n x planes pairs (A: everything but the buffers), the values to the host; complete on return */
+static int ssim_run(h264e_hip_pool_t *p, h264e_ssim_args_t &A, int n, int planes, double *out)
+{
+    const size_t nres = (size_t)n*(size_t)planes;
+    A.out = (double *)(p->qual_dev + QUAL_HEAD);
+    A.partial = A.out + nres;
+    if (p->q_timed) HIPCHK(hipEventRecord(p->ev_q[0], p->stream));
+    bk_launch_ssim(A, n, planes, p->stream);
+    HIPCHK(hipGetLastError());
+    if (p->q_timed) HIPCHK(hipEventRecord(p->ev_q[1], p->stream));
+    HIPCHK(hipMemcpyAsync(out, A.out, sizeof(double)*nres, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (p->q_timed)
+    {
+        float f = 0;
+        HIPCHK(hipEventElapsedTime(&f, p->ev_q[0], p->ev_q[1]));
+        p->q_ssim_ms += f; p->q_frames += n;
+    }
+    return 0;
+}
+
+/* frames of the pool's picture size: the input slots against the first pictures of `chains` */
+static int ssim_frames_run(h264e_hip_pool_t *p, const char *who, int n, int cap, int in0, int in_mod, const h264e_chain_dev_t *chains, int pic0, int pic_mod, double *out)
+{
+    const h264e_geom_t &G = p->G;
+    h264e_ssim_args_t A;
+    if (G.width < 2*SSIM_MIN_DIM || G.height < 2*SSIM_MIN_DIM)
+        FAIL("%s: a %d x %d picture has a chroma plane without an 8 x 8 window: SSIM needs 16 x 16 at least", who, G.width, G.height);
+    memset(&A, 0, sizeof(A));
+    A.a = p->clip; A.frame_bytes = p->frame_bytes; A.in0 = in0; A.in_mod = in_mod;
+    A.chains = chains; A.pic0 = pic0; A.pic_mod = pic_mod;
+    A.width = G.width; A.height = G.height; A.W = G.W;
+    A.max_tiles = ssim_max_tiles(G.width, G.height);
+    if (qual_reserve(p, 3*(size_t)cap*(1 + (size_t)A.max_tiles))) return -1;
+    return ssim_run(p, A, n, 3, out);
+}
+
+extern "C" int h264e_hip_ssim_frames(h264e_hip_pool_t *p, int n, int in0, int in_mod, int pic0, int pic_mod, double *out)
+{
+    if (!p || !out || n <= 0 || n > p->nchains || in_mod <= 0 || in_mod > p->frames_resident || pic_mod <= 0 || pic_mod > p->nchains) FAIL("ssim_frames: bad argument");
+    HIPCHK(hipSetDevice(p->device));
+    return ssim_frames_run(p, "ssim_frames", n, p->nchains, in0, in_mod, (const h264e_chain_dev_t *)p->chains_dev, pic0, pic_mod, out);
+}
+
+extern "C" int h264e_hip_ssim_planes(h264e_hip_pool_t *p, const void *a, int a_stride, const void *b, int b_stride, int w, int h, double *out)
+{
+    h264e_ssim_args_t A;
+    if (!p || !a || !b || !out) FAIL("ssim_planes: null argument");
+    if (w < SSIM_MIN_DIM || w > SSIM_MAX_DIM) FAIL("ssim_planes: width %d (%d to %d: one 8 x 8 window at least)", w, SSIM_MIN_DIM, SSIM_MAX_DIM);
+    if (h < SSIM_MIN_DIM || h > SSIM_MAX_DIM) FAIL("ssim_planes: height %d (%d to %d: one 8 x 8 window at least)", h, SSIM_MIN_DIM, SSIM_MAX_DIM);
+    if (a_stride < w) FAIL("ssim_planes: stride %d of plane a is below its %d row bytes", a_stride, w);
+    if (b_stride < w) FAIL("ssim_planes: stride %d of plane b is below its %d row bytes", b_stride, w);
+    HIPCHK(hipSetDevice(p->device));
+#ifndef H264E_EMU
+    if (!ingest_is_device_memory(p, a, (size_t)(h - 1)*(size_t)a_stride + (size_t)w))
+        FAIL("ssim_planes: plane a (%p, %d rows %d bytes apart) is not memory of device %d, or not inside one allocation", a, h, a_stride, p->device);
+    if (!ingest_is_device_memory(p, b, (size_t)(h - 1)*(size_t)b_stride + (size_t)w))
+        FAIL("ssim_planes: plane b (%p, %d rows %d bytes apart) is not memory of device %d, or not inside one allocation", b, h, b_stride, p->device);
+#endif
+    memset(&A, 0, sizeof(A));
+    A.a = (const uint8_t *)a; A.b = (const uint8_t *)b; A.a_stride = a_stride; A.b_stride = b_stride;
+    A.width = w; A.height = h; A.W = w;
+    A.max_tiles = ssim_max_tiles(w, h);
+    if (qual_reserve(p, 1 + (size_t)A.max_tiles)) return -1;
+    return ssim_run(p, A, 1, 1, out);
+}
+
+/* frame at a time: input slot 0 against the picture h264e_hip_read_recon / h264e_hip_egress_last read, through a one-entry descriptor whose
+ * first picture it is, so that both kernels see the pair the way a stream pool hands it over */
+extern "C" int h264e_hip_quality_last(h264e_hip_pool_t *p, int chain, uint64_t ssd[3], double ssim[3])
+{
+    if (!p) FAIL("quality_last: null pool");
+    if (chain < 0 || chain >= p->nchains) FAIL("quality_last: chain %d outside the pool's %d", chain, p->nchains);
+    if (!ssd && !ssim) FAIL("quality_last: both outputs are NULL");
+    if (ssim && (p->G.width < 2*SSIM_MIN_DIM || p->G.height < 2*SSIM_MIN_DIM))
+        FAIL("quality_last: a %d x %d picture has a chroma plane without an 8 x 8 window: SSIM needs 16 x 16 at least", p->G.width, p->G.height);
+    HIPCHK(hipSetDevice(p->device));
+    if (qual_reserve(p, ssim ? 3*(1 + (size_t)ssim_max_tiles(p->G.width, p->G.height)) : 1)) return -1;
+    h264e_chain_dev_t d = p->chains_host[chain];
+    for (int pl = 0; pl < 3; pl++) d.rec[0][pl] = d.rec[p->ref_sel[chain]][pl];
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipMemcpy(p->qual_dev, &d, sizeof(d), hipMemcpyHostToDevice));
+    if (ssd && ssd_run(p, 1, 0, 1, (const h264e_chain_dev_t *)p->qual_dev, 0, 1, ssd)) return -1;
+    if (ssim && ssim_frames_run(p, "quality_last", 1, 1, 0, 1, (const h264e_chain_dev_t *)p->qual_dev, 0, 1, ssim)) return -1;
+    return 0;
+}
+
+/* HIP-event time of the SSD and SSIM launches made while `enable` was set: the totals since the pool was created (the probe) */
+extern "C" int h264e_hip_quality_time(h264e_hip_pool_t *p, int enable, double *ssd_ms, double *ssim_ms, long long *frames)
+{
+    if (!p) FAIL("quality_time: null pool");
+    p->q_timed = enable != 0;
+    if (ssd_ms) *ssd_ms = p->q_ssd_ms;
+    if (ssim_ms) *ssim_ms = p->q_ssim_ms;
+    if (frames) *frames = p->q_frames > p->q_ssd_frames ? p->q_frames : p->q_ssd_frames;      /* both cover the same frames when both are on */
+    return 0;
+}
+
 extern "C" void *h264e_hip_dev_malloc(int device, size_t bytes)
 {
     void *q = 0;

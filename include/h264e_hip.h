@@ -215,6 +215,22 @@ int  h264e_hip_egress_time(h264e_hip_pool_t *pool, int enable, double *ms, long 
 /* sums of squared differences between resident input frames and stream pictures, one small kernel per call: frame i uses input
  * slot (in0 + i) % in_mod and picture slot (pic0 + i) % pic_mod; out = host [n][3] (Y, U, V), picture size width x height */
 int  h264e_hip_ssd_frames(h264e_hip_pool_t *pool, int n, int in0, int in_mod, int pic0, int pic_mod, uint64_t *out);
+/* Structural similarity (enc_ssim.h: 8x8 windows in steps of 4, the SSIM of x264 and of ffmpeg's filter, per plane) of the same pairs of
+ * pictures, with h264e_hip_ssd_frames' arguments and checks: out = host [n][3] (Y, U, V), each the mean over its plane's windows.  Two
+ * launches on the pool's stream (tile partials, then their sums in tile order: no atomics, the values do not depend on scheduling),
+ * complete on return.  A picture below 16 x 16 has a chroma plane without a window and is refused, with the size in the message.  The
+ * partials and results buffer is allocated with the first call.
+ * _planes: ONE pair of 8-bit planes of w x h samples in device memory (rows a_stride / b_stride bytes apart, any addresses) through the same
+ * kernel; out = host [1].  Refused without a launch, with the value in the message: NULL, w or h below 8, a stride below w, and memory
+ * that the runtime does not report as one allocation of the pool's device.  The caller has synchronised whatever wrote the planes.
+ * _quality_last: for a pool that encodes frame at a time -- input slot 0 against the picture h264e_hip_egress_last reads for `chain`: the sums of
+ * squared differences into ssd[3], the SSIM into ssim[3]; either may be NULL (SSIM: 16 x 16 at least).
+ * _quality_time: enable != 0 times the later SSD and SSIM launches with HIP events; the totals since the pool was created, and the frames
+ * they covered (tools/quality_probe.py). */
+int  h264e_hip_ssim_frames(h264e_hip_pool_t *pool, int n, int in0, int in_mod, int pic0, int pic_mod, double *out);
+int  h264e_hip_ssim_planes(h264e_hip_pool_t *pool, const void *a, int a_stride, const void *b, int b_stride, int w, int h, double *out);
+int  h264e_hip_quality_last(h264e_hip_pool_t *pool, int chain, uint64_t ssd[3], double ssim[3]);
+int  h264e_hip_quality_time(h264e_hip_pool_t *pool, int enable, double *ssd_ms, double *ssim_ms, long long *frames);
 /* drop the chain's last submitted frame (stream_mode = 0): undo the reference/reconstruction swap, so the frame can be
  * submitted again (re-encode path) */
 int  h264e_hip_rewind_frame(h264e_hip_pool_t *pool, int chain);

@@ -350,6 +350,25 @@ int  H264E_clip_read_recon_device(H264E_clip_t *clip, int frame, const H264E_dev
 int  H264E_clip_output_time(H264E_clip_t *clip, int enable, double *kernel_ms, long long *frames);
 /* per encoded frame [3] sums of squared differences input vs reconstruction (Y, U, V), computed on the device: encode_app --psnr */
 void H264E_clip_set_ssd_output(H264E_clip_t *clip, uint64_t *ssd);
+/* ... and [3] SSIM values (Y, U, V), indexed like the SSD output: the 8x8-window, step-4 SSIM of x264 and of ffmpeg's `ssim` filter, per
+ * plane of the PICTURE (cropped size), the mean over the plane's windows, computed on the device with a fixed order of the sum (two runs
+ * give the same doubles); ffmpeg's "All" is (4 Y + U + V) / 6.  Both metrics compare the RAW input with the reconstruction, also with the
+ * denoiser on.  NULL switches it off.  -1, with the size named in H264E_last_error, for a picture below 16 x 16 (a chroma plane without
+ * a window). */
+int  H264E_clip_set_ssim_output(H264E_clip_t *clip, double *ssim);
+/* diagnostic: enable != 0 times the SSD and SSIM launches of later calls with HIP events; the totals since open and the frames they
+ * covered (tools/quality_probe.py) */
+int  H264E_clip_quality_time(H264E_clip_t *clip, int enable, double *ssd_ms, double *ssim_ms, long long *frames);
+/* frame at a time: after a successful H264E_encode / H264E_encode_device / H264E_encode_device_scaled, that call's input as it lies in the
+ * encoder's input slot (host or device input, either const_input_flag) against the reconstruction it left: the sums of squared differences
+ * into ssd[3] and the SSIM into ssim[3] (Y, U, V); either may be NULL.  After a transparent VBV-overflow frame the reconstruction is the
+ * unchanged picture, which is what a decoder shows.  H264E_STATUS_BAD_ARGUMENT, with H264E_last_error saying why: before the first frame,
+ * both pointers NULL, SSIM for a picture below 16 x 16 (the SSD works at every size). */
+int  H264E_read_quality(H264E_persist_t *enc, uint64_t ssd[3], double ssim[3]);
+/* the same SSIM of ONE pair of 8-bit planes of width x height samples in memory of `device` (-1: the default device), rows a_stride /
+ * b_stride bytes apart, any addresses, through the same kernel; the caller has synchronised whatever wrote them.  -1, with the value
+ * named in H264E_last_error: NULL, width or height below 8, a stride below width, memory that is not one allocation of that device. */
+int  H264E_ssim_planes(int device, const void *a, int a_stride, const void *b, int b_stride, int width, int height, double *ssim);
 /* The temporal denoiser for the clip encoder (see H264E_set_denoise; the clip's speed < 2 selects it for every frame): only while the
  * clip stands at frame 0 (after open or rewind); the denoised pictures are a pure function of the inputs, kept across a rewind and
  * made again from the first frame that is uploaded again.  The sums of squared differences compare the RAW input with the
