@@ -66,6 +66,21 @@ DEV_SAMPLE_U8, DEV_SAMPLE_F16, DEV_SAMPLE_BF16, DEV_SAMPLE_F32 = 0x00, 0x10, 0x2
 DEV_FORMAT_RGBP_F16, DEV_FORMAT_RGBP_BF16, DEV_FORMAT_RGBP_F32 = DEV_FORMAT_RGBP | DEV_SAMPLE_F16, DEV_FORMAT_RGBP | DEV_SAMPLE_BF16, DEV_FORMAT_RGBP | DEV_SAMPLE_F32
 _DEV_FORMATS = {"i420": DEV_FORMAT_I420, "nv12": DEV_FORMAT_NV12, "rgb": DEV_FORMAT_RGB, "rgbp": DEV_FORMAT_RGBP,
                 "rgbp_f16": DEV_FORMAT_RGBP_F16, "rgbp_bf16": DEV_FORMAT_RGBP_BF16, "rgbp_f32": DEV_FORMAT_RGBP_F32}
+# decoder surfaces: 16-bit samples with `depth` significant bits (bits 8-11 of the format: I420 and NV12) and 4:4:4 chroma (bit 12: I420)
+DEV_CHROMA_444 = 0x1000
+DEV_FORMAT_I444 = DEV_FORMAT_I420 | DEV_CHROMA_444
+
+
+def DEV_DEPTH(d):
+    """H264E_DEV_DEPTH: the format bits of 16-bit samples with d = 9 .. 16 significant bits, LSB aligned (an MSB-aligned P010 surface: 16)"""
+    return (int(d) - 8) << 8
+
+
+DEV_FORMAT_P016 = DEV_FORMAT_P010 = DEV_FORMAT_NV12 | DEV_DEPTH(16)
+_DEV_FORMATS["i444"] = DEV_FORMAT_I444
+# the names of the 16-bit formats: (layout bits, the only depth the name allows or None for depth=)
+_HBD_FORMATS = {"i420_16": (DEV_FORMAT_I420, None), "nv12_16": (DEV_FORMAT_NV12, None), "i444_16": (DEV_FORMAT_I444, None),
+                "p010": (DEV_FORMAT_NV12, 16), "p016": (DEV_FORMAT_NV12, 16)}
 # float planar RGB: format code -> (bytes per sample, the torch dtype's name, the __cuda_array_interface__ typestr or None)
 _FLOAT_SAMPLES = {DEV_FORMAT_RGBP_F16: (2, "float16", "<f2"), DEV_FORMAT_RGBP_BF16: (2, "bfloat16", None), DEV_FORMAT_RGBP_F32: (4, "float32", "<f4")}
 
@@ -103,13 +118,15 @@ def _float_format_of(a):
     return None, "a (pointer, stride) pair"
 
 
-def _dev_array(a, f=None):
+def _dev_array(a, f=None, u16=None):
     """(pointer, shape, strides in bytes, producer stream or None) of one device array: an object with data_ptr() / stride() / shape
     (a torch tensor), one with __cuda_array_interface__, or an explicit (pointer, row stride in bytes) pair -- whose shape is not
     known, so nothing about it is checked here.  f: one of the float planar RGB formats -- the array must hold that sample type;
-    otherwise 8-bit samples."""
+    u16: the name of a 16-bit format -- the array must hold uint16 or int16 samples; otherwise 8-bit samples."""
     if isinstance(a, (tuple, list)) and len(a) == 2 and all(isinstance(x, int) for x in a):
         return int(a[0]), None, (int(a[1]),), None
+    if u16 is not None:
+        return _dev_array16(a, u16)
     if f is not None and _float_format_of(a)[0] != f:
         raise H264EError("device input: format %r takes %s samples, not %s" % ([k for k, v in _DEV_FORMATS.items() if v == f][0], _FLOAT_SAMPLES[f][1], _float_format_of(a)[1]))
     item = _FLOAT_SAMPLES[f][0] if f is not None else 1
@@ -135,6 +152,66 @@ def _dev_array(a, f=None):
         st = cai.get("stream")
         return int(cai["data"][0]), shape, tuple(int(x) for x in strides), (st if st not in (None, 1, 2) else None)
     raise H264EError("device input: expected a tensor, an object with __cuda_array_interface__ or a (pointer, stride) pair, got %r" % type(a))
+
+
+def _dev_array16(a, name):
+    """_dev_array for uint16 / int16 samples (strides in bytes); anything else is refused with its type in the message"""
+    if hasattr(a, "data_ptr") and hasattr(a, "stride"):
+        if str(getattr(a, "dtype", "?")) not in ("torch.uint16", "torch.int16"):
+            raise H264EError("device input: format %r takes 16-bit samples (uint16 or int16), not %s" % (name, getattr(a, "dtype", "?")))
+        stream = None
+        torch = sys.modules.get("torch")
+        if torch is not None and getattr(a, "is_cuda", False):
+            stream = torch.cuda.current_stream(a.device)
+        return int(a.data_ptr()), tuple(a.shape), tuple(int(x) * 2 for x in a.stride()), stream
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is not None:
+        if cai["typestr"] not in ("<u2", "<i2"):
+            raise H264EError("device input: format %r takes 16-bit samples (<u2 or <i2), not %s" % (name, cai["typestr"]))
+        shape = tuple(cai["shape"])
+        strides = cai.get("strides")
+        if strides is None:
+            strides, acc = [], 2
+            for d in reversed(shape):
+                strides.insert(0, acc)
+                acc *= d
+        st = cai.get("stream")
+        return int(cai["data"][0]), shape, tuple(int(x) for x in strides), (st if st not in (None, 1, 2) else None)
+    raise H264EError("device input: expected a tensor, an object with __cuda_array_interface__ or a (pointer, stride) pair, got %r" % type(a))
+
+
+def _plane_n(a, rows, w, sb, what, u16):
+    """one (rows, w) plane of sb-byte samples, last axis contiguous, any row stride: (pointer, row stride in bytes, stream)"""
+    ptr, shape, strides, stream = _dev_array(a, u16=u16)
+    if shape is not None and (tuple(shape) != (rows, w) or strides[1] != sb):
+        raise H264EError("device input: %s must be a (%d, %d) array whose last axis is contiguous, got shape %r strides %r (bytes)" % (what, rows, w, shape, strides))
+    return ptr, strides[0], stream
+
+
+def _hbd_planes(frame, f, name, w, h):
+    """the planes of a 16-bit and / or 4:4:4 frame: [(pointer, row stride in bytes, stream)]"""
+    sb = 2 if f & 0xf00 else 1
+    u16 = name if sb == 2 else None
+    if f & DEV_CHROMA_444:
+        if isinstance(frame, (tuple, list)) and len(frame) == 3:
+            return [_plane_n(a, h, w, sb, what, u16) for a, what in zip(frame, "YUV")]
+        ptr, shape, strides, st = _dev_array(frame, u16=u16)
+        if shape is None or tuple(shape) != (3, h, w) or strides[2] != sb:
+            raise H264EError("device input: 4:4:4 must be a (3, %d, %d) array whose last axis is contiguous (any channel and row strides), "
+                             "or three (%d, %d) planes, got shape %r strides %r (bytes)" % (h, w, h, w, shape, strides))
+        return [(ptr + c * strides[0], strides[1], st) for c in range(3)]
+    if (f & 3) == DEV_FORMAT_NV12:
+        if not isinstance(frame, (tuple, list)) or len(frame) != 2:
+            raise H264EError("device input: NV12 takes (y, uv)")
+        return [_plane_n(frame[0], h, w, sb, "Y", u16), _plane_n(frame[1], h // 2, w, sb, "UV", u16)]
+    if isinstance(frame, (tuple, list)) and len(frame) == 3:
+        return [_plane_n(frame[0], h, w, sb, "Y", u16), _plane_n(frame[1], h // 2, w // 2, sb, "U", u16), _plane_n(frame[2], h // 2, w // 2, sb, "V", u16)]
+    ptr, shape, strides, st = _dev_array(frame, u16=u16)
+    if shape is not None and (tuple(shape) != (h * 3 // 2, w) or tuple(strides) != (w * sb, sb)):
+        raise H264EError("device input: packed 16-bit I420 must be a contiguous (%d, %d) array, got shape %r strides %r (bytes)" % (h * 3 // 2, w, shape, strides))
+    if shape is None and strides[0] != w * sb:
+        raise H264EError("device input: packed 16-bit I420 has row stride %d, got %d" % (w * sb, strides[0]))
+    return [(ptr, w * sb, st), (ptr + w * h * sb, w // 2 * sb, st), (ptr + (w * h + (w // 2) * (h // 2)) * sb, w // 2 * sb, st)]
 
 
 def _require_uint8(a):
@@ -171,9 +248,18 @@ def _float_plane(a, f, rows, w, what):
     return ptr, strides[0], stream
 
 
-def dev_format(fmt, frame=None):
+def dev_format(fmt, frame=None, depth=None):
     """the H264E_DEV_FORMAT_* code of a format name or number; "rgbpf" is float planar RGB with the sample type of `frame` (a float16,
-    bfloat16 or float32 array, or three such planes)"""
+    bfloat16 or float32 array, or three such planes); depth: the significant bits (9 .. 16, default 16) of the 16-bit names "i420_16",
+    "nv12_16" and "i444_16" ("p010" and "p016" are MSB aligned: 16)"""
+    if isinstance(fmt, str) and fmt in _HBD_FORMATS:
+        base, fixed = _HBD_FORMATS[fmt]
+        d = 16 if depth is None else int(depth)
+        if not 9 <= d <= 16 or (fixed is not None and d != fixed):
+            raise H264EError("device input: depth %r for format %r (%s)" % (depth, fmt, "9 .. 16" if fixed is None else "an MSB-aligned surface: %d, or leave it out" % fixed))
+        return base | DEV_DEPTH(d)
+    if depth is not None:
+        raise H264EError("device input: depth=%r with format %r: a depth belongs to the 16-bit formats %s" % (depth, fmt, ", ".join(sorted(_HBD_FORMATS))))
     if fmt != "rgbpf":
         return _DEV_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
     arrays = list(frame) if isinstance(frame, (tuple, list)) and len(frame) == 3 else [frame]
@@ -184,17 +270,22 @@ def dev_format(fmt, frame=None):
     return found[0][0]
 
 
-def dev_frame(frame, fmt, w, h, stream=None):
+def dev_frame(frame, fmt, w, h, stream=None, depth=None):
     """H264E_dev_frame_t for one frame of a w x h picture.  fmt "i420": three 2-D planes (y, u, v) or one packed (h*3/2, w) array;
     "nv12": (y of (h, w), uv of (h/2, w)); "rgb": one (h, w, 3 | 4) array; "rgbp": one uint8 (3, h, w) array (CHW: any channel and row
     strides, so views work without a copy) or three 2-D planes (r, g, b); "rgbp_f16", "rgbp_bf16", "rgbp_f32": the same of float
-    samples in [0, 1], and "rgbpf" whichever of the three the array's dtype says.  Arrays: torch tensors, anything with
+    samples in [0, 1], and "rgbpf" whichever of the three the array's dtype says; "i444": three (h, w) planes (y, u, v) or one (3, h, w)
+    array with any channel and row strides; "i420_16", "nv12_16" ("p010", "p016"), "i444_16": the same shapes as their 8-bit layouts of
+    torch.uint16 / torch.int16 ("<u2" / "<i2") samples with `depth` significant bits, LSB aligned (default 16: an MSB-aligned decoder
+    surface), quantised to 8 bits as they are loaded.  Arrays: torch tensors, anything with
     __cuda_array_interface__ (no bfloat16 there), or (pointer, row stride in bytes) pairs.  stream: the hipStream_t (an int) that writes
     the frame; by default torch's current stream for torch tensors.  Returns (DevFrame, the objects that must stay alive during the call)."""
-    f = dev_format(fmt, frame)
+    f = dev_format(fmt, frame, depth)
     pb, planes = 0, []
     _one_runtime()
-    if f == DEV_FORMAT_I420:
+    if f & 0x1f00 and not f & ~0x1f03 and (f & 3) < 2:
+        planes = _hbd_planes(frame, f, fmt, w, h)
+    elif f == DEV_FORMAT_I420:
         if isinstance(frame, (tuple, list)) and len(frame) == 3:
             planes = [_dev_plane(frame[0], h, w, "Y"), _dev_plane(frame[1], h // 2, w // 2, "U"), _dev_plane(frame[2], h // 2, w // 2, "V")]
         else:
@@ -510,12 +601,13 @@ class Encoder:
             raise _err(self.L, "H264E_encode status %d" % st)
         return C.string_at(data, n.value)
 
-    def encode_device(self, frame, fmt, frame_type=FRAME_TYPE_DEFAULT, stream=None, src_size=None, crop=None):
+    def encode_device(self, frame, fmt, frame_type=FRAME_TYPE_DEFAULT, stream=None, src_size=None, crop=None, depth=None):
         """H264E_encode_device: the frame is taken from GPU memory (see dev_frame for what `frame` may be: fmt "i420", "nv12", "rgb", "rgbp" or float "rgbp_f16" / "rgbp_bf16" / "rgbp_f32" / "rgbpf");
         needs const_input=1.  The frame's memory may be reused as soon as this returns.  src_size=(w, h): the frame has that size and is
-        reduced to the encoder's picture (H264E_encode_device_scaled), crop=(x, y, w, h): only that window of it."""
+        reduced to the encoder's picture (H264E_encode_device_scaled), crop=(x, y, w, h): only that window of it.  depth: the significant
+        bits of the 16-bit formats "i420_16" / "nv12_16" / "i444_16" (9 .. 16, default 16)."""
         win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)
-        d, _keep = dev_frame(frame, fmt, sw, sh, stream)
+        d, _keep = dev_frame(frame, fmt, sw, sh, stream, depth)
         self.rp.frame_type = frame_type
         data, n = C.c_void_p(), C.c_int()
         if win is not None:
@@ -685,12 +777,13 @@ class ClipEncoder:
         if self.L.H264E_clip_upload(self.c, first, n, clip.ctypes.data):
             raise _err(self.L, "H264E_clip_upload")
 
-    def upload_device(self, frames, fmt, first=0, stream=None, src_size=None, crop=None):
+    def upload_device(self, frames, fmt, first=0, stream=None, src_size=None, crop=None, depth=None):
         """H264E_clip_upload_device: `frames` is a sequence of frames in GPU memory (see dev_frame: fmt "i420", "nv12", "rgb", "rgbp" or float "rgbp_f16" / "rgbp_bf16" / "rgbp_f32" / "rgbpf"), frame
         first + i from frames[i].  Their memory may be reused as soon as this returns.  src_size=(w, h): the frames have that size and are
-        reduced to the clip's picture (H264E_clip_upload_device_scaled), crop=(x, y, w, h): only that window of them."""
+        reduced to the clip's picture (H264E_clip_upload_device_scaled), crop=(x, y, w, h): only that window of them.  depth: the
+        significant bits of the 16-bit formats "i420_16" / "nv12_16" / "i444_16" (9 .. 16, default 16)."""
         win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)
-        made = [dev_frame(f, fmt, sw, sh, stream) for f in frames]
+        made = [dev_frame(f, fmt, sw, sh, stream, depth) for f in frames]
         arr = (DevFrame * max(len(made), 1))(*[m[0] for m in made])
         if win is not None:
             if self.L.H264E_clip_upload_device_scaled(self.c, first, len(made), arr, C.byref(win)):
@@ -822,12 +915,13 @@ class ClipEncoder:
             pass
 
 
-def encode_ladder(frames, fmt, src_size, rungs, crop=None, **common):
+def encode_ladder(frames, fmt, src_size, rungs, crop=None, depth=None, **common):
     """One source in GPU memory, several encodes of it at different sizes.  frames: the device frames (see dev_frame), all of
     src_size=(w, h); rungs: a list of (width, height, dict of ClipEncoder options); crop=(x, y, w, h): the window of the source that every
     rung shows; common: ClipEncoder options of all rungs (a rung's own win).  One ClipEncoder per rung is fed from the same frames -- by
     the scaling kernel, or the plain ingest where a rung has the window's size -- rungs of equal picture size are encoded at the same
-    time (ClipEncoder.encode_multi), the others one after another.  Returns one (bytes, sizes, stats) per rung, in the order given."""
+    time (ClipEncoder.encode_multi), the others one after another.  depth: the significant bits of a 16-bit fmt (see dev_frame).
+    Returns one (bytes, sizes, stats) per rung, in the order given."""
     frames = list(frames)
     sw, sh = (int(v) for v in src_size)
     encs, out = [], [None] * len(rungs)
@@ -836,9 +930,9 @@ def encode_ladder(frames, fmt, src_size, rungs, crop=None, **common):
             ce = ClipEncoder(w, h, len(frames), **dict(common, **(opts or {})))
             encs.append(ce)
             if crop is None and (w, h) == (sw, sh):
-                ce.upload_device(frames, fmt)
+                ce.upload_device(frames, fmt, depth=depth)
             else:
-                ce.upload_device(frames, fmt, src_size=(sw, sh), crop=crop)
+                ce.upload_device(frames, fmt, src_size=(sw, sh), crop=crop, depth=depth)
         groups = {}
         for i, ce in enumerate(encs):
             groups.setdefault((ce.w, ce.h), []).append(i)

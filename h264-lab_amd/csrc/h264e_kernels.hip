@@ -16,6 +16,7 @@
  *   h264e_egress_kernel  device-resident output (enc_egress.h): a reconstructed picture -> I420 / NV12 / RGB / planar RGB in the caller's HBM.
  *   h264e_scale_kernel   the same as the ingest for a source of another size (enc_scale.h): a window of an I420 / NV12 frame, box-filtered down to the slot.
  *   h264e_scale_rgb_kernel  ... of a planar RGB frame (enc_scale_rgb.h): the three channels box-filtered into LDS, converted to I420 from there.
+ *   h264e_ingest_hbd_kernel<SB, C444>, h264e_scale_hbd_kernel<SB>  the I420 / NV12 paths for 16-bit samples and 4:4:4 chroma (enc_hbd.h).
  *   h264e_ingest_float_kernel<ST>, h264e_scale_rgb_float_kernel<ST>, h264e_egress_float_kernel<ST>  the planar RGB paths for float16 /
  *                        bfloat16 / float32 samples in [0, 1], quantised on the way in and divided by 255 on the way out.
  *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
@@ -33,6 +34,7 @@
 #include "enc_egress.h"
 #include "enc_scale.h"
 #include "enc_scale_rgb.h"
+#include "enc_hbd.h"
 #include "enc_scenecut.h"
 #include "enc_ssim.h"
 #include "../../include/h264e_hip.h"
@@ -748,6 +750,15 @@ template <int ST> __global__ void __launch_bounds__(256) h264e_ingest_float_kern
     else ingest_float_chroma<ST>(S, (GLOBAL_AS uint8_t *)dst, g, y);
 }
 
+/* ... of 16-bit samples (SB = 2) and / or 4:4:4 chroma (enc_hbd.h): the same grid; kernels of their own, so that the 8-bit 4:2:0 kernel
+ * stays the code it is */
+template <int SB, int C444> __global__ void __launch_bounds__(256) h264e_ingest_hbd_kernel(h264e_ingest_src_t S, uint8_t *dst)
+{
+    const int g = (int)(blockIdx.x*blockDim.x + threadIdx.x), y = (int)blockIdx.y;
+    if (blockIdx.z == 0) ingest_hbd_luma<SB>(S, (GLOBAL_AS uint8_t *)dst, g, y);
+    else ingest_hbd_chroma<SB, C444>(S, (GLOBAL_AS uint8_t *)dst, g, y);
+}
+
 /* device-resident output over one picture (enc_egress.h): grid.z = 0 luma / 1 both chroma planes for I420 and NV12, grid.y = row; the RGB
  * formats have grid.z = 0 alone and grid.y = a PAIR of rows (one chroma row); grid.x * 256 lanes x 4 samples along the row.  Every workgroup
  * reads its own bytes of the picture and writes its own bytes of the destination (no inter-workgroup traffic, no LDS). */
@@ -776,6 +787,26 @@ __global__ void __launch_bounds__(256) h264e_scale_kernel(h264e_scale_src_t S, u
     __syncthreads();
     const int items = scale_src_rows(L, T) << 6;
     for (int it = (int)threadIdx.x; it < items; it += 256) scale_hpass(L, S.c[comp], T, it);
+    __syncthreads();
+    for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_vpass(L, T, (GLOBAL_AS uint8_t *)(dst + scale_plane_offset(S, comp)), it);
+}
+
+/* ... of 16-bit samples and / or 4:4:4 chroma (enc_hbd.h): the same three steps with a source geometry per plane; SB = 2 quantises the
+ * taps as the horizontal pass loads them.  grid.y covers the plane with the most rows of tiles */
+template <int SB> __global__ void __launch_bounds__(256) h264e_scale_hbd_kernel(h264e_scale_src_t S, uint8_t *dst)
+{
+    __shared__ __attribute__((aligned(16))) ScaleLds lds;
+    LDS_AS ScaleLds *L = (LDS_AS ScaleLds *)&lds;
+    const int comp = (int)blockIdx.z;
+    ScaleTile T;
+    if (!scale_tile_hbd(S, comp, (int)blockIdx.x, (int)blockIdx.y, T)) return;  /* uniform per workgroup */
+    scale_tables(L, T, (int)threadIdx.x);
+    __syncthreads();
+    const int items = scale_src_rows(L, T) << 6;
+    for (int it = (int)threadIdx.x; it < items; it += 256)
+    {
+        if (SB == 2) scale_hpass_hbd(L, S.c[comp], T, S.qround, S.qshift, it); else scale_hpass(L, S.c[comp], T, it);
+    }
     __syncthreads();
     for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_vpass(L, T, (GLOBAL_AS uint8_t *)(dst + scale_plane_offset(S, comp)), it);
 }
@@ -910,6 +941,14 @@ static void bk_launch_denoise(const uint8_t *in, const uint8_t *prev, uint8_t *o
 static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t st)
 {
     const unsigned gx = (unsigned)((((S.width + 3) >> 2) + 255) >> 8);
+    if (S.depth || S.c444)
+    {
+        const dim3 grid(gx, (unsigned)S.height, 2);
+        if (!S.depth) hipLaunchKernelGGL((h264e_ingest_hbd_kernel<1, 1>), grid, dim3(256), 0, st, S, dst);
+        else if (S.c444) hipLaunchKernelGGL((h264e_ingest_hbd_kernel<2, 1>), grid, dim3(256), 0, st, S, dst);
+        else hipLaunchKernelGGL((h264e_ingest_hbd_kernel<2, 0>), grid, dim3(256), 0, st, S, dst);
+        return;
+    }
     LAUNCH_BY_SAMPLE(S.sample, h264e_ingest_kernel, h264e_ingest_float_kernel, dim3(gx, (unsigned)S.height, 2), st, S, dst);
 }
 static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hipStream_t st)
@@ -920,6 +959,13 @@ static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hi
 }
 static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t st)
 {
+    if (S.depth || S.c444)
+    {
+        const dim3 grid((unsigned)((S.dw + SCL_TW - 1)/SCL_TW), (unsigned)S.tiles_y, 3);
+        if (S.depth) hipLaunchKernelGGL(h264e_scale_hbd_kernel<2>, grid, dim3(256), 0, st, S, dst);
+        else hipLaunchKernelGGL(h264e_scale_hbd_kernel<1>, grid, dim3(256), 0, st, S, dst);
+        return;
+    }
     hipLaunchKernelGGL(h264e_scale_kernel, dim3((unsigned)((S.dw + SCL_TW - 1)/SCL_TW), (unsigned)((S.dh + S.th - 1)/S.th), 3), dim3(256), 0, st, S, dst);
 }
 static void bk_launch_scale_rgb(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t st)

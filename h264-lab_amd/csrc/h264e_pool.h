@@ -16,6 +16,7 @@
 #include "enc_egress.h"
 #include "enc_scale.h"
 #include "enc_scale_rgb.h"
+#include "enc_hbd.h"
 #include "enc_scenecut.h"
 #include "enc_ssim.h"
 
@@ -791,7 +792,19 @@ template <int ST> static void emu_ingest(const h264e_ingest_src_t &S, uint8_t *d
             else { ingest_float_luma<ST>(S, dst, g, y); ingest_float_chroma<ST>(S, dst, g, y); }
         }
 }
-static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t) { EMU_BY_SAMPLE(S.sample, emu_ingest, S, dst); }
+/* ... of 16-bit samples and / or 4:4:4 chroma (enc_hbd.h) */
+template <int SB, int C444> static void emu_ingest_hbd(const h264e_ingest_src_t &S, uint8_t *dst)
+{
+    for (int y = 0; y < S.height; y++)
+        for (int g = 0; g < (S.width + 3)/4; g++) { ingest_hbd_luma<SB>(S, dst, g, y); ingest_hbd_chroma<SB, C444>(S, dst, g, y); }
+}
+static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t)
+{
+    if (S.depth && S.c444) emu_ingest_hbd<2, 1>(S, dst);
+    else if (S.depth) emu_ingest_hbd<2, 0>(S, dst);
+    else if (S.c444) emu_ingest_hbd<1, 1>(S, dst);
+    else EMU_BY_SAMPLE(S.sample, emu_ingest, S, dst);
+}
 /* ... and the egress's (enc_egress.h): the same, per part */
 template <int ST> static void emu_egress(const h264e_egress_dst_t &D, const uint8_t *src)
 {
@@ -809,6 +822,26 @@ static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_
 {
     ScaleLds *L = (ScaleLds *)malloc(sizeof(ScaleLds));
     if (!L) return;
+    if (S.depth || S.c444)              /* enc_hbd.h: a source geometry per plane, 16-bit taps quantised by the horizontal pass */
+    {
+        for (int comp = 0; comp < 3; comp++)
+            for (int ty = 0; ty < S.tiles_y; ty++)
+                for (int tx = 0; tx < (S.dw + SCL_TW - 1)/SCL_TW; tx++)
+                {
+                    ScaleTile T;
+                    if (!scale_tile_hbd(S, comp, tx, ty, T)) continue;
+                    memset(L, 0xEE, sizeof(*L));
+                    for (int t = 0; t < 256; t++) scale_tables(L, T, t);
+                    const int items = scale_src_rows(L, T) << 6;
+                    for (int it = 0; it < items; it++)
+                    {
+                        if (S.depth) scale_hpass_hbd(L, S.c[comp], T, S.qround, S.qshift, it); else scale_hpass(L, S.c[comp], T, it);
+                    }
+                    for (int it = 0; it < T.nrows*16; it++) scale_vpass(L, T, dst + scale_plane_offset(S, comp), it);
+                }
+        free(L);
+        return;
+    }
     for (int comp = 0; comp < 3; comp++)
         for (int ty = 0; ty < (S.dh + S.th - 1)/S.th; ty++)
             for (int tx = 0; tx < (S.dw + SCL_TW - 1)/SCL_TW; tx++)
@@ -866,13 +899,29 @@ static int ingest_is_device_memory(const h264e_hip_pool_t *p, const void *q, siz
 }
 #endif
 
-/* H264E_dev_frame_t.format: the layout in bits 0-1, the sample type in bits 4-5 (planar RGB only), nothing else; *sb = a sample's bytes */
-static const char *const k_format_names[4] = { "I420", "NV12", "RGB", "RGBP" }, *const k_sample_names[4] = { "u8", "f16", "bf16", "f32" };
-static int dev_format_split(const char *who, int format, int *base, int *sample, int *sb)
+/* H264E_dev_frame_t.format: the layout in bits 0-1, the sample type in bits 4-5 (planar RGB only) and, on the way in alone (hbd != NULL),
+ * the depth of 16-bit samples in bits 8-11 (depth - 8: I420 and NV12) and 4:4:4 chroma in bit 12 (I420); nothing else.  *sb = a sample's
+ * bytes, hbd[0] = the depth (0: 8-bit samples), hbd[1] = 4:4:4 */
+#define H264E_SAMPLE_U16 4              /* the name of a 16-bit sample in the messages */
+static const char *const k_format_names[4] = { "I420", "NV12", "RGB", "RGBP" }, *const k_sample_names[5] = { "u8", "f16", "bf16", "f32", "u16" };
+static int dev_format_split(const char *who, int format, int *base, int *sample, int *sb, int *hbd)
 {
-    if (format & ~0x33) FAIL("%s: unknown format %d", who, format);
+    const int dcode = hbd ? (format >> 8) & 15 : 0, c444 = hbd ? (format >> 12) & 1 : 0;
+    if (format & ~(hbd ? 0x1f33 : 0x33) || dcode > 8) FAIL("%s: unknown format %d", who, format);
     *base = format & 3; *sample = (format >> 4) & 3;
-    *sb = *sample == H264E_SAMPLE_F32 ? 4 : *sample ? 2 : 1;
+    if (hbd)
+    {
+        hbd[0] = dcode ? dcode + 8 : 0; hbd[1] = c444;
+        if (dcode && *sample)
+            FAIL("%s: format %d asks for both %d-bit integer samples (0x%x) and %s samples (0x%x) of %s (format %d): one sample type", who, format, dcode + 8, dcode << 8,
+                 k_sample_names[*sample], *sample << 4, k_format_names[*base], *base);
+        if ((dcode || c444) && (*base == H264E_INGEST_RGB || *base == H264E_INGEST_RGBP))
+            FAIL("%s: format %d asks for %s of %s (format %d): 16-bit samples are I420 and NV12 only, 4:4:4 chroma I420 only", who, format,
+                 dcode ? "16-bit samples" : "4:4:4 chroma", k_format_names[*base], *base);
+        if (c444 && *base == H264E_INGEST_NV12)
+            FAIL("%s: format %d asks for 4:4:4 chroma (0x1000) of NV12 (format %d): 4:4:4 is three planes, I420 (format %d) only", who, format, *base, H264E_INGEST_I420);
+    }
+    *sb = *sample == H264E_SAMPLE_F32 ? 4 : *sample || dcode ? 2 : 1;
     if (*sample && *base != H264E_INGEST_RGBP)
         FAIL("%s: format %d asks for %s samples (0x%x) of %s (format %d): float samples are planar RGB (format %d) only", who, format, k_sample_names[*sample], *sample << 4,
              k_format_names[*base], *base, H264E_INGEST_RGBP);
@@ -881,6 +930,7 @@ static int dev_format_split(const char *who, int format, int *base, int *sample,
 /* float planes: every pointer and stride a multiple of the sample's bytes (what the kernels' loads and stores rest on) */
 static int dev_sample_aligned(const char *who, int k, const void *plane, int stride, int sb, int sample)
 {
+    if (sb == 2 && !sample) sample = H264E_SAMPLE_U16;
     if ((uintptr_t)plane % (unsigned)sb) FAIL("%s: plane %d (%p) is not a multiple of the %d bytes of a %s sample", who, k, plane, sb, k_sample_names[sample]);
     if (stride % sb) FAIL("%s: stride %d of plane %d is not a multiple of the %d bytes of a %s sample", who, stride, k, sb, k_sample_names[sample]);
     return 0;
@@ -897,25 +947,27 @@ extern "C" int h264e_hip_set_color(h264e_hip_pool_t *p, int bt709, int full_rang
 /* everything that is refused, without a launch; fills the kernel's view of the source */
 static int ingest_check(const h264e_hip_pool_t *p, int slot, int dev_format, const void *const planes[3], const int strides[3], int pixel_bytes, h264e_ingest_src_t *S)
 {
-    int format, sample, sb;
+    int format, sample, sb, hbd[2];
     if (!p || !planes || !strides) FAIL("ingest_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("ingest_device: slot %d outside the %d resident frames", slot, p->frames_resident);
-    if (dev_format_split("ingest_device", dev_format, &format, &sample, &sb)) return -1;
+    if (dev_format_split("ingest_device", dev_format, &format, &sample, &sb, hbd)) return -1;
     if (format == H264E_INGEST_RGB && pixel_bytes != 3 && pixel_bytes != 4) FAIL("ingest_device: RGB pixels of %d bytes (3 or 4)", pixel_bytes);
     memset(S, 0, sizeof(*S));
     S->format = format; S->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1; S->sample = sample;
     S->width = p->G.width; S->height = p->G.height;
     S->cm = p->cm;
+    S->depth = hbd[0]; S->c444 = hbd[1];
+    if (hbd[0]) { S->qround = 1 << (hbd[0] - 9); S->qshift = hbd[0] - 8; }
     const int nplanes = format == H264E_INGEST_I420 || format == H264E_INGEST_RGBP ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
     for (int k = 0; k < nplanes; k++)
     {
-        /* bytes and rows of source plane k: RGB pixels; full-size luma and R, G, B planes (sb bytes per sample); half-size chroma (NV12: U,V pairs, so `width` bytes again) */
-        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP) ? S->width*sb : S->width/2;
+        /* bytes and rows of source plane k: RGB pixels; full-size luma, R, G, B and 4:4:4 chroma planes (sb bytes per sample); half-size chroma (NV12: U,V pairs, so `width` samples again) */
+        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP || hbd[1]) ? S->width*sb : (S->width/2)*sb;
         if (!planes[k]) FAIL("ingest_device: plane %d is NULL", k);
         if (dev_sample_aligned("ingest_device", k, planes[k], strides[k], sb, sample)) return -1;
         if (strides[k] < row_bytes) FAIL("ingest_device: stride %d of plane %d is below its %d row bytes", strides[k], k, row_bytes);
 #ifndef H264E_EMU
-        const int rows = k == 0 || format == H264E_INGEST_RGBP ? S->height : S->height/2;
+        const int rows = k == 0 || format == H264E_INGEST_RGBP || hbd[1] ? S->height : S->height/2;
         const void *q = planes[k];
         if (!ingest_is_device_memory(p, q, (size_t)(rows - 1)*(size_t)strides[k] + (size_t)row_bytes))
             FAIL("ingest_device: plane %d (%p, %d rows %d bytes apart) is not memory of device %d, or not inside one allocation", k, planes[k], rows, strides[k], p->device);
@@ -982,10 +1034,10 @@ extern "C" int h264e_hip_ingest_device(h264e_hip_pool_t *p, int slot, int format
  * device memory inside one allocation is [the window's first byte, the last byte of its last row] of every plane. */
 static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, const void *const planes[3], const int strides[3], const int *win, h264e_scale_src_t *S)
 {
-    int format, sample, sb;
+    int format, sample, sb, hbd[2];
     if (!p || !planes || !strides || !win) FAIL("scale_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("scale_device: slot %d outside the %d resident frames", slot, p->frames_resident);
-    if (dev_format_split("scale_device", dev_format, &format, &sample, &sb)) return -1;
+    if (dev_format_split("scale_device", dev_format, &format, &sample, &sb, hbd)) return -1;
     if (format == H264E_INGEST_RGB) FAIL("scale_device: interleaved RGB (format %d) cannot be combined with a window: convert at the picture's size, or hand over planar RGB (format %d), I420 or NV12", format, H264E_INGEST_RGBP);
     const int srcw = win[0], srch = win[1], dw = p->G.width, dh = p->G.height;
     if (srcw <= 0 || srch <= 0) FAIL("scale_device: source of %d x %d samples", srcw, srch);
@@ -1002,6 +1054,11 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, cons
     if (sh < dh) FAIL("scale_device: window height %d below the picture's %d (no upscaling)", sh, dh);
     if (sw > SCL_MAX_RATIO*dw) FAIL("scale_device: window width %d is more than %d times the picture's %d", sw, SCL_MAX_RATIO, dw);
     if (sh > SCL_MAX_RATIO*dh) FAIL("scale_device: window height %d is more than %d times the picture's %d", sh, SCL_MAX_RATIO, dh);
+    /* a 4:4:4 chroma plane goes from the luma's window to half the picture: no plane by more than SCL_MAX_RATIO */
+    if (hbd[1] && sw > SCL_MAX_RATIO/2*dw)
+        FAIL("scale_device: 4:4:4 window width %d is more than %d times the picture's %d (its chroma planes are reduced to %d columns: at most %d to 1)", sw, SCL_MAX_RATIO/2, dw, dw/2, SCL_MAX_RATIO);
+    if (hbd[1] && sh > SCL_MAX_RATIO/2*dh)
+        FAIL("scale_device: 4:4:4 window height %d is more than %d times the picture's %d (its chroma planes are reduced to %d rows: at most %d to 1)", sh, SCL_MAX_RATIO/2, dh, dh/2, SCL_MAX_RATIO);
     memset(S, 0, sizeof(*S));
     S->sw = sw; S->sh = sh; S->dw = dw; S->dh = dh;
     S->cm = p->cm; S->sample = sample;
@@ -1009,13 +1066,19 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, cons
     if (S->th > SCL_TH_MAX) S->th = SCL_TH_MAX;
     const int rgbp = format == H264E_INGEST_RGBP;
     if (rgbp) S->th &= ~1;                                      /* a tile of all three output planes: whole 2x2 blocks (>= 4 rows at 16:1) */
+    S->depth = hbd[0]; S->c444 = hbd[1];
+    if (hbd[0]) { S->qround = 1 << (hbd[0] - 9); S->qshift = hbd[0] - 8; }
+    S->thc = (int)((long long)(SCL_ROWS - 2)*(dh/2)/sh);        /* 4:4:4 chroma: sh rows -> dh/2, so thc*sh/(dh/2) + 2 source rows at most (>= 4 rows at 8:1) */
+    if (S->thc > SCL_TH_MAX) S->thc = SCL_TH_MAX;
+    S->tiles_y = (dh + S->th - 1)/S->th;
+    if (hbd[1] && (dh/2 + S->thc - 1)/S->thc > S->tiles_y) S->tiles_y = (dh/2 + S->thc - 1)/S->thc;
     const int nplanes = format == H264E_INGEST_NV12 ? 2 : 3, cw = (srcw + 1)/2;
     for (int k = 0; k < nplanes; k++)
     {
         /* bytes of a source row, and the window in this plane: x0 bytes into row y0, wbytes x rows (planar RGB: every plane as luma, sb bytes per sample) */
-        const int nv = k && format == H264E_INGEST_NV12, full = k == 0 || rgbp;
-        const int row_bytes = full ? srcw*sb : nv ? 2*cw : cw;
-        const int x0 = full ? cx*sb : nv ? cx : cx/2, y0 = full ? cy : cy/2, wbytes = full ? sw*sb : nv ? sw : sw/2, rows = full ? sh : sh/2;
+        const int nv = k && format == H264E_INGEST_NV12, full = k == 0 || rgbp || hbd[1];
+        const int row_bytes = full ? srcw*sb : nv ? 2*cw*sb : cw*sb;
+        const int x0 = full ? cx*sb : nv ? cx*sb : cx/2*sb, y0 = full ? cy : cy/2, wbytes = full ? sw*sb : nv ? sw*sb : sw/2*sb, rows = full ? sh : sh/2;
         if (!planes[k]) FAIL("scale_device: plane %d is NULL", k);
         if (dev_sample_aligned("scale_device", k, planes[k], strides[k], sb, sample)) return -1;
         if (strides[k] < row_bytes) FAIL("scale_device: stride %d of plane %d is below the %d bytes of a source row", strides[k], k, row_bytes);
@@ -1028,8 +1091,8 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, cons
 #endif
         for (int c = k; c < (nv ? 3 : k + 1); c++)
         {
-            S->c[c].base = lo + (nv && c == 2 ? 1 : 0); S->c[c].lo = lo; S->c[c].hi = lo + nbytes;
-            S->c[c].stride = strides[k]; S->c[c].step = nv ? 2 : sb;
+            S->c[c].base = lo + (nv && c == 2 ? sb : 0); S->c[c].lo = lo; S->c[c].hi = lo + nbytes;
+            S->c[c].stride = strides[k]; S->c[c].step = nv ? 2*sb : sb;
         }
     }
     return 0;
@@ -1069,7 +1132,7 @@ static int egress_check(const h264e_hip_pool_t *p, int slot, int dev_format, voi
     int format, sample, sb;
     if (!p || !planes || !strides) FAIL("egress: null argument");
     if (slot < 0 || slot >= p->nchains) FAIL("egress: picture slot %d outside the pool's %d", slot, p->nchains);
-    if (dev_format_split("egress", dev_format, &format, &sample, &sb)) return -1;
+    if (dev_format_split("egress", dev_format, &format, &sample, &sb, NULL)) return -1;
     if (format == H264E_INGEST_RGB && pixel_bytes != 3 && pixel_bytes != 4) FAIL("egress: RGB pixels of %d bytes (3 or 4)", pixel_bytes);
     memset(D, 0, sizeof(*D));
     D->format = format; D->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1; D->sample = sample;

@@ -208,6 +208,18 @@ typedef struct
  *                .clamp(0, 255), nan=0).to(uint8).  From q on the frame IS the 8-bit RGBP frame: the stream and the input slot are
  *                exactly those of the quantised planes (tests/float_model.py restates it).  Strides stay in bytes; plane pointers and
  *                strides must be multiples of the sample's size.
+ *          I420 | H264E_DEV_DEPTH(d), NV12 | H264E_DEV_DEPTH(d), d = 9 .. 16 (bits 8-11 of format; on RGB and RGBP, together with a float
+ *                sample type, and on the way out they are refused): what hardware decoders and 10-bit software decoders leave.  Samples are
+ *                unsigned 16-bit little-endian words with d significant bits, LSB aligned (yuv420p10le: d = 10); a P010 / P012 / P016
+ *                surface is MSB aligned, which is simply d = 16 (H264E_DEV_FORMAT_P016, alias _P010).  Every word v is quantised as
+ *                it is loaded, q = min(255, (v + (1 << (d - 9))) >> (d - 8)): round half up, one clamp; words above 2^d - 1 (garbage
+ *                in the unused high bits) saturate to 255; 10-bit limited range maps 64 -> 16 and 940 -> 235.  From q on the frame IS
+ *                the 8-bit frame: the stream and the input slot are exactly those of the quantised planes (tests/hbd_model.py restates
+ *                it).  Strides stay in bytes; plane pointers and strides must be multiples of 2.
+ *          I420 | H264E_DEV_CHROMA_444 (bit 12: H264E_DEV_FORMAT_I444; the I420 layout only, with or without a depth): U and V have the
+ *                luma's size.  Luma is copied (or quantised); U(i,j) = (a + b + c + d + 2) >> 2 over the 2x2 block of the 8-bit
+ *                (quantised first) chroma samples, the rounded mean of the RGB path; V likewise.  The slot is that of an I420 frame
+ *                with those chroma planes.
  * stride: bytes from row to row, at least the row's bytes; no alignment is asked of pointers or strides of 8-bit samples.  producer_stream: the
  * hipStream_t on which the work that writes the frame was queued -- the encoder waits for everything queued there so far -- or NULL
  * when the caller has synchronised.  Every call that takes such frames returns when they have been read: the memory may be reused
@@ -220,9 +232,14 @@ typedef struct
 #define H264E_DEV_SAMPLE_F16   0x10
 #define H264E_DEV_SAMPLE_BF16  0x20
 #define H264E_DEV_SAMPLE_F32   0x30
+#define H264E_DEV_DEPTH(d) (((d) - 8) << 8)  /* 16-bit samples with d = 9 .. 16 significant bits, OR-ed into format: I420 and NV12, input only */
+#define H264E_DEV_CHROMA_444   0x1000       /* U and V of the luma's size, OR-ed into format: I420, input only */
+#define H264E_DEV_FORMAT_I444  (H264E_DEV_FORMAT_I420 | H264E_DEV_CHROMA_444)
+#define H264E_DEV_FORMAT_P016  (H264E_DEV_FORMAT_NV12 | H264E_DEV_DEPTH(16))
+#define H264E_DEV_FORMAT_P010  H264E_DEV_FORMAT_P016       /* MSB aligned: the unused low bits take part in the rounding, as they should */
 typedef struct
 {
-    int format;                             /* H264E_DEV_FORMAT_*, for RGBP | H264E_DEV_SAMPLE_* */
+    int format;                             /* H264E_DEV_FORMAT_*, for RGBP | H264E_DEV_SAMPLE_*, for I420 / NV12 | H264E_DEV_DEPTH(d), for I420 | H264E_DEV_CHROMA_444 */
     int pixel_bytes;                        /* RGB: 3 or 4; ignored otherwise (RGBP included) */
     const void *plane[3];
     int stride[3];
@@ -246,6 +263,10 @@ int  H264E_encode_device(H264E_persist_t *enc, H264E_scratch_t *scratch, const H
  * the order a caller scaling and converting in two steps would use; chroma is the matrix of the rounded 2x2 mean of already rounded
  * samples (tests/rgbp_model.py restates it).  A pure crop equals the plain ingest of the cropped region, a constant colour stays the
  * same at every ratio.  Float RGBP: the window filters the QUANTISED samples, so the slot is that of the quantised 8-bit planes.
+ * 16-bit samples: likewise, the filter runs on the quantised samples of every plane.  4:4:4 (H264E_DEV_CHROMA_444): a chroma plane's
+ * window is the luma's, Sw x Sh at (crop_x, crop_y), reduced directly to Dw/2 x Dh/2 by the same formula -- at Sw = Dw exactly the 2x2
+ * rounded mean of the plain ingest, so a pure crop equals the ingest of the cropped region; no plane is reduced by more than 16:1, so a
+ * 4:4:4 window may be at most 8 times the picture in an axis.
  * Refused (H264E_last_error names the value): interleaved RGB
  * with a window, odd or negative crop values, a window that leaves the source, is smaller than the picture in an axis (no upscaling),
  * larger than 4096 samples or more than 16 times the picture in an axis, a stride below the source row's bytes, and planes that are

@@ -4,6 +4,10 @@ planar RGB from a CHW tensor with the default matrix and with BT.709 full range 
 over as interleaved RGB, the two steps the planar format replaces; with --fmt also float planar RGB, "rgbp_f16" / "rgbp_bf16" / "rgbp_f32":
 the same picture as a float CHW tensor in [0, 1] through the float ingest, and "rgbp_f16_via_quantise" / ...: that tensor quantised by
 torch, (x * 255).round().clamp(0, 255).to(uint8), and handed over as "rgbp", the two steps the float formats replace):
+with --fmt also the decoder surfaces, "i420_16" / "nv12_16" / "i444" / "i444_16": the same picture as 10-bit words in int16 tensors and /
+or with chroma of the luma's size through the kernels of enc_hbd.h, and "i420_16_via_torch" / ...: those tensors quantised by torch,
+((x.int() + r) >> s).clamp(max=255).to(uint8) per plane, plus the rounded 2x2 mean for 4:4:4, and handed over as "i420" / "nv12", the steps
+the new formats replace):
 the time per frame of H264E_clip_upload_device over `--frames` frames handed over in one call (one ingest kernel launch per frame, one
 wait at the end: launch + kernel, host wall clock around a call that ends in a device synchronise), next to H264E_clip_upload of the
 same frames from host memory -- the copy it replaces.  Then the per-frame API: H264E_encode (host planes) against H264E_encode_device
@@ -30,6 +34,37 @@ import pkg  # noqa: E402
 W, H, QP, GOP = 1920, 1080, 26, 30
 FORMATS = ("i420", "nv12", "rgb3", "rgb4", "rgbp", "rgbp_bt709_full", "rgbp_via_permute")
 FLOAT_FORMATS = tuple("rgbp_" + k + v for k in ("f16", "bf16", "f32") for v in ("", "_via_quantise"))
+HBD_FORMATS = tuple(k + v for k in ("i420_16", "nv12_16", "i444", "i444_16") for v in ("", "_via_torch"))
+HBD_DEPTH = 10
+
+
+def hbd_sources(torch, c, base):
+    """the frames of the packed I420 clip c as `base` takes them: 10-bit words (sample << 2) in int16 tensors for the 16-bit layouts,
+    chroma repeated 2 x 2 for 4:4:4 -- both quantise / average back to c"""
+    out = []
+    for f in c:
+        y, u, v = f[:W * H].reshape(H, W), f[W * H:W * H * 5 // 4].reshape(H // 2, W // 2), f[W * H * 5 // 4:].reshape(H // 2, W // 2)
+        if base.startswith("i444"):
+            u, v = u.repeat(2, 0).repeat(2, 1), v.repeat(2, 0).repeat(2, 1)
+        planes = [y, u, v]
+        if base.endswith("_16"):
+            planes = [(p.astype(np.int16) << (HBD_DEPTH - 8)) for p in planes]
+        if base.startswith("nv12"):
+            uv = np.empty((H // 2, W), planes[1].dtype)
+            uv[:, 0::2], uv[:, 1::2] = planes[1], planes[2]
+            planes = [planes[0], uv]
+        out.append(tuple(torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in planes))
+    return out
+
+
+def hbd_two_step(torch, frame, base):
+    """what a caller writes today in front of the 8-bit formats: (frame, format name)"""
+    if base.endswith("_16"):
+        r, s = 1 << (HBD_DEPTH - 9), HBD_DEPTH - 8
+        frame = tuple(((x.int() + r) >> s).clamp(max=255).to(torch.uint8) for x in frame)
+    if base.startswith("i444"):
+        frame = (frame[0],) + tuple(((x[0::2, 0::2].int() + x[0::2, 1::2] + x[1::2, 0::2] + x[1::2, 1::2] + 2) >> 2).to(torch.uint8) for x in frame[1:])
+    return frame, "nv12" if base.startswith("nv12") else "i420"
 
 
 def host_frames(P, n):
@@ -67,18 +102,22 @@ def main():
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--perframe", type=int, default=60)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--fmt", default=",".join(FORMATS), help="comma-separated, of: %s" % ", ".join(FORMATS + FLOAT_FORMATS))
+    ap.add_argument("--fmt", default=",".join(FORMATS), help="comma-separated, of: %s" % ", ".join(FORMATS + FLOAT_FORMATS + HBD_FORMATS))
     a = ap.parse_args()
     fmts = [f for f in a.fmt.split(",") if f]
     for f in fmts:
-        if f not in FORMATS + FLOAT_FORMATS:
-            ap.error("--fmt %s: one of %s" % (f, ", ".join(FORMATS + FLOAT_FORMATS)))
+        if f not in FORMATS + FLOAT_FORMATS + HBD_FORMATS:
+            ap.error("--fmt %s: one of %s" % (f, ", ".join(FORMATS + FLOAT_FORMATS + HBD_FORMATS)))
     import torch
     P = pkg.load_pkg()
     c = host_frames(P, max(a.frames, a.perframe))
     line = {"clip": "1080p synth_v1, QP %d, GOP %d" % (QP, GOP), "frames": a.frames, "reps": a.reps, "formats": {}}
     for fmt in fmts:
-        src, name, model = sources(torch, c[: a.frames], fmt)
+        base = fmt[: -len("_via_torch")] if fmt.endswith("_via_torch") else fmt
+        if fmt in HBD_FORMATS:
+            src, name, model = hbd_sources(torch, c[: a.frames], base), base, c[: a.frames]
+        else:
+            src, name, model = sources(torch, c[: a.frames], fmt)
         torch.cuda.synchronize()
         ce = P.ClipEncoder(W, H, a.frames, gop=GOP, qp=QP, color="bt709-full" if fmt == "rgbp_bt709_full" else None)
         dev_ms, host_ms = [], []
@@ -86,6 +125,11 @@ def main():
             t0 = time.perf_counter()
             if fmt == "rgbp_via_permute":
                 ce.upload_device([t.permute(1, 2, 0).contiguous() for t in src], "rgb")
+            elif fmt.endswith("_via_torch"):
+                made = [hbd_two_step(torch, f, base) for f in src]
+                ce.upload_device([m[0] for m in made], made[0][1])
+            elif fmt in HBD_FORMATS:
+                ce.upload_device(src, name, **(dict(depth=HBD_DEPTH) if name.endswith("_16") else {}))
             elif fmt.endswith("_via_quantise"):
                 ce.upload_device([(t * 255).round().clamp(0, 255).to(torch.uint8) for t in src], "rgbp")
             else:

@@ -8,9 +8,13 @@ cases alternate within every repetition.  The slot of the first frame of every c
 anything is timed.  Planar RGB (enc_scale_rgb.h, h264e_scale_rgb_kernel): 3840x2160 "rgbp" -> 1920x1080 from CHW tensors (24.9 MB of
 source), and at 1920x1080 the plain "rgbp" ingest next to the interleaved "rgb" ingest of the same image and to the copy a caller
 without the planar format pays first, torch's permute(1, 2, 0).contiguous() of the CHW frame (torch events around a batch of them).
+--hbd times the decoder surfaces instead (enc_hbd.h): 3840x2160 -> 1920x1080 of "i420_16", "nv12_16", "i444" and "i444_16" frames (10-bit
+words in int16 tensors) through h264e_scale_hbd_kernel, next to the two steps they replace -- torch's quantiser per plane,
+((x.int() + r) >> s).clamp(max=255).to(uint8), plus the rounded 2x2 mean for 4:4:4 (torch events around a batch of them), followed by the
+existing 8-bit "i420" / "nv12" window of the result.
 Prints one JSON line.
 
-    python tools/scale_probe.py [--batch 8] [--reps 25] [--warmup 3]
+    python tools/scale_probe.py [--batch 8] [--reps 25] [--warmup 3] [--hbd]
 """
 import argparse
 import json
@@ -64,12 +68,68 @@ def model(fmt, host, size, dw, dh, crop, plain, color=(0, 0)):
     return CM.to_i420(host, *color) if plain else CM.scale_to_i420(host, dw, dh, crop, *color)
 
 
+HBD_DEPTH = 10
+
+
+def hbd_main(a):
+    """4K -> 1080p of the 16-bit and 4:4:4 layouts against torch's quantiser / 2x2 mean in front of the 8-bit window"""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import hbd_model as HM
+    from ingest_probe import hbd_two_step
+    P = pkg.load_pkg()
+    assert P.load().h264e_hip_device_count() > 0, "no HIP device visible"
+    (sw, sh), (dw, dh) = (3840, 2160), (1920, 1080)
+    rng = np.random.default_rng(3)
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    line = {"batch": a.batch, "reps": a.reps, "warmup": a.warmup, "depth": HBD_DEPTH, "window": "3840x2160 -> 1920x1080", "us_per_frame": {}, "min_max_us": {}}
+    for fmt in HM.FORMATS:
+        cw, ch = (sw, sh) if HM.is_444(fmt) else (sw // 2, sh // 2)
+        top = 1 << (HBD_DEPTH if HM.is_16(fmt) else 8)
+        host = [[rng.integers(0, top, s).astype(np.int16 if HM.is_16(fmt) else np.uint8) for s in ((sh, sw), (ch, cw), (ch, cw))] for _ in range(a.batch)]
+        parts = [[f[0], HM.interleave(f[1], f[2])] if fmt.startswith("nv12") else f for f in host]
+        dev = [tuple(torch.from_numpy(p).cuda() for p in f) for f in parts]
+        kw = dict(depth=HBD_DEPTH) if HM.is_16(fmt) else {}
+        ce, ce8 = (P.ClipEncoder(dw, dh, a.batch, gop=30, qp=26) for _ in range(2))
+        ce.upload_device(dev, fmt, src_size=(sw, sh), **kw)
+        assert np.array_equal(ce.download(0, 1)[0], HM.slot(host[0], fmt, HBD_DEPTH, dw, dh)), fmt + ": the slot differs from the model"
+        new_ms, torch_ms, old_ms = [], [], []
+        for rep in range(a.warmup + a.reps):
+            before = ce.input_time(True)
+            ce.upload_device(dev, fmt, src_size=(sw, sh), **kw)
+            after = ce.input_time(True)
+            ev[0].record()
+            made = [hbd_two_step(torch, f, fmt) for f in dev]
+            ev[1].record()
+            ev[1].synchronize()
+            before8 = ce8.input_time(True)
+            # 4:4:4: the mean has halved the chroma planes, the 8-bit source is a 4:2:0 frame of the luma's size
+            ce8.upload_device([m[0] for m in made], made[0][1], src_size=(sw, sh))
+            after8 = ce8.input_time(True)
+            if rep >= a.warmup:
+                new_ms.append((after[0] - before[0]) / a.batch)
+                torch_ms.append(ev[0].elapsed_time(ev[1]) / a.batch)
+                old_ms.append((after8[0] - before8[0]) / a.batch)
+        if not HM.is_444(fmt):                      # 4:4:4's two steps average before they scale: another (twice rounded) picture
+            assert np.array_equal(ce8.download(0, 1)[0], ce.download(0, 1)[0]), fmt + ": the two paths differ"
+        ce.close()
+        ce8.close()
+        for name, ms in ((fmt, new_ms), (fmt + "_torch_part", torch_ms), (fmt + "_8bit_window_part", old_ms), (fmt + "_via_torch", [x + y for x, y in zip(torch_ms, old_ms)])):
+            line["us_per_frame"][name] = round(1e3 * statistics.median(ms), 2)
+            line["min_max_us"][name] = [round(1e3 * min(ms), 2), round(1e3 * max(ms), 2)]
+        line[fmt + "_over_via_torch"] = round(line["us_per_frame"][fmt] / line["us_per_frame"][fmt + "_via_torch"], 3)
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--hbd", action="store_true", help="time the 16-bit and 4:4:4 layouts (enc_hbd.h) against torch + the 8-bit window instead")
     a = ap.parse_args()
+    if a.hbd:
+        return hbd_main(a)
     import torch
     P = pkg.load_pkg()
     assert P.load().h264e_hip_device_count() > 0, "no HIP device visible"
