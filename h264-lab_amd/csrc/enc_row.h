@@ -523,7 +523,7 @@ DEV void row_end(RowLds &L, const h264e_geom_t &G, const ChainG &C, int row)
     gu8 *M = (gu8 *)(C.rowmeta + row);       /* {nbits, lead_skips, trail_skips, overflow}: read by the finalizer workgroup */
     if (wave_lane() == 0)
     {
-        g_atomic_add(C.far_reads, L.far_reads[0] + L.far_reads[1] + L.far_reads[2]);
+        g_atomic_store(C.far_reads + row, L.far_reads[0] + L.far_reads[1] + L.far_reads[2]);      /* stays with the row, like its bits, when the frame goes again from a lower one */
         cstore32(M, nbits);
         cstore32(M + 4, (uint32_t)(L.coded_any ? L.lead_skips : G.nmbx));
         cstore32(M + 8, (uint32_t)(L.coded_any ? L.skip_run : 0));
@@ -712,7 +712,7 @@ struct JobWalk
     }
 };
 
-struct SpliceOut { uint32_t start, nbytes; int overflow, all_skipped; };
+struct SpliceOut { uint32_t start, nbytes; int overflow, all_skipped, far_reads; };
 
 /* The slices' RBSPs from the row bit buffers.  on_row(first row of the slice, row) is called before a row is touched: the caller waits
  * for the row there (and walks it); a non-zero return ends the splice with that code (nothing is committed). */
@@ -721,7 +721,7 @@ template <class ROW> DEV int splice_frame(const h264e_geom_t &G, const ChainG &C
     SpliceState s;
     const uint32_t start = T.arena_reset ? 0u : ((*C.cursor + 15u) & ~15u);
     uint32_t off = 0;                                                           /* of the current slice, relative to start */
-    int overflow = 0, all_skipped = 0, spl_overflow = 0;
+    int overflow = 0, all_skipped = 0, spl_overflow = 0, far_reads = 0;
     GLOBAL_AS h264e_frameout_t &F = C.fout[T.frame_slot];
     /* one RBSP per slice (row band); the slices of a frame lie behind each other, each starting 16-byte aligned */
     for (int k = 0; k < T.nslices; k++)
@@ -741,6 +741,7 @@ template <class ROW> DEV int splice_frame(const h264e_geom_t &G, const ChainG &C
             if (stop) return stop;
             const GLOBAL_AS h264e_rowmeta_t &M = C.rowmeta[row];
             overflow |= M.overflow;
+            far_reads += C.far_reads[row];      /* the frame's own rows only: a frame that was stopped leaves nothing behind in one that ends */
             run += M.lead_skips;
             if (M.lead_skips < G.nmbx || M.nbits)
             {
@@ -762,7 +763,7 @@ template <class ROW> DEV int splice_frame(const h264e_geom_t &G, const ChainG &C
         if (k + 1 < T.nslices) off += (nbytes + 15u) & ~15u; else off += nbytes;
         wave_sync();
     }
-    o.start = start; o.nbytes = off; o.overflow = overflow | spl_overflow; o.all_skipped = all_skipped;
+    o.start = start; o.nbytes = off; o.overflow = overflow | spl_overflow; o.all_skipped = all_skipped; o.far_reads = far_reads;
     return 0;
 }
 
@@ -794,8 +795,7 @@ DEV void finalize_commit(const h264e_geom_t &G, const ChainG &C, const h264e_fra
     F.all_skipped = o.all_skipped;
     F.clusters_moved = moved;
     F.overflow = o.overflow;
-    F.far_reads = g_atomic_load(C.far_reads);
-    if (wave_lane() == 0) g_atomic_store(C.far_reads, 0);
+    F.far_reads = o.far_reads;
     *C.cursor = o.start + ((o.nbytes + 15u) & ~15u);
     stepflags[0] = moved;
     stepflags[1] = o.overflow;

@@ -149,7 +149,7 @@ typedef struct
     uint32_t nal_cap;
     uint32_t *cursor;
     h264e_frameout_t *fout;             /* [frame slots] */
-    int *far_reads;                     /* counter of the frame being encoded (rows add, the finalizer reads and clears) */
+    int *far_reads;                     /* [nmby]: every row's count, written at its end; the finalizer of a frame that ends adds up its rows' */
     unsigned long long *prof;           /* [32] phase cycle sums, written only by the -DH264E_STAMPS diagnostic build */
 } h264e_chain_dev_t;
 

@@ -1032,7 +1032,7 @@ struct H264E_clip_tag
     int first_row;                          /* ... which restarts at this macroblock row */
     int32_t after[2]; int have_after;       /* predicted state behind that frame */
     int narrow;                             /* reference-window geometry in use (h264e_dev.h) */
-    int narrow_ok;                          /* the picture size allows the narrow geometry at all */
+    int narrow_ok;                          /* the picture size allows the narrow geometry at all, and H264E_WIDE_WINDOW was not set when the clip was opened */
     int wide_until, wide_hold;              /* wide geometry until this frame; length of the next wide spell (doubles when narrow fails again) */
     int launch_base, launch_frames;         /* frames per launch: the pipeline depth after a mis-speculation, growing after clean launches (H264E_clip_open) */
     int stopped_before;                     /* the previous launch was stopped before its last frame (statistics: the next one pays a pipeline refill) */
@@ -1123,7 +1123,7 @@ void H264E_clip_rewind(H264E_clip_t *c)
     /* reference-window geometry (h264e_dev.h): narrow = consecutive frames 4 macroblock steps apart, as long as vectors rarely
      * reach more than 12 samples right / down of their macroblock; wide (7 steps) for the rest of the clip otherwise.  Large
      * pictures already fill the GPU's resident workgroups with the wide geometry: the narrow one only pays below ~12k macroblocks */
-    c->narrow_ok = c->narrow = (getenv("H264E_WIDE_WINDOW") || c->seq.nmb > 12000) ? 0 : 1;
+    c->narrow = c->narrow_ok;
     c->wide_until = 0; c->wide_hold = 30; c->far_acc = 0; c->far_frames = 0;
     clip_launch_frames_reset(c);
     memset(&c->rcs, 0, sizeof(c->rcs));
@@ -1144,6 +1144,9 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     c->par.qp = imin(imax(par->qp, 10), 51);
     seq_init(&c->seq, par->width, par->height, par->vbv_size_bytes, 0);
     c->nframes = nframes;
+    /* H264E_WIDE_WINDOW is read here, once: the clip keeps the answer for life, whatever the variable says at a later rewind (clips
+     * opened with and without it can share a launch group) */
+    c->narrow_ok = (getenv("H264E_WIDE_WINDOW") || c->seq.nmb > 12000) ? 0 : 1;
     /* ring of picture / result slots = frames per launch + 1.  Not bounded by residency: workgroups only wait for lower
      * block indices, so a launch larger than the GPU simply streams through it in order. */
     /* default: 96 frames per launch at 1080p and above; small pictures have short pipelines and cheap slots, so they get
@@ -1686,7 +1689,8 @@ typedef struct
     int desired_frame_bytes, qp_min, qp_max, pic_init_qp;
     uint16_t qdat_i[2][42], qdat_p[2][42];  /* constant QP: the quantizer tables of every I / P frame */
     int spin_retries;                       /* launches in a row that a bounded wait ended before a single frame got through */
-    long long far_reads;                    /* of the last launch that delivered its first frame */
+    long long far_reads;                    /* of the frames the current launch delivered (0 when it delivered none) */
+    int debug;                              /* H264E_DEBUG: one line per launch and one per delivered frame */
     H264E_clip_stats_t stats;
 } clip_call_t;
 
@@ -1895,8 +1899,7 @@ static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_
     int rc_miss = 0;
     l->leaf = -1;
     l->t_last = t0;
-    if (ti == 0) { l->t_first = t0; x->far_reads = 0; }
-    x->far_reads += r->far_reads;
+    if (ti == 0) l->t_first = t0;
     if (r->overflow) { snprintf(g_host_err, sizeof(g_host_err), "bit buffer overflow (frame %d)", f); return clip_abort_launch(c); }
     /* the frame as the kernel exported it: complete NALs (start codes and emulation prevention done on the device) */
     if (r->in_device && c->big_cap < r->nbytes) { free(c->big); c->big_cap = (size_t)r->nbytes*2; c->big = (uint8_t *)malloc(c->big_cap); }
@@ -1948,6 +1951,8 @@ static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_
     if (ti == 0) c->first_dev = 0;
     x->stats.assemble_ms += now_ms() - t0;
     l->nvalid++;
+    x->far_reads += r->far_reads;           /* delivered frames only: what clip_adapt divides by */
+    if (x->debug) fprintf(stderr, "clip frame %d: %d far reads\n", f, r->far_reads);
     if (is_hedge) { l->moved_from = slot; l->moved_to = f % c->ring; }
     if (rc_miss)
     {
@@ -2032,6 +2037,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
     h264e_hip_profile(c->pool, profile);
     x.stats.chains = c->ring - 1;
     x.stats.first_frame = x.first;
+    x.debug = getenv("H264E_DEBUG") != NULL;
     l.step = CLIP_GO_ON;
 
     while (c->next < c->avail && l.step != CLIP_STOP_FULL)
@@ -2041,6 +2047,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         if (clip_prepass_scenecut(c, l.limit)) return clip_end(c, &x, st, -1);
         clip_plan_launch(c, &x, &l);
         x.stats.rounds++;
+        x.far_reads = 0;
         l.t_submit = now_ms();
         if (clip_prepass_denoise(c, l.limit) || h264e_hip_submit(c->pool, c->tasks)) return clip_end(c, &x, st, -1);
         /* consume the frames in stream order while the launch is still running */
@@ -2053,7 +2060,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         } while (l.step == CLIP_TAKE_LEAF || (l.step == CLIP_GO_ON && ti < l.F));
         if (l.step == CLIP_ERROR || clip_settle(c, &x, &l)) return clip_end(c, &x, st, -1);
         clip_adapt(c, &x, &l);
-        if (getenv("H264E_DEBUG")) clip_debug_line(c, &x, &l);
+        if (x.debug) clip_debug_line(c, &x, &l);
         if (l.step == CLIP_STOP_FULL && c->next == x.first)
         {
             snprintf(g_host_err, sizeof(g_host_err), "output buffer too small for one frame");

@@ -533,7 +533,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
             C.cursor = (uint32_t *)carve(16, 256);
             C.fout = (h264e_frameout_t *)carve(sizeof(h264e_frameout_t), 256);
             C.prof = (unsigned long long *)carve(sizeof(unsigned long long)*48, 256);     /* 0..31 the rows' phases, 32..47 the finalizer's */
-            C.far_reads = (int *)carve(16, 256);
+            C.far_reads = (int *)carve(sizeof(int)*(size_t)G.nmby, 256);
             p->clu_dev[c] = (int32_t *)carve(sizeof(int32_t)*2*(size_t)G.nmb, 256);      /* per-macroblock mv_clusters array of a re-encode */
             p->traj_dev[c] = (int32_t *)carve(sizeof(int32_t)*4*(size_t)G.nmb, 256);    /* two walk trajectories (device-side validation) */
             /* one result per chain slot, exported by its frame's finalizer to these host-mapped mirrors */

@@ -24,6 +24,21 @@ def pan(w, h, n, step=12):
     return out
 
 
+def vpan(w, h, n, dy, moving):
+    """synth_v1 luma sliding down `dy` samples between frames t and t + 1 wherever moving(t) says so, still otherwise; chroma 128.
+    With dy beyond the search window's height the vectors leave it (far reads), and the spans of motion and stillness decide when the
+    streaming encoder changes its window geometry (tests/test_emu_geometry_switch.py)"""
+    rows = h + dy * n + 16
+    big = synth.frame(w, rows, 0)[: w * rows].reshape(rows, w)
+    out = np.empty((n, w * h * 3 // 2), np.uint8)
+    off = 0
+    for t in range(n):
+        out[t, : w * h] = big[off : off + h].ravel()
+        out[t, w * h :] = 128
+        off += dy if moving(t) else 0
+    return out
+
+
 def extremes(w, h, n, salt=7):
     """0/255 checker blocks of 4x4: saturating residuals and clipping in every stage"""
     out = np.empty((n, w * h * 3 // 2), np.uint8)

@@ -6,6 +6,7 @@ import os
 import tempfile
 
 import clips
+import geometry_switch_cases
 import pkg
 
 LOG_ENV = "H264E_EMU_LAUNCH_LOG"
@@ -62,6 +63,26 @@ def _group(P, w, h, specs, **kw):
             e.close()
 
 
+def _adaptive(P, name):
+    """tests/geometry_switch_cases.py: a stream that changes its window geometry on its own, twice there and once back"""
+    kw, instalments = geometry_switch_cases.SOLO[name]
+    geometry_switch_cases.encode(P, geometry_switch_cases.clip(), geometry_switch_cases.W, geometry_switch_cases.H, instalments, lib=pkg.EMU_LIB, **kw)
+
+
+def _group_mixed_geometry(P):
+    """members that disagree about the geometry, one of them wide for life: rounds of two launches, the wide one first"""
+    saved = os.environ.get("H264E_WIDE_WINDOW")
+    encs = []
+    try:
+        encs = geometry_switch_cases.open_group(P, os.environ.__setitem__, os.environ.pop, lib=pkg.EMU_LIB)
+        P.ClipEncoder.encode_multi(encs)
+    finally:
+        for e in encs:
+            e.close()
+        if saved is not None:
+            os.environ["H264E_WIDE_WINDOW"] = saved
+
+
 # name -> (environment of the case, what runs).  Every kernel variant and both order paths (plain, XCD bands) are reached:
 CASES = {
     "intra_64x48": ({}, lambda P: _one_clip(P, 64, 48, 4, gop=1, qp=26)),                               # variant 0
@@ -77,6 +98,9 @@ CASES = {
     "group_16x2048": ({}, lambda P: _group(P, 16, 2048, (("synth", 8, 30), ("ramp", 6, 30)))),          # variant 4 because two streams are parallel work
     "bands_8_64x48": ({"H264E_XCD_BANDS": "8"}, lambda P: _one_clip(P, 64, 48, 6, gop=30, qp=26)),      # the banded order through submit
     "uhd_3840x2160": ({}, lambda P: _one_clip(P, 3840, 2160, 2, gop=30, qp=30)),                        # the default band policy
+    "adaptive_96x80": ({}, lambda P: _adaptive(P, "cqp")),                                              # narrow, wide, narrow, wide within one stream
+    "adaptive_kbps_96x80": ({}, lambda P: _adaptive(P, "kbps")),                                        # ... with hedge leaves under both
+    "group_mixed_geometry_96x80": ({}, _group_mixed_geometry),                                          # one member opened under H264E_WIDE_WINDOW
 }
 
 

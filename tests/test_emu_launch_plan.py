@@ -25,6 +25,10 @@ def test_the_recorded_plan_has_every_case_and_reaches_every_variant_and_both_ord
     lines = [ln for v in PLAN.values() for ln in v]
     assert {ln.split()[1] for ln in lines} == {"variant=0", "variant=2", "variant=3", "variant=4"}
     assert {ln.split()[0] for ln in lines} == {"narrow=0", "narrow=1"}
+    # both geometries within one stream's own launches -- with and without rate control -- and within one launch group (that a ROUND of it
+    # holds both: tests/test_emu_geometry_switch.py)
+    for name in ("adaptive_96x80", "adaptive_kbps_96x80", "group_mixed_geometry_96x80"):
+        assert {ln.split()[0] for ln in PLAN[name]} == {"narrow=0", "narrow=1"}, name
     # XCD bands pad the order: 8 queues of (ceil(nmby / 8) + 1) entries per job instead of nmby + 1 entries per job
     assert PLAN["bands_8_64x48"] != PLAN["cqp_64x48"] and "nblocks=96 " in PLAN["bands_8_64x48"][0] and "nblocks=24 " in PLAN["cqp_64x48"][0]
     assert "nblocks=288 " in PLAN["uhd_3840x2160"][0]              # the default policy bands a single-slice 4K launch: 2 x 8 x 18, not 2 x 136

@@ -5,13 +5,13 @@ load at the left border; 21 macroblocks (many slides between both borders).  Con
 the strip just loaded, and reads that leave the window), noise (no macroblock is skipped), synth_v1 (skipped and searched macroblocks
 alternate).  Both window geometries, one and two slices, and a relaunch that starts at a macroblock row greater than 0."""
 import functools
-import re
 import subprocess
 import os
 
 import pytest
 
 import clips
+import launch_lines
 import oracle_lib
 import pkg
 
@@ -77,6 +77,6 @@ def test_relaunch_from_a_lower_row_loads_the_whole_window_first(monkeypatch, cap
     name, w, h, n, gop = "pan", 176, 144, 8, 30
     want, want_sizes = reference(name, w, h, n, 0, gop)
     out, sizes, st = encode(name, w, h, n, 0, gop, lib=pkg.EMU_LIB)
-    first_rows = [int(m) for m in re.findall(r"clip launch \d+ \(first row (\d+),", capfd.readouterr().err)]
+    first_rows = [l.first_row for l in launch_lines.parse(capfd.readouterr().err)]
     assert st.reencoded_gops > 0 and max(first_rows) > 0, first_rows
     assert sizes == want_sizes and out == want
