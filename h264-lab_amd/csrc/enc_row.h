@@ -767,13 +767,10 @@ template <class ROW> DEV int splice_frame(const h264e_geom_t &G, const ChainG &C
     return 0;
 }
 
-/* ... and the frame's result record, once the frame stands */
-DEV void finalize_commit(const h264e_geom_t &G, const ChainG &C, const h264e_frame_task_t &T, const SpliceOut &o, GLOBAL_AS int *stepflags)
+/* mv_clusters speculation check of the frame-at-a-time path (its host walks exactly when this says "moved"): is the speculated state
+ * a fixed point of every update of this frame?  Frames validated by the device walk do not need it. */
+DEV int clusters_moved(const h264e_geom_t &G, const h264e_frame_task_t &T, const GLOBAL_AS h264e_mbrec_t *rec)
 {
-    GLOBAL_AS h264e_frameout_t &F = C.fout[T.frame_slot];
-    /* mv_clusters speculation check of the frame-at-a-time path (its host walks exactly when this says "moved"): is the speculated state
-     * a fixed point of every update of this frame?  Frames validated by the device walk do not need it. */
-    const GLOBAL_AS h264e_mbrec_t *rec = C.mbrec + (size_t)T.frame_slot*G.nmb;
     int moved = 0;
     if (!T.clusters_per_mb && !T.walk_on_device)
     {
@@ -789,6 +786,14 @@ DEV void finalize_commit(const h264e_geom_t &G, const ChainG &C, const h264e_fra
             if (bad) moved = 1;
         }
     }
+    return moved;
+}
+
+/* ... and the frame's result record, once the frame stands */
+DEV void finalize_commit(const h264e_geom_t &G, const ChainG &C, const h264e_frame_task_t &T, const SpliceOut &o, GLOBAL_AS int *stepflags)
+{
+    GLOBAL_AS h264e_frameout_t &F = C.fout[T.frame_slot];
+    const int moved = clusters_moved(G, T, C.mbrec + (size_t)T.frame_slot*G.nmb);
     F.offset = o.start;
     F.nbytes = o.nbytes;
     F.nslices = T.nslices;

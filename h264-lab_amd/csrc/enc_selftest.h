@@ -1,6 +1,6 @@
 /*
  * enc_selftest.h -- device-level code that only tests and the bench input use: the per-stage test hook (one wave-level stage of the
- * macroblock pipeline on caller-supplied operands) and the synth_v1 clip generator.  Wave64 model like the rest (wave.h).
+ * macroblock pipeline on caller-supplied operands), the finalizer test hook and the synth_v1 clip generator.  Wave64 model like the rest (wave.h).
  */
 #ifndef H264E_ENC_SELFTEST_H
 #define H264E_ENC_SELFTEST_H
@@ -295,6 +295,75 @@ DEV void stage_selftest(StageLds &S, RowLds &L, int stage, const GLOBAL_AS uint8
         const uint32_t nbits = bw_bits(b);
         if (b.nacc) bw_put(b, 32 - b.nacc, 0);
         if (wave_lane() == 0) { oi[0] = (int32_t)nbits; oi[1] = b.overflow; }
+    }
+}
+
+/* ------------------------------------------------------------------ finalizer test hook (tests/test_finalizer.py)
+ * Runs the finalizer wave's own functions (enc_row.h "slice splice") on caller-supplied operands, in the geometry of the pool (nmbx, nmby,
+ * row_words).  The host side (h264e_pool.h h264e_hip_selftest_finalizer) builds the task and the chain descriptor in device memory as a
+ * submit would, pointing at the operands; nothing here waits: on_row returns 0 at once, no counter, abort word or verdict is polled.
+ *   1 splice   splice_frame (splice_put / splice_words / put_ue64) over C.rowmeta / C.far_reads / C.rowbits into C.arena
+ *              hdr: int32 status, start, nbytes, overflow, all_skipped, far_reads, 0, 0, slice_nbytes[16]
+ *   2 walk     JobWalk begin / rows(upto) ... / end, device_clusters_walk and clusters_moved over C.mbrec
+ *              args: [2..3] start state, [6] n, [32..32+n) the upto values      traj: JobWalk's [nmb][2], then the whole-frame walk's
+ *              hdr: int32 JobWalk first_bad, state[2] | whole-frame walk first_bad, state[2] | moved
+ *   3 step     clusters_step and mvround            args: [0] n      in: n x int32 (c0, c1, mv)
+ *              out: n x int32 (c0', c1', mvround(c0), mvround(c1), mvround(mv))
+ */
+#define FZ_NARGS 96
+#define FZ_HDR_INTS 32
+#define FZ_STEP_MAX 4096
+DEV void finalizer_selftest(const h264e_geom_t &G, const h264e_frame_task_t &T, int mode, const int *args, const GLOBAL_AS int32_t *in, GLOBAL_AS int32_t *hdr, GLOBAL_AS mv32 *traj)
+{
+    if (mode == 1)
+    {
+        const ChainG C = chain_view(*T.chain_desc);
+        SpliceOut so = { 0, 0, 0, 0, 0 };
+        const int st = splice_frame(G, C, T, so, [&](int, int) -> int { return 0; });
+        drain_stores();
+        wave_sync();
+        if (wave_lane() == 0)
+        {
+            hdr[0] = st; hdr[1] = (int32_t)so.start; hdr[2] = (int32_t)so.nbytes; hdr[3] = so.overflow; hdr[4] = so.all_skipped; hdr[5] = so.far_reads;
+            for (int k = 0; k < H264E_MAX_SLICES; k++) hdr[8 + k] = k < T.nslices ? (int32_t)C.fout[T.frame_slot].slice_nbytes[k] : 0;
+        }
+    } else if (mode == 2)
+    {
+        const ChainG C = chain_view(*T.chain_desc);
+        const GLOBAL_AS h264e_mbrec_t *rec = C.mbrec + (size_t)T.frame_slot*G.nmb;
+        const mv32 s0[2] = { (mv32)uni(args[2]), (mv32)uni(args[3]) };
+        const int n = uni(args[6]);
+        JobWalk W;
+        W.begin(s0);
+        for (int i = 0; i < n; i++) W.rows(G, T, rec, traj, uni(args[32 + i]));
+        W.end(T);
+        mv32 s[2] = { s0[0], s0[1] };
+        const int fb = device_clusters_walk(G, T, rec, s, traj + 2*(size_t)G.nmb);
+        const int moved = clusters_moved(G, T, rec);
+        if (wave_lane() == 0)
+        {
+            hdr[0] = W.first_bad; hdr[1] = W.s[0]; hdr[2] = W.s[1];
+            hdr[3] = fb; hdr[4] = s[0]; hdr[5] = s[1];
+            hdr[6] = moved;
+        }
+    } else if (mode == 3)
+    {
+        const int n = uni(args[0]);
+        for (int base = 0; base < n; base += 64)
+        {
+            WAVE_FOR(l)
+            {
+                const int k = base + l;
+                if (k < n)
+                {
+                    mv32 c[2] = { in[3*k], in[3*k + 1] };
+                    const mv32 mv = in[3*k + 2];
+                    clusters_step(c, mv);
+                    hdr[5*k] = c[0]; hdr[5*k + 1] = c[1];
+                    hdr[5*k + 2] = mvround(in[3*k]); hdr[5*k + 3] = mvround(in[3*k + 1]); hdr[5*k + 4] = mvround(mv);
+                }
+            }
+        }
     }
 }
 

@@ -350,6 +350,12 @@ static int clusters_walk(int32_t c[2], const h264e_hip_mbrec_t *rec, int nmbx, i
     return first_bad;
 }
 
+/* test hook: clusters_walk itself (tests/test_finalizer.py compares it with the device's walks and the plain model) */
+int h264e_hip_selftest_host_clusters_walk(int32_t state[2], const h264e_hip_mbrec_t *rec, int nmbx, int nmby, int nslices, const int32_t *used, int per_mb, int32_t *traj)
+{
+    return clusters_walk(state, rec, nmbx, nmby, nslices, used, per_mb, traj);
+}
+
 /* ------------------------------------------------------------------ rate control (frame level) */
 
 typedef struct { int qp, prev_qp, vbv_bits, qp_smooth, dqp_smooth, max_dqp, bit_budget, vbv_target_level; } rc_t;

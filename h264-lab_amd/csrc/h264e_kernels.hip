@@ -658,6 +658,11 @@ __global__ void __launch_bounds__(64) h264e_stage_selftest_kernel(int stage, con
     stage_selftest(S, L, stage, (const GLOBAL_AS uint8_t *)in, args, (GLOBAL_AS uint8_t *)out);
 }
 
+__global__ void __launch_bounds__(64) h264e_finalizer_selftest_kernel(h264e_geom_t G, const h264e_frame_task_t *task, int mode, const int *args, const int32_t *in, int32_t *hdr, mv32 *traj)
+{
+    finalizer_selftest(G, *task, mode, args, (const GLOBAL_AS int32_t *)in, (GLOBAL_AS int32_t *)hdr, (GLOBAL_AS mv32 *)traj);
+}
+
 __global__ void h264e_synth_kernel(uint8_t *dst, int w, int h, int t, uint32_t seed)
 {
     const int n = w*h*3/2;
@@ -983,6 +988,10 @@ static void bk_launch_scenecut(const uint8_t *luma, uint32_t nbytes, int *record
 static void bk_launch_stage_selftest(int stage, const uint8_t *in, const int *args, uint8_t *out, hipStream_t st)
 {
     hipLaunchKernelGGL(h264e_stage_selftest_kernel, dim3(1), dim3(64), 0, st, stage, in, args, out);
+}
+static void bk_launch_finalizer_selftest(const h264e_geom_t &G, const h264e_frame_task_t *task, int mode, const int *args, const int32_t *in, int32_t *hdr, mv32 *traj, hipStream_t st)
+{
+    hipLaunchKernelGGL(h264e_finalizer_selftest_kernel, dim3(1), dim3(64), 0, st, G, task, mode, args, in, hdr, traj);
 }
 /* n frames x planes (3, or 1 for a plane pair) in one launch, then the means */
 static void bk_launch_ssim(const h264e_ssim_args_t &A, int n, int planes, hipStream_t st)

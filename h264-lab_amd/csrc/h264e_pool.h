@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut and bk_launch_ssim; the emulation's versions of those seven are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those eight are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -2096,6 +2096,120 @@ extern "C" int h264e_hip_selftest_stage(h264e_hip_pool_t *p, int stage, const ui
     if (e == hipSuccess) e = hipMemcpy(out, buf + STAGE_IN_MAX + 128, nout, hipMemcpyDeviceToHost);
     (void)hipFree(buf);
     if (e != hipSuccess) FAIL("selftest_stage: %s", hipGetErrorString(e));
+    return 0;
+}
+
+/* test hook: the finalizer wave's functions on caller-supplied operands in this pool's geometry (enc_selftest.h finalizer_selftest lists
+ * the modes).  The task and the chain descriptor are built in device memory as a submit builds them, pointing into one allocation:
+ *   args (all modes that have slices): [5] nslices, [10..26] slice_row[17]
+ *   1 splice  args: [0] slice_type, [1] hdr_nal, [2] hdr_nbits, [3] / [4] low / high word of hdr_bits, [6] arena_reset, [7] cursor,
+ *                   [8] arena capacity, [9] guard bytes behind it
+ *             in:   h264e_rowmeta_t[nmby] | int32 far_reads[nmby] | per row its first (nbits + 31)/32 words, row after row
+ *             out:  int32 hdr[32] | the arena, capacity + guard bytes; it holds 0xA5 wherever the splice did not write
+ *   2 walk    args: [1] per-macroblock candidates, [2..3] start state, [6] n, [7..8] the frame's candidate pair, [32..32+n) upto values
+ *             in:   h264e_mbrec_t[nmb] | mv32 per_mb[nmb][2] (with args[1])
+ *             out:  int32 hdr[32] | mv32 traj[2][nmb][2] (0xA5 bytes where nothing was written)
+ *   3 step    args: [0] n     in: n x 3 int32     out: n x 5 int32 */
+#ifdef H264E_EMU
+/* the emulation's launch: the one wave as a lane loop (here, not in the emulation's backend, so that a backend written before this hook still builds) */
+static void bk_launch_finalizer_selftest(const h264e_geom_t &G, const h264e_frame_task_t *task, int mode, const int *args, const int32_t *in, int32_t *hdr, mv32 *traj, hipStream_t)
+{
+    finalizer_selftest(G, *task, mode, args, in, hdr, traj);
+}
+#endif
+extern "C" int h264e_hip_selftest_finalizer(h264e_hip_pool_t *p, int mode, const int *args /* [96] */, const uint8_t *in, uint32_t nin, uint8_t *out, uint32_t nout)
+{
+    if (!p || !args || !in || !out || mode < 1 || mode > 3) FAIL("selftest_finalizer: bad argument");
+    const h264e_geom_t &G = p->G;
+    const size_t A = 256;
+    const auto up = [&](size_t n) { return (n + A - 1) & ~(A - 1); };
+    h264e_frame_task_t T;
+    h264e_chain_dev_t D;
+    memset(&T, 0, sizeof(T)); memset(&D, 0, sizeof(D));
+    T.active = 1;
+    size_t in_bytes = 0, out_bytes = 0, row_off = 0;
+    if (mode != 3)
+    {
+        T.nslices = args[5];
+        if (T.nslices < 1 || T.nslices > H264E_MAX_SLICES || T.nslices > G.nmby || args[10] != 0 || args[10 + T.nslices] != G.nmby) FAIL("selftest_finalizer: bad slice rows");
+        for (int k = 0; k <= T.nslices; k++)
+        {
+            if (k && args[10 + k] <= args[10 + k - 1]) FAIL("selftest_finalizer: bad slice rows");
+            T.slice_row[k] = (int16_t)args[10 + k];
+        }
+    }
+    const h264e_rowmeta_t *meta = (const h264e_rowmeta_t *)in;
+    if (mode == 1)
+    {
+        const uint32_t cap = (uint32_t)args[8], guard = (uint32_t)args[9];
+        row_off = (size_t)G.nmby*(sizeof(h264e_rowmeta_t) + sizeof(int));
+        if (args[2] < 0 || args[2] > 56 || cap > (4u << 20) || guard > 4096u || (uint32_t)args[7] > (4u << 20) || nin < row_off) FAIL("selftest_finalizer: bad splice argument");
+        in_bytes = row_off;
+        for (int r = 0; r < G.nmby; r++)
+        {
+            if (meta[r].nbits > (uint32_t)G.row_words*32u || meta[r].lead_skips < 0 || meta[r].lead_skips > G.nmbx || meta[r].trail_skips < 0 || meta[r].trail_skips > G.nmbx)
+                FAIL("selftest_finalizer: bad row %d", r);
+            in_bytes += 4*(size_t)((meta[r].nbits + 31) >> 5);
+        }
+        out_bytes = FZ_HDR_INTS*4 + (size_t)cap + guard;
+        T.slice_type = args[0]; T.hdr_nal = args[1]; T.hdr_nbits = args[2]; T.hdr_bits = (uint64_t)(uint32_t)args[3] | ((uint64_t)(uint32_t)args[4] << 32);
+        T.arena_reset = args[6];
+        D.arena_cap = cap;
+    } else if (mode == 2)
+    {
+        const int n = args[6];
+        if (n < 1 || n > FZ_NARGS - 32 || args[32 + n - 1] != G.nmby - 1) FAIL("selftest_finalizer: bad walk argument");
+        for (int i = 0; i < n; i++) if (args[32 + i] < 0 || args[32 + i] >= G.nmby) FAIL("selftest_finalizer: bad walk argument");
+        in_bytes = (size_t)G.nmb*(sizeof(h264e_mbrec_t) + (args[1] ? 2*sizeof(mv32) : 0));
+        out_bytes = FZ_HDR_INTS*4 + (size_t)G.nmb*16;
+        T.clusters[0] = args[7]; T.clusters[1] = args[8];
+    } else
+    {
+        if (args[0] < 1 || args[0] > FZ_STEP_MAX) FAIL("selftest_finalizer: bad step argument");
+        in_bytes = (size_t)args[0]*12; out_bytes = (size_t)args[0]*20;
+    }
+    if (nin != in_bytes || nout != out_bytes) FAIL("selftest_finalizer: operands of %u / %u bytes where mode %d takes %zu / %zu", nin, nout, mode, in_bytes, out_bytes);
+    /* one allocation: task | chain descriptor | args | input | row bit buffers (splice) | frame record + cursor | output */
+    const size_t oT = 0, oD = oT + up(sizeof(T)), oA = oD + up(sizeof(D)), oIn = oA + up(FZ_NARGS*sizeof(int)), oRows = oIn + up(in_bytes);
+    const size_t oF = oRows + (mode == 1 ? up((size_t)G.nmby*G.row_words*4) : 0), oOut = oF + up(sizeof(h264e_frameout_t) + 16), total = oOut + up(out_bytes);
+    uint8_t *buf = 0;
+    HIPCHK(hipSetDevice(p->device));
+    if (hipMalloc((void **)&buf, total) != hipSuccess) FAIL("selftest_finalizer: device allocation failed");
+    uint8_t *const body = buf + oOut + FZ_HDR_INTS*4;
+    D.rowmeta = (h264e_rowmeta_t *)(buf + oIn); D.far_reads = (int *)(buf + oIn + (size_t)G.nmby*sizeof(h264e_rowmeta_t));
+    D.rowbits = (uint32_t *)(buf + oRows);
+    D.mbrec = (h264e_mbrec_t *)(buf + oIn);
+    D.fout = (h264e_frameout_t *)(buf + oF); D.cursor = (uint32_t *)(buf + oF + sizeof(h264e_frameout_t));
+    D.arena = body;
+    T.chain_desc = (const h264e_chain_dev_t *)(buf + oD);
+    if (mode == 2 && args[1]) T.clusters_per_mb = (const mv32 *)(buf + oIn + (size_t)G.nmb*sizeof(h264e_mbrec_t));
+    hipError_t e = hipMemset(buf + oF, 0, oOut - oF + FZ_HDR_INTS*4);
+    if (e == hipSuccess && mode != 3) e = hipMemset(body, 0xA5, out_bytes - FZ_HDR_INTS*4);
+    if (e == hipSuccess) e = hipMemcpy(buf + oT, &T, sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + oD, &D, sizeof(D), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + oA, args, FZ_NARGS*sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + oIn, in, mode == 1 ? row_off : in_bytes, hipMemcpyHostToDevice);
+    if (mode == 1)
+    {
+        const uint32_t cursor = (uint32_t)args[7];
+        const uint8_t *src = in + row_off;
+        if (e == hipSuccess) e = hipMemcpy(D.cursor, &cursor, 4, hipMemcpyHostToDevice);
+        for (int r = 0; r < G.nmby && e == hipSuccess; r++)
+        {
+            const size_t n = 4*(size_t)((meta[r].nbits + 31) >> 5);
+            if (n) e = hipMemcpy(buf + oRows + (size_t)r*G.row_words*4, src, n, hipMemcpyHostToDevice);
+            src += n;
+        }
+    }
+    if (e == hipSuccess)
+    {
+        int32_t *hdr = (int32_t *)(buf + oOut);
+        bk_launch_finalizer_selftest(G, (const h264e_frame_task_t *)(buf + oT), mode, (const int *)(buf + oA), (const int32_t *)(buf + oIn), hdr, (mv32 *)body, p->stream);
+        e = hipStreamSynchronize(p->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, buf + oOut, out_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) FAIL("selftest_finalizer: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -257,6 +257,13 @@ int  h264e_hip_selftest_nal_escape(h264e_hip_pool_t *pool, const uint8_t *src, u
 /* test hook: one wave-level stage of the macroblock pipeline on caller-supplied operands (h264e_kernels.hip stage_selftest lists
  * the stages and their operand layouts; tests/test_stages.py and tests/test_stage_edges.py compare them with the reference's own functions) */
 int  h264e_hip_selftest_stage(h264e_hip_pool_t *pool, int stage, const uint8_t *in, uint32_t nin, const int *args /* [24] */, uint8_t *out, uint32_t nout);
+/* test hook: the finalizer wave's own functions -- the slice splice, the mv_clusters walks, the single update step -- on caller-supplied
+ * operands in the pool's geometry (h264e_pool.h lists the modes and operand layouts; tests/test_finalizer.py compares them with
+ * tests/finalizer_model.py and tests/golden/finalizer.json) */
+int  h264e_hip_selftest_finalizer(h264e_hip_pool_t *pool, int mode, const int *args /* [96] */, const uint8_t *in, uint32_t nin, uint8_t *out, uint32_t nout);
+/* test hook: the host's own mv_clusters walk of one frame (h264e_host.c clusters_walk; slices split nmby evenly as the encoder splits them);
+ * returns the first mismatching macroblock or -1, state = the state behind the frame, traj (optional) [nmb][2] */
+int  h264e_hip_selftest_host_clusters_walk(int32_t state[2], const h264e_hip_mbrec_t *rec, int nmbx, int nmby, int nslices, const int32_t *used, int per_mb, int32_t *traj);
 const char *h264e_hip_last_error(void);
 
 #ifdef __cplusplus

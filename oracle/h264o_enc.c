@@ -1364,6 +1364,17 @@ void h264o_test_strengths(uint32_t nzflag, const int32_t *df_mv /* [25] */, int 
 
 void h264o_test_partition_hints(const int *sad, int *mode) { partition_hints(sad, mode); }
 
+/* the mv_clusters update and the quarter-sample rounding on packed vectors (tests/golden/finalizer.json) */
+void h264o_test_clusters_update(int32_t c[2], int32_t mv)
+{
+    static h264o_enc_t e;
+    e.clusters[0] = c[0]; e.clusters[1] = c[1];
+    clusters_update(&e, mv);
+    c[0] = e.clusters[0]; c[1] = e.clusters[1];
+}
+
+int32_t h264o_test_mvround(int32_t v) { return mvround(v); }
+
 int h264o_test_mv_cost(int vx, int vy, int px, int py, int qp)
 {
     static h264o_enc_t e;

@@ -25,6 +25,10 @@
  *   df_strength                         h264-lab.h:5535     here for the strengths themselves
  *   mb_inter_partition, me_mv_cost      h264-lab.h:5224/4952
  *   h264e_bs_put_bits / _golomb / _sgolomb   h264-lab.h:2688/2738/2760
+ * `stage_harness finalizer` prints tests/golden/finalizer.json (own seed; finalizer() at the end of this file): what the frame finalizer's
+ * exact mv_clusters walk restates, from the reference's own
+ *   mv_clusters_update                  h264-lab.h:5263     single steps at the edges of both comparisons and of the vector range, seeded sequences
+ *   mv_round_qpel                       h264-lab.h:3498     every component in -8..8
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -59,6 +63,7 @@ static void fill_pic(uint8_t *p, int w, int h, int amp)
 }
 
 static int edges(h264e_enc_t *enc);
+static int finalizer(h264e_enc_t *enc);
 
 int main(int argc, char **argv)
 {
@@ -81,6 +86,13 @@ int main(int argc, char **argv)
         int r;
         enc->scratch = (scratch_t *)scratch;
         r = edges(enc);
+        free(scratch); free(enc);
+        return r;
+    }
+
+    if (argc > 1 && !strcmp(argv[1], "finalizer"))
+    {
+        int r = finalizer(enc);
         free(scratch); free(enc);
         return r;
     }
@@ -1251,5 +1263,61 @@ static int edges(h264e_enc_t *enc)
         }
     }
     printf("\n ]\n}\n");
+    return 0;
+}
+
+/* ================================================================== `stage_harness finalizer` -> tests/golden/finalizer.json
+ * The two functions the finalizer's mv_clusters walk restates (oracle, host and device each have their own copy): inputs and the
+ * reference's outputs, vectors as [x, y] in quarter samples. */
+static int finalizer(h264e_enc_t *enc)
+{
+    /* states (short | long): zero; ordinary; all negative (the >> 6 acts on a negative sum); long shorter than short (a vector can move
+     * neither); mixed signs; +-2048; the int16 extremes (never both components -32768: the squared norm would leave int) */
+    static const int st[][4] = {
+        { 0, 0, 0, 0 }, { 3, 4, 30, 40 }, { -3, -4, -30, -40 }, { 40, 30, 3, 4 }, { -7, 9, 64, -64 }, { 2048, -2048, -2048, 2048 },
+        { 32767, -32768, -32768, 32767 }, { -32768, 0, 0, 32767 }, { 1, -1, -1, 1 }, { 0, 0, -2048, 2048 }, { -129, 63, -1, -63 } };
+    /* vectors: norms equal to, just under and over those of the states above (25, 2500), every sign, the same extremes */
+    static const int vs[][2] = {
+        { 0, 0 }, { 5, 0 }, { -4, 3 }, { 0, -5 }, { 4, -2 }, { 50, 0 }, { -30, -40 }, { 10, 0 }, { -1, -1 }, { 1, 1 }, { -33, 31 }, { 31, -33 },
+        { 2048, 2048 }, { -2048, -2048 }, { 2048, -2048 }, { 32767, 32767 }, { -32768, 32767 }, { 32767, -32768 }, { -32768, 0 }, { 0, -32768 },
+        { -64, 64 }, { 63, -63 }, { 49, 9 }, { 51, 0 } };
+    int i, j, k, first = 1;
+    g_seed = 24680;
+    printf("{\n \"generator\": \"oracle/stage_harness.c finalizer against the reference header (h264-lab.h), make -C oracle finalizer\",\n");
+    printf(" \"round\": [");                                     /* [v, x of mv_round_qpel(v, -v), y of it] */
+    for (i = -8; i <= 8; i++)
+    {
+        const point_t r = mv_round_qpel(point(i, -i));
+        printf("%s[%d,%d,%d]", i > -8 ? "," : "", i, r.s.x, r.s.y);
+    }
+    printf("],\n \"steps\": [\n");                              /* [short, long, vector, short', long'] */
+    for (i = 0; i < (int)(sizeof(st)/sizeof(st[0])); i++)
+        for (j = 0; j < (int)(sizeof(vs)/sizeof(vs[0])); j++)
+        {
+            enc->mv_clusters[0] = point(st[i][0], st[i][1]); enc->mv_clusters[1] = point(st[i][2], st[i][3]);
+            mv_clusters_update(enc, point(vs[j][0], vs[j][1]));
+            printf("%s  [%d,%d,%d,%d,%d,%d,%d,%d,%d,%d]", first ? "" : ",\n", st[i][0], st[i][1], st[i][2], st[i][3], vs[j][0], vs[j][1],
+                   enc->mv_clusters[0].s.x, enc->mv_clusters[0].s.y, enc->mv_clusters[1].s.x, enc->mv_clusters[1].s.y);
+            first = 0;
+        }
+    printf("\n ],\n \"sequences\": [\n");
+    for (k = 0; k < 3; k++)
+    {
+        /* 0: small vectors around zero with a rare long one; 1: two populations, a short and a long one; 2: the whole +-2048 range */
+        static const int start[3][4] = { { 0, 0, 0, 0 }, { 2, 1, -100, 36 }, { -600, 200, 900, -1500 } };
+        enc->mv_clusters[0] = point(start[k][0], start[k][1]); enc->mv_clusters[1] = point(start[k][2], start[k][3]);
+        printf("  {\"steps\": [\n");                            /* [short, long in front of the vector, vector] */
+        for (i = 0; i < 300; i++)
+        {
+            int x, y;
+            if (k == 0) { const int big = rnd() % 16 == 0; x = (int)(rnd() % (big ? 257u : 33u)) - (big ? 128 : 16); y = (int)(rnd() % (big ? 257u : 33u)) - (big ? 128 : 16); }
+            else if (k == 1) { const int lg = rnd() % 3 == 0; x = (lg ? -120 : 2) + (int)(rnd() % 9u) - 4; y = (lg ? 40 : 1) + (int)(rnd() % 9u) - 4; }
+            else { x = (int)(rnd() % 4097u) - 2048; y = (int)(rnd() % 4097u) - 2048; }
+            printf("%s   [%d,%d,%d,%d,%d,%d]", i ? ",\n" : "", enc->mv_clusters[0].s.x, enc->mv_clusters[0].s.y, enc->mv_clusters[1].s.x, enc->mv_clusters[1].s.y, x, y);
+            mv_clusters_update(enc, point(x, y));
+        }
+        printf("\n  ], \"end\": [%d,%d,%d,%d]}%s\n", enc->mv_clusters[0].s.x, enc->mv_clusters[0].s.y, enc->mv_clusters[1].s.x, enc->mv_clusters[1].s.y, k < 2 ? "," : "");
+    }
+    printf(" ]\n}\n");
     return 0;
 }

@@ -96,7 +96,27 @@ def ramp(w, h, n, salt=5):
     return out
 
 
+def still(w, h, n):
+    """synth_v1 frame 0 held for all frames but the last, which is frame 3 (A, A, A, B at n = 4): the P frames in the middle find nothing
+    to code -- wholly skipped frames, one run over the whole picture -- and the last one codes again"""
+    a, b = synth.frame(w, h, 0), synth.frame(w, h, 3)
+    return np.stack([a] * (n - 1) + [b])
+
+
+def half_still(w, h, n):
+    """the upper macroblock rows hold synth_v1 frame 0, the lower ones follow the clip: wholly skipped rows above coded ones"""
+    out = synth.clip(w, h, n)
+    top = max(h // 32, 1) * 16
+    a = out[0].copy()
+    cw = w // 2
+    for t in range(1, n):
+        out[t, : w * top] = a[: w * top]
+        for o in (w * h, w * h + cw * (h // 2)):
+            out[t, o: o + cw * (top // 2)] = a[o: o + cw * (top // 2)]
+    return out
+
+
 def make(name, w, h, n):
     if name == "synth":
         return synth.clip(w, h, n)
-    return {"noise": noise, "pan": pan, "extremes": extremes, "scene": scene, "ramp": ramp}[name](w, h, n)
+    return {"noise": noise, "pan": pan, "extremes": extremes, "scene": scene, "ramp": ramp, "still": still, "half_still": half_still}[name](w, h, n)
