@@ -479,6 +479,10 @@ def load(path=None):
     L.H264E_clip_set_scenecut.argtypes = [C.c_void_p, C.c_int]
     L.H264E_clip_read_scenecut.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.H264E_clip_scenecut_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
+    L.H264E_clip_set_qp_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.H264E_clip_set_lookahead.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.H264E_clip_read_lookahead.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.H264E_clip_lookahead_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.H264E_clip_position.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.H264E_clip_position.restype = None
     L.H264E_clip_revalidate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -677,7 +681,7 @@ class ClipEncoder:
 
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
                  clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0,
-                 color=None, fps=None, quality=None):
+                 color=None, fps=None, quality=None, qp_schedule=None, abr_kbps=0, lookahead=0, qp_range=(0, 0)):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
         self._ssd = self._ssim = None           # the registered metric arrays [nframes][3], owned here while registered
@@ -699,6 +703,10 @@ class ClipEncoder:
                 self.set_frame_rate(fps)
             if quality:
                 self.set_quality(**(quality if isinstance(quality, dict) else {}))
+            if qp_schedule is not None and len(qp_schedule):
+                self.set_qp_schedule(qp_schedule)
+            if abr_kbps:
+                self.set_lookahead(abr_kbps, lookahead, qp_range)
         except H264EError:
             self.close()
             raise
@@ -764,6 +772,43 @@ class ClipEncoder:
         if self.L.H264E_clip_read_scenecut(self.c, 0, nxt.value, dist.ctypes.data, cut.ctypes.data):
             raise _err(self.L, "H264E_clip_read_scenecut")
         return dist, cut.astype(bool)
+
+    def set_qp_schedule(self, qp):
+        """A QP per frame (H264E_clip_set_qp_schedule): one value in 10..51 for every frame of the clip, [] clears it; only while the clip
+        stands at frame 0.  The stream is the reference's for qp_min = qp_max = qp[f] on frame f."""
+        q = np.asarray(qp, np.int64).reshape(-1)
+        bad = np.flatnonzero((q < 0) | (q > 255))           # what a byte cannot carry to the library is refused here, in its words
+        if len(bad):
+            raise H264EError("H264E_clip_set_qp_schedule: set_qp_schedule: QP %d of frame %d is outside 10..51" % (q[bad[0]], bad[0]))
+        q = np.ascontiguousarray(q, np.uint8)
+        if self.L.H264E_clip_set_qp_schedule(self.c, q.ctypes.data if len(q) else None, len(q)):
+            raise _err(self.L, "H264E_clip_set_qp_schedule")
+
+    def set_lookahead(self, kbps, window=0, qp_range=(0, 0)):
+        """The lookahead rate control (H264E_clip_set_lookahead): this project's own controller, NOT the reference's kbps mode -- one
+        QP per window of `window` frames (0 = default), chosen inside qp_range (zeros = 10..50) from a cost pass over the input;
+        kbps 0 switches it off; only while the clip stands at frame 0."""
+        if self.L.H264E_clip_set_lookahead(self.c, int(kbps), int(window), int(qp_range[0]), int(qp_range[1])):
+            raise _err(self.L, "H264E_clip_set_lookahead")
+
+    def read_lookahead(self, costs=True, qp=True):
+        """((intra uint64, inter uint64, intra_blocks int32), qp uint8) of the frames encoded so far: the cost records I(f), P(f), N(f)
+        of the lookahead controller's cost pass as a triple, and the QP each frame was given; costs=False gives (None, None, None) for
+        the triple, qp=False gives None for the QPs."""
+        nxt = C.c_int()
+        self.L.H264E_clip_position(self.c, C.byref(nxt), None)
+        n = nxt.value
+        i, p, b, q = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        if self.L.H264E_clip_read_lookahead(self.c, 0, n, i.ctypes.data if costs else None, p.ctypes.data if costs else None,
+                                            b.ctypes.data if costs else None, q.ctypes.data if qp else None):
+            raise _err(self.L, "H264E_clip_read_lookahead")
+        return (i, p, b) if costs else (None, None, None), None if not qp else q
+
+    def lookahead_time(self):
+        """(HIP-event milliseconds inside the cost pass' kernel launches since open, frames they analysed)"""
+        ms, n = C.c_double(), C.c_longlong()
+        self.L.H264E_clip_lookahead_time(self.c, C.byref(ms), C.byref(n))
+        return ms.value, n.value
 
     def scenecut_time(self):
         """(HIP-event milliseconds inside the detector's kernel launches since open, frames they analysed)"""

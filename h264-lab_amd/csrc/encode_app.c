@@ -27,6 +27,10 @@
  * --colour bt709|bt601|bt709-full|bt601-full and --fps N[/D] say in every SPS what the file's samples are and how fast they play
  * (H264E_set_color / H264E_set_frame_rate and their clip forms): the input is YUV, so nothing is converted.  They work on both paths and
  * with --gpus; a value that is not understood ends the run.
+ * --qpfile FILE gives every frame its own QP (H264E_clip_set_qp_schedule: one number in 10..51 per frame, whitespace separated).
+ * --lookahead W together with --kbps K selects this encoder's own window rate control (H264E_clip_set_lookahead, window W frames; `x` =
+ * 32) instead of the reference's controller, which --kbps alone stays; with --stats it adds ONE stdout line, "lookahead: window W, QP
+ * a..b, X kbps for a target of K".  Both belong to the clip path and are refused like --keyframes / --scenecut.
  */
 #define _FILE_OFFSET_BITS 64
 #include <math.h>
@@ -41,6 +45,8 @@ static struct
     int have_input, have_output;
     int gop, qp, kbps, max_frames, speed, stats, psnr, ssim, device, clip, chains, threads, gpus;
     int scenecut, nkey, key_frames[1024];   /* --scenecut threshold (0 = off), --keyframes list */
+    char qp_file[1024];                 /* --qpfile: one QP per frame */
+    int have_qp_file, lookahead, lookahead_kbps;      /* --lookahead W (with --kbps K: the window controller; 0 = not given, -1 = the default window) */
     int matrix, full_range, fps_num, fps_den;   /* --colour, --fps (all 0: nothing is signalled) */
     int unsupported;                    /* a reference option this encoder refuses was given: no stream is written, exit 1 */
 } cmd;
@@ -98,6 +104,8 @@ static void parse_long(const char *p, const char *val)
             cmd.unsupported = 1;
         } else { cmd.fps_num = (int)num; cmd.fps_den = (int)den; }
     }
+    else if (starts("qpfile", p)) { snprintf(cmd.qp_file, sizeof(cmd.qp_file), "%s", v); cmd.have_qp_file = 1; }
+    else if (starts("lookahead", p)) cmd.lookahead = atoi(v) > 0 ? atoi(v) : -1;
     else if (starts("scenecut", p)) cmd.scenecut = atoi(v) > 0 ? atoi(v) : H264E_SCENECUT_DEFAULT;
     else if (starts("gop", p)) cmd.gop = atoi(v);
     else if (starts("qp", p)) cmd.qp = atoi(v);
@@ -152,6 +160,8 @@ static int read_cmdline(int argc, char **argv)
                "    --input,  -i <f>  --output, -o <f>  --gop <n>  --qp <n>  --kbps <n>  --maxframes <n>\n"
                "    --speed <n>  --threads <n>  --stats x  --psnr x  --ssim x  --device <n>  --clip 0|1  --chains <n>  --gpus <n>\n"
                "    --keyframes f1,f2,...  --scenecut <threshold|x>   (clip path only)\n"
+               "    --qpfile <f>   one QP (10..51) per frame, whitespace separated   (clip path only)\n"
+               "    --kbps <n> --lookahead <frames|x>   this encoder's own window rate control instead of the reference's   (clip path only)\n"
                "    --colour bt709|bt601|bt709-full|bt601-full  --fps <n[/d]>   (signalled in the SPS; the samples are not touched)\n");
         return 0;
     }
@@ -444,6 +454,7 @@ static int shard_encode_from(shard_t *s, int from)
             if (ssim_tmp) memcpy(s->ssim + 3*(size_t)f, ssim_tmp + 3*(size_t)i, 3*sizeof(double));
         }
         s->mem_len += nb;
+        if (cmd.lookahead && !st.frames) usleep(200);       /* the window controller starts a window only when its last frame is there: let the uploader work */
         done += st.frames; s->rounds += st.rounds; s->relaunches += st.reencoded_gops; s->enc_ms += st.encode_ms; s->chains = st.chains;
     }
     rc = 0;
@@ -475,6 +486,24 @@ static void *shard_thread(void *arg)
  * it is final, its exact end state is handed over (8 bytes) and H264E_clip_revalidate names the GOP from which the block has
  * to be encoded again, if any; idr_pic_id parity is computed.  The blocks' bytes are written in order at the end.
  */
+/* --qpfile: n whitespace-separated numbers, or NULL with the reason printed */
+static uint8_t *read_qp_file(int n)
+{
+    FILE *f = fopen(cmd.qp_file, "r");
+    uint8_t *qp = (uint8_t *)malloc((size_t)n + 1);
+    int i = 0, v, extra;
+    if (!f || !qp) { printf("ERROR: --qpfile: cant open %s\n", cmd.qp_file); if (f) fclose(f); free(qp); return NULL; }
+    while (i < n && fscanf(f, "%d", &v) == 1)
+    {
+        if (v < 0 || v > 255) { printf("ERROR: --qpfile: %d is not a QP (frame %d)\n", v, i); fclose(f); free(qp); return NULL; }
+        qp[i++] = (uint8_t)v;
+    }
+    extra = fscanf(f, "%d", &v) == 1;
+    fclose(f);
+    if (i < n || extra) { printf("ERROR: --qpfile: %s values for %d frames\n", extra ? "more" : "fewer", n); free(qp); return NULL; }
+    return qp;
+}
+
 static int run_clip_mode(FILE *fout, int w, int h, long long total)
 {
     const size_t fsz = (size_t)w*h*3/2;
@@ -499,11 +528,28 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
         s->fout = nsh == 1 ? fout : NULL;
         s->par.width = w; s->par.height = h; s->par.gop = cmd.gop; s->par.qp = cmd.qp; s->par.speed = cmd.speed; s->par.vbv_size_bytes = 100000/8;
         s->par.device = s->device; s->par.max_chains = cmd.chains; s->par.slices = cmd.threads; s->par.kbps = cmd.kbps;
+        if (cmd.lookahead && !s->par.qp) s->par.qp = 26;            /* (the window controller chooses the QPs: --qp only must not mean the reference's controller) */
         s->par.first_idr_pic_id_state = g0 & 1;         /* idr_pic_id toggles with every key frame (h264-lab.h:6774) */
         s->par.keep_records = nsh > 1;
         if (shard_open(s)) goto out;
         if (cmd.nkey && H264E_clip_set_key_frames(s->clip, cmd.key_frames, cmd.nkey)) { printf("ERROR: --keyframes: %s\n", H264E_last_error()); goto out; }
         if (cmd.scenecut && H264E_clip_set_scenecut(s->clip, cmd.scenecut)) { printf("ERROR: --scenecut: %s\n", H264E_last_error()); goto out; }
+        if (cmd.have_qp_file)
+        {
+            uint8_t *qp = read_qp_file(n);
+            const int bad = !qp || H264E_clip_set_qp_schedule(s->clip, qp, n);
+            if (qp && bad) printf("ERROR: --qpfile: %s\n", H264E_last_error());
+            free(qp);
+            if (bad) goto out;
+        }
+        if (cmd.lookahead)
+        {
+            /* the window's last frame must fit the input ring together with the staging chunk that carries it */
+            const int W = cmd.lookahead > 0 ? cmd.lookahead : n < 32 ? n : 32;
+            if (s->par.resident_frames < n && W + s->chunk - 1 > s->par.resident_frames) { printf("ERROR: --lookahead %d does not fit the input ring (%d frames, staged %d at a time)\n", W, s->par.resident_frames, s->chunk); goto out; }
+            if (H264E_clip_set_lookahead(s->clip, cmd.lookahead_kbps, W, 0, 0)) { printf("ERROR: --lookahead: %s\n", H264E_last_error()); goto out; }
+            cmd.lookahead = W;
+        }
         if (cmd.matrix && H264E_clip_set_color(s->clip, cmd.matrix, cmd.full_range)) { printf("ERROR: --colour: %s\n", H264E_last_error()); goto out; }
         if (cmd.fps_num && H264E_clip_set_frame_rate(s->clip, cmd.fps_num, cmd.fps_den)) { printf("ERROR: --fps: %s\n", H264E_last_error()); goto out; }
         g0 = g1;
@@ -555,6 +601,16 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
     }
     if (cmd.psnr) psnr_print();
     if (cmd.ssim) ssim_print();
+    if (cmd.lookahead && cmd.stats)
+    {
+        uint8_t *qp = (uint8_t *)calloc((size_t)n, 1);
+        long long bytes = 0;
+        int lo = 99, hi = 0;
+        if (!qp || H264E_clip_read_lookahead(sh[0].clip, 0, n, NULL, NULL, NULL, qp)) { printf("ERROR: %s\n", qp ? H264E_last_error() : "not enough memory"); free(qp); goto out; }
+        for (f = 0; f < n; f++) { bytes += sh[0].fsize[f]; if (qp[f] < lo) lo = qp[f]; if (qp[f] > hi) hi = qp[f]; }
+        printf("lookahead: window %d, QP %d..%d, %.1f kbps for a target of %d\n", cmd.lookahead, lo, hi, (double)bytes*8.0*30.0/n/1000.0, cmd.lookahead_kbps);
+        free(qp);
+    }
     if (cmd.scenecut)
     {
         uint8_t *cut = (uint8_t *)calloc((size_t)n, 1);
@@ -599,6 +655,14 @@ int main(int argc, char **argv)
         printf("ERROR: --keyframes / --scenecut belong to the clip path: not with %s\n", cmd.gpus > 1 ? "--gpus stream sharding" : "--clip 0 (or --maxframes 0)");
         return 1;
     }
+    if ((cmd.have_qp_file || cmd.lookahead) && (cmd.gpus > 1 || cmd.clip == 0 || !cmd.max_frames))
+    {
+        printf("ERROR: --qpfile / --lookahead belong to the clip path: not with %s\n", cmd.gpus > 1 ? "--gpus stream sharding" : "--clip 0 (or --maxframes 0)");
+        return 1;
+    }
+    if (cmd.lookahead && cmd.kbps <= 0) { printf("ERROR: --lookahead needs --kbps\n"); return 1; }
+    if (cmd.lookahead && cmd.have_qp_file) { printf("ERROR: --lookahead and --qpfile exclude each other\n"); return 1; }
+    if (cmd.lookahead) { cmd.lookahead_kbps = cmd.kbps; cmd.kbps = 0; }      /* --kbps alone stays the reference's controller */
     guess_format(cmd.input_file, &w, &h);
     fin = fopen(cmd.input_file, "rb");
     if (!fin) { printf("ERROR: cant open input file %s\n", cmd.input_file); return 1; }
@@ -635,6 +699,7 @@ int main(int argc, char **argv)
         }
         if (cmd.gpus > 1) { printf("ERROR: --gpus needs a seekable input file\n"); return 1; }
         if (cmd.nkey || cmd.scenecut) { printf("ERROR: --keyframes / --scenecut need a seekable input file (the clip path)\n"); return 1; }
+        if (cmd.have_qp_file || cmd.lookahead) { printf("ERROR: --qpfile / --lookahead need a seekable input file (the clip path)\n"); return 1; }
         clearerr(fin);
     }
 

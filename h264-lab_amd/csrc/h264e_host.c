@@ -1073,6 +1073,20 @@ struct H264E_clip_tag
     uint32_t *sc_hist;                      /* [nframes][64] */
     int *sc_dist; uint8_t *sc_cut;          /* [nframes] D(f); f was made a key frame by the detector */
     double sc_kernel_ms; long long sc_frames;   /* HIP-event time of the detector's launches and the frames they analysed, since open */
+    /* a QP per frame (H264E_clip_set_qp_schedule, or written window by window by the lookahead controller): frame f is coded as
+     * H264E_encode codes it with qp_min = qp_max = qp_sched[f]; NULL = the clip's own QP / rate control */
+    uint8_t *qp_sched;                      /* [nframes] */
+    int qp_explicit;                        /* the caller's schedule (kept across a rewind), not the controller's */
+    /* lookahead rate control (H264E_clip_set_lookahead): the project's own controller, defined in include/h264e_mi355x.h.  Frames
+     * [0, la_done) have their cost records (enc_lookahead.h) on the host; re-uploading frame f makes f onward stale, a rewind keeps them. */
+    int la_kbps, la_window, la_qmin, la_qmax;   /* la_kbps 0 = off */
+    int la_done;
+    uint64_t *la_rec;                       /* [nframes][3] I, P, N */
+    int *la_bits;                           /* [nframes] coded bits of the accepted frames of the current pass */
+    int la_planned, la_closed;              /* windows whose QP has been chosen / whose frames have all been accepted (calibration and carry done) */
+    uint64_t la_k[2];                       /* the calibration factors, P and key frames */
+    long long la_debt;                      /* sum over the closed windows of target - actual bits */
+    double la_kernel_ms; long long la_frames;
 };
 
 /* The schedule rule, once.  frame_num restarts at every key frame, and so does the periodic counter: the next periodic key frame
@@ -1119,6 +1133,12 @@ static double now_ms(void)
     return ts.tv_sec*1e3 + ts.tv_nsec*1e-6;
 }
 
+/* the lookahead controller's initial calibration factors, P and key frames (bits << 24 per unit of cost x the reference's
+ * bits-per-macroblock entry): medians over the test clips at CIF, QP 20..38 (tools/lookahead_calibrate.py); every
+ * accepted window replaces them */
+#define LOOKAHEAD_K0_P 15086u
+#define LOOKAHEAD_K0_KEY 14322u
+
 void H264E_clip_rewind(H264E_clip_t *c)
 {
     if (!c) return;
@@ -1134,6 +1154,9 @@ void H264E_clip_rewind(H264E_clip_t *c)
     clip_launch_frames_reset(c);
     memset(&c->rcs, 0, sizeof(c->rcs));
     c->rc_frame = -1; c->rc_qp = c->par.qp; c->rc_last_bytes[0] = c->rc_last_bytes[1] = 0;
+    /* lookahead controller: every pass starts from the same factors and no carry, so it chooses the same QPs again */
+    c->la_planned = c->la_closed = 0; c->la_debt = 0;
+    c->la_k[0] = LOOKAHEAD_K0_P; c->la_k[1] = LOOKAHEAD_K0_KEY;
 }
 
 int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nframes)
@@ -1223,6 +1246,7 @@ void H264E_clip_close(H264E_clip_t *c)
     free(c->rec_store); free(c->used_store); free(c->permb_store);
     free(c->traj); free(c->tasks); free(c->used); free(c->big);
     free(c->sched); free(c->forced); free(c->sc_hist); free(c->sc_dist); free(c->sc_cut);
+    free(c->qp_sched); free(c->la_rec); free(c->la_bits);
     free(c);
 }
 
@@ -1234,6 +1258,12 @@ static int clip_put_allowed(const H264E_clip_t *c, int first, int n)
     if (c->denoise && first > 0 && first < c->den_done && first - 1 < c->den_done - c->resident)
     {
         snprintf(g_host_err, sizeof(g_host_err), "upload: frame %d would be denoised again, but the denoised picture in front of it has left the input ring (rewind and upload from frame 0)", first);
+        return -1;
+    }
+    /* the cost pass measures frame `first` against the half-resolution picture of the frame in front of it (enc_lookahead.h) */
+    if (c->la_kbps && first > 0 && first < c->la_done && first - 1 < c->la_done - imax(c->resident, 2))
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "upload: frame %d would be analysed again, but the half-resolution picture in front of it has left the ring (rewind and upload from frame 0)", first);
         return -1;
     }
     return 0;
@@ -1260,6 +1290,7 @@ static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int 
     else if (first + n > c->avail) c->avail = first + n;
     if (first < c->den_done) c->den_done = first;       /* new inputs: their denoised pictures (and all behind them) are made again */
     if (first < c->sc_done) c->sc_done = first;         /* ... and their histograms */
+    if (first < c->la_done) c->la_done = first;         /* ... and their cost records */
     return 0;
 }
 
@@ -1295,6 +1326,7 @@ static int clip_put_device(H264E_clip_t *c, int first, int nframes, const H264E_
     if (first + nframes > c->avail) c->avail = first + nframes;
     if (first < c->den_done) c->den_done = first;
     if (first < c->sc_done) c->sc_done = first;
+    if (first < c->la_done) c->la_done = first;
     return 0;
 }
 
@@ -1366,6 +1398,7 @@ int H264E_clip_generate_synth(H264E_clip_t *c, int first, int nframes, int t0, u
     if (first + nframes > c->avail) c->avail = first + nframes;
     if (first < c->den_done) c->den_done = first;
     if (first < c->sc_done) c->sc_done = first;
+    if (first < c->la_done) c->la_done = first;
     return h264e_hip_sync(c->pool);
 }
 
@@ -1656,6 +1689,193 @@ static int clip_prepass_scenecut(H264E_clip_t *c, int limit)
     return 0;
 }
 
+/* ---- a QP per frame, and the lookahead controller that writes one (include/h264e_mi355x.h has the definitions) */
+
+static int clip_nslices(const H264E_clip_t *c) { return c->par.slices > 1 ? imin(imin(c->par.slices, H264E_HIP_MAX_SLICES), c->seq.nmby) : 1; }
+
+/* what both calls refuse: the reference's own controller, GOP shards, a clip that has moved */
+static int clip_qp_mode_refused(const H264E_clip_t *c, const char *who)
+{
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "%s: only at frame 0 (after open or rewind), not at frame %d", who, c->next); return -1; }
+    if (c->par.kbps > 0) { snprintf(g_host_err, sizeof(g_host_err), "%s: not with kbps = %d (the reference's rate control chooses the QPs)", who, c->par.kbps); return -1; }
+    if (c->rc_on) { snprintf(g_host_err, sizeof(g_host_err), "%s: not with qp = 0 (the reference's rate control chooses the QPs)", who); return -1; }
+    if (c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "%s: not with keep_records = %d (GOP shards)", who, c->par.keep_records); return -1; }
+    return 0;
+}
+
+static int clip_qp_arrays(H264E_clip_t *c)
+{
+    if (!c->qp_sched) c->qp_sched = (uint8_t *)calloc((size_t)c->nframes, 1);
+    if (!c->qp_sched) { snprintf(g_host_err, sizeof(g_host_err), "out of host memory"); return -1; }
+    return 0;
+}
+
+int H264E_clip_set_qp_schedule(H264E_clip_t *c, const uint8_t *qp, int n)
+{
+    int i;
+    g_host_err[0] = 0;
+    if (!c || n < 0 || (n && !qp)) { snprintf(g_host_err, sizeof(g_host_err), "set_qp_schedule: bad argument"); return -1; }
+    if (clip_qp_mode_refused(c, "set_qp_schedule")) return -1;
+    if (!n) { c->qp_explicit = 0; return 0; }
+    if (c->la_kbps) { snprintf(g_host_err, sizeof(g_host_err), "set_qp_schedule: not together with the lookahead controller (%d kbps)", c->la_kbps); return -1; }
+    if (n != c->nframes) { snprintf(g_host_err, sizeof(g_host_err), "set_qp_schedule: %d values for a clip of %d frames", n, c->nframes); return -1; }
+    for (i = 0; i < n; i++)
+        if (qp[i] < 10 || qp[i] > 51) { snprintf(g_host_err, sizeof(g_host_err), "set_qp_schedule: QP %d of frame %d is outside 10..51", qp[i], i); return -1; }
+    if (clip_qp_arrays(c)) return -1;
+    memcpy(c->qp_sched, qp, (size_t)n);
+    c->qp_explicit = 1;
+    return 0;
+}
+
+#define LOOKAHEAD_WINDOW_DEFAULT 32
+#define LOOKAHEAD_QP_STEP 6             /* a window's QP is within this of the window's before it */
+#define LOOKAHEAD_K_MAX ((uint64_t)1 << 40)
+#define LOOKAHEAD_BITS_MAX ((uint64_t)1 << 50)
+
+int H264E_clip_set_lookahead(H264E_clip_t *c, int kbps, int window, int qp_min, int qp_max)
+{
+    g_host_err[0] = 0;
+    if (!c || kbps < 0 || window < 0) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: bad argument"); return -1; }
+    if (clip_qp_mode_refused(c, "set_lookahead")) return -1;
+    if (!kbps) { c->la_kbps = 0; return 0; }
+    if (c->qp_explicit) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: not together with an explicit QP schedule"); return -1; }
+    if (c->par.width < 16 || c->par.height < 16) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: pictures below 16x16 have no cost block (%dx%d)", c->par.width, c->par.height); return -1; }
+    if (!qp_min) qp_min = 10;
+    if (!qp_max) qp_max = 50;
+    if (qp_min < 10 || qp_max > 51 || qp_min > qp_max) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: QP range %d..%d is not inside 10..51", qp_min, qp_max); return -1; }
+    if (!window) window = imin(LOOKAHEAD_WINDOW_DEFAULT, imin(c->resident, c->ring - 1));
+    if (c->resident < c->nframes && window > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: a window of %d frames does not fit the input ring (%d resident frames)", window, c->resident); return -1; }
+    if (window > c->ring - 1) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: a window of %d frames does not fit one launch (%d slots)", window, c->ring - 1); return -1; }
+    if (clip_qp_arrays(c)) return -1;
+    if (!c->la_rec)
+    {
+        c->la_rec = (uint64_t *)calloc((size_t)c->nframes*3, sizeof(uint64_t));
+        c->la_bits = (int *)calloc((size_t)c->nframes, sizeof(int));
+        c->la_done = 0;
+        if (!c->la_rec || !c->la_bits)
+        {
+            free(c->la_rec); free(c->la_bits); c->la_rec = NULL; c->la_bits = NULL;
+            snprintf(g_host_err, sizeof(g_host_err), "out of host memory");
+            return -1;
+        }
+    }
+    c->la_kbps = kbps; c->la_window = window; c->la_qmin = qp_min; c->la_qmax = qp_max;
+    return 0;
+}
+
+int H264E_clip_read_lookahead(H264E_clip_t *c, int first, int n, uint64_t *intra, uint64_t *inter, int *intra_blocks, uint8_t *qp)
+{
+    int i;
+    g_host_err[0] = 0;
+    if (!c || first < 0 || n < 0) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead: bad argument"); return -1; }
+    if (intra || inter || intra_blocks)
+    {
+        const int have = c->la_rec ? c->la_done : 0;
+        if (first + n > have) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead: frames %d..%d have not been analysed (%d have)", first, first + n - 1, have); return -1; }
+    }
+    if (qp)
+    {
+        const int have = c->qp_explicit ? c->nframes : c->la_kbps ? imin(c->la_planned*c->la_window, c->nframes) : 0;
+        if (first + n > have) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead: frames %d..%d have no QP yet (%d have)", first, first + n - 1, have); return -1; }
+    }
+    for (i = 0; i < n; i++)
+    {
+        if (intra) intra[i] = c->la_rec[3*(size_t)(first + i)];
+        if (inter) inter[i] = c->la_rec[3*(size_t)(first + i) + 1];
+        if (intra_blocks) intra_blocks[i] = (int)c->la_rec[3*(size_t)(first + i) + 2];
+        if (qp) qp[i] = c->qp_sched[first + i];
+    }
+    return 0;
+}
+
+/* diagnostic (tools/lookahead_probe.py): HIP-event time of the cost pass' kernel launches since open, and the frames they analysed */
+int H264E_clip_lookahead_time(H264E_clip_t *c, double *kernel_ms, long long *frames)
+{
+    if (!c) return -1;
+    if (kernel_ms) *kernel_ms = c->la_kernel_ms;
+    if (frames) *frames = c->la_frames;
+    return 0;
+}
+
+/* the pre-pass in front of a window's plan: the cost records of the frames uploaded so far and not yet analysed, in stream order */
+static int clip_prepass_lookahead(H264E_clip_t *c, int limit)
+{
+    const int a = c->la_done;
+    float ms = 0;
+    if (a >= limit) return 0;
+    if (limit - a > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "lookahead: frames %d..%d do not fit the input ring", a, limit - 1); return -1; }
+    if (h264e_hip_lookahead_frames(c->pool, a, limit - a, (unsigned long long *)(c->la_rec + 3*(size_t)a), &ms)) return -1;
+    c->la_kernel_ms += ms; c->la_frames += limit - a;
+    c->la_done = limit;
+    return 0;
+}
+
+/* the bits the host itself writes for a frame, independent of its QP: start code and NAL header of every slice, and a key frame's
+ * parameter sets at their size for pic_init_qp 26 */
+static int clip_la_header_bits(const H264E_clip_t *c, int key)
+{
+    uint8_t ps[128];
+    return 40*clip_nslices(c) + (key ? 8*(int)write_sps_pps(&c->seq, 26, ps, NULL, NULL) : 0);
+}
+
+static uint64_t clip_la_texture_bits(uint64_t k, uint64_t cost, int q, int key)
+{
+    const unsigned __int128 v = ((unsigned __int128)k*cost*k_bits_per_mb[key][imin(q, 50) - 10]) >> 24;
+    return v > LOOKAHEAD_BITS_MAX ? LOOKAHEAD_BITS_MAX : (uint64_t)v;
+}
+
+/* window j = frames [j*W, (j + 1)*W): one QP, the smallest whose predicted bits fit the window's budget and the clamped carry */
+static void clip_la_plan_window(H264E_clip_t *c, int j)
+{
+    const int W = c->la_window, a = j*W, b = imin(a + W, c->nframes), dfb = c->la_kbps*1000/8/30;
+    const long long T = 8LL*dfb*W, carry = c->la_debt > T/2 ? T/2 : c->la_debt < -(T/2) ? -(T/2) : c->la_debt, Tj = 8LL*dfb*(b - a) + carry;
+    const int hk = clip_la_header_bits(c, 1), hp = clip_la_header_bits(c, 0);
+    /* the factors were measured at the QP of the window before: the table does not carry them far from it */
+    const int prev = j ? c->qp_sched[a - 1] : 0, qlo = prev ? imax(c->la_qmin, prev - LOOKAHEAD_QP_STEP) : c->la_qmin, qhi = prev ? imin(c->la_qmax, prev + LOOKAHEAD_QP_STEP) : c->la_qmax;
+    int q, f;
+    for (q = qlo; q < qhi; q++)
+    {
+        long long sum = 0;
+        for (f = a; f < b; f++)
+        {
+            const int key = c->sched[f].key;
+            sum += (key ? hk : hp) + (long long)clip_la_texture_bits(c->la_k[key], c->la_rec[3*(size_t)f + (key ? 0 : 1)], q, key);
+        }
+        if (sum <= Tj) break;
+    }
+    memset(c->qp_sched + a, q, (size_t)(b - a));
+    c->la_planned = j + 1;
+}
+
+/* window j has been accepted: what it missed goes into the carry, and the factors become what would have predicted its frames */
+static void clip_la_close_window(H264E_clip_t *c, int j)
+{
+    const int W = c->la_window, a = j*W, b = imin(a + W, c->nframes), dfb = c->la_kbps*1000/8/30;
+    const int hk = clip_la_header_bits(c, 1), hp = clip_la_header_bits(c, 0);
+    long long actual = 0, num[2] = { 0, 0 };
+    unsigned __int128 den[2] = { 0, 0 };
+    int present[2] = { 0, 0 }, f, t;
+    for (f = a; f < b; f++)
+    {
+        const int key = c->sched[f].key;
+        actual += c->la_bits[f];
+        num[key] += c->la_bits[f] - (key ? hk : hp);
+        den[key] += (unsigned __int128)c->la_rec[3*(size_t)f + (key ? 0 : 1)]*k_bits_per_mb[key][imin(c->qp_sched[f], 50) - 10];
+        present[key] = 1;
+    }
+    c->la_debt += 8LL*dfb*(b - a) - actual;
+    for (t = 0; t < 2; t++)
+        if (present[t] && den[t])
+        {
+            const uint64_t old = c->la_k[t], lo = old/4, hi = old*4 > LOOKAHEAD_K_MAX ? LOOKAHEAD_K_MAX : old*4;
+            const unsigned __int128 kn = ((unsigned __int128)(num[t] > 0 ? num[t] : 0) << 24)/den[t];
+            uint64_t k = kn > hi ? hi : (uint64_t)kn;
+            if (k < lo) k = lo;
+            c->la_k[t] = k ? k : 1;
+        }
+    c->la_closed = j + 1;
+}
+
 int H264E_clip_stamps(H264E_clip_t *c, unsigned long long *dst) { return c ? h264e_hip_stamps_read(c->pool, dst, 1) : -1; }
 
 /* ---- H264E_clip_encode: launches until the uploaded frames are encoded or the caller's buffer is full; every launch is
@@ -1733,13 +1953,25 @@ static clip_step_t clip_abort_launch(H264E_clip_t *c)
 
 /* a task's QP: quantizer tables and slice header.  frame_num restarts at every key frame; idr_pic_id toggles with every key frame
  * (h264-lab.h:6774-6775) */
+/* a QP per frame is in force (the caller's schedule or the lookahead controller's) */
+static int clip_qp_per_frame(const H264E_clip_t *c) { return c->qp_explicit || c->la_kbps; }
+
+/* pic_init_qp of the parameter sets in force at frame f: one value per call, or -- with a QP per frame -- a property of the last key
+ * frame: clamp(30, qp_min, qp_max) with qp_min = qp_max = that frame's QP (h264-lab.h:6766-6773) */
+static int clip_pic_init_qp(const H264E_clip_t *c, const clip_call_t *x, int f)
+{
+    if (!clip_qp_per_frame(c)) return x->pic_init_qp;
+    while (f > 0 && !c->sched[f].key) f--;
+    return c->qp_sched[f];
+}
+
 static void clip_task_set_qp(const H264E_clip_t *c, const clip_call_t *x, h264e_hip_task_t *t, int f, int qp)
 {
     const struct clip_sched *s = c->sched + f;
     t->qp = qp;
-    if (c->rc_on) build_qdat(t->qdat, qp, !s->key);
+    if (c->rc_on || clip_qp_per_frame(c)) build_qdat(t->qdat, qp, !s->key);
     else memcpy(t->qdat, s->key ? x->qdat_i : x->qdat_p, sizeof(t->qdat));
-    slice_header_bits(&c->seq, s->key, s->frame_num, x->idr_state ^ s->idr, qp, x->pic_init_qp, x->no_deblock, x->nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
+    slice_header_bits(&c->seq, s->key, s->frame_num, x->idr_state ^ s->idr, qp, clip_pic_init_qp(c, x, f), x->no_deblock, x->nslices, &t->hdr_nal, &t->hdr_bits, &t->hdr_nbits);
 }
 
 /* the launch that starts at frame l->n: how many frames, and their tasks */
@@ -1778,7 +2010,7 @@ static void clip_plan_launch(H264E_clip_t *c, const clip_call_t *x, clip_launch_
                 qp = rc_frame_start(&rc_ahead, c->par.gop, nmb, c->par.vbv_size_bytes, x->desired_frame_bytes, x->qp_min, x->qp_max, key);
             }
             l->qp_task[i] = qp;
-        }
+        } else if (clip_qp_per_frame(c)) qp = c->qp_sched[f];
         t->active = 1; t->frame_index = f % c->resident;
         t->slice_type = key ? SLICE_I : SLICE_P;
         t->speed = c->par.speed;
@@ -1913,11 +2145,12 @@ static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_
     if (!nals) { c->big_cap = 0; return clip_abort_launch(c); }
     /* the caller's buffer is full: stop here, the stream continues with this frame in the next call */
     if (x->pos + need > x->cap) return h264e_hip_stream_abort(c->pool) ? CLIP_ERROR : CLIP_STOP_FULL;
-    if (key) x->pos += write_sps_pps(&c->seq, x->pic_init_qp, x->out + x->pos, NULL, NULL);
+    if (key) x->pos += write_sps_pps(&c->seq, clip_pic_init_qp(c, x, f), x->out + x->pos, NULL, NULL);
     w = emit_slices(x->out + x->pos, x->cap - x->pos, nals, r, NULL, NULL);
     if (!w) { snprintf(g_host_err, sizeof(g_host_err), "malformed frame export"); return clip_abort_launch(c); }
     x->pos += w;
     if (x->frame_bytes) x->frame_bytes[f - x->first] = (int)(x->pos - start);
+    if (c->la_kbps) c->la_bits[f] = 8*(int)(x->pos - start);
     if (c->rc_on)
     {
         rc_frame_end(&c->rcs, nmb, c->par.vbv_size_bytes, x->desired_frame_bytes, (int)(x->pos - start), key, r->all_skipped);
@@ -2051,6 +2284,19 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         int ti = 0;
         l.n = c->next; l.limit = c->avail;          /* frames uploaded from the idle hook during this launch join the next one */
         if (clip_prepass_scenecut(c, l.limit)) return clip_end(c, &x, st, -1);
+        if (c->la_kbps)
+        {
+            /* the lookahead controller: window j is planned once, when its first frame is, from the windows up to j - 1 -- and only
+             * when all its frames are there; a launch never crosses a window boundary */
+            const int j = l.n/c->la_window, wend = imin((j + 1)*c->la_window, c->nframes);
+            if (c->la_planned <= j)
+            {
+                if (c->avail < wend) break;
+                if (clip_prepass_lookahead(c, l.limit)) return clip_end(c, &x, st, -1);
+                clip_la_plan_window(c, j);
+            }
+            l.limit = wend;
+        }
         clip_plan_launch(c, &x, &l);
         x.stats.rounds++;
         x.far_reads = 0;
@@ -2066,6 +2312,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         } while (l.step == CLIP_TAKE_LEAF || (l.step == CLIP_GO_ON && ti < l.F));
         if (l.step == CLIP_ERROR || clip_settle(c, &x, &l)) return clip_end(c, &x, st, -1);
         clip_adapt(c, &x, &l);
+        while (c->la_kbps && c->la_closed < c->la_planned && c->next >= imin((c->la_closed + 1)*c->la_window, c->nframes)) clip_la_close_window(c, c->la_closed);
         if (x.debug) clip_debug_line(c, &x, &l);
         if (l.step == CLIP_STOP_FULL && c->next == x.first)
         {

@@ -20,6 +20,7 @@
  *   h264e_ingest_float_kernel<ST>, h264e_scale_rgb_float_kernel<ST>, h264e_egress_float_kernel<ST>  the planar RGB paths for float16 /
  *                        bfloat16 / float32 samples in [0, 1], quantised on the way in and divided by 255 on the way out.
  *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
+ *   h264e_lookahead_kernel the cost pass of the lookahead rate control (enc_lookahead.h): intra / inter cost sums of one resident input frame.
  *
  * HIP only (hipcc --offload-arch=gfx950).  The host side of the boundary is h264e_pool.h, included at the end; the test-only
  * emulation of tests/emu compiles the same kernel HEADERS with its own launch functions and never sees this file.
@@ -36,6 +37,7 @@
 #include "enc_scale_rgb.h"
 #include "enc_hbd.h"
 #include "enc_scenecut.h"
+#include "enc_lookahead.h"
 #include "enc_ssim.h"
 #include "../../include/h264e_hip.h"
 
@@ -891,6 +893,42 @@ __global__ void __launch_bounds__(256) h264e_scenecut_kernel(const uint8_t *luma
     if (threadIdx.x < SCENECUT_BINS) scenecut_flush((const LDS_AS uint32_t *)hist, (GLOBAL_AS int *)record, (int)threadIdx.x);
 }
 
+/* the cost sums of one resident input frame (enc_lookahead.h): a wave takes 8 blocks at a time, 8 lanes per block and one block row per
+ * lane; a workgroup of four waves takes 32 consecutive blocks per pass, so a wave's loads cover 128 contiguous bytes of 16 luma rows and
+ * its stores 512 contiguous bytes of the half-resolution entry.  Lanes behind the last block load nothing and add nothing, but take part
+ * in the butterflies. */
+DEV int lookahead_oct_sum(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);      /* quad_perm [1,0,3,2] */
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);      /* quad_perm [2,3,0,1] */
+    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);     /* row_half_mirror: the other quad of the 8 lanes */
+    return v;
+}
+__global__ void __launch_bounds__(256) h264e_lookahead_kernel(lookahead_args_t A)
+{
+    __shared__ int part[4][3];
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6), r = lane & 7;
+    int si = 0, sp = 0, sn = 0;             /* at most a few passes of one block each: far below 2^31 */
+    for (int b0 = (int)blockIdx.x*32; b0 < A.nblk; b0 += (int)gridDim.x*32)
+    {
+        const int b = b0 + wave*8 + (lane >> 3), on = b < A.nblk;
+        lookahead_row_t R = { { 0u, 0u }, { 0u, 0u } };
+        if (on) R = lookahead_row(A, b, r);
+        const int m = (lookahead_oct_sum(lookahead_row_sum(R)) + 32) >> 6;
+        const int intra = lookahead_oct_sum(lookahead_row_intra(R, m));
+        const int inter = A.prev ? lookahead_oct_sum(lookahead_row_inter(R)) : intra;
+        if (on && r == 0) { si += intra; sp += intra < inter ? intra : inter; sn += intra < inter; }
+    }
+    si = wave_reduce_add(si); sp = wave_reduce_add(sp); sn = wave_reduce_add(sn);
+    if (lane == 0) { part[wave][0] = si; part[wave][1] = sp; part[wave][2] = sn; }
+    __syncthreads();
+    if (threadIdx.x < 3)
+    {
+        const int k = (int)threadIdx.x;
+        lookahead_record_add(A.record + k, (unsigned long long)(part[0][k] + part[1][k] + part[2][k] + part[3][k]));
+    }
+}
+
 /* ------------------------------------------------------------------ launches (what h264e_pool.h calls) */
 
 /* variant: 0 = intra frames only (one wave per row, 4 per SIMD), 1 = one wave per row, 2 = two waves per row (3 per SIMD), 3 = the latency variant: four
@@ -984,6 +1022,13 @@ static void bk_launch_scenecut(const uint8_t *luma, uint32_t nbytes, int *record
     uint32_t wgs = (ndw + per_wg - 1)/per_wg;
     if (wgs > 256) wgs = 256;
     hipLaunchKernelGGL(h264e_scenecut_kernel, dim3(wgs ? wgs : 1), dim3(256), 0, st, luma, nbytes, record);
+}
+/* one workgroup per 32 blocks, at most 1024 (8K: 4 passes each) */
+static void bk_launch_lookahead(const lookahead_args_t &A, hipStream_t st)
+{
+    int wgs = (A.nblk + 31)/32;
+    if (wgs > 1024) wgs = 1024;
+    hipLaunchKernelGGL(h264e_lookahead_kernel, dim3((unsigned)(wgs > 0 ? wgs : 1)), dim3(256), 0, st, A);
 }
 static void bk_launch_stage_selftest(int stage, const uint8_t *in, const int *args, uint8_t *out, hipStream_t st)
 {

@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those eight are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those nine are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -18,6 +18,7 @@
 #include "enc_scale_rgb.h"
 #include "enc_hbd.h"
 #include "enc_scenecut.h"
+#include "enc_lookahead.h"
 #include "enc_ssim.h"
 
 /* The matrix rows (tests/color_model.py): Kr / Kb scaled by 219/255 and 224/255 (limited) or 1 (full), times 256,
@@ -179,8 +180,12 @@ struct h264e_hip_pool
     uint8_t *den;
     int den_frames, den_flip;
     hipEvent_t ev_copy;                  /* the copy stream's uploads, waited for by a denoise / scene-cut launch */
-    hipEvent_t ev_sc[2];                 /* around the scene-cut launches of one call (their HIP-event time) */
+    hipEvent_t ev_sc[2];                 /* around the scene-cut / cost-pass launches of one call (their HIP-event time) */
     int *sc_rec;                         /* device [frames_resident][64]: luma histogram records of the scene-cut detector; NULL until it is switched on */
+    /* cost pass of the lookahead rate control (enc_lookahead.h); NULL until it first runs */
+    uint8_t *la_lo;                      /* device [la_entries][la_entry_bytes]: the half-resolution pictures, frame f in entry f % la_entries */
+    unsigned long long *la_rec;          /* device [la_entries][3]: I, P, N of the frame in that entry */
+    int la_entries; size_t la_entry_bytes;
     h264e_color_t cm;                    /* the RGB -> YCbCr matrix of the RGB / RGBP ingest and scale launches (h264e_hip_set_color) */
     hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
     hipEvent_t ev_in[2];                 /* h264e_hip_copy_timer_*: around a caller's launches on the copy stream */
@@ -303,6 +308,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     dev_free(p->heap);
     dev_free(p->den);
     dev_free(p->sc_rec);
+    dev_free(p->la_lo); dev_free(p->la_rec);
     dev_free(p->qual_dev);
     if (p->stream)
     {
@@ -744,6 +750,80 @@ extern "C" int h264e_hip_scenecut_frames(h264e_hip_pool_t *p, int first, int n, 
     {
         const int s = (first + done) % R, run = imin_h(n - done, R - s);
         HIPCHK(hipMemcpyAsync(hist + (size_t)done*SCENECUT_BINS, p->sc_rec + (size_t)s*SCENECUT_BINS, sizeof(int)*SCENECUT_BINS*(size_t)run, hipMemcpyDeviceToHost, p->stream));
+        done += run;
+    }
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, p->ev_sc[0], p->ev_sc[1]));
+    return 0;
+}
+
+/* ---- cost pass of the lookahead rate control (enc_lookahead.h): one h264e_lookahead_kernel launch per frame on the pool's stream */
+
+#ifdef H264E_EMU
+/* the emulation's launch: the kernel's lane-level code as a loop over the blocks and their eight row lanes */
+static void bk_launch_lookahead(const lookahead_args_t &A, hipStream_t)
+{
+    unsigned long long sum[3] = { 0, 0, 0 };
+    for (int b = 0; b < A.nblk; b++)
+    {
+        lookahead_row_t R[8];
+        int s = 0, intra = 0, inter = 0;
+        for (int r = 0; r < 8; r++) { R[r] = lookahead_row(A, b, r); s += lookahead_row_sum(R[r]); }
+        const int m = (s + 32) >> 6;
+        for (int r = 0; r < 8; r++) { intra += lookahead_row_intra(R[r], m); inter += lookahead_row_inter(R[r]); }
+        if (!A.prev) inter = intra;
+        sum[0] += (unsigned)intra; sum[1] += (unsigned)(intra < inter ? intra : inter); sum[2] += intra < inter;
+    }
+    for (int k = 0; k < 3; k++) lookahead_record_add(A.record + k, sum[k]);
+}
+#endif
+
+/* frames first, first + 1, ... of the STREAM (input slot f % frames_resident): their records into rec [n][3] on return */
+extern "C" int h264e_hip_lookahead_frames(h264e_hip_pool_t *p, int first, int n, unsigned long long *rec, float *kernel_ms)
+{
+    const int R = p ? p->frames_resident : 0;
+    if (!p || !rec || first < 0 || n < 0 || n > R) FAIL("lookahead_frames: bad argument");
+    if (p->G.width < LOOKAHEAD_MIN_SIDE || p->G.height < LOOKAHEAD_MIN_SIDE) FAIL("lookahead: pictures below %dx%d have no cost block (%dx%d)", LOOKAHEAD_MIN_SIDE, LOOKAHEAD_MIN_SIDE, p->G.width, p->G.height);
+    if (kernel_ms) *kernel_ms = 0;
+    if (!n) return 0;
+    HIPCHK(hipSetDevice(p->device));
+    lookahead_args_t A;
+    A.width = p->G.width; A.nbx = (p->G.width >> 1) >> 3; A.nblk = A.nbx*((p->G.height >> 1) >> 3);
+    if (!p->la_lo)
+    {
+        p->la_entries = R > 1 ? R : 2;
+        p->la_entry_bytes = (size_t)A.nblk*LOOKAHEAD_BLOCK_BYTES;
+        if (dev_malloc((void **)&p->la_lo, p->la_entry_bytes*(size_t)p->la_entries)) { p->la_lo = 0; FAIL("lookahead: device allocation failed (%d half-resolution pictures)", p->la_entries); }
+        if (dev_malloc((void **)&p->la_rec, sizeof(unsigned long long)*3*(size_t)p->la_entries)) { dev_free(p->la_lo); p->la_lo = 0; p->la_rec = 0; FAIL("lookahead: device allocation failed (%d records)", p->la_entries); }
+    }
+    const int E = p->la_entries;
+    /* the inputs may have come over the copy stream (asynchronous uploads, device input): the launches wait for everything issued there */
+    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
+    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
+    HIPCHK(hipEventRecord(p->ev_sc[0], p->stream));
+    /* n <= frames_resident <= entries: no entry is used twice in a call and the entries wrap at most once, so the records are zeroed
+     * in front of the launches and read back behind them in one or two pieces */
+    for (int done = 0; done < n;)
+    {
+        const int e = (first + done) % E, run = imin_h(n - done, E - e);
+        HIPCHK(hipMemsetAsync(p->la_rec + 3*(size_t)e, 0, sizeof(unsigned long long)*3*(size_t)run, p->stream));
+        done += run;
+    }
+    for (int i = 0; i < n; i++)
+    {
+        const int f = first + i, e = f % E;
+        A.luma = p->clip + p->frame_bytes*(size_t)(f % R);
+        A.prev = f ? p->la_lo + p->la_entry_bytes*(size_t)((f - 1) % E) : NULL;
+        A.cur = p->la_lo + p->la_entry_bytes*(size_t)e;
+        A.record = p->la_rec + 3*(size_t)e;
+        bk_launch_lookahead(A, p->stream);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(p->ev_sc[1], p->stream));
+    for (int done = 0; done < n;)
+    {
+        const int e = (first + done) % E, run = imin_h(n - done, E - e);
+        HIPCHK(hipMemcpyAsync(rec + 3*(size_t)done, p->la_rec + 3*(size_t)e, sizeof(unsigned long long)*3*(size_t)run, hipMemcpyDeviceToHost, p->stream));
         done += run;
     }
     HIPCHK(hipStreamSynchronize(p->stream));

@@ -160,6 +160,12 @@ int  h264e_hip_read_denoised(h264e_hip_pool_t *pool, int slot, uint8_t *dst);
  * hist [n][64] on return (the call waits for the stream).  The device records are allocated on first use.  kernel_ms (optional): the HIP-event
  * time of the launches of this call. */
 int  h264e_hip_scenecut_frames(h264e_hip_pool_t *pool, int first, int n, uint32_t *hist, float *kernel_ms);
+/* Cost pass of the lookahead rate control (enc_lookahead.h): the records {I, P, N} of STREAM frames first, first + 1, ... (input slot
+ * f % frames_resident; n <= frames_resident), one kernel launch per frame in order on the pool's stream after every upload issued on
+ * the copy stream, read back into rec [n][3] on return (the call waits for the stream).  Frame f > 0 is measured against the
+ * half-resolution picture that the pass made of frame f - 1, kept in a ring of the pool (allocated on first use): frames must be
+ * analysed in order, and f - 1 no more than the ring's length before.  Refused below 16x16.  kernel_ms (optional): as above. */
+int  h264e_hip_lookahead_frames(h264e_hip_pool_t *pool, int first, int n, unsigned long long *rec, float *kernel_ms);
 /* Launch groups: the submits of the member pools (same device, same picture size, one host thread each) are merged into ONE kernel
  * launch per round -- the streams' jobs interleaved in dispatch order, every job with its own pool's buffers / abort word / results --
  * so that independent streams fill each other's pipeline drains.  h264e_hip_submit of a member blocks until all members that are

@@ -423,6 +423,44 @@ int  H264E_clip_set_scenecut(H264E_clip_t *clip, int threshold);
 int  H264E_clip_read_scenecut(H264E_clip_t *clip, int first, int n, int *dist, uint8_t *is_cut);
 /* diagnostic: HIP-event time of the detector's kernel launches since open, and the frames they analysed (tools/scenecut_probe.py) */
 int  H264E_clip_scenecut_time(H264E_clip_t *clip, double *kernel_ms, long long *frames);
+/* A QP per frame: qp[0..n), n = the clip's nframes (0 clears the schedule), every value in 10..51.  The stream is byte for byte what
+ * H264E_encode writes when frame f is given qp_min = qp_max = qp[f] and desired_frame_bytes = 0; frame types, slices, speed,
+ * denoiser, colour and forced / detected key frames stay as the clip is set up.  The PPS of a key frame carries that frame's
+ * pic_init_qp (clamp(30, qp_min, qp_max) = its own QP), the P frames behind it code slice_qp_delta against it.  Launches keep their
+ * length: nothing is speculated and no QP stops a launch.  While the clip stands at frame 0; kept across a rewind.  Refused -- nothing
+ * changes, H264E_last_error names the value -- with kbps > 0 or qp == 0 (the reference's rate control chooses the QPs), with
+ * keep_records, with another n, with a value outside 10..51, and while the lookahead controller below is on. */
+int  H264E_clip_set_qp_schedule(H264E_clip_t *clip, const uint8_t *qp, int n);
+/* Lookahead rate control: THIS PROJECT'S OWN controller, not the reference's (whose kbps mode, H264E_clip_param_t.kbps, is untouched
+ * and makes every frame's QP a function of the frame before it).  It chooses one QP per window of `window` frames before the window
+ * is launched and writes it into the per-frame schedule above: the QPs are this project's choice, the bytes for those QPs are the
+ * reference's.  kbps 0 = off; window 0 = the default (32, or what the input ring and the slot ring allow); qp_min = 0 / qp_max = 0
+ * select 10 / 50.  While the clip stands at frame 0; settings and cost records are kept across a rewind, the controller's state is
+ * reset, so the same stream results.  Refused with an explicit schedule, kbps > 0, qp == 0, keep_records, pictures below 16x16, and
+ * a window above a bounded input ring's resident_frames or above the slot ring minus one.
+ *   Cost pass (enc_lookahead.h, one kernel launch per frame in front of the launch that plans its window; tests/lookahead_model.py):
+ * L_f = 2x2 rounded means of the RAW luma; 8x8 blocks of L_f wholly inside it; m = (sum + 32) >> 6; intra(b) = sum |L_f - m|;
+ * inter(b) = sum |L_f - L_{f-1}| co-located (frame 0: intra(b)); I(f) = sum intra, P(f) = sum min(intra, inter),
+ * N(f) = #{intra < inter}.  Uploading frame f again makes the records from f onward new.
+ *   Controller: dfb = kbps*1000/8/30; windows [jW, (j+1)W) over frame numbers, W_j frames long; T = 8*dfb*W;
+ * T_j = 8*dfb*W_j + clamp(sum over finished windows of (8*dfb*W_i - actual bits), -T/2, +T/2).  Predicted bits of frame f at QP q:
+ * H(f) + min((k[t]*C(f)*Lq[t][min(q,50) - 10]) >> 24, 2^50), t = 1 and C = I for key frames, t = 0 and C = P otherwise, Lq the
+ * reference's bits-per-macroblock table, H(f) = 40 bits per slice (start code, NAL header) + for key frames the parameter sets at
+ * their size for pic_init_qp 26.  QP_j = the smallest q in [lo_j, hi_j] whose predicted window sum is <= T_j, else hi_j, where
+ * [lo_0, hi_0] = [qp_min, qp_max] and, for j > 0, [lo_j, hi_j] = [max(qp_min, QP_{j-1} - 6), min(qp_max, QP_{j-1} + 6)]: a window's QP
+ * stays within 6 (one doubling of the quantiser step) of the window before it, because k was measured at that window's QP and the
+ * table does not carry it far.  When
+ * window j has been accepted, for each frame type in it k[t] = ((actual bits - H of those frames, at least 0) << 24) /
+ * sum C(f)*Lq[t][q_f - 10], clamped to [k_old/4, min(4*k_old, 2^40)] and to at least 1; left alone when the divisor is 0.  A launch never
+ * crosses a window boundary, and a window whose frames are not all uploaded is not started: H264E_clip_encode returns with what it
+ * encoded (zero frames is not an error) -- except the clip's last window once all frames are uploaded.  Zero-motion inter cost
+ * overestimates pans; the calibration absorbs a steady bias.  VBV compliance is not claimed. */
+int  H264E_clip_set_lookahead(H264E_clip_t *clip, int kbps, int window, int qp_min, int qp_max);
+/* I(f), P(f), N(f) and the QP of frames first .. first + n - 1; each pointer may be NULL.  Costs: only frames already analysed; QPs:
+ * only frames of an explicit schedule or of windows already planned in this pass; -1 otherwise. */
+int  H264E_clip_read_lookahead(H264E_clip_t *clip, int first, int n, uint64_t *intra, uint64_t *inter, int *intra_blocks, uint8_t *qp);
+/* diagnostic: HIP-event time of the cost pass' kernel launches since open, and the frames they analysed (tools/lookahead_probe.py) */
+int  H264E_clip_lookahead_time(H264E_clip_t *clip, double *kernel_ms, long long *frames);
 /* GOP shards of ONE stream (one clip encoder per shard / GPU, the shard starting at a key frame with first_idr_pic_id_state =
  * its GOP index & 1 and a SPECULATED mv_clusters_in): once the exact state in front of the shard is known, revalidate walks the
  * kept records (keep_records) and either confirms the shard (*restart_frame = -1, end_state = exact state behind it) or names the
