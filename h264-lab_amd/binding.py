@@ -483,6 +483,8 @@ def load(path=None):
     L.H264E_clip_set_lookahead.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
     L.H264E_clip_read_lookahead.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.H264E_clip_lookahead_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
+    L.H264E_clip_set_lookahead_search.argtypes = [C.c_void_p, C.c_int]
+    L.H264E_clip_read_lookahead_motion.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.H264E_clip_position.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.H264E_clip_position.restype = None
     L.H264E_clip_revalidate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -681,7 +683,7 @@ class ClipEncoder:
 
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
                  clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0,
-                 color=None, fps=None, quality=None, qp_schedule=None, abr_kbps=0, lookahead=0, qp_range=(0, 0)):
+                 color=None, fps=None, quality=None, qp_schedule=None, abr_kbps=0, lookahead=0, qp_range=(0, 0), lookahead_search=0):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
         self._ssd = self._ssim = None           # the registered metric arrays [nframes][3], owned here while registered
@@ -707,6 +709,8 @@ class ClipEncoder:
                 self.set_qp_schedule(qp_schedule)
             if abr_kbps:
                 self.set_lookahead(abr_kbps, lookahead, qp_range)
+            if lookahead_search:
+                self.set_lookahead_search(lookahead_search)
         except H264EError:
             self.close()
             raise
@@ -803,6 +807,25 @@ class ClipEncoder:
                                             b.ctypes.data if costs else None, q.ctypes.data if qp else None):
             raise _err(self.L, "H264E_clip_read_lookahead")
         return (i, p, b) if costs else (None, None, None), None if not qp else q
+
+    def set_lookahead_search(self, r):
+        """Motion search in the lookahead's cost pass (H264E_clip_set_lookahead_search): r = 0 switches it off, 1..8 searches +-r
+        half-resolution samples per 8x8 block; only while the clip stands at frame 0 and before any frame has been analysed with
+        another range."""
+        if self.L.H264E_clip_set_lookahead_search(self.c, int(r)):
+            raise _err(self.L, "H264E_clip_set_lookahead_search")
+
+    def read_lookahead_motion(self, frame):
+        """(mv int8 [nby, nbx, 2] as (dx, dy), cost uint16 [nby, nbx]) of an analysed frame whose field is still in the device's ring
+        (H264E_clip_read_lookahead_motion): per 8x8 block of the half-resolution picture the vector the cost pass found, in
+        half-resolution samples, and its SAD."""
+        nbx, nby = C.c_int(), C.c_int()
+        self.L.H264E_clip_read_lookahead_motion(self.c, -1, None, C.byref(nbx), C.byref(nby))
+        cells = np.zeros((nby.value, nbx.value), np.uint32)
+        if self.L.H264E_clip_read_lookahead_motion(self.c, int(frame), cells.ctypes.data, None, None):
+            raise _err(self.L, "H264E_clip_read_lookahead_motion")
+        mv = np.stack([(cells & 0xff).astype(np.uint8).view(np.int8), ((cells >> 8) & 0xff).astype(np.uint8).view(np.int8)], axis=-1)
+        return mv, (cells >> 16).astype(np.uint16)
 
     def lookahead_time(self):
         """(HIP-event milliseconds inside the cost pass' kernel launches since open, frames they analysed)"""

@@ -32,6 +32,8 @@
  * the lane with r = 0 keeps I, P, N of its blocks, a wave reduction and one LDS cell per wave make the workgroup's sums, and thread 0 adds
  * them to the frame's record with three 64-bit vector global atomics.  Nothing scalar writes memory.
  * h264e_kernels.hip runs it as h264e_lookahead_kernel, h264e_pool.h's emulation launch (H264E_EMU) as a lane loop over the blocks.
+ * enc_lookahead_search.h is the same pass with a motion search in inter(b) (H264E_clip_set_lookahead_search); it uses lookahead_row, the
+ * row sums and the record as they stand here and writes the same entries.
  */
 #ifndef H264E_ENC_LOOKAHEAD_H
 #define H264E_ENC_LOOKAHEAD_H

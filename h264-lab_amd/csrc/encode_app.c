@@ -31,6 +31,8 @@
  * --lookahead W together with --kbps K selects this encoder's own window rate control (H264E_clip_set_lookahead, window W frames; `x` =
  * 32) instead of the reference's controller, which --kbps alone stays; with --stats it adds ONE stdout line, "lookahead: window W, QP
  * a..b, X kbps for a target of K".  Both belong to the clip path and are refused like --keyframes / --scenecut.
+ * --lookahead-search R (1..8; 0 = off) lets that controller's cost pass search +-R half-resolution samples per block
+ * (H264E_clip_set_lookahead_search); it is refused without --lookahead.
  */
 #define _FILE_OFFSET_BITS 64
 #include <math.h>
@@ -46,6 +48,7 @@ static struct
     int gop, qp, kbps, max_frames, speed, stats, psnr, ssim, device, clip, chains, threads, gpus;
     int scenecut, nkey, key_frames[1024];   /* --scenecut threshold (0 = off), --keyframes list */
     char qp_file[1024];                 /* --qpfile: one QP per frame */
+    int lookahead_search;               /* --lookahead-search R */
     int have_qp_file, lookahead, lookahead_kbps;      /* --lookahead W (with --kbps K: the window controller; 0 = not given, -1 = the default window) */
     int matrix, full_range, fps_num, fps_den;   /* --colour, --fps (all 0: nothing is signalled) */
     int unsupported;                    /* a reference option this encoder refuses was given: no stream is written, exit 1 */
@@ -105,6 +108,7 @@ static void parse_long(const char *p, const char *val)
         } else { cmd.fps_num = (int)num; cmd.fps_den = (int)den; }
     }
     else if (starts("qpfile", p)) { snprintf(cmd.qp_file, sizeof(cmd.qp_file), "%s", v); cmd.have_qp_file = 1; }
+    else if (starts("lookahead-search", p)) cmd.lookahead_search = atoi(v);
     else if (starts("lookahead", p)) cmd.lookahead = atoi(v) > 0 ? atoi(v) : -1;
     else if (starts("scenecut", p)) cmd.scenecut = atoi(v) > 0 ? atoi(v) : H264E_SCENECUT_DEFAULT;
     else if (starts("gop", p)) cmd.gop = atoi(v);
@@ -162,6 +166,7 @@ static int read_cmdline(int argc, char **argv)
                "    --keyframes f1,f2,...  --scenecut <threshold|x>   (clip path only)\n"
                "    --qpfile <f>   one QP (10..51) per frame, whitespace separated   (clip path only)\n"
                "    --kbps <n> --lookahead <frames|x>   this encoder's own window rate control instead of the reference's   (clip path only)\n"
+               "    --lookahead-search <r>   with --lookahead: motion search of +-r (1..8) half-resolution samples in its cost pass\n"
                "    --colour bt709|bt601|bt709-full|bt601-full  --fps <n[/d]>   (signalled in the SPS; the samples are not touched)\n");
         return 0;
     }
@@ -549,6 +554,7 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
             if (s->par.resident_frames < n && W + s->chunk - 1 > s->par.resident_frames) { printf("ERROR: --lookahead %d does not fit the input ring (%d frames, staged %d at a time)\n", W, s->par.resident_frames, s->chunk); goto out; }
             if (H264E_clip_set_lookahead(s->clip, cmd.lookahead_kbps, W, 0, 0)) { printf("ERROR: --lookahead: %s\n", H264E_last_error()); goto out; }
             cmd.lookahead = W;
+            if (cmd.lookahead_search && H264E_clip_set_lookahead_search(s->clip, cmd.lookahead_search)) { printf("ERROR: --lookahead-search: %s\n", H264E_last_error()); goto out; }
         }
         if (cmd.matrix && H264E_clip_set_color(s->clip, cmd.matrix, cmd.full_range)) { printf("ERROR: --colour: %s\n", H264E_last_error()); goto out; }
         if (cmd.fps_num && H264E_clip_set_frame_rate(s->clip, cmd.fps_num, cmd.fps_den)) { printf("ERROR: --fps: %s\n", H264E_last_error()); goto out; }
@@ -661,6 +667,7 @@ int main(int argc, char **argv)
         return 1;
     }
     if (cmd.lookahead && cmd.kbps <= 0) { printf("ERROR: --lookahead needs --kbps\n"); return 1; }
+    if (cmd.lookahead_search && !cmd.lookahead) { printf("ERROR: --lookahead-search needs --lookahead\n"); return 1; }
     if (cmd.lookahead && cmd.have_qp_file) { printf("ERROR: --lookahead and --qpfile exclude each other\n"); return 1; }
     if (cmd.lookahead) { cmd.lookahead_kbps = cmd.kbps; cmd.kbps = 0; }      /* --kbps alone stays the reference's controller */
     guess_format(cmd.input_file, &w, &h);

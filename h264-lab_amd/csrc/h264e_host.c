@@ -1087,6 +1087,9 @@ struct H264E_clip_tag
     uint64_t la_k[2];                       /* the calibration factors, P and key frames */
     long long la_debt;                      /* sum over the closed windows of target - actual bits */
     double la_kernel_ms; long long la_frames;
+    /* motion search in the cost pass (H264E_clip_set_lookahead_search): the range, 0 = off; a frame has been analysed since open (its
+     * records belong to that range); frames [la_ring_lo, la_done) still have their entries in the device's rings of max(resident, 2) */
+    int la_search, la_any, la_ring_lo;
 };
 
 /* The schedule rule, once.  frame_num restarts at every key frame, and so does the periodic counter: the next periodic key frame
@@ -1138,6 +1141,8 @@ static double now_ms(void)
  * accepted window replaces them */
 #define LOOKAHEAD_K0_P 15086u
 #define LOOKAHEAD_K0_KEY 14322u
+/* ... of P frames when the cost pass searches (H264E_clip_set_lookahead_search): the same medians over the searched P(f), range 8 */
+#define LOOKAHEAD_K0_SEARCH 53818u
 
 void H264E_clip_rewind(H264E_clip_t *c)
 {
@@ -1156,7 +1161,7 @@ void H264E_clip_rewind(H264E_clip_t *c)
     c->rc_frame = -1; c->rc_qp = c->par.qp; c->rc_last_bytes[0] = c->rc_last_bytes[1] = 0;
     /* lookahead controller: every pass starts from the same factors and no carry, so it chooses the same QPs again */
     c->la_planned = c->la_closed = 0; c->la_debt = 0;
-    c->la_k[0] = LOOKAHEAD_K0_P; c->la_k[1] = LOOKAHEAD_K0_KEY;
+    c->la_k[0] = c->la_search ? LOOKAHEAD_K0_SEARCH : LOOKAHEAD_K0_P; c->la_k[1] = LOOKAHEAD_K0_KEY;
 }
 
 int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nframes)
@@ -1788,6 +1793,44 @@ int H264E_clip_read_lookahead(H264E_clip_t *c, int first, int n, uint64_t *intra
     return 0;
 }
 
+int H264E_clip_set_lookahead_search(H264E_clip_t *c, int range)
+{
+    g_host_err[0] = 0;
+    if (!c) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: bad argument"); return -1; }
+    if (range < 0 || range > 8) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: range %d is outside 0..8", range); return -1; }
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
+    if (c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: not with keep_records = %d (GOP shards)", c->par.keep_records); return -1; }
+    if (range != c->la_search && c->la_any)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: range %d after frames have been analysed with range %d (their records cannot be made again)", range, c->la_search);
+        return -1;
+    }
+    c->la_search = range;
+    c->la_k[0] = range ? LOOKAHEAD_K0_SEARCH : LOOKAHEAD_K0_P;      /* (the clip stands at frame 0: no window has been planned) */
+    return 0;
+}
+
+static int clip_la_entries(const H264E_clip_t *c) { return imax(c->resident, 2); }
+
+int H264E_clip_read_lookahead_motion(H264E_clip_t *c, int frame, void *dst, int *nbx, int *nby)
+{
+    int lo, hi;
+    g_host_err[0] = 0;
+    if (!c) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: bad argument"); return -1; }
+    if (nbx) *nbx = (c->par.width >> 1) >> 3;
+    if (nby) *nby = (c->par.height >> 1) >> 3;
+    if (!dst) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: bad argument"); return -1; }
+    if (!c->la_search) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: the search is off (H264E_clip_set_lookahead_search), no frame has a motion field"); return -1; }
+    hi = c->la_rec ? c->la_done : 0; lo = imin(c->la_ring_lo, hi);
+    if (frame < lo || frame >= hi)
+    {
+        if (lo < hi) snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: frame %d has no motion field on the device (frames %d..%d have)", frame, lo, hi - 1);
+        else snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: frame %d has no motion field on the device (no frame has)", frame);
+        return -1;
+    }
+    return h264e_hip_lookahead_read_field(c->pool, frame, dst);
+}
+
 /* diagnostic (tools/lookahead_probe.py): HIP-event time of the cost pass' kernel launches since open, and the frames they analysed */
 int H264E_clip_lookahead_time(H264E_clip_t *c, double *kernel_ms, long long *frames)
 {
@@ -1804,9 +1847,13 @@ static int clip_prepass_lookahead(H264E_clip_t *c, int limit)
     float ms = 0;
     if (a >= limit) return 0;
     if (limit - a > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "lookahead: frames %d..%d do not fit the input ring", a, limit - 1); return -1; }
-    if (h264e_hip_lookahead_frames(c->pool, a, limit - a, (unsigned long long *)(c->la_rec + 3*(size_t)a), &ms)) return -1;
+    if (c->la_search ? h264e_hip_lookahead_search_frames(c->pool, a, limit - a, c->la_search, (unsigned long long *)(c->la_rec + 3*(size_t)a), &ms)
+                     : h264e_hip_lookahead_frames(c->pool, a, limit - a, (unsigned long long *)(c->la_rec + 3*(size_t)a), &ms)) return -1;
     c->la_kernel_ms += ms; c->la_frames += limit - a;
     c->la_done = limit;
+    /* frames a.. took the entries of frames a - entries..: what was intact in front of a still is, from limit - entries on */
+    c->la_any = 1;
+    c->la_ring_lo = imax(imin(c->la_ring_lo, a), limit - clip_la_entries(c));
     return 0;
 }
 

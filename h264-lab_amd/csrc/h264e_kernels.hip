@@ -21,6 +21,8 @@
  *                        bfloat16 / float32 samples in [0, 1], quantised on the way in and divided by 255 on the way out.
  *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
  *   h264e_lookahead_kernel the cost pass of the lookahead rate control (enc_lookahead.h): intra / inter cost sums of one resident input frame.
+ *   h264e_lookahead_search_kernel the same pass with a motion search of up to +-8 half-resolution samples per block
+ *                        (enc_lookahead_search.h): the sums from the searched inter cost, and a motion field.
  *
  * HIP only (hipcc --offload-arch=gfx950).  The host side of the boundary is h264e_pool.h, included at the end; the test-only
  * emulation of tests/emu compiles the same kernel HEADERS with its own launch functions and never sees this file.
@@ -38,6 +40,7 @@
 #include "enc_hbd.h"
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
+#include "enc_lookahead_search.h"
 #include "enc_ssim.h"
 #include "../../include/h264e_hip.h"
 
@@ -929,6 +932,62 @@ __global__ void __launch_bounds__(256) h264e_lookahead_kernel(lookahead_args_t A
     }
 }
 
+/* the cost pass with a motion search (enc_lookahead_search.h): one wave per workgroup and strip of 8 blocks, blockIdx.x the strip and
+ * blockIdx.y the block row.  The only LDS traffic between lanes is inside the one wave: wave_sync orders it. */
+DEV int lookahead_wave_min(int v)
+{
+    v = imin_raw(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));     /* quad_perm [1,0,3,2] */
+    v = imin_raw(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));     /* quad_perm [2,3,0,1] */
+    v = imin_raw(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));    /* row_half_mirror */
+    v = imin_raw(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false));    /* row_mirror */
+    return imin_raw(imin_raw(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), imin_raw(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+__global__ void __launch_bounds__(64) h264e_lookahead_search_kernel(lookahead_search_args_t S)
+{
+    __shared__ lookahead_search_lds_t sh;
+    LDS_AS uint32_t *prev = (LDS_AS uint32_t *)sh.prev, *cur = (LDS_AS uint32_t *)sh.cur;
+    LDS_AS int *intra_of = (LDS_AS int *)sh.intra;
+    const int lane = (int)threadIdx.x, i = lane >> 3, r = lane & 7;
+    const int bx0 = (int)blockIdx.x*LOOKAHEAD_SEARCH_STRIP, by = (int)blockIdx.y, nb = imin_raw(LOOKAHEAD_SEARCH_STRIP, S.a.nbx - bx0);
+    const int b = by*S.a.nbx + bx0 + i, on = i < nb;
+    lookahead_row_t R = { { 0u, 0u }, { 0u, 0u } };
+    if (on) R = lookahead_row(S.a, b, r);
+    const int m = (lookahead_oct_sum(lookahead_row_sum(R)) + 32) >> 6;
+    const int intra = lookahead_oct_sum(lookahead_row_intra(R, m));
+    int key = LOOKAHEAD_SEARCH_NO_KEY;          /* lane i < nb: the winning key of strip block i */
+    if (r == 0) intra_of[i] = intra;
+    if (S.a.prev)
+    {
+        cur[2*lane] = R.lo[0]; cur[2*lane + 1] = R.lo[1];
+        for (int c = lane; c < LOOKAHEAD_SEARCH_CELLS; c += 64) lookahead_search_stage(S, bx0, by, c, prev);
+        if (lane == 0) prev[LOOKAHEAD_SEARCH_PREV_DWORDS - 1] = 0u;
+    }
+    wave_sync();
+    if (S.a.prev)
+    {
+        const int side = 2*S.range + 1, rounds = (side*side + 63) >> 6;
+        int cand[LOOKAHEAD_SEARCH_ROUNDS];
+#pragma unroll
+        for (int k = 0; k < LOOKAHEAD_SEARCH_ROUNDS; k++) cand[k] = lookahead_search_candidate(S.range, 64*k + lane);
+        for (int j = 0; j < nb; j++)
+        {
+            const int best = lookahead_wave_min(lookahead_search_lane(S, prev, cur, bx0 + j, by, j, cand, rounds));
+            if (lane == j) key = best;
+        }
+    }
+    int si = 0, sp = 0, sn = 0;
+    if (lane < nb)
+    {
+        /* frame 0 of the clip: inter = intra, the vector (0, 0) */
+        const int mine = intra_of[lane];
+        const int inter = S.a.prev ? key >> 15 : mine;
+        lookahead_search_field_store(S, by*S.a.nbx + bx0 + lane, lookahead_search_cell(S.a.prev ? key : lookahead_search_key(mine, 0, 0)));
+        si = mine; sp = mine < inter ? mine : inter; sn = mine < inter;
+    }
+    si = wave_reduce_add(si); sp = wave_reduce_add(sp); sn = wave_reduce_add(sn);
+    if (lane < 3) lookahead_record_add(S.a.record + lane, (unsigned long long)(lane == 0 ? si : lane == 1 ? sp : sn));
+}
+
 /* ------------------------------------------------------------------ launches (what h264e_pool.h calls) */
 
 /* variant: 0 = intra frames only (one wave per row, 4 per SIMD), 1 = one wave per row, 2 = two waves per row (3 per SIMD), 3 = the latency variant: four
@@ -1029,6 +1088,11 @@ static void bk_launch_lookahead(const lookahead_args_t &A, hipStream_t st)
     int wgs = (A.nblk + 31)/32;
     if (wgs > 1024) wgs = 1024;
     hipLaunchKernelGGL(h264e_lookahead_kernel, dim3((unsigned)(wgs > 0 ? wgs : 1)), dim3(256), 0, st, A);
+}
+/* one single-wave workgroup per strip of 8 blocks of a block row (1080p: 8 x 67) */
+static void bk_launch_lookahead_search(const lookahead_search_args_t &S, hipStream_t st)
+{
+    hipLaunchKernelGGL(h264e_lookahead_search_kernel, dim3((unsigned)((S.a.nbx + LOOKAHEAD_SEARCH_STRIP - 1)/LOOKAHEAD_SEARCH_STRIP), (unsigned)S.nby), dim3(64), 0, st, S);
 }
 static void bk_launch_stage_selftest(int stage, const uint8_t *in, const int *args, uint8_t *out, hipStream_t st)
 {

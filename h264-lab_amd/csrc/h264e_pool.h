@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those nine are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_lookahead_search, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those ten are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -19,6 +19,7 @@
 #include "enc_hbd.h"
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
+#include "enc_lookahead_search.h"
 #include "enc_ssim.h"
 
 /* The matrix rows (tests/color_model.py): Kr / Kb scaled by 219/255 and 224/255 (limited) or 1 (full), times 256,
@@ -186,6 +187,7 @@ struct h264e_hip_pool
     uint8_t *la_lo;                      /* device [la_entries][la_entry_bytes]: the half-resolution pictures, frame f in entry f % la_entries */
     unsigned long long *la_rec;          /* device [la_entries][3]: I, P, N of the frame in that entry */
     int la_entries; size_t la_entry_bytes;
+    uint32_t *la_field;                  /* device [la_entries][nblk]: the motion fields of the pass with search (enc_lookahead_search.h); NULL until it first runs */
     h264e_color_t cm;                    /* the RGB -> YCbCr matrix of the RGB / RGBP ingest and scale launches (h264e_hip_set_color) */
     hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
     hipEvent_t ev_in[2];                 /* h264e_hip_copy_timer_*: around a caller's launches on the copy stream */
@@ -308,7 +310,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     dev_free(p->heap);
     dev_free(p->den);
     dev_free(p->sc_rec);
-    dev_free(p->la_lo); dev_free(p->la_rec);
+    dev_free(p->la_lo); dev_free(p->la_rec); dev_free(p->la_field);
     dev_free(p->qual_dev);
     if (p->stream)
     {
@@ -776,13 +778,55 @@ static void bk_launch_lookahead(const lookahead_args_t &A, hipStream_t)
     }
     for (int k = 0; k < 3; k++) lookahead_record_add(A.record + k, sum[k]);
 }
+/* ... with search: strip after strip, the wave's lanes once as (block, row) and once per block as the candidates */
+static void bk_launch_lookahead_search(const lookahead_search_args_t &S, hipStream_t)
+{
+    unsigned long long sum[3] = { 0, 0, 0 };
+    const int side = 2*S.range + 1, rounds = (side*side + 63) >> 6;
+    for (int by = 0; by < S.nby; by++)
+        for (int bx0 = 0; bx0 < S.a.nbx; bx0 += LOOKAHEAD_SEARCH_STRIP)
+        {
+            lookahead_search_lds_t sh;
+            const int nb = imin_h(LOOKAHEAD_SEARCH_STRIP, S.a.nbx - bx0);
+            memset(&sh, 0, sizeof(sh));
+            for (int i = 0; i < nb; i++)
+            {
+                lookahead_row_t R[8];
+                int s = 0, intra = 0;
+                for (int r = 0; r < 8; r++) { R[r] = lookahead_row(S.a, by*S.a.nbx + bx0 + i, r); s += lookahead_row_sum(R[r]); sh.cur[16*i + 2*r] = R[r].lo[0]; sh.cur[16*i + 2*r + 1] = R[r].lo[1]; }
+                for (int r = 0; r < 8; r++) intra += lookahead_row_intra(R[r], (s + 32) >> 6);
+                sh.intra[i] = intra;
+            }
+            if (S.a.prev) for (int c = 0; c < LOOKAHEAD_SEARCH_CELLS; c++) lookahead_search_stage(S, bx0, by, c, sh.prev);
+            for (int i = 0; i < nb; i++)
+            {
+                const int intra = sh.intra[i];
+                int key = lookahead_search_key(intra, 0, 0);
+                if (S.a.prev)
+                {
+                    key = LOOKAHEAD_SEARCH_NO_KEY;
+                    WAVE_FOR(l)
+                    {
+                        int cand[LOOKAHEAD_SEARCH_ROUNDS];
+                        for (int k = 0; k < LOOKAHEAD_SEARCH_ROUNDS; k++) cand[k] = lookahead_search_candidate(S.range, 64*k + l);
+                        key = imin_h(key, lookahead_search_lane(S, sh.prev, sh.cur, bx0 + i, by, i, cand, rounds));
+                    }
+                }
+                const int inter = key >> 15;
+                lookahead_search_field_store(S, by*S.a.nbx + bx0 + i, lookahead_search_cell(key));
+                sum[0] += (unsigned)intra; sum[1] += (unsigned)(intra < inter ? intra : inter); sum[2] += intra < inter;
+            }
+        }
+    for (int k = 0; k < 3; k++) lookahead_record_add(S.a.record + k, sum[k]);
+}
 #endif
 
-/* frames first, first + 1, ... of the STREAM (input slot f % frames_resident): their records into rec [n][3] on return */
-extern "C" int h264e_hip_lookahead_frames(h264e_hip_pool_t *p, int first, int n, unsigned long long *rec, float *kernel_ms)
+/* frames first, first + 1, ... of the STREAM (input slot f % frames_resident): their records into rec [n][3] on return; range 0 = the
+ * pass without search, 1..8 = h264e_lookahead_search_kernel, which also fills the frames' entries of the field ring */
+static int lookahead_frames(h264e_hip_pool_t *p, int first, int n, int range, unsigned long long *rec, float *kernel_ms)
 {
     const int R = p ? p->frames_resident : 0;
-    if (!p || !rec || first < 0 || n < 0 || n > R) FAIL("lookahead_frames: bad argument");
+    if (!p || !rec || first < 0 || n < 0 || n > R || range < 0 || range > LOOKAHEAD_SEARCH_MAX_RANGE) FAIL("lookahead_frames: bad argument");
     if (p->G.width < LOOKAHEAD_MIN_SIDE || p->G.height < LOOKAHEAD_MIN_SIDE) FAIL("lookahead: pictures below %dx%d have no cost block (%dx%d)", LOOKAHEAD_MIN_SIDE, LOOKAHEAD_MIN_SIDE, p->G.width, p->G.height);
     if (kernel_ms) *kernel_ms = 0;
     if (!n) return 0;
@@ -796,6 +840,7 @@ extern "C" int h264e_hip_lookahead_frames(h264e_hip_pool_t *p, int first, int n,
         if (dev_malloc((void **)&p->la_lo, p->la_entry_bytes*(size_t)p->la_entries)) { p->la_lo = 0; FAIL("lookahead: device allocation failed (%d half-resolution pictures)", p->la_entries); }
         if (dev_malloc((void **)&p->la_rec, sizeof(unsigned long long)*3*(size_t)p->la_entries)) { dev_free(p->la_lo); p->la_lo = 0; p->la_rec = 0; FAIL("lookahead: device allocation failed (%d records)", p->la_entries); }
     }
+    if (range && !p->la_field && dev_malloc((void **)&p->la_field, (size_t)A.nblk*LOOKAHEAD_FIELD_CELL_BYTES*(size_t)p->la_entries)) { p->la_field = 0; FAIL("lookahead: device allocation failed (%d motion fields)", p->la_entries); }
     const int E = p->la_entries;
     /* the inputs may have come over the copy stream (asynchronous uploads, device input): the launches wait for everything issued there */
     HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
@@ -816,7 +861,13 @@ extern "C" int h264e_hip_lookahead_frames(h264e_hip_pool_t *p, int first, int n,
         A.prev = f ? p->la_lo + p->la_entry_bytes*(size_t)((f - 1) % E) : NULL;
         A.cur = p->la_lo + p->la_entry_bytes*(size_t)e;
         A.record = p->la_rec + 3*(size_t)e;
-        bk_launch_lookahead(A, p->stream);
+        if (range)
+        {
+            lookahead_search_args_t S;
+            S.a = A; S.field = p->la_field + (size_t)A.nblk*(size_t)e; S.range = range; S.nby = A.nblk/A.nbx;
+            bk_launch_lookahead_search(S, p->stream);
+        }
+        else bk_launch_lookahead(A, p->stream);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(p->ev_sc[1], p->stream));
@@ -828,6 +879,26 @@ extern "C" int h264e_hip_lookahead_frames(h264e_hip_pool_t *p, int first, int n,
     }
     HIPCHK(hipStreamSynchronize(p->stream));
     if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, p->ev_sc[0], p->ev_sc[1]));
+    return 0;
+}
+
+extern "C" int h264e_hip_lookahead_frames(h264e_hip_pool_t *p, int first, int n, unsigned long long *rec, float *kernel_ms) { return lookahead_frames(p, first, n, 0, rec, kernel_ms); }
+
+extern "C" int h264e_hip_lookahead_search_frames(h264e_hip_pool_t *p, int first, int n, int range, unsigned long long *rec, float *kernel_ms)
+{
+    if (range < 1) FAIL("lookahead_search_frames: bad argument");
+    return lookahead_frames(p, first, n, range, rec, kernel_ms);
+}
+
+/* the field of STREAM frame `frame` from its ring entry: what is there is the caller's to know */
+extern "C" int h264e_hip_lookahead_read_field(h264e_hip_pool_t *p, int frame, void *dst)
+{
+    if (!p || !dst || frame < 0) FAIL("lookahead_read_field: bad argument");
+    if (!p->la_field) FAIL("lookahead_read_field: no frame has been analysed with a search");
+    HIPCHK(hipSetDevice(p->device));
+    const size_t bytes = p->la_entry_bytes/LOOKAHEAD_BLOCK_BYTES*LOOKAHEAD_FIELD_CELL_BYTES;
+    HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)p->la_field + bytes*(size_t)(frame % p->la_entries), bytes, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
     return 0;
 }
 

@@ -166,6 +166,15 @@ int  h264e_hip_scenecut_frames(h264e_hip_pool_t *pool, int first, int n, uint32_
  * half-resolution picture that the pass made of frame f - 1, kept in a ring of the pool (allocated on first use): frames must be
  * analysed in order, and f - 1 no more than the ring's length before.  Refused below 16x16.  kernel_ms (optional): as above. */
 int  h264e_hip_lookahead_frames(h264e_hip_pool_t *pool, int first, int n, unsigned long long *rec, float *kernel_ms);
+/* The same pass with a motion search of +-range half-resolution samples per block, range in 1..8 (enc_lookahead_search.h): P and N of
+ * the records come from the searched inter cost, and every analysed frame's motion field -- one cell {int8 dx, int8 dy, uint16 cost}
+ * per block, nbx x nby = ((width/2) >> 3) x ((height/2) >> 3) of them, row by row -- goes into a field ring of the pool with the entries of
+ * the half-resolution ring (allocated on first use).  The half-resolution entries are those of the call above: frames analysed with and
+ * without search may follow each other. */
+int  h264e_hip_lookahead_search_frames(h264e_hip_pool_t *pool, int first, int n, int range, unsigned long long *rec, float *kernel_ms);
+/* The field ring's entry of STREAM frame `frame` (entry frame % max(frames_resident, 2)) into dst [nbx*nby*4 bytes]; the call waits for
+ * the stream.  Which frame the entry holds is the caller's to know.  Refused before the first call with a search. */
+int  h264e_hip_lookahead_read_field(h264e_hip_pool_t *pool, int frame, void *dst);
 /* Launch groups: the submits of the member pools (same device, same picture size, one host thread each) are merged into ONE kernel
  * launch per round -- the streams' jobs interleaved in dispatch order, every job with its own pool's buffers / abort word / results --
  * so that independent streams fill each other's pipeline drains.  h264e_hip_submit of a member blocks until all members that are

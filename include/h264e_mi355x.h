@@ -454,11 +454,30 @@ int  H264E_clip_set_qp_schedule(H264E_clip_t *clip, const uint8_t *qp, int n);
  * sum C(f)*Lq[t][q_f - 10], clamped to [k_old/4, min(4*k_old, 2^40)] and to at least 1; left alone when the divisor is 0.  A launch never
  * crosses a window boundary, and a window whose frames are not all uploaded is not started: H264E_clip_encode returns with what it
  * encoded (zero frames is not an error) -- except the clip's last window once all frames are uploaded.  Zero-motion inter cost
- * overestimates pans; the calibration absorbs a steady bias.  VBV compliance is not claimed. */
+ * overestimates pans; the calibration absorbs a steady bias, H264E_clip_set_lookahead_search below removes the cause.  VBV compliance
+ * is not claimed. */
 int  H264E_clip_set_lookahead(H264E_clip_t *clip, int kbps, int window, int qp_min, int qp_max);
 /* I(f), P(f), N(f) and the QP of frames first .. first + n - 1; each pointer may be NULL.  Costs: only frames already analysed; QPs:
  * only frames of an explicit schedule or of windows already planned in this pass; -1 otherwise. */
 int  H264E_clip_read_lookahead(H264E_clip_t *clip, int first, int n, uint64_t *intra, uint64_t *inter, int *intra_blocks, uint8_t *qp);
+/* Motion search in the cost pass: range 0 = off (the pass above, the default), 1..8 = every block's inter cost is the smallest SAD over
+ * the displacements of up to +-range half-resolution samples (enc_lookahead_search.h, tests/lookahead_motion_model.py).  With
+ * A = [0, 8*nbx) x [0, 8*nby), nbx = (width/2) >> 3, nby = (height/2) >> 3: candidates d = (dx, dy), |dx|, |dy| <= range, whose 8x8
+ * block at (8bx + dx, 8by + dy) lies wholly inside A (left out otherwise, not clamped); sad(b, d) = sum |L_f(x, y) - L_{f-1}(x + dx,
+ * y + dy)|; inter(b) = the smallest sad, mv(b) = the candidate that reaches it and is first by (|dx| + |dy|, dy, dx) -- no vector
+ * penalty; frame 0 of the clip: inter = intra, mv = (0, 0).  I, P, N are formed as above from this inter(b), so
+ * H264E_clip_read_lookahead returns the searched P and N, and the controller is the one above with C(f) = the searched P(f) and the
+ * initial k[0] = 53818 instead of 15086 (measured the same way).  The setting takes effect whenever the controller runs
+ * its cost pass.  While the clip stands at frame 0; kept across a rewind.  Refused -- nothing changes, H264E_last_error names the
+ * value -- with a range outside 0..8, with keep_records, and with another range than the current one once a frame of the clip has been
+ * analysed (the stored records belong to the old range, and a bounded input ring cannot make them again). */
+int  H264E_clip_set_lookahead_search(H264E_clip_t *clip, int range);
+/* The motion field of an analysed frame: nbx*nby cells {int8 dx, int8 dy, uint16 cost = inter(b)}, row by row, into dst; *nbx, *nby
+ * (optional) receive the field's size for every clip, also when the call is refused (a call with dst NULL asks for the size alone
+ * and returns -1).  The fields live in a ring of max(resident_frames, 2) entries on the device: -1, with the readable
+ * frames named in H264E_last_error, when the frame has not been analysed, when its entry has been taken by a later frame, and when the
+ * search is off.  Uploading frame f again makes the fields from f onward new. */
+int  H264E_clip_read_lookahead_motion(H264E_clip_t *clip, int frame, void *dst, int *nbx, int *nby);
 /* diagnostic: HIP-event time of the cost pass' kernel launches since open, and the frames they analysed (tools/lookahead_probe.py) */
 int  H264E_clip_lookahead_time(H264E_clip_t *clip, double *kernel_ms, long long *frames);
 /* GOP shards of ONE stream (one clip encoder per shard / GPU, the shard starting at a key frame with first_idr_pic_id_state =

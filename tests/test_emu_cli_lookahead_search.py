@@ -1,0 +1,61 @@
+"""CPU: encode_app --lookahead-search R (the product CLI against the emulation library): the binding's stream, and the refusals."""
+import os
+import subprocess
+
+import pytest
+
+import clips
+import pkg
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+APP = os.path.join(HERE, "emu", "build", "encode_app_emu")
+W, H, N, GOP, WINDOW, KBPS, R = 176, 144, 12, 8, 4, 120, 8
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _emu():
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu")], stdout=subprocess.DEVNULL)
+
+
+def _app(tmp_path, c, args, name="o.264"):
+    yuv = tmp_path / ("ls_%dx%d.yuv" % (W, H))
+    c.tofile(yuv)
+    out = tmp_path / name
+    r = subprocess.run([APP, "--input", str(yuv), "--output", str(out), "--stats", "x"] + args, capture_output=True, text=True, timeout=600)
+    return r, (out.read_bytes() if out.exists() else b"")
+
+
+def _binding(c, search):
+    P = pkg.load_pkg()
+    ce = P.ClipEncoder(W, H, N, lib=pkg.EMU_LIB, gop=GOP, qp=26, abr_kbps=KBPS, lookahead=WINDOW, lookahead_search=search)
+    ce.upload(c)
+    out, sizes, _ = ce.encode()
+    _, qp = ce.read_lookahead(costs=False)
+    ce.close()
+    return out, sizes, qp
+
+
+def test_cli_lookahead_search(tmp_path):
+    c = clips.make("pan", W, H, N)
+    want, sizes, qp = _binding(c, R)
+    plain, _, _ = _binding(c, 0)
+    assert want != plain, "clip and target tell the two cost passes apart"
+    base = ["--gop", str(GOP), "--kbps", str(KBPS)]
+    r, out = _app(tmp_path, c, base + ["--lookahead", str(WINDOW), "--lookahead-search", str(R)])
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert out == want
+    line = "lookahead: window %d, QP %d..%d, %.1f kbps for a target of %d" % (WINDOW, qp.min(), qp.max(), sum(sizes) * 8.0 * 30.0 / N / 1000.0, KBPS)
+    assert [l for l in r.stdout.splitlines() if l.startswith("lookahead")] == [line]
+    r, out = _app(tmp_path, c, base + ["--lookahead", str(WINDOW)])
+    assert r.returncode == 0 and out == plain, "--lookahead alone stays the pass without search"
+    r, out = _app(tmp_path, c, base + ["--lookahead", str(WINDOW), "--lookahead-search", "0"])
+    assert r.returncode == 0 and out == plain
+
+
+def test_cli_lookahead_search_refusals(tmp_path):
+    c = clips.make("pan", W, H, N)
+    base = ["--gop", str(GOP), "--kbps", str(KBPS)]
+    for args in (base + ["--lookahead-search", str(R)], ["--gop", str(GOP), "--qp", "30", "--lookahead-search", str(R)],
+                 base + ["--lookahead", str(WINDOW), "--lookahead-search", "9"], base + ["--lookahead", str(WINDOW), "--lookahead-search", "-1"]):
+        r, out = _app(tmp_path, c, args, name="refused.264")
+        assert r.returncode == 1 and "ERROR" in r.stdout and "lookahead-search" in r.stdout, (args, r.stdout)

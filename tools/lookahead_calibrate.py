@@ -5,9 +5,17 @@ tests/lookahead_model.py), measured on the CPU: over synth, pan, scene and noise
     ((coded bits - H) << 24) / (C * Lq[t][qp - 10])
 
 per frame type, with the coded sizes from the oracle (the reference's bytes) and C from the numpy model of the cost pass.  Prints the
-table that DESIGN.md 4.5k quotes.
+table that DESIGN.md 4.5k quotes.  --search R measures the same with the cost pass' motion search of range R
+(tests/lookahead_motion_model.py): the P-frame median is LOOKAHEAD_K0_SEARCH / K0_SEARCH; the key-frame column does not move, I(f) is not
+searched.
 
-    python tools/lookahead_calibrate.py [frames] [gop]
+    python tools/lookahead_calibrate.py [frames] [gop] [--search R]
+
+--step replays the controller instead (the model's plan, sizes from the oracle at the planned QPs) on the clip the search exists for: CIF,
+still for its first half and sliding down 8 samples a frame afterwards, 128 frames, GOP 30, W = 16, 300 kbit/s, with the range given by
+--search and without; prints per window the QP and the coded bits against the budget 8*dfb*W.
+
+    python tools/lookahead_calibrate.py --step [--search R]
 """
 import os
 import sys
@@ -19,13 +27,57 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import clips  # noqa: E402
 import lookahead_model as M  # noqa: E402
+import lookahead_motion_model as ML  # noqa: E402
 import oracle_lib  # noqa: E402
 import scenecut_model  # noqa: E402
 
 
+def oracle_bits(c, w, h, gop, qp):
+    """coded bits per frame with a QP per frame: the oracle frame by frame with qp_min = qp_max = qp[f]"""
+    e = oracle_lib.Encoder(w, h, gop=gop, qp=26)
+    bits = []
+    for f in range(len(qp)):
+        assert oracle_lib.lib().h264o_set_run_param(e.e, 0, 0, 0, int(qp[f]), int(qp[f]), 0) == 0
+        bits.append(8 * len(e.encode(c[f])))
+    e.close()
+    return bits
+
+
+def step_report(search):
+    w, h, n, gop, W, kbps = 352, 288, 128, 30, 16, 300
+    c = clips.vpan(w, h, n, 8, lambda t: t >= n // 2)
+    kinds = [int(k) for k in scenecut_model.kinds(n, gop, [])]
+    hdr = (40, 40 + 8 * M.parameter_set_bytes(oracle_lib.encode_clip(c[:1], w, h, gop=gop, qp=26)[0]))
+    budget = 8 * (kbps * 1000 // 8 // 30) * W
+    rows = {}
+    for R in (0, search):
+        cost = ML.costs(c, w, h, R)
+        bits, qp = [], []
+        for a in range(0, n, W):
+            # the plan reads the sizes of finished windows only: what lies behind window a does not matter yet
+            plan = ML.plan(cost, kinds, hdr, bits + [0] * (n - len(bits)), kbps, W, search=R)
+            qp += plan[a:a + W].tolist()
+            bits = oracle_bits(c, w, h, gop, qp)
+        rows[R] = [(qp[a], sum(bits[a:a + W])) for a in range(0, n, W)]
+        print("range %d: %d bits for a target of %d" % (R, sum(bits), 8 * (kbps * 1000 // 8 // 30) * n))
+    print("| window | frames | QP, no search | bits / budget | QP, search %d | bits / budget |" % search)
+    print("|---|---|---|---|---|---|")
+    for j in range(n // W):
+        (q0, b0), (q1, b1) = rows[0][j], rows[search][j]
+        print("| %d | %d..%d | %d | %d / %d = %.2f | %d | %d / %d = %.2f |" % (j, j * W, j * W + W - 1, q0, b0, budget, b0 / budget, q1, b1, budget, b1 / budget))
+
+
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 24
-    gop = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+    argv = sys.argv[1:]
+    search = 0
+    if "--search" in argv:
+        i = argv.index("--search")
+        search = int(argv[i + 1])
+        del argv[i:i + 2]
+    if "--step" in argv:
+        return step_report(search or ML.MAX_RANGE)
+    n = int(argv[0]) if len(argv) > 0 else 24
+    gop = int(argv[1]) if len(argv) > 1 else 8
     w, h = 352, 288
     kinds = [int(k) for k in scenecut_model.kinds(n, gop, [])]
     ratios = {0: [], 1: []}
@@ -33,7 +85,7 @@ def main():
     print("|---|---|---|---|")
     for name in ("synth", "pan", "scene", "noise"):
         c = clips.make(name, w, h, n)
-        cost = M.costs(c, w, h)
+        cost = ML.costs(c, w, h, search) if search else M.costs(c, w, h)
         for qp in (20, 26, 32, 38):
             stream, sizes = oracle_lib.encode_clip(c, w, h, gop=gop, qp=qp)
             hdr = (40, 40 + 8 * M.parameter_set_bytes(stream))

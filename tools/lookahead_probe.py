@@ -5,7 +5,11 @@ frame's QP follows the frame before it) and constant QP 26.  Per mode: fps of a 
 pass, launches, frames encoded again, achieved bitrate and QP range; for the window controller the cost pass' kernel time per frame
 from HIP events (H264E_clip_lookahead_time) and a sweep of the window over 8 / 16 / 32 / 64.  Prints one JSON line.
 
-    python tools/lookahead_probe.py [--frames 600] [--reps 3] [--kbps 4000]
+--search R adds a fourth mode behind the first, the window controller with the cost pass' motion search of range R
+(H264E_clip_set_lookahead_search), in the same process and order, and leaves the window sweep out: what the search costs per frame and
+in first-pass fps against the same run without it (profiles/lookahead_motion_probe.json).
+
+    python tools/lookahead_probe.py [--frames 600] [--reps 3] [--kbps 4000] [--search R]
 """
 import argparse
 import hashlib
@@ -56,10 +60,15 @@ def main():
     ap.add_argument("--frames", type=int, default=600)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--kbps", type=int, default=4000)
+    ap.add_argument("--search", type=int, default=0)
     a = ap.parse_args()
     P = pkg.load_pkg()
-    modes = {"lookahead_w32": dict(qp=QP, abr_kbps=a.kbps, lookahead=32), "reference_kbps": dict(kbps=a.kbps), "constant_qp": dict(qp=QP)}
-    clip_passes(P, min(a.frames, 64), **modes["lookahead_w32"])          # warm-up: code objects, page tables
+    modes = {"lookahead_w32": dict(qp=QP, abr_kbps=a.kbps, lookahead=32)}
+    if a.search:
+        modes["lookahead_w32_search"] = dict(qp=QP, abr_kbps=a.kbps, lookahead=32, lookahead_search=a.search)
+    modes.update({"reference_kbps": dict(kbps=a.kbps), "constant_qp": dict(qp=QP)})
+    for m in ("lookahead_w32", "lookahead_w32_search")[:2 if a.search else 1]:
+        clip_passes(P, min(a.frames, 64), **modes[m])                     # warm-up: code objects, page tables
     res = {m: [] for m in modes}
     for _ in range(a.reps):
         for m, kw in modes.items():
@@ -67,7 +76,13 @@ def main():
     line = {"clip": "1080p synth_v1 x %d, GOP %d, target %d kbit/s, constant QP %d" % (a.frames, GOP, a.kbps, QP), "reps": a.reps}
     for m in modes:
         line[m] = summary(res[m])
-    line["window_sweep"] = {str(w): summary([clip_passes(P, a.frames, qp=QP, abr_kbps=a.kbps, lookahead=w)]) for w in (8, 16, 32, 64)}
+    if a.search:
+        off, on = line["lookahead_w32"], line["lookahead_w32_search"]
+        line["search"] = {"range": a.search, "cost_pass_us_per_frame_over_without": round(on["cost_pass_kernel_us_per_frame"] / off["cost_pass_kernel_us_per_frame"], 2),
+                          "first_pass_fps_over_without": round(on["first_pass_fps"] / off["first_pass_fps"], 3),
+                          "first_pass_spread_without": round((max(off["samples_first"]) - min(off["samples_first"])) / off["first_pass_fps"], 3)}
+    else:
+        line["window_sweep"] = {str(w): summary([clip_passes(P, a.frames, qp=QP, abr_kbps=a.kbps, lookahead=w)]) for w in (8, 16, 32, 64)}
     line["lookahead_over_reference_kbps_rewound"] = round(line["lookahead_w32"]["rewound_pass_fps"] / line["reference_kbps"]["rewound_pass_fps"], 2)
     line["lookahead_over_reference_kbps_first"] = round(line["lookahead_w32"]["first_pass_fps"] / line["reference_kbps"]["first_pass_fps"], 2)
     print(json.dumps(line))
