@@ -485,6 +485,10 @@ def load(path=None):
     L.H264E_clip_lookahead_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.H264E_clip_set_lookahead_search.argtypes = [C.c_void_p, C.c_int]
     L.H264E_clip_read_lookahead_motion.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.H264E_clip_set_denoise_motion.argtypes = [C.c_void_p, C.c_int]
+    L.H264E_clip_read_denoised.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.H264E_clip_read_denoise_motion.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.H264E_clip_denoise_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.H264E_clip_position.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.H264E_clip_position.restype = None
     L.H264E_clip_revalidate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -683,7 +687,8 @@ class ClipEncoder:
 
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
                  clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0,
-                 color=None, fps=None, quality=None, qp_schedule=None, abr_kbps=0, lookahead=0, qp_range=(0, 0), lookahead_search=0):
+                 color=None, fps=None, quality=None, qp_schedule=None, abr_kbps=0, lookahead=0, qp_range=(0, 0), lookahead_search=0,
+                 denoise_motion=0):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
         self._ssd = self._ssim = None           # the registered metric arrays [nframes][3], owned here while registered
@@ -711,6 +716,8 @@ class ClipEncoder:
                 self.set_lookahead(abr_kbps, lookahead, qp_range)
             if lookahead_search:
                 self.set_lookahead_search(lookahead_search)
+            if denoise_motion:
+                self.set_denoise_motion(denoise_motion)
         except H264EError:
             self.close()
             raise
@@ -744,6 +751,40 @@ class ClipEncoder:
         """The temporal denoiser (H264E_clip_set_denoise): only while the clip stands at frame 0."""
         if self.L.H264E_clip_set_denoise(self.c, int(bool(on))):
             raise _err(self.L, "H264E_clip_set_denoise")
+
+    def set_denoise_motion(self, mode):
+        """The motion-compensated temporal denoiser (H264E_clip_set_denoise_motion): 0 = off, 1 = the previous denoised picture displaced
+        by the lookahead's motion field, 2 = by that field refined; needs set_lookahead_search(1..8) first; only while the clip stands at
+        frame 0.  denoise=True / set_denoise(True) stay the plain denoiser."""
+        if self.L.H264E_clip_set_denoise_motion(self.c, int(mode)):
+            raise _err(self.L, "H264E_clip_set_denoise_motion")
+
+    def read_denoised(self, frame):
+        """The denoised picture of a frame whose slot is still in the device's ring (H264E_clip_read_denoised), either denoiser's: packed
+        I420, uint8 [w*h*3/2]"""
+        out = np.empty(self.w * self.h * 3 // 2, np.uint8)
+        if self.L.H264E_clip_read_denoised(self.c, int(frame), out.ctypes.data):
+            raise _err(self.L, "H264E_clip_read_denoised")
+        return out
+
+    def read_denoise_motion(self, frame):
+        """(mv int8 [nby, nbx, 2] as (vx, vy), sad uint16 [nby, nbx]) of a filtered frame that is still in the device's ring
+        (H264E_clip_read_denoise_motion): per 16x16 luma block the vector the motion-compensated denoiser used, in luma samples, and
+        its SAD against the previous denoised picture."""
+        nbx, nby = C.c_int(), C.c_int()
+        self.L.H264E_clip_read_denoise_motion(self.c, -1, None, C.byref(nbx), C.byref(nby))
+        cells = np.zeros((nby.value, nbx.value), np.uint32)
+        if self.L.H264E_clip_read_denoise_motion(self.c, int(frame), cells.ctypes.data, None, None):
+            raise _err(self.L, "H264E_clip_read_denoise_motion")
+        mv = np.stack([(cells & 0xff).astype(np.uint8).view(np.int8), ((cells >> 8) & 0xff).astype(np.uint8).view(np.int8)], axis=-1)
+        return mv, (cells >> 16).astype(np.uint16)
+
+    def denoise_time(self):
+        """(HIP-event milliseconds inside the motion-compensated denoiser's kernel launches since open, frames they filtered)"""
+        ms, n = C.c_double(), C.c_longlong()
+        if self.L.H264E_clip_denoise_time(self.c, C.byref(ms), C.byref(n)):
+            raise _err(self.L, "H264E_clip_denoise_time")
+        return ms.value, n.value
 
     def set_color(self, color):
         """H264E_clip_set_color (see Encoder.set_color): only while the clip stands at frame 0, and BEFORE the frames are uploaded --

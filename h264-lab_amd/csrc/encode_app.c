@@ -33,6 +33,9 @@
  * a..b, X kbps for a target of K".  Both belong to the clip path and are refused like --keyframes / --scenecut.
  * --lookahead-search R (1..8; 0 = off) lets that controller's cost pass search +-R half-resolution samples per block
  * (H264E_clip_set_lookahead_search); it is refused without --lookahead.
+ * --denoise-motion M (1 = the search's vectors, 2 = refined; 0 = off) filters every frame with this encoder's motion-compensated temporal
+ * denoiser in front of the encoder (H264E_clip_set_denoise_motion); it reads the search's motion field and is refused without
+ * --lookahead-search.  --denoise alone, the reference's filter, stays refused.
  */
 #define _FILE_OFFSET_BITS 64
 #include <math.h>
@@ -49,6 +52,7 @@ static struct
     int scenecut, nkey, key_frames[1024];   /* --scenecut threshold (0 = off), --keyframes list */
     char qp_file[1024];                 /* --qpfile: one QP per frame */
     int lookahead_search;               /* --lookahead-search R */
+    int denoise_motion;                 /* --denoise-motion M */
     int have_qp_file, lookahead, lookahead_kbps;      /* --lookahead W (with --kbps K: the window controller; 0 = not given, -1 = the default window) */
     int matrix, full_range, fps_num, fps_den;   /* --colour, --fps (all 0: nothing is signalled) */
     int unsupported;                    /* a reference option this encoder refuses was given: no stream is written, exit 1 */
@@ -61,7 +65,8 @@ static void parse_long(const char *p, const char *val)
     const char *v = val ? val : "";
     /* T:135 --gen and T:163 --denoise are options of the reference this encoder does not implement: a stream that silently differs
      * from the reference's would be worse than none, so they end the run (main: exit 1) instead of being skipped like a typo */
-    if (starts("gen", p) || starts("denoise", p))
+    if (starts("denoise-motion", p)) cmd.denoise_motion = atoi(v);
+    else if (starts("gen", p) || starts("denoise", p))
     {
         printf("ERROR: option --%s is not supported by the MI355X encoder (reference-only: %s)\n", p,
                starts("gen", p) ? "libm-generated synthetic input" : "temporal denoiser");
@@ -167,6 +172,7 @@ static int read_cmdline(int argc, char **argv)
                "    --qpfile <f>   one QP (10..51) per frame, whitespace separated   (clip path only)\n"
                "    --kbps <n> --lookahead <frames|x>   this encoder's own window rate control instead of the reference's   (clip path only)\n"
                "    --lookahead-search <r>   with --lookahead: motion search of +-r (1..8) half-resolution samples in its cost pass\n"
+               "    --denoise-motion 1|2   with --lookahead-search: motion-compensated temporal denoiser from its vectors (2: refined by one sample)\n"
                "    --colour bt709|bt601|bt709-full|bt601-full  --fps <n[/d]>   (signalled in the SPS; the samples are not touched)\n");
         return 0;
     }
@@ -555,6 +561,7 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
             if (H264E_clip_set_lookahead(s->clip, cmd.lookahead_kbps, W, 0, 0)) { printf("ERROR: --lookahead: %s\n", H264E_last_error()); goto out; }
             cmd.lookahead = W;
             if (cmd.lookahead_search && H264E_clip_set_lookahead_search(s->clip, cmd.lookahead_search)) { printf("ERROR: --lookahead-search: %s\n", H264E_last_error()); goto out; }
+            if (cmd.denoise_motion && H264E_clip_set_denoise_motion(s->clip, cmd.denoise_motion)) { printf("ERROR: --denoise-motion: %s\n", H264E_last_error()); goto out; }
         }
         if (cmd.matrix && H264E_clip_set_color(s->clip, cmd.matrix, cmd.full_range)) { printf("ERROR: --colour: %s\n", H264E_last_error()); goto out; }
         if (cmd.fps_num && H264E_clip_set_frame_rate(s->clip, cmd.fps_num, cmd.fps_den)) { printf("ERROR: --fps: %s\n", H264E_last_error()); goto out; }
@@ -668,6 +675,7 @@ int main(int argc, char **argv)
     }
     if (cmd.lookahead && cmd.kbps <= 0) { printf("ERROR: --lookahead needs --kbps\n"); return 1; }
     if (cmd.lookahead_search && !cmd.lookahead) { printf("ERROR: --lookahead-search needs --lookahead\n"); return 1; }
+    if (cmd.denoise_motion && !cmd.lookahead_search) { printf("ERROR: --denoise-motion needs --lookahead-search\n"); return 1; }
     if (cmd.lookahead && cmd.have_qp_file) { printf("ERROR: --lookahead and --qpfile exclude each other\n"); return 1; }
     if (cmd.lookahead) { cmd.lookahead_kbps = cmd.kbps; cmd.kbps = 0; }      /* --kbps alone stays the reference's controller */
     guess_format(cmd.input_file, &w, &h);

@@ -1090,6 +1090,9 @@ struct H264E_clip_tag
     /* motion search in the cost pass (H264E_clip_set_lookahead_search): the range, 0 = off; a frame has been analysed since open (its
      * records belong to that range); frames [la_ring_lo, la_done) still have their entries in the device's rings of max(resident, 2) */
     int la_search, la_any, la_ring_lo;
+    /* motion-compensated filter (H264E_clip_set_denoise_motion): 0 = the plain denoiser fills the ring, 1 / 2 = enc_mcdenoise.h does, from
+     * the motion field of the searched cost pass; frames [den_ring_lo, den_done) still have their pictures (and vector cells) on the device */
+    int den_motion, den_ring_lo;
 };
 
 /* The schedule rule, once.  frame_num restarts at every key frame, and so does the periodic counter: the next periodic key frame
@@ -1266,7 +1269,7 @@ static int clip_put_allowed(const H264E_clip_t *c, int first, int n)
         return -1;
     }
     /* the cost pass measures frame `first` against the half-resolution picture of the frame in front of it (enc_lookahead.h) */
-    if (c->la_kbps && first > 0 && first < c->la_done && first - 1 < c->la_done - imax(c->resident, 2))
+    if ((c->la_kbps || c->den_motion) && first > 0 && first < c->la_done && first - 1 < c->la_done - imax(c->resident, 2))
     {
         snprintf(g_host_err, sizeof(g_host_err), "upload: frame %d would be analysed again, but the half-resolution picture in front of it has left the ring (rewind and upload from frame 0)", first);
         return -1;
@@ -1547,26 +1550,31 @@ int H264E_clip_restart(H264E_clip_t *c, int frame, const int32_t state[2])
  * denoised on the device, in stream order, before the launch that first encodes it; the denoised pictures are a pure function of the
  * inputs, so a rewind keeps them until frames are uploaded again.  Refused together with keep_records (a GOP shard's first frame
  * would need the denoised picture of the frame in front of it, which lives in another encoder). */
+/* the denoised ring of a clip whose denoiser is off: the budget check, the allocation, the zero state */
+static int clip_denoise_ring(H264E_clip_t *c, const char *who)
+{
+    /* the denoised frames (one per resident input slot + the zero state) count in the HBM budget that sized the slot ring */
+    const double fsz = (double)c->seq.width*c->seq.height*3/2, den = fsz*(c->resident == 1 ? 3 : c->resident + 1);
+    if (c->par.max_chains <= 0 && (double)c->ring*clip_dev_slot_bytes(c->seq.nmb) + den > CLIP_DEV_BUDGET)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "%s: %d slots + %.0f MB of denoised frames exceed the %.0f GB budget: open with max_chains or resident_frames",
+                 who, c->ring, den/1048576.0, CLIP_DEV_BUDGET/1073741824.0);
+        return -1;
+    }
+    if (h264e_hip_denoise_reset(c->pool)) return -1;
+    c->den_done = c->den_ring_lo = 0;
+    return 0;
+}
+
 int H264E_clip_set_denoise(H264E_clip_t *c, int on)
 {
     g_host_err[0] = 0;
     if (!c) return -1;
     if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise: only at frame 0 (after open or rewind)"); return -1; }
     if (on && c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise: not with keep_records (GOP shards)"); return -1; }
-    if (on && !c->denoise)
-    {
-        /* the denoised frames (one per resident input slot + the zero state) count in the HBM budget that sized the slot ring */
-        const double fsz = (double)c->seq.width*c->seq.height*3/2, den = fsz*(c->resident == 1 ? 3 : c->resident + 1);
-        if (c->par.max_chains <= 0 && (double)c->ring*clip_dev_slot_bytes(c->seq.nmb) + den > CLIP_DEV_BUDGET)
-        {
-            snprintf(g_host_err, sizeof(g_host_err), "set_denoise: %d slots + %.0f MB of denoised frames exceed the %.0f GB budget: open with max_chains or resident_frames",
-                     c->ring, den/1048576.0, CLIP_DEV_BUDGET/1073741824.0);
-            return -1;
-        }
-        if (h264e_hip_denoise_reset(c->pool)) return -1;
-        c->den_done = 0;
-    }
+    if (on && !c->denoise && clip_denoise_ring(c, "set_denoise")) return -1;
     c->denoise = !!on;
+    if (!on) c->den_motion = 0;         /* off is off for the motion-compensated filter too; on leaves the kernel that fills the ring as it is */
     return 0;
 }
 
@@ -1737,6 +1745,22 @@ int H264E_clip_set_qp_schedule(H264E_clip_t *c, const uint8_t *qp, int n)
 #define LOOKAHEAD_K_MAX ((uint64_t)1 << 40)
 #define LOOKAHEAD_BITS_MAX ((uint64_t)1 << 50)
 
+/* the host's cost records, for the controller or for the cost pass run for its motion field alone (H264E_clip_set_denoise_motion) */
+static int clip_la_arrays(H264E_clip_t *c)
+{
+    if (c->la_rec) return 0;
+    c->la_rec = (uint64_t *)calloc((size_t)c->nframes*3, sizeof(uint64_t));
+    c->la_bits = (int *)calloc((size_t)c->nframes, sizeof(int));
+    c->la_done = 0;
+    if (!c->la_rec || !c->la_bits)
+    {
+        free(c->la_rec); free(c->la_bits); c->la_rec = NULL; c->la_bits = NULL;
+        snprintf(g_host_err, sizeof(g_host_err), "out of host memory");
+        return -1;
+    }
+    return 0;
+}
+
 int H264E_clip_set_lookahead(H264E_clip_t *c, int kbps, int window, int qp_min, int qp_max)
 {
     g_host_err[0] = 0;
@@ -1751,19 +1775,7 @@ int H264E_clip_set_lookahead(H264E_clip_t *c, int kbps, int window, int qp_min, 
     if (!window) window = imin(LOOKAHEAD_WINDOW_DEFAULT, imin(c->resident, c->ring - 1));
     if (c->resident < c->nframes && window > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: a window of %d frames does not fit the input ring (%d resident frames)", window, c->resident); return -1; }
     if (window > c->ring - 1) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: a window of %d frames does not fit one launch (%d slots)", window, c->ring - 1); return -1; }
-    if (clip_qp_arrays(c)) return -1;
-    if (!c->la_rec)
-    {
-        c->la_rec = (uint64_t *)calloc((size_t)c->nframes*3, sizeof(uint64_t));
-        c->la_bits = (int *)calloc((size_t)c->nframes, sizeof(int));
-        c->la_done = 0;
-        if (!c->la_rec || !c->la_bits)
-        {
-            free(c->la_rec); free(c->la_bits); c->la_rec = NULL; c->la_bits = NULL;
-            snprintf(g_host_err, sizeof(g_host_err), "out of host memory");
-            return -1;
-        }
-    }
+    if (clip_qp_arrays(c) || clip_la_arrays(c)) return -1;
     c->la_kbps = kbps; c->la_window = window; c->la_qmin = qp_min; c->la_qmax = qp_max;
     return 0;
 }
@@ -1800,6 +1812,7 @@ int H264E_clip_set_lookahead_search(H264E_clip_t *c, int range)
     if (range < 0 || range > 8) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: range %d is outside 0..8", range); return -1; }
     if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
     if (c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: not with keep_records = %d (GOP shards)", c->par.keep_records); return -1; }
+    if (!range && c->den_motion) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: range 0 while the motion-compensated denoiser (mode %d) reads the motion field: H264E_clip_set_denoise_motion(clip, 0) first", c->den_motion); return -1; }
     if (range != c->la_search && c->la_any)
     {
         snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: range %d after frames have been analysed with range %d (their records cannot be made again)", range, c->la_search);
@@ -1854,6 +1867,81 @@ static int clip_prepass_lookahead(H264E_clip_t *c, int limit)
     /* frames a.. took the entries of frames a - entries..: what was intact in front of a still is, from limit - entries on */
     c->la_any = 1;
     c->la_ring_lo = imax(imin(c->la_ring_lo, a), limit - clip_la_entries(c));
+    return 0;
+}
+
+/* The motion-compensated temporal denoiser (include/h264e_mi355x.h, enc_mcdenoise.h): a mode of the denoiser.  It shares the plain
+ * denoiser's ring, budget check, flag (c->denoise) and pre-pass; den_motion selects the kernel that fills the ring. */
+int H264E_clip_set_denoise_motion(H264E_clip_t *c, int mode)
+{
+    g_host_err[0] = 0;
+    if (!c) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise_motion: bad argument"); return -1; }
+    if (mode < 0 || mode > 2) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise_motion: mode %d is outside 0..2", mode); return -1; }
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise_motion: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
+    if (!mode)
+    {
+        if (c->den_motion) c->denoise = c->den_motion = 0;
+        return 0;
+    }
+    if (c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise_motion: not with keep_records = %d (GOP shards)", c->par.keep_records); return -1; }
+    if (!c->la_search) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise_motion: lookahead search range 0, no frame has a motion field: call H264E_clip_set_lookahead_search first"); return -1; }
+    if (c->par.width < 16 || c->par.height < 16) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise_motion: pictures below 16x16 have no block (%dx%d)", c->par.width, c->par.height); return -1; }
+    if (c->par.speed >= 2) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise_motion: speed %d: the denoiser runs for speed 0 and 1 only, no frame would be filtered", c->par.speed); return -1; }
+    if (clip_la_arrays(c)) return -1;
+    if (!c->denoise && clip_denoise_ring(c, "set_denoise_motion")) return -1;
+    if (c->den_motion != mode) c->den_done = c->den_ring_lo = 0;       /* pictures of another kernel: made again from the zero state */
+    c->denoise = 1; c->den_motion = mode;
+    return 0;
+}
+
+/* frames [lo, hi) have their denoised pictures and vector cells on the device */
+static void clip_den_resident(const H264E_clip_t *c, int *lo, int *hi)
+{
+    *hi = c->denoise ? c->den_done : 0;
+    *lo = imin(c->den_ring_lo, *hi);
+}
+
+static void clip_den_not_there(const H264E_clip_t *c, const char *who, const char *what, int frame)
+{
+    int lo, hi;
+    clip_den_resident(c, &lo, &hi);
+    if (lo < hi) snprintf(g_host_err, sizeof(g_host_err), "%s: frame %d has no %s on the device (frames %d..%d have)", who, frame, what, lo, hi - 1);
+    else snprintf(g_host_err, sizeof(g_host_err), "%s: frame %d has no %s on the device (no frame has)", who, frame, what);
+}
+
+int H264E_clip_read_denoised(H264E_clip_t *c, int frame, uint8_t *i420)
+{
+    int lo, hi;
+    g_host_err[0] = 0;
+    if (!c || !i420) { snprintf(g_host_err, sizeof(g_host_err), "read_denoised: bad argument"); return -1; }
+    if (!c->denoise) { snprintf(g_host_err, sizeof(g_host_err), "read_denoised: the denoiser is off (H264E_clip_set_denoise, H264E_clip_set_denoise_motion)"); return -1; }
+    clip_den_resident(c, &lo, &hi);
+    if (frame < lo || frame >= hi) { clip_den_not_there(c, "read_denoised", "denoised picture", frame); return -1; }
+    if (h264e_hip_read_denoised(c->pool, frame % c->resident, i420)) { g_host_err[0] = 0; return -1; }
+    return 0;
+}
+
+int H264E_clip_read_denoise_motion(H264E_clip_t *c, int frame, void *dst, int *nbx, int *nby)
+{
+    int lo, hi;
+    g_host_err[0] = 0;
+    if (!c) { snprintf(g_host_err, sizeof(g_host_err), "read_denoise_motion: bad argument"); return -1; }
+    if (nbx) *nbx = (c->par.width >> 1) >> 3;
+    if (nby) *nby = (c->par.height >> 1) >> 3;
+    if (!dst) { snprintf(g_host_err, sizeof(g_host_err), "read_denoise_motion: bad argument"); return -1; }
+    if (!c->den_motion) { snprintf(g_host_err, sizeof(g_host_err), "read_denoise_motion: the motion-compensated denoiser is off (H264E_clip_set_denoise_motion), no frame has vectors"); return -1; }
+    clip_den_resident(c, &lo, &hi);
+    if (frame < lo || frame >= hi) { clip_den_not_there(c, "read_denoise_motion", "vectors", frame); return -1; }
+    if (h264e_hip_mcdenoise_read_vectors(c->pool, frame, dst)) { g_host_err[0] = 0; return -1; }
+    return 0;
+}
+
+/* diagnostic (tools/mcdenoise_probe.py): HIP-event time of the motion-compensated filter's launches since open, and the frames they filtered */
+int H264E_clip_denoise_time(H264E_clip_t *c, double *kernel_ms, long long *frames)
+{
+    g_host_err[0] = 0;
+    if (!c) return -1;
+    if (h264e_hip_mcdenoise_time(c->pool, kernel_ms, frames)) return -1;
     return 0;
 }
 
@@ -2117,10 +2205,22 @@ static void clip_plan_launch(H264E_clip_t *c, const clip_call_t *x, clip_launch_
  * that reads them */
 static int clip_prepass_denoise(H264E_clip_t *c, int limit)
 {
-    if (!c->denoise || c->par.speed >= 2 || c->den_done >= limit) return 0;
-    if (limit - c->den_done > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "denoise: frames %d..%d do not fit the input ring", c->den_done, limit - 1); return -1; }
-    if (h264e_hip_denoise_frames(c->pool, c->den_done % c->resident, limit - c->den_done, c->den_done == 0)) return -1;
+    const int a = c->den_done;
+    if (!c->denoise || c->par.speed >= 2 || a >= limit) return 0;
+    if (limit - a > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "denoise: frames %d..%d do not fit the input ring", a, limit - 1); return -1; }
+    if (c->den_motion)
+    {
+        /* the searched cost pass comes first, also with the controller off and constant QP: it then runs for its motion field alone.
+         * Frame f's field entry cannot have been overwritten: the field ring and the input ring use the same indexing (f % entries,
+         * entries >= resident), so the frame that takes f's entry is one whose input could only be uploaded over f's slot -- after f
+         * was encoded, and this pre-pass runs in front of the launch that first encodes f. */
+        if (clip_prepass_lookahead(c, limit)) return -1;
+        if (h264e_hip_mcdenoise_frames(c->pool, a, limit - a, c->den_motion, a == 0)) return -1;
+    }
+    else if (h264e_hip_denoise_frames(c->pool, a % c->resident, limit - a, a == 0)) return -1;
     c->den_done = limit;
+    /* frames a.. took the slots of frames a - resident..: what was intact in front of a still is, from limit - resident on */
+    c->den_ring_lo = imax(imin(c->den_ring_lo, a), limit - c->resident);
     return 0;
 }
 

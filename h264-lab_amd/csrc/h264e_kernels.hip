@@ -23,6 +23,8 @@
  *   h264e_lookahead_kernel the cost pass of the lookahead rate control (enc_lookahead.h): intra / inter cost sums of one resident input frame.
  *   h264e_lookahead_search_kernel the same pass with a motion search of up to +-8 half-resolution samples per block
  *                        (enc_lookahead_search.h): the sums from the searched inter cost, and a motion field.
+ *   h264e_mcdenoise_kernel the motion-compensated temporal denoiser (enc_mcdenoise.h): the denoiser's filter against the previous
+ *                        denoised picture displaced by that motion field, refined by one sample per 16x16 block.
  *
  * HIP only (hipcc --offload-arch=gfx950).  The host side of the boundary is h264e_pool.h, included at the end; the test-only
  * emulation of tests/emu compiles the same kernel HEADERS with its own launch functions and never sees this file.
@@ -41,6 +43,7 @@
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
 #include "enc_lookahead_search.h"
+#include "enc_mcdenoise.h"
 #include "enc_ssim.h"
 #include "../../include/h264e_hip.h"
 
@@ -988,6 +991,14 @@ __global__ void __launch_bounds__(64) h264e_lookahead_search_kernel(lookahead_se
     if (lane < 3) lookahead_record_add(S.a.record + lane, (unsigned long long)(lane == 0 ? si : lane == 1 ? sp : sn));
 }
 
+/* the motion-compensated denoiser (enc_mcdenoise.h): one wave per workgroup and tile of 16x16 luma + 8x8 + 8x8 chroma samples, blockIdx.x
+ * / .y the tile.  The only LDS traffic between lanes is inside the one wave: wave_sync orders it. */
+template <int MODE> __global__ void __launch_bounds__(64) h264e_mcdenoise_kernel(mcdenoise_args_t A)
+{
+    __shared__ mcdenoise_lds_t sh;
+    mcdenoise_block<MODE>(A, (LDS_AS mcdenoise_lds_t *)&sh, (int)blockIdx.x, (int)blockIdx.y);
+}
+
 /* ------------------------------------------------------------------ launches (what h264e_pool.h calls) */
 
 /* variant: 0 = intra frames only (one wave per row, 4 per SIMD), 1 = one wave per row, 2 = two waves per row (3 per SIMD), 3 = the latency variant: four
@@ -1114,6 +1125,13 @@ static void bk_launch_ssim(const h264e_ssim_args_t &A, int n, int planes, hipStr
         hipLaunchKernelGGL(h264e_ssim_kernel<1>, dim3((unsigned)A.max_tiles, (unsigned)n, 1), dim3(256), 0, st, A);
         hipLaunchKernelGGL(h264e_ssim_mean_kernel<1>, dim3((unsigned)n, 1), dim3(256), 0, st, A);
     }
+}
+/* (the last launch here: its kernels are instantiated, and so emitted, behind all the others) */
+static void bk_launch_mcdenoise(const mcdenoise_args_t &A, int mode, hipStream_t st)
+{
+    const dim3 grid((unsigned)((A.width + 15)/16), (unsigned)((A.height + 15)/16));
+    if (mode == 2) hipLaunchKernelGGL(h264e_mcdenoise_kernel<2>, grid, dim3(64), 0, st, A);
+    else hipLaunchKernelGGL(h264e_mcdenoise_kernel<1>, grid, dim3(64), 0, st, A);
 }
 
 #include "h264e_pool.h"

@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_lookahead_search, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those ten are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_lookahead_search, bk_launch_mcdenoise, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those eleven are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -20,6 +20,7 @@
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
 #include "enc_lookahead_search.h"
+#include "enc_mcdenoise.h"
 #include "enc_ssim.h"
 
 /* The matrix rows (tests/color_model.py): Kr / Kb scaled by 219/255 and 224/255 (limited) or 1 (full), times 256,
@@ -243,6 +244,12 @@ struct h264e_hip_pool
     hipEvent_t ev_t0, ev_t1, ev_prep;
     hipEvent_t ev[TASK_RING][3];         /* per pending submit: before / between / after the two kernels */
     int ev_pending;
+    /* motion-compensated denoiser (enc_mcdenoise.h, h264e_hip_mcdenoise_*): its vector cells, a ring beside la_field with the same
+     * entries and indexing; NULL until it first runs.  ev_mcd: around the launches of one call, read when the next call or
+     * h264e_hip_mcdenoise_time asks (mcd_pending: the frames between them) */
+    uint32_t *mcd_cells;
+    hipEvent_t ev_mcd[2];
+    int mcd_pending; double mcd_ms; long long mcd_frames;
 };
 
 /* One description of a launch, computed in ONE place from the host tasks (submit_check): what pick_variant, the dispatch order and a
@@ -310,7 +317,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     dev_free(p->heap);
     dev_free(p->den);
     dev_free(p->sc_rec);
-    dev_free(p->la_lo); dev_free(p->la_rec); dev_free(p->la_field);
+    dev_free(p->la_lo); dev_free(p->la_rec); dev_free(p->la_field); dev_free(p->mcd_cells);
     dev_free(p->qual_dev);
     if (p->stream)
     {
@@ -320,6 +327,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
         (void)hipEventDestroy(p->ev_ingest[0]); (void)hipEventDestroy(p->ev_ingest[1]); (void)hipEventDestroy(p->ev_in[0]); (void)hipEventDestroy(p->ev_in[1]);
         (void)hipEventDestroy(p->ev_out[0]); (void)hipEventDestroy(p->ev_out[1]);
         (void)hipEventDestroy(p->ev_sc[0]); (void)hipEventDestroy(p->ev_sc[1]);
+        (void)hipEventDestroy(p->ev_mcd[0]); (void)hipEventDestroy(p->ev_mcd[1]);
         (void)hipStreamDestroy(p->stream);
         if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
         if (p->abort_stream) (void)hipStreamDestroy(p->abort_stream);
@@ -473,6 +481,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     (void)hipEventCreate(&p->ev_ingest[0]); (void)hipEventCreate(&p->ev_ingest[1]); (void)hipEventCreate(&p->ev_in[0]); (void)hipEventCreate(&p->ev_in[1]);
     (void)hipEventCreate(&p->ev_out[0]); (void)hipEventCreate(&p->ev_out[1]);
     (void)hipEventCreate(&p->ev_sc[0]); (void)hipEventCreate(&p->ev_sc[1]);
+    (void)hipEventCreate(&p->ev_mcd[0]); (void)hipEventCreate(&p->ev_mcd[1]);
     (void)hipEventCreate(&p->ev_q[0]); (void)hipEventCreate(&p->ev_q[1]);
     p->chains_host = (h264e_chain_dev_t *)calloc((size_t)nchains, sizeof(h264e_chain_dev_t));
     p->clu_dev = (int32_t **)calloc((size_t)nchains, sizeof(int32_t *));
@@ -708,6 +717,91 @@ extern "C" int h264e_hip_read_denoised(h264e_hip_pool_t *p, int slot, uint8_t *d
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipStreamSynchronize(p->stream));
     HIPCHK(hipMemcpy(dst, den_frame(p, den_index(p, slot)), p->frame_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* ---- motion-compensated denoiser (enc_mcdenoise.h): one h264e_mcdenoise_kernel launch per frame on the pool's stream, into the
+ * denoised ring above, from the field ring of the searched cost pass (below) */
+
+#ifdef H264E_EMU
+/* the emulation's launch: the workgroup's code, tile after tile */
+static void bk_launch_mcdenoise(const mcdenoise_args_t &A, int mode, hipStream_t)
+{
+    for (int by = 0; by < (A.height + 15)/16; by++)
+        for (int bx = 0; bx < (A.width + 15)/16; bx++)
+        {
+            mcdenoise_lds_t sh;
+            memset(&sh, 0, sizeof(sh));
+            if (mode == 2) mcdenoise_block<2>(A, &sh, bx, by);
+            else mcdenoise_block<1>(A, &sh, bx, by);
+        }
+}
+#endif
+
+/* the HIP-event time of the last call's launches, once they are over */
+static int mcdenoise_collect(h264e_hip_pool_t *p)
+{
+    if (!p->mcd_pending) return 0;
+    float f = 0;
+    HIPCHK(hipEventSynchronize(p->ev_mcd[1]));
+    HIPCHK(hipEventElapsedTime(&f, p->ev_mcd[0], p->ev_mcd[1]));
+    p->mcd_ms += f; p->mcd_frames += p->mcd_pending; p->mcd_pending = 0;
+    return 0;
+}
+
+/* frames first, first + 1, ... of the STREAM: input slot f % frames_resident and field entry f % la_entries, as the cost pass counts */
+extern "C" int h264e_hip_mcdenoise_frames(h264e_hip_pool_t *p, int first, int n, int mode, int from_zero)
+{
+    const int R = p ? p->frames_resident : 0;
+    if (!p || !p->den || first < 0 || n < 0 || n > R || mode < 1 || mode > 2) FAIL("mcdenoise_frames: bad argument (or the denoiser is not on)");
+    if (!p->la_field) FAIL("mcdenoise_frames: no frame of this pool has a motion field (h264e_hip_lookahead_search_frames comes first)");
+    if (p->G.width < MCDENOISE_MIN_SIDE || p->G.height < MCDENOISE_MIN_SIDE) FAIL("mcdenoise: pictures below %dx%d have no block (%dx%d)", MCDENOISE_MIN_SIDE, MCDENOISE_MIN_SIDE, p->G.width, p->G.height);
+    if (!n) return 0;
+    HIPCHK(hipSetDevice(p->device));
+    mcdenoise_args_t A;
+    A.width = p->G.width; A.height = p->G.height; A.nbx = (p->G.width >> 1) >> 3; A.nby = (p->G.height >> 1) >> 3;
+    const size_t nblk = (size_t)A.nbx*(size_t)A.nby;
+    if (!p->mcd_cells && dev_malloc((void **)&p->mcd_cells, nblk*MCDENOISE_CELL_BYTES*(size_t)p->la_entries)) { p->mcd_cells = 0; FAIL("mcdenoise: device allocation failed (%d vector fields)", p->la_entries); }
+    if (mcdenoise_collect(p)) return -1;
+    /* the inputs may have come over the copy stream (h264e_hip_upload_i420_async): the launches wait for everything issued there */
+    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
+    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
+    HIPCHK(hipEventRecord(p->ev_mcd[0], p->stream));
+    for (int i = 0; i < n; i++)
+    {
+        const int f = first + i, s = f % R, e = f % p->la_entries;
+        const int prev = (i == 0 && from_zero) ? p->den_frames - 1 : R == 1 ? p->den_flip : (s + R - 1) % R;
+        const int out = R == 1 ? p->den_flip ^ 1 : s;
+        A.cur = p->clip + p->frame_bytes*(size_t)s; A.prev = den_frame(p, prev); A.out = den_frame(p, out);
+        A.field = p->la_field + nblk*(size_t)e; A.cells = p->mcd_cells + nblk*(size_t)e;
+        bk_launch_mcdenoise(A, mode, p->stream);
+        if (R == 1) p->den_flip ^= 1;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->ev_mcd[1], p->stream));
+    p->mcd_pending = n;
+    return 0;
+}
+
+/* the vector cells of STREAM frame `frame` from its ring entry: what is there is the caller's to know */
+extern "C" int h264e_hip_mcdenoise_read_vectors(h264e_hip_pool_t *p, int frame, void *dst)
+{
+    if (!p || !dst || frame < 0) FAIL("mcdenoise_read_vectors: bad argument");
+    if (!p->mcd_cells) FAIL("mcdenoise_read_vectors: no frame has been filtered");
+    HIPCHK(hipSetDevice(p->device));
+    const size_t bytes = (size_t)((p->G.width >> 1) >> 3)*(size_t)((p->G.height >> 1) >> 3)*MCDENOISE_CELL_BYTES;
+    HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)p->mcd_cells + bytes*(size_t)(frame % p->la_entries), bytes, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+extern "C" int h264e_hip_mcdenoise_time(h264e_hip_pool_t *p, double *kernel_ms, long long *frames)
+{
+    if (!p) FAIL("mcdenoise_time: null pool");
+    HIPCHK(hipSetDevice(p->device));
+    if (mcdenoise_collect(p)) return -1;
+    if (kernel_ms) *kernel_ms = p->mcd_ms;
+    if (frames) *frames = p->mcd_frames;
     return 0;
 }
 

@@ -175,6 +175,20 @@ int  h264e_hip_lookahead_search_frames(h264e_hip_pool_t *pool, int first, int n,
 /* The field ring's entry of STREAM frame `frame` (entry frame % max(frames_resident, 2)) into dst [nbx*nby*4 bytes]; the call waits for
  * the stream.  Which frame the entry holds is the caller's to know.  Refused before the first call with a search. */
 int  h264e_hip_lookahead_read_field(h264e_hip_pool_t *pool, int frame, void *dst);
+/* Motion-compensated temporal denoiser (enc_mcdenoise.h), a sibling of h264e_hip_denoise_frames: STREAM frames first, first + 1, ...
+ * (input slot f % frames_resident, n <= frames_resident) are filtered against the previous denoised picture displaced by frame f's
+ * entry of the field ring, one kernel launch per frame in order on the pool's stream after every upload issued on the copy stream.
+ * It writes the SAME denoised ring (slot f % frames_resident, the zero state with from_zero, the single-slot pool's ping-pong), so a
+ * task's `denoised` flag and h264e_hip_read_denoised work as they do for the plain denoiser; h264e_hip_denoise_reset comes first.
+ * mode: 1 = the field's vectors, 2 = refined by one luma sample with a zero-vector candidate.  Each frame's vectors -- one cell {int8
+ * vx, int8 vy, uint16 sad} per block, in luma samples -- go into a ring beside the field ring (same entries, same indexing, allocated
+ * on first use).  Refused while the pool has no field ring (no searched cost pass has run), and below 16x16.
+ * read_vectors: that ring's entry of STREAM frame `frame` into dst [nbx*nby*4 bytes]; the call waits for the stream; which frame the
+ * entry holds is the caller's to know.  time: the HIP-event time of the filter's launches since the pool was created and the frames
+ * they filtered (the call waits for the last ones). */
+int  h264e_hip_mcdenoise_frames(h264e_hip_pool_t *pool, int first, int n, int mode, int from_zero);
+int  h264e_hip_mcdenoise_read_vectors(h264e_hip_pool_t *pool, int frame, void *dst);
+int  h264e_hip_mcdenoise_time(h264e_hip_pool_t *pool, double *kernel_ms, long long *frames);
 /* Launch groups: the submits of the member pools (same device, same picture size, one host thread each) are merged into ONE kernel
  * launch per round -- the streams' jobs interleaved in dispatch order, every job with its own pool's buffers / abort word / results --
  * so that independent streams fill each other's pipeline drains.  h264e_hip_submit of a member blocks until all members that are

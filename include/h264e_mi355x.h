@@ -480,6 +480,38 @@ int  H264E_clip_set_lookahead_search(H264E_clip_t *clip, int range);
 int  H264E_clip_read_lookahead_motion(H264E_clip_t *clip, int frame, void *dst, int *nbx, int *nby);
 /* diagnostic: HIP-event time of the cost pass' kernel launches since open, and the frames they analysed (tools/lookahead_probe.py) */
 int  H264E_clip_lookahead_time(H264E_clip_t *clip, double *kernel_ms, long long *frames);
+/* Motion-compensated temporal denoiser: THIS PROJECT'S OWN filter, a mode of the denoiser above.  mode 0 = off, 1 = the previous
+ * denoised picture is displaced by the motion field of the searched cost pass, 2 = by that field refined (enc_mcdenoise.h,
+ * tests/mcdenoise_model.py).  Per frame f: cur = the RAW input, D_{f-1} = the previous output of this filter (zeros in front of frame 0),
+ * (dx, dy) = frame f's field cell of block (bx, by) (H264E_clip_read_lookahead_motion; frame 0 has a zero field).
+ *   Luma vector of the 16x16 block at (16bx, 16by): mode 1 (2dx, 2dy); mode 2 the first candidate with the smallest
+ * sad = sum |Y_f(x, y) - D_{f-1}(x + vx, y + vy)| among (0, 0) and then (2dx + rx, 2dy + ry), rx, ry in -1..1 in the order
+ * (|rx| + |ry|, ry, rx); a candidate whose displaced block does not lie wholly inside the plane is left out.  Chroma vector of the 8x8
+ * block (bx, by): (dx, dy), in both modes.  Samples that no block covers: (0, 0).
+ *   Filter, per plane, with the vector v of the sample's own block: first / last row and column out = cur; otherwise the plain
+ * denoiser's formula with p = D_{f-1}(clamp(s + v)) and the neighbour sum over cur(n) - D_{f-1}(clamp(n + v)), coordinates clamped to the
+ * plane.  The output is the picture that is encoded and the next frame's state.  With an all-zero field it is the plain denoiser.
+ *   It shares the plain denoiser's pictures, HBM budget check and rules: while the clip stands at frame 0, kept across a rewind;
+ * uploading frame f again makes cost records, fields and filtered pictures from f onward new; the SSD / SSIM metrics compare the RAW
+ * input with the reconstruction.  H264E_clip_set_denoise(clip, 0) switches it off too; H264E_clip_set_denoise(clip, 1) leaves the mode
+ * as it is; changing the mode makes every picture again from frame 0.  In front of every launch the searched cost pass runs for the
+ * frames about to be filtered -- with the lookahead controller off it runs for its field alone (H264E_clip_read_lookahead then returns
+ * costs, no QPs), and H264E_clip_set_lookahead_search's refusal to change the range applies as before; range 0 is refused while this
+ * filter is on.  Refused -- nothing changes, H264E_last_error names the value -- with a mode outside 0..2, with keep_records, while the
+ * lookahead search range is 0 (call H264E_clip_set_lookahead_search first), below 16x16, and with speed >= 2 (the denoiser runs for
+ * speed 0 and 1 only). */
+int  H264E_clip_set_denoise_motion(H264E_clip_t *clip, int mode);
+/* The denoised picture of a frame (either denoiser's) as packed I420, width*height*3/2 bytes: the pictures live in a ring of
+ * resident_frames slots on the device; -1, with the readable frames named in H264E_last_error, when the frame has not been denoised,
+ * when its slot has been taken by a later frame, and when the denoiser is off. */
+int  H264E_clip_read_denoised(H264E_clip_t *clip, int frame, uint8_t *i420);
+/* The vectors the motion-compensated filter used: nbx*nby cells {int8 vx, int8 vy, uint16 sad}, in luma samples, row by row; sad is
+ * that of the luma vector (mode 1: of (2dx, 2dy)).  Size-only call and *nbx, *nby as for H264E_clip_read_lookahead_motion; the same
+ * frames are readable as for H264E_clip_read_denoised. */
+int  H264E_clip_read_denoise_motion(H264E_clip_t *clip, int frame, void *dst, int *nbx, int *nby);
+/* diagnostic: HIP-event time of the motion-compensated filter's kernel launches since open, and the frames they filtered
+ * (tools/mcdenoise_probe.py) */
+int  H264E_clip_denoise_time(H264E_clip_t *clip, double *kernel_ms, long long *frames);
 /* GOP shards of ONE stream (one clip encoder per shard / GPU, the shard starting at a key frame with first_idr_pic_id_state =
  * its GOP index & 1 and a SPECULATED mv_clusters_in): once the exact state in front of the shard is known, revalidate walks the
  * kept records (keep_records) and either confirms the shard (*restart_frame = -1, end_state = exact state behind it) or names the
