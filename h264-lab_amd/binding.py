@@ -49,7 +49,8 @@ class ClipStats(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("upload_ms", "encode_ms", "readback_ms", "assemble_ms", "mb_kernel_ms", "splice_kernel_ms")] + \
                [(n, C.c_int) for n in ("kernel_launches", "chains", "rounds", "reencoded_gops")] + \
                [("mv_clusters_out", C.c_int32 * 2), ("next_idr_pic_id_state", C.c_int), ("first_frame", C.c_int), ("frames", C.c_int), ("spin_relaunches", C.c_int),
-                ("relaunches_timed", C.c_int), ("processed_mbs", C.c_longlong), ("delivered_mbs", C.c_longlong), ("first_frame_ms_after_relaunch", C.c_double)]
+                ("relaunches_timed", C.c_int), ("processed_mbs", C.c_longlong), ("delivered_mbs", C.c_longlong), ("first_frame_ms_after_relaunch", C.c_double),
+                ("kept_key_frames", C.c_int), ("kept_key_rows", C.c_int)]
 
 
 class DevFrame(C.Structure):  # H264E_dev_frame_t: a frame in device memory (checked against H264E_struct_size(2) at load)

@@ -1018,6 +1018,7 @@ int H264E_dev_memcpy(void *dst, const void *src, size_t bytes, int to_device) { 
  * control, reference pictures -- for the next call.  Input frames live in a ring of `resident` HBM slots, so a file of any
  * length streams through a bounded amount of host and device memory (encode_app --clip).
  */
+#define CLIP_KEEP_MAX 8         /* key frames of one stopped launch whose rows are kept */
 struct H264E_clip_tag
 {
     H264E_clip_param_t par;
@@ -1093,7 +1094,22 @@ struct H264E_clip_tag
     /* motion-compensated filter (H264E_clip_set_denoise_motion): 0 = the plain denoiser fills the ring, 1 / 2 = enc_mcdenoise.h does, from
      * the motion field of the searched cost pass; frames [den_ring_lo, den_done) still have their pictures (and vector cells) on the device */
     int den_motion, den_ring_lo;
+    /* Key frames that a stopped launch left encoded, wholly or down to some macroblock row: a key frame reads no reference
+     * picture and no mv_clusters candidates, so what the next launch would make of those rows is what already lies in the frame's slot.
+     * Collected when a launch has stopped cleanly (clip_keep_collect), used and forgotten by the next plan (clip_plan_launch); an entry
+     * carries everything the rows' bits depend on besides the input picture. */
+    int keep_on;                            /* H264E_KEEP_KEY_ROWS, read once at open */
+    int nkeep;
+    struct clip_keep { int frame, rows, qp, nslices, speed, denoised; } keep[CLIP_KEEP_MAX];
 };
+
+/* the kept rows of frames `from` and later are void: their inputs are being replaced, or the stream goes back */
+static void clip_keep_drop(H264E_clip_t *c, int from)
+{
+    int i, k = 0;
+    for (i = 0; i < c->nkeep; i++) if (c->keep[i].frame < from) c->keep[k++] = c->keep[i];
+    c->nkeep = k;
+}
 
 /* The schedule rule, once.  frame_num restarts at every key frame, and so does the periodic counter: the next periodic key frame
  * comes `gop` frames after the last key frame of either kind.  The wrap of the counter (h264-lab.h:6611) happens only on a DEFAULT
@@ -1154,6 +1170,7 @@ void H264E_clip_rewind(H264E_clip_t *c)
     c->state[0] = c->par.mv_clusters_in[0]; c->state[1] = c->par.mv_clusters_in[1];
     c->first_dev = 0;
     c->first_row = 0; c->have_after = 0; c->recon_floor = 0; c->stopped_before = 0;
+    clip_keep_drop(c, 0);
     /* reference-window geometry (h264e_dev.h): narrow = consecutive frames 4 macroblock steps apart, as long as vectors rarely
      * reach more than 12 samples right / down of their macroblock; wide (7 steps) for the rest of the clip otherwise.  Large
      * pictures already fill the GPU's resident workgroups with the wide geometry: the narrow one only pays below ~12k macroblocks */
@@ -1184,6 +1201,8 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     /* H264E_WIDE_WINDOW is read here, once: the clip keeps the answer for life, whatever the variable says at a later rewind (clips
      * opened with and without it can share a launch group) */
     c->narrow_ok = (getenv("H264E_WIDE_WINDOW") || c->seq.nmb > 12000) ? 0 : 1;
+    /* ... and so is H264E_KEEP_KEY_ROWS (0 = every launch encodes its key frames from row 0) */
+    c->keep_on = getenv("H264E_KEEP_KEY_ROWS") ? atoi(getenv("H264E_KEEP_KEY_ROWS")) != 0 : 1;
     /* ring of picture / result slots = frames per launch + 1.  Not bounded by residency: workgroups only wait for lower
      * block indices, so a launch larger than the GPU simply streams through it in order. */
     /* default: 96 frames per launch at 1080p and above; small pictures have short pipelines and cheap slots, so they get
@@ -1299,6 +1318,7 @@ static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int 
     if (first < c->den_done) c->den_done = first;       /* new inputs: their denoised pictures (and all behind them) are made again */
     if (first < c->sc_done) c->sc_done = first;         /* ... and their histograms */
     if (first < c->la_done) c->la_done = first;         /* ... and their cost records */
+    clip_keep_drop(c, first);                           /* ... and no row of an earlier encode of theirs stands */
     return 0;
 }
 
@@ -1335,6 +1355,7 @@ static int clip_put_device(H264E_clip_t *c, int first, int nframes, const H264E_
     if (first < c->den_done) c->den_done = first;
     if (first < c->sc_done) c->sc_done = first;
     if (first < c->la_done) c->la_done = first;
+    clip_keep_drop(c, first);
     return 0;
 }
 
@@ -1407,6 +1428,7 @@ int H264E_clip_generate_synth(H264E_clip_t *c, int first, int nframes, int t0, u
     if (first < c->den_done) c->den_done = first;
     if (first < c->sc_done) c->sc_done = first;
     if (first < c->la_done) c->la_done = first;
+    clip_keep_drop(c, first);
     return h264e_hip_sync(c->pool);
 }
 
@@ -1541,6 +1563,7 @@ int H264E_clip_restart(H264E_clip_t *c, int frame, const int32_t state[2])
     c->state[0] = state[0]; c->state[1] = state[1];
     c->first_dev = 0;
     c->first_row = 0; c->have_after = 0;
+    clip_keep_drop(c, 0);
     c->rc_frame = -1;
     return 0;
 }
@@ -2062,8 +2085,10 @@ typedef struct
     int F, nh;                              /* frames in the chain, hedge leaves */
     int qp_task[CLIP_RC_DEPTH_MAX];         /* rate control: the QP the chain's frames were given */
     int hedge_level[CLIP_HEDGE_MAX], hedge_qp[CLIP_HEDGE_MAX];      /* the chain index of the frame a leaf encodes, and its QP */
+    int kept_frames, kept_rows;             /* key frames that start below row 0 on what the stopped launch in front left of them, and those rows */
     int after_stop;                         /* follows a launch that was stopped (mis-speculation, rate-control miss): its first frame pays the refill */
     double t_submit, t_first, t_last;       /* submit; first and last frame consumed */
+    double t_prev;                          /* ... and the one in front of the last */
     int nvalid;                             /* frames accepted */
     int leaf;                               /* CLIP_TAKE_LEAF: the task to take */
     int moved_from, moved_to;               /* an accepted leaf's slot, and the slot its frame number owns */
@@ -2073,7 +2098,7 @@ typedef struct
 /* a failure between submit and sync gives the device's launch lock back; the statistics so far go out either way */
 static int clip_end(H264E_clip_t *c, const clip_call_t *x, H264E_clip_stats_t *st, int rc)
 {
-    if (rc) h264e_hip_release(c->pool);
+    if (rc) { h264e_hip_release(c->pool); c->nkeep = 0; }
     if (st) *st = x->stats;
     return rc;
 }
@@ -2193,10 +2218,26 @@ static void clip_plan_launch(H264E_clip_t *c, const clip_call_t *x, clip_launch_
             }
     }
     if (l->nh) c->recon_floor = n;              /* the leaves' slots held the pictures of frames n - K + F .. : gone now */
+    /* Key frames the stopped launch in front left in their slots: the same frame lands in the same slot (f % K), and with the same QP,
+     * slices, speed and input it makes the same rows again, so it starts at the first row that was not complete -- below the last row:
+     * only its finalizer runs.  Not next to hedge leaves: their spare slots are other frames' slots.  What is not used now is dropped:
+     * the launch resets every counter. */
+    l->kept_frames = l->kept_rows = 0;
+    for (i = 0; i < c->nkeep && !l->nh; i++)
+    {
+        const struct clip_keep *k = c->keep + i;
+        const int ti = k->frame - n;
+        h264e_hip_task_t *t = tasks + imax(imin(ti, F - 1), 0);
+        if (ti < 0 || ti >= F || !sched[k->frame].key || t->traj_from_device) continue;
+        if (t->qp != k->qp || t->nslices != k->nslices || t->speed != k->speed || t->denoised != k->denoised) continue;
+        t->first_row = k->rows;
+        l->kept_frames++; l->kept_rows += k->rows;
+    }
+    c->nkeep = 0;
     l->F = F;
     l->after_stop = c->stopped_before;
     c->have_after = 0;
-    l->t_first = l->t_last = 0;
+    l->t_first = l->t_last = l->t_prev = 0;
     l->nvalid = 0; l->leaf = l->moved_from = l->moved_to = -1;
     l->step = CLIP_GO_ON;
 }
@@ -2283,7 +2324,7 @@ static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_
     size_t w;
     int rc_miss = 0;
     l->leaf = -1;
-    l->t_last = t0;
+    l->t_prev = l->t_last; l->t_last = t0;
     if (ti == 0) l->t_first = t0;
     if (r->overflow) { snprintf(g_host_err, sizeof(g_host_err), "bit buffer overflow (frame %d)", f); return clip_abort_launch(c); }
     /* the frame as the kernel exported it: complete NALs (start codes and emulation prevention done on the device) */
@@ -2339,6 +2380,10 @@ static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_
     l->nvalid++;
     x->far_reads += r->far_reads;           /* delivered frames only: what clip_adapt divides by */
     if (x->debug) fprintf(stderr, "clip frame %d: %d far reads\n", f, r->far_reads);
+    /* a key frame behind the launch's first frame: when it came, next to when the frame in front of it did (a key frame that the launch
+     * encodes from row 0 is what the stream waits for after a relaunch) */
+    if (x->debug && key && ti > 0 && !is_hedge)
+        fprintf(stderr, "clip key frame %d (task %d, first row %d): taken %.2f ms after the submit, %.2f ms after frame %d\n", f, ti, c->tasks[ti].first_row, t0 - l->t_submit, t0 - l->t_prev, f - 1);
     if (is_hedge) { l->moved_from = slot; l->moved_to = f % c->ring; }
     if (rc_miss)
     {
@@ -2349,6 +2394,32 @@ static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_
     return l->leaf >= 0 ? CLIP_TAKE_LEAF : CLIP_GO_ON;
 }
 
+/* The launch was stopped cleanly -- a mis-speculation, a full output buffer, a QP miss without hedge leaves -- and has drained: what is
+ * left of the key frames it did not deliver.  A frame whose done word is up is whole (h264e_hip_stream_rows_complete); of the others a row
+ * is complete when its counter says so; the counters are read with one small copy per
+ * key frame, after the drain, when no row moves any more (the finalizer of a stopped job could report the count instead, but it leaves as
+ * soon as the verdict in front of its frame is void, at whatever row it follows then, and would under-count; and it would be a change to the
+ * kernel; the copy costs some 20 us next to a relaunch of 8 ms).  Key frames are asked in stream order until one has no complete row: the frames behind it
+ * were dispatched later still.  The launch's chain owns F different slots, so no other job of it wrote a key frame's slot. */
+static int clip_keep_collect(H264E_clip_t *c, const clip_launch_t *l)
+{
+    int ti;
+    c->nkeep = 0;
+    if (!c->keep_on || l->nh || (l->step != CLIP_STOP_MISSPEC && l->step != CLIP_STOP_FULL && l->step != CLIP_STOP_QP_MISS)) return 0;
+    for (ti = l->nvalid; ti < l->F && c->nkeep < CLIP_KEEP_MAX; ti++)
+    {
+        const h264e_hip_task_t *t = c->tasks + ti;
+        struct clip_keep *k = c->keep + c->nkeep;
+        int rows = 0;
+        if (t->slice_type != SLICE_I) continue;
+        if (h264e_hip_stream_rows_complete(c->pool, t->slot, &rows)) return -1;
+        if (rows <= 0) break;
+        k->frame = l->n + ti; k->rows = rows; k->qp = t->qp; k->nslices = t->nslices; k->speed = t->speed; k->denoised = t->denoised;
+        c->nkeep++;
+    }
+    return 0;
+}
+
 /* the launch is over: drained, an accepted leaf's picture in the slot its frame owns, the stream position behind the accepted frames */
 static int clip_settle(H264E_clip_t *c, clip_call_t *x, const clip_launch_t *l)
 {
@@ -2356,6 +2427,7 @@ static int clip_settle(H264E_clip_t *c, clip_call_t *x, const clip_launch_t *l)
     if (l->step == CLIP_RELAUNCH) (void)clip_abort_launch(c);       /* (the failure was reported by the sync that found it; the launch is over) */
     else if (h264e_hip_sync(c->pool)) return -1;    /* the launch has drained (immediately after an abort) */
     if (nvalid) x->spin_retries = 0;
+    if (clip_keep_collect(c, l)) return -1;
     if (l->moved_from >= 0 && h264e_hip_stream_copy_picture(c->pool, l->moved_from, l->moved_to)) return -1;
     x->stats.encode_ms += now_ms() - l->t_submit;
     /* device-side sums of squared differences of the frames just validated: their pictures are still in their slots */
@@ -2400,8 +2472,8 @@ static void clip_debug_line(const H264E_clip_t *c, const clip_call_t *x, const c
     const double t_end = now_ms();
     const int nvalid = l->nvalid;
     const double t_first = nvalid ? l->t_first : t_end, t_last = nvalid ? l->t_last : t_end;     /* no frame of it was delivered: "first frame after" = when its verdict was in */
-    fprintf(stderr, "clip launch %d (first row %d, %s window, %lld far reads): %d frames in flight, %d valid, next %d; first frame after %.2f ms, then %.3f ms/frame, drained %.2f ms after the last; ended by: %s%s\n",
-            x->stats.rounds, c->tasks[0].first_row, c->tasks[0].narrow_window ? "narrow" : "wide", x->far_reads, l->F, nvalid, c->next, t_first - l->t_submit, nvalid > 1 ? (t_last - t_first)/(nvalid - 1 + (nvalid < l->F)) : 0.0, t_end - t_last,
+    fprintf(stderr, "clip launch %d (first row %d, %s window, %lld far reads): %d frames in flight, %d valid, next %d; first frame after %.2f ms, then %.3f ms/frame, drained %.2f ms after the last, %d key rows kept in %d frames; ended by: %s%s\n",
+            x->stats.rounds, c->tasks[0].first_row, c->tasks[0].narrow_window ? "narrow" : "wide", x->far_reads, l->F, nvalid, c->next, t_first - l->t_submit, nvalid > 1 ? (t_last - t_first)/(nvalid - 1 + (nvalid < l->F)) : 0.0, t_end - t_last, l->kept_rows, l->kept_frames,
             k_clip_ended_by[l->step], l->nh ? " (+ hedge leaves)" : "");
 }
 
@@ -2446,6 +2518,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         }
         clip_plan_launch(c, &x, &l);
         x.stats.rounds++;
+        x.stats.kept_key_frames += l.kept_frames; x.stats.kept_key_rows += l.kept_rows;
         x.far_reads = 0;
         l.t_submit = now_ms();
         if (clip_prepass_denoise(c, l.limit) || h264e_hip_submit(c->pool, c->tasks)) return clip_end(c, &x, st, -1);

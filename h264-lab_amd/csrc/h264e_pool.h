@@ -237,6 +237,7 @@ struct h264e_hip_pool
     int group_round;                     /* the group round of its last submit */
     int waves;                           /* wavefronts per macroblock row forced by H264E_WAVES (1 or 2); 0 = chosen per launch (h264e_hip_submit) */
     int test_upload_fail_at, async_uploads;     /* fault injection (H264E_TEST_KNOBS): the n-th asynchronous upload of this pool fails */
+    int test_keep_rows_cap;              /* H264E_TEST_KNOBS: h264e_hip_stream_rows_complete reports at most this many rows; -1 = off */
     double prof_mb_ms, prof_splice_ms;
     hipStream_t stream;
     hipStream_t copy_stream;             /* uploads that overlap with kernels on `stream` */
@@ -452,8 +453,10 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     G.test_stall_row = -1;
     G.fz_wait_all = getenv("H264E_FZ_WAIT_ALL") ? atoi(getenv("H264E_FZ_WAIT_ALL")) : 0;
     p->test_upload_fail_at = -1;
+    p->test_keep_rows_cap = -1;
     if (knobs)
     {
+        if (getenv("H264E_TEST_KEEP_ROWS_CAP")) p->test_keep_rows_cap = atoi(getenv("H264E_TEST_KEEP_ROWS_CAP"));
         if (getenv("H264E_TEST_ROW_BYTES_PER_MB")) { const int b = atoi(getenv("H264E_TEST_ROW_BYTES_PER_MB"))/4; G.row_words = G.nmbx*(b > 1 ? b : 1); }
         if (getenv("H264E_TEST_SPIN_LIMIT")) G.spin_limit = (unsigned)atol(getenv("H264E_TEST_SPIN_LIMIT"));
         if (getenv("H264E_TEST_STALL_ROW")) G.test_stall_row = atoi(getenv("H264E_TEST_STALL_ROW"));
@@ -2085,7 +2088,8 @@ static int fill_task(h264e_hip_pool_t *p, const h264e_hip_task_t *tasks, int c, 
     d.chain_desc = p->chains_dev + d.chain;
     d.errflag = p->errflag;
     d.mb_counter = p->mb_counter;
-    d.first_row = (t.stream_mode && t.first_row > 0 && t.first_row < G.nmby) ? t.first_row : 0;
+    /* (first_row == nmby: every row is kept, only the job's finalizer runs -- a key frame that a stopped launch had completed) */
+    d.first_row = (t.stream_mode && t.first_row > 0 && t.first_row <= G.nmby) ? t.first_row : 0;
     d.narrow = t.stream_mode && t.narrow_window;
     d.hdr_nal = t.hdr_nal; d.hdr_nbits = t.hdr_nbits; d.hdr_bits = t.hdr_bits;
     fill_slice_rows(G, t.nslices, d);
@@ -2184,6 +2188,34 @@ extern "C" int h264e_hip_stream_done(h264e_hip_pool_t *p, int slot, h264e_hip_re
         }
     }
     return v > 0 ? 1 : 2;                                   /* 2: the job was aborted (or failed its own validation: walk_status) */
+}
+
+/* Macroblock rows of `slot`, counted from the top, that the last launch left complete (counter = nmbx + 1: row buffer, records, samples
+ * and the lines pending for the row below are all written).  Call after h264e_hip_sync and before the next submit, which resets the
+ * counters.  A job of that launch whose finalizer raised its done word has spliced every row: all of them, without a look at the
+ * counters (the answer for the frames behind a full output buffer, which were simply not taken; the emulation, whose rows publish no
+ * counters, knows complete frames only this way).  Otherwise the counters are copied, on the pool's own stream: a copy on the null
+ * stream would wait for every other stream of the device. */
+extern "C" int h264e_hip_stream_rows_complete(h264e_hip_pool_t *p, int slot, int *rows)
+{
+    if (!p || !rows || slot < 0 || slot >= p->nchains) FAIL("stream_rows_complete: bad argument");
+    const h264e_geom_t &G = p->G;
+    int n = 0;
+    if (p->slot_launch[slot] == p->launch_counter && ((const volatile h264e_hostdone_t *)p->host_done)[slot].done == p->launch_counter) n = G.nmby;
+    else
+    {
+        int *host = (int *)malloc(sizeof(int)*(size_t)G.nmby);
+        if (!host) FAIL("out of host memory");
+        (void)hipSetDevice(p->device);
+        hipError_t e = hipMemcpyAsync(host, p->chains_host[slot].progress, sizeof(int)*(size_t)G.nmby, hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+        while (e == hipSuccess && n < G.nmby && host[n] == G.nmbx + 1) n++;
+        free(host);
+        if (e != hipSuccess) FAIL("stream_rows_complete: %s", hipGetErrorString(e));
+    }
+    if (p->test_keep_rows_cap >= 0 && n > p->test_keep_rows_cap) n = p->test_keep_rows_cap;
+    *rows = n;
+    return 0;
 }
 
 extern "C" int h264e_hip_stream_fetch_traj(h264e_hip_pool_t *p, int slot, int consumed, int32_t *dst)

@@ -219,6 +219,9 @@ int  h264e_hip_stream_copy_picture(h264e_hip_pool_t *pool, int from, int to);
 /* resident input frames back to the host (measurement helper) */
 int  h264e_hip_download_i420(h264e_hip_pool_t *pool, int first, int nframes, uint8_t *host_i420);
 int  h264e_hip_stream_abort(h264e_hip_pool_t *pool);
+/* macroblock rows of `slot`, from the top, that the last launch completed (after h264e_hip_sync, before the next submit): what a task
+ * for the same frame in the same slot may pass as first_row -- up to all of them, then only the job's finalizer runs */
+int  h264e_hip_stream_rows_complete(h264e_hip_pool_t *pool, int slot, int *rows);
 int  h264e_hip_busy(h264e_hip_pool_t *pool);
 /* reconstructed picture of the chain's last frame, coded size, packed I420 */
 int  h264e_hip_read_recon(h264e_hip_pool_t *pool, int chain, uint8_t *dst);

@@ -188,6 +188,7 @@ typedef struct
     long long processed_mbs;                                    /* macroblocks reconstructed by the kernel, including those of frames that were thrown away */
     long long delivered_mbs;                                    /* macroblocks of the frames that were accepted = frames x macroblocks per frame */
     double first_frame_ms_after_relaunch;                       /* SUM over relaunches_timed launches of: submit -> first accepted frame (host wall clock) */
+    int kept_key_frames, kept_key_rows;                         /* key frames that started below row 0 on rows a stopped launch had completed, and those rows (H264E_KEEP_KEY_ROWS) */
 } H264E_clip_stats_t;
 
 /* Device-resident input: a frame that already lies in the memory of the encoder's GPU (left there by a decoder, a renderer, a
