@@ -1019,6 +1019,9 @@ int H264E_dev_memcpy(void *dst, const void *src, size_t bytes, int to_device) { 
  * length streams through a bounded amount of host and device memory (encode_app --clip).
  */
 #define CLIP_KEEP_MAX 8         /* key frames of one stopped launch whose rows are kept */
+/* the progress of one frame pass: frames [0, done) are made, [ring_lo, done) still have their entries on the device,
+ * which keeps `entries` of them, frame f in entry f % entries (0: the results live on the host only) */
+typedef struct { int done, ring_lo, entries; } clip_pass_t;
 struct H264E_clip_tag
 {
     H264E_clip_param_t par;
@@ -1058,9 +1061,10 @@ struct H264E_clip_tag
     uint8_t *big; size_t big_cap;           /* scratch: NALs of a frame that did not fit the host mirror */
     h264e_hip_task_t *tasks;                /* scratch [ring] */
     int32_t (*used)[2];                     /* scratch [ring] */
-    /* temporal denoiser (H264E_clip_set_denoise): frames [0, den_done) have been denoised; the denoised picture of frame f lives in the
-     * pool's denoised slot f % resident, the one of den_done - 1 is the state in front of frame den_done */
-    int denoise, den_done;
+    clip_pass_t sc, la, den;                /* the frame passes' progress: scene cut, cost pass, denoiser */
+    /* temporal denoiser (H264E_clip_set_denoise), and the kernel that fills its ring (H264E_clip_set_denoise_motion): 0 = the plain
+     * denoiser, 1 / 2 = enc_mcdenoise.h, from the motion field of the searched cost pass */
+    int denoise, den_motion;
     /* The key-frame schedule: what H264E_encode would make of frame f when it is handed H264E_FRAME_TYPE_KEY on the frames of the
      * explicit list (H264E_clip_set_key_frames) and on the detected scene cuts, and H264E_FRAME_TYPE_DEFAULT on all others
      * (h264-lab.h:6725-6775, :6611-6614).  [nframes + 1]; built by clip_sched_build, the ONLY place that knows the rule; everything
@@ -1068,9 +1072,8 @@ struct H264E_clip_tag
     struct clip_sched { uint8_t key, idr; int frame_num; } *sched;      /* idr: parity of the key frames up to and including this one */
     int *forced, nforced;                   /* the explicit list, ascending */
     int all_key;                            /* every frame is a key frame (launches as long as memory allows: nothing to mis-speculate) */
-    /* scene-cut detection (H264E_clip_set_scenecut, enc_scenecut.h): frames [0, sc_done) have their luma histogram on the host; re-uploading
-     * frame f makes f onward stale, a rewind keeps them.  The arrays exist once the detector has been switched on. */
-    int scenecut, sc_done;                  /* threshold (0 = off) */
+    /* scene-cut detection (H264E_clip_set_scenecut, enc_scenecut.h).  The arrays exist once the detector has been switched on. */
+    int scenecut;                           /* threshold (0 = off) */
     uint32_t *sc_hist;                      /* [nframes][64] */
     int *sc_dist; uint8_t *sc_cut;          /* [nframes] D(f); f was made a key frame by the detector */
     double sc_kernel_ms; long long sc_frames;   /* HIP-event time of the detector's launches and the frames they analysed, since open */
@@ -1078,10 +1081,8 @@ struct H264E_clip_tag
      * H264E_encode codes it with qp_min = qp_max = qp_sched[f]; NULL = the clip's own QP / rate control */
     uint8_t *qp_sched;                      /* [nframes] */
     int qp_explicit;                        /* the caller's schedule (kept across a rewind), not the controller's */
-    /* lookahead rate control (H264E_clip_set_lookahead): the project's own controller, defined in include/h264e_mi355x.h.  Frames
-     * [0, la_done) have their cost records (enc_lookahead.h) on the host; re-uploading frame f makes f onward stale, a rewind keeps them. */
+    /* lookahead rate control (H264E_clip_set_lookahead): the project's own controller, defined in include/h264e_mi355x.h */
     int la_kbps, la_window, la_qmin, la_qmax;   /* la_kbps 0 = off */
-    int la_done;
     uint64_t *la_rec;                       /* [nframes][3] I, P, N */
     int *la_bits;                           /* [nframes] coded bits of the accepted frames of the current pass */
     int la_planned, la_closed;              /* windows whose QP has been chosen / whose frames have all been accepted (calibration and carry done) */
@@ -1089,11 +1090,8 @@ struct H264E_clip_tag
     long long la_debt;                      /* sum over the closed windows of target - actual bits */
     double la_kernel_ms; long long la_frames;
     /* motion search in the cost pass (H264E_clip_set_lookahead_search): the range, 0 = off; a frame has been analysed since open (its
-     * records belong to that range); frames [la_ring_lo, la_done) still have their entries in the device's rings of max(resident, 2) */
-    int la_search, la_any, la_ring_lo;
-    /* motion-compensated filter (H264E_clip_set_denoise_motion): 0 = the plain denoiser fills the ring, 1 / 2 = enc_mcdenoise.h does, from
-     * the motion field of the searched cost pass; frames [den_ring_lo, den_done) still have their pictures (and vector cells) on the device */
-    int den_motion, den_ring_lo;
+     * records belong to that range) */
+    int la_search, la_any;
     /* Key frames that a stopped launch left encoded, wholly or down to some macroblock row: a key frame reads no reference
      * picture and no mv_clusters candidates, so what the next launch would make of those rows is what already lies in the frame's slot.
      * Collected when a launch has stopped cleanly (clip_keep_collect), used and forgotten by the next plan (clip_plan_launch); an entry
@@ -1111,6 +1109,52 @@ static void clip_keep_drop(H264E_clip_t *c, int from)
     c->nkeep = k;
 }
 
+/* ---- the frame passes' bookkeeping; the passes themselves are further down (clip_prepass_*) */
+
+/* How many frames a call with frames [0, limit) uploaded has to make, from p->done on: 0 = none, -1 = more than the input ring holds.
+ * (An upload is checked against the frames not encoded yet at its upper end only, so a caller can get here.) */
+static int clip_pass_pending(const H264E_clip_t *c, const clip_pass_t *p, const char *pass, int limit)
+{
+    if (limit - p->done > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "%s: frames %d..%d do not fit the input ring", pass, p->done, limit - 1); return -1; }
+    return imax(limit - p->done, 0);
+}
+
+/* frames [a, limit) have been made */
+static void clip_pass_made(clip_pass_t *p, int a, int limit)
+{
+    p->done = limit;
+    /* frames a.. took the entries of frames a - entries..: what was intact in front of a still is, from limit - entries on (no entries: nothing) */
+    p->ring_lo = imax(imin(p->ring_lo, a), limit - p->entries);
+}
+
+/* is `frame` among the frames whose entries are still on the device?  If not, the reader's error text */
+static int clip_pass_resident(const clip_pass_t *p, int frame, const char *who, const char *what)
+{
+    const int hi = p->done, lo = imin(p->ring_lo, hi);
+    if (frame >= lo && frame < hi) return 1;
+    if (lo < hi) snprintf(g_host_err, sizeof(g_host_err), "%s: frame %d has no %s on the device (frames %d..%d have)", who, frame, what, lo, hi - 1);
+    else snprintf(g_host_err, sizeof(g_host_err), "%s: frame %d has no %s on the device (no frame has)", who, frame, what);
+    return 0;
+}
+
+/* new inputs from frame `first` on: what the passes made of them, and of all behind them, is made again, and no row of an earlier
+ * encode of theirs stands */
+static void clip_inputs_replaced(H264E_clip_t *c, int first)
+{
+    if (first < c->sc.done) c->sc.done = first;
+    if (first < c->la.done) c->la.done = first;
+    if (first < c->den.done) c->den.done = first;
+    clip_keep_drop(c, first);
+}
+
+/* frame `first` would be made again, from what the pass kept of frame first - 1: refused when that has left the ring */
+static int clip_pass_predecessor_gone(const clip_pass_t *p, int first, const char *made, const char *kept, const char *ring)
+{
+    if (first <= 0 || first >= p->done || first - 1 >= p->done - p->entries) return 0;
+    snprintf(g_host_err, sizeof(g_host_err), "upload: frame %d would be %s again, but the %s in front of it has left the %s (rewind and upload from frame 0)", first, made, kept, ring);
+    return -1;
+}
+
 /* The schedule rule, once.  frame_num restarts at every key frame, and so does the periodic counter: the next periodic key frame
  * comes `gop` frames after the last key frame of either kind.  The wrap of the counter (h264-lab.h:6611) happens only on a DEFAULT
  * call: with gop = 1 the frame behind a forced key frame is a P frame.  A detected cut is a forced key frame on a frame that would
@@ -1126,7 +1170,7 @@ static void clip_sched_build(H264E_clip_t *c)
         forced = k < c->nforced && c->forced[k] == f;
         if (c->sc_cut && f < c->nframes)
         {
-            c->sc_cut[f] = (uint8_t)(!forced && fn && c->scenecut && f < c->sc_done && c->sc_dist[f] > c->scenecut);
+            c->sc_cut[f] = (uint8_t)(!forced && fn && c->scenecut && f < c->sc.done && c->sc_dist[f] > c->scenecut);
             forced |= c->sc_cut[f];
         }
         key = forced || fn == 0;
@@ -1137,6 +1181,8 @@ static void clip_sched_build(H264E_clip_t *c)
     }
     c->all_key = all;
 }
+
+static int clip_nslices(const H264E_clip_t *c) { return c->par.slices > 1 ? imin(imin(c->par.slices, H264E_HIP_MAX_SLICES), c->seq.nmby) : 1; }
 
 /* frames per launch at frame 0: optimistic where mis-speculations are rare by construction (row bands restart the state, intra frames
  * do not read it): as long as memory allows; else the pipeline depth, growing with every clean launch */
@@ -1236,6 +1282,7 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     if (getenv("H264E_LAUNCH_BASE")) c->launch_base = atoi(getenv("H264E_LAUNCH_BASE"));      /* experiments */
     c->launch_base = imax(1, imin(c->launch_base, c->ring - 1));
     c->resident = par->resident_frames > 0 ? imin(par->resident_frames, nframes) : nframes;
+    c->den.entries = c->resident; c->la.entries = imax(c->resident, 2);         /* as the pool sizes its rings (h264e_pool.h) */
     c->traj = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)c->seq.nmb);
     c->tasks = (h264e_hip_task_t *)calloc((size_t)c->ring, sizeof(*c->tasks));
     c->used = (int32_t (*)[2])calloc((size_t)c->ring, sizeof(int32_t[2]));
@@ -1282,43 +1329,38 @@ static int clip_put_allowed(const H264E_clip_t *c, int first, int n)
 {
     if (!c || first < 0 || n < 0 || first + n > c->nframes) { snprintf(g_host_err, sizeof(g_host_err), "upload: bad frame range"); return -1; }
     if (first + n - c->resident > c->next) { snprintf(g_host_err, sizeof(g_host_err), "upload: input ring full (frames %d.. are not encoded yet)", c->next); return -1; }
-    if (c->denoise && first > 0 && first < c->den_done && first - 1 < c->den_done - c->resident)
-    {
-        snprintf(g_host_err, sizeof(g_host_err), "upload: frame %d would be denoised again, but the denoised picture in front of it has left the input ring (rewind and upload from frame 0)", first);
-        return -1;
-    }
+    if (c->denoise && clip_pass_predecessor_gone(&c->den, first, "denoised", "denoised picture", "input ring")) return -1;
     /* the cost pass measures frame `first` against the half-resolution picture of the frame in front of it (enc_lookahead.h) */
-    if ((c->la_kbps || c->den_motion) && first > 0 && first < c->la_done && first - 1 < c->la_done - imax(c->resident, 2))
-    {
-        snprintf(g_host_err, sizeof(g_host_err), "upload: frame %d would be analysed again, but the half-resolution picture in front of it has left the ring (rewind and upload from frame 0)", first);
-        return -1;
-    }
+    if ((c->la_kbps || c->den_motion) && clip_pass_predecessor_gone(&c->la, first, "analysed", "half-resolution picture", "ring")) return -1;
     return 0;
+}
+
+/* the input ring wraps: the slot of frame f, and in *run how many of the n frames from f on lie in consecutive slots */
+static int clip_ring_piece(const H264E_clip_t *c, int f, int n, int *run)
+{
+    *run = imin(n, c->resident - f % c->resident);
+    return f % c->resident;
 }
 
 /* frames [first, first + n) of the stream into their ring slots */
 static int clip_put(H264E_clip_t *c, int first, int n, const uint8_t *i420, int async)
 {
     size_t fsz;
-    int done = 0;
+    int done, slot, run;
     if (clip_put_allowed(c, first, n)) return -1;
     fsz = (size_t)c->seq.width*c->seq.height*3/2;
-    while (done < n)
+    for (done = 0; done < n; done += run)
     {
-        const int slot = (first + done) % c->resident, run = imin(n - done, c->resident - slot);
+        slot = clip_ring_piece(c, first + done, n - done, &run);
         if (async ? h264e_hip_upload_i420_async(c->pool, slot, run, i420 + fsz*(size_t)done) : h264e_hip_upload_i420(c->pool, slot, run, i420 + fsz*(size_t)done))
         {
             g_host_err[0] = 0;          /* H264E_last_error() -> the device layer's text */
             return -1;
         }
-        done += run;
     }
     if (async) { if (first + n > c->pending_avail) c->pending_avail = first + n; }
     else if (first + n > c->avail) c->avail = first + n;
-    if (first < c->den_done) c->den_done = first;       /* new inputs: their denoised pictures (and all behind them) are made again */
-    if (first < c->sc_done) c->sc_done = first;         /* ... and their histograms */
-    if (first < c->la_done) c->la_done = first;         /* ... and their cost records */
-    clip_keep_drop(c, first);                           /* ... and no row of an earlier encode of theirs stands */
+    clip_inputs_replaced(c, first);
     return 0;
 }
 
@@ -1328,14 +1370,13 @@ int H264E_clip_upload(H264E_clip_t *c, int first, int nframes, const uint8_t *i4
     return h264e_hip_sync(c->pool);
 }
 
-/* The same from device memory: one ingest kernel per frame on the pool's copy stream (enc_ingest.h) -- with a window one scaling kernel
- * (enc_scale.h) -- all of them complete on return.  Every frame is checked before the first one is launched, so a refused call leaves
- * the input ring as it was. */
+/* The same from device memory, for a range that clip_put_allowed has passed: one ingest kernel per frame on the pool's copy stream
+ * (enc_ingest.h) -- with a window one scaling kernel (enc_scale.h) -- all of them complete on return.  Every frame is checked before
+ * the first one is launched, so a refused call leaves the input ring as it was. */
 static int clip_put_device(H264E_clip_t *c, int first, int nframes, const H264E_dev_frame_t *frames, const H264E_dev_window_t *win)
 {
     int i, rc = 0;
     double ms = 0;
-    if (clip_put_allowed(c, first, nframes)) return -1;
     for (i = 0; i < nframes; i++)
     {
         const H264E_dev_frame_t *f = &frames[i];
@@ -1352,10 +1393,7 @@ static int clip_put_device(H264E_clip_t *c, int first, int nframes, const H264E_
     if (c->time_input && !h264e_hip_copy_timer_stop(c->pool, &ms)) { c->input_ms += ms; c->input_frames += i; }
     if (h264e_hip_upload_wait(c->pool) || rc) return -1;        /* (after a failure too: what was launched has read its source) */
     if (first + nframes > c->avail) c->avail = first + nframes;
-    if (first < c->den_done) c->den_done = first;
-    if (first < c->sc_done) c->sc_done = first;
-    if (first < c->la_done) c->la_done = first;
-    clip_keep_drop(c, first);
+    clip_inputs_replaced(c, first);
     return 0;
 }
 
@@ -1416,19 +1454,15 @@ void H264E_clip_host_free(void *p) { h264e_hip_host_free(p); }
 
 int H264E_clip_generate_synth(H264E_clip_t *c, int first, int nframes, int t0, uint32_t seed)
 {
-    int done = 0;
-    if (!c || first < 0 || nframes < 0 || first + nframes > c->nframes || first + nframes - c->resident > c->next) return -1;
-    while (done < nframes)
+    int done, slot, run;
+    if (clip_put_allowed(c, first, nframes)) return -1;
+    for (done = 0; done < nframes; done += run)
     {
-        const int slot = (first + done) % c->resident, run = imin(nframes - done, c->resident - slot);
-        if (h264e_hip_generate_synth(c->pool, slot, run, t0 + done, seed)) return -1;
-        done += run;
+        slot = clip_ring_piece(c, first + done, nframes - done, &run);
+        if (h264e_hip_generate_synth(c->pool, slot, run, t0 + done, seed)) { g_host_err[0] = 0; return -1; }
     }
     if (first + nframes > c->avail) c->avail = first + nframes;
-    if (first < c->den_done) c->den_done = first;
-    if (first < c->sc_done) c->sc_done = first;
-    if (first < c->la_done) c->la_done = first;
-    clip_keep_drop(c, first);
+    clip_inputs_replaced(c, first);
     return h264e_hip_sync(c->pool);
 }
 
@@ -1519,10 +1553,10 @@ int H264E_clip_quality_time(H264E_clip_t *c, int enable, double *ssd_ms, double 
  */
 int H264E_clip_revalidate(H264E_clip_t *c, const int32_t exact_in[2], int *restart_frame, int32_t restart_state[2], int32_t end_state[2])
 {
-    const int nslices = c && c->par.slices > 1 ? imin(imin(c->par.slices, H264E_HIP_MAX_SLICES), c->seq.nmby) : 1;
     int32_t s[2], gop_state[2];
-    int f;
+    int f, nslices;
     if (!c || !c->rec_store || !exact_in || !restart_frame) return -1;
+    nslices = clip_nslices(c);
     s[0] = gop_state[0] = exact_in[0]; s[1] = gop_state[1] = exact_in[1];
     *restart_frame = -1;
     for (f = 0; f < c->next; f++)
@@ -1585,7 +1619,7 @@ static int clip_denoise_ring(H264E_clip_t *c, const char *who)
         return -1;
     }
     if (h264e_hip_denoise_reset(c->pool)) return -1;
-    c->den_done = c->den_ring_lo = 0;
+    c->den.done = c->den.ring_lo = 0;
     return 0;
 }
 
@@ -1663,7 +1697,6 @@ int H264E_clip_set_scenecut(H264E_clip_t *c, int threshold)
         c->sc_hist = (uint32_t *)calloc((size_t)c->nframes*64, sizeof(uint32_t));
         c->sc_dist = (int *)calloc((size_t)c->nframes, sizeof(int));
         c->sc_cut = (uint8_t *)calloc((size_t)c->nframes, 1);
-        c->sc_done = 0;
         if (!c->sc_hist || !c->sc_dist || !c->sc_cut)
         {
             free(c->sc_hist); free(c->sc_dist); free(c->sc_cut);
@@ -1683,7 +1716,7 @@ int H264E_clip_read_scenecut(H264E_clip_t *c, int first, int n, int *dist, uint8
     int i;
     g_host_err[0] = 0;
     if (!c || !c->sc_dist) { snprintf(g_host_err, sizeof(g_host_err), "read_scenecut: the detector has not been switched on"); return -1; }
-    if (first < 0 || n < 0 || first + n > c->sc_done) { snprintf(g_host_err, sizeof(g_host_err), "read_scenecut: frames %d..%d have not been analysed (%d have)", first, first + n - 1, c->sc_done); return -1; }
+    if (first < 0 || n < 0 || first + n > c->sc.done) { snprintf(g_host_err, sizeof(g_host_err), "read_scenecut: frames %d..%d have not been analysed (%d have)", first, first + n - 1, c->sc.done); return -1; }
     for (i = 0; i < n; i++)
     {
         if (dist) dist[i] = c->sc_dist[first + i];
@@ -1701,33 +1734,7 @@ int H264E_clip_scenecut_time(H264E_clip_t *c, double *kernel_ms, long long *fram
     return 0;
 }
 
-/* the pre-pass in front of the tasks, the detector: the histograms of the frames uploaded so far and not yet analysed, read back, D(f)
- * from consecutive records, and the schedule with the cuts among them -- all before the tasks of the launch that first encodes them
- * are built */
-static int clip_prepass_scenecut(H264E_clip_t *c, int limit)
-{
-    const int a = c->sc_done;
-    float ms = 0;
-    int f, b;
-    if (!c->scenecut || a >= limit) return 0;
-    if (limit - a > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "scenecut: frames %d..%d do not fit the input ring", a, limit - 1); return -1; }
-    if (h264e_hip_scenecut_frames(c->pool, a % c->resident, limit - a, c->sc_hist + (size_t)a*64, &ms)) return -1;
-    for (f = a; f < limit; f++)
-    {
-        const uint32_t *h = c->sc_hist + (size_t)f*64;
-        uint64_t sum = 0;
-        for (b = 0; f && b < 64; b++) sum += h[b] > h[b - 64] ? h[b] - h[b - 64] : h[b - 64] - h[b];
-        c->sc_dist[f] = (int)(sum*1024u/(2u*(uint64_t)c->seq.width*(uint64_t)c->seq.height));
-    }
-    c->sc_kernel_ms += ms; c->sc_frames += limit - a;
-    c->sc_done = limit;
-    clip_sched_build(c);
-    return 0;
-}
-
 /* ---- a QP per frame, and the lookahead controller that writes one (include/h264e_mi355x.h has the definitions) */
-
-static int clip_nslices(const H264E_clip_t *c) { return c->par.slices > 1 ? imin(imin(c->par.slices, H264E_HIP_MAX_SLICES), c->seq.nmby) : 1; }
 
 /* what both calls refuse: the reference's own controller, GOP shards, a clip that has moved */
 static int clip_qp_mode_refused(const H264E_clip_t *c, const char *who)
@@ -1774,7 +1781,6 @@ static int clip_la_arrays(H264E_clip_t *c)
     if (c->la_rec) return 0;
     c->la_rec = (uint64_t *)calloc((size_t)c->nframes*3, sizeof(uint64_t));
     c->la_bits = (int *)calloc((size_t)c->nframes, sizeof(int));
-    c->la_done = 0;
     if (!c->la_rec || !c->la_bits)
     {
         free(c->la_rec); free(c->la_bits); c->la_rec = NULL; c->la_bits = NULL;
@@ -1810,7 +1816,7 @@ int H264E_clip_read_lookahead(H264E_clip_t *c, int first, int n, uint64_t *intra
     if (!c || first < 0 || n < 0) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead: bad argument"); return -1; }
     if (intra || inter || intra_blocks)
     {
-        const int have = c->la_rec ? c->la_done : 0;
+        const int have = c->la_rec ? c->la.done : 0;
         if (first + n > have) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead: frames %d..%d have not been analysed (%d have)", first, first + n - 1, have); return -1; }
     }
     if (qp)
@@ -1846,24 +1852,15 @@ int H264E_clip_set_lookahead_search(H264E_clip_t *c, int range)
     return 0;
 }
 
-static int clip_la_entries(const H264E_clip_t *c) { return imax(c->resident, 2); }
-
 int H264E_clip_read_lookahead_motion(H264E_clip_t *c, int frame, void *dst, int *nbx, int *nby)
 {
-    int lo, hi;
     g_host_err[0] = 0;
     if (!c) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: bad argument"); return -1; }
     if (nbx) *nbx = (c->par.width >> 1) >> 3;
     if (nby) *nby = (c->par.height >> 1) >> 3;
     if (!dst) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: bad argument"); return -1; }
     if (!c->la_search) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: the search is off (H264E_clip_set_lookahead_search), no frame has a motion field"); return -1; }
-    hi = c->la_rec ? c->la_done : 0; lo = imin(c->la_ring_lo, hi);
-    if (frame < lo || frame >= hi)
-    {
-        if (lo < hi) snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: frame %d has no motion field on the device (frames %d..%d have)", frame, lo, hi - 1);
-        else snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_motion: frame %d has no motion field on the device (no frame has)", frame);
-        return -1;
-    }
+    if (!clip_pass_resident(&c->la, frame, "read_lookahead_motion", "motion field")) return -1;
     return h264e_hip_lookahead_read_field(c->pool, frame, dst);
 }
 
@@ -1873,23 +1870,6 @@ int H264E_clip_lookahead_time(H264E_clip_t *c, double *kernel_ms, long long *fra
     if (!c) return -1;
     if (kernel_ms) *kernel_ms = c->la_kernel_ms;
     if (frames) *frames = c->la_frames;
-    return 0;
-}
-
-/* the pre-pass in front of a window's plan: the cost records of the frames uploaded so far and not yet analysed, in stream order */
-static int clip_prepass_lookahead(H264E_clip_t *c, int limit)
-{
-    const int a = c->la_done;
-    float ms = 0;
-    if (a >= limit) return 0;
-    if (limit - a > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "lookahead: frames %d..%d do not fit the input ring", a, limit - 1); return -1; }
-    if (c->la_search ? h264e_hip_lookahead_search_frames(c->pool, a, limit - a, c->la_search, (unsigned long long *)(c->la_rec + 3*(size_t)a), &ms)
-                     : h264e_hip_lookahead_frames(c->pool, a, limit - a, (unsigned long long *)(c->la_rec + 3*(size_t)a), &ms)) return -1;
-    c->la_kernel_ms += ms; c->la_frames += limit - a;
-    c->la_done = limit;
-    /* frames a.. took the entries of frames a - entries..: what was intact in front of a still is, from limit - entries on */
-    c->la_any = 1;
-    c->la_ring_lo = imax(imin(c->la_ring_lo, a), limit - clip_la_entries(c));
     return 0;
 }
 
@@ -1912,49 +1892,30 @@ int H264E_clip_set_denoise_motion(H264E_clip_t *c, int mode)
     if (c->par.speed >= 2) { snprintf(g_host_err, sizeof(g_host_err), "set_denoise_motion: speed %d: the denoiser runs for speed 0 and 1 only, no frame would be filtered", c->par.speed); return -1; }
     if (clip_la_arrays(c)) return -1;
     if (!c->denoise && clip_denoise_ring(c, "set_denoise_motion")) return -1;
-    if (c->den_motion != mode) c->den_done = c->den_ring_lo = 0;       /* pictures of another kernel: made again from the zero state */
+    if (c->den_motion != mode) c->den.done = c->den.ring_lo = 0;       /* pictures of another kernel: made again from the zero state */
     c->denoise = 1; c->den_motion = mode;
     return 0;
 }
 
-/* frames [lo, hi) have their denoised pictures and vector cells on the device */
-static void clip_den_resident(const H264E_clip_t *c, int *lo, int *hi)
-{
-    *hi = c->denoise ? c->den_done : 0;
-    *lo = imin(c->den_ring_lo, *hi);
-}
-
-static void clip_den_not_there(const H264E_clip_t *c, const char *who, const char *what, int frame)
-{
-    int lo, hi;
-    clip_den_resident(c, &lo, &hi);
-    if (lo < hi) snprintf(g_host_err, sizeof(g_host_err), "%s: frame %d has no %s on the device (frames %d..%d have)", who, frame, what, lo, hi - 1);
-    else snprintf(g_host_err, sizeof(g_host_err), "%s: frame %d has no %s on the device (no frame has)", who, frame, what);
-}
-
 int H264E_clip_read_denoised(H264E_clip_t *c, int frame, uint8_t *i420)
 {
-    int lo, hi;
     g_host_err[0] = 0;
     if (!c || !i420) { snprintf(g_host_err, sizeof(g_host_err), "read_denoised: bad argument"); return -1; }
     if (!c->denoise) { snprintf(g_host_err, sizeof(g_host_err), "read_denoised: the denoiser is off (H264E_clip_set_denoise, H264E_clip_set_denoise_motion)"); return -1; }
-    clip_den_resident(c, &lo, &hi);
-    if (frame < lo || frame >= hi) { clip_den_not_there(c, "read_denoised", "denoised picture", frame); return -1; }
+    if (!clip_pass_resident(&c->den, frame, "read_denoised", "denoised picture")) return -1;
     if (h264e_hip_read_denoised(c->pool, frame % c->resident, i420)) { g_host_err[0] = 0; return -1; }
     return 0;
 }
 
 int H264E_clip_read_denoise_motion(H264E_clip_t *c, int frame, void *dst, int *nbx, int *nby)
 {
-    int lo, hi;
     g_host_err[0] = 0;
     if (!c) { snprintf(g_host_err, sizeof(g_host_err), "read_denoise_motion: bad argument"); return -1; }
     if (nbx) *nbx = (c->par.width >> 1) >> 3;
     if (nby) *nby = (c->par.height >> 1) >> 3;
     if (!dst) { snprintf(g_host_err, sizeof(g_host_err), "read_denoise_motion: bad argument"); return -1; }
     if (!c->den_motion) { snprintf(g_host_err, sizeof(g_host_err), "read_denoise_motion: the motion-compensated denoiser is off (H264E_clip_set_denoise_motion), no frame has vectors"); return -1; }
-    clip_den_resident(c, &lo, &hi);
-    if (frame < lo || frame >= hi) { clip_den_not_there(c, "read_denoise_motion", "vectors", frame); return -1; }
+    if (!clip_pass_resident(&c->den, frame, "read_denoise_motion", "vectors")) return -1;
     if (h264e_hip_mcdenoise_read_vectors(c->pool, frame, dst)) { g_host_err[0] = 0; return -1; }
     return 0;
 }
@@ -1965,6 +1926,59 @@ int H264E_clip_denoise_time(H264E_clip_t *c, double *kernel_ms, long long *frame
     g_host_err[0] = 0;
     if (!c) return -1;
     if (h264e_hip_mcdenoise_time(c->pool, kernel_ms, frames)) return -1;
+    return 0;
+}
+
+/* ---- the frame passes: what is uploaded and not yet made, in stream order, in front of the launch that first encodes it */
+
+/* the detector, in front of the tasks: the histograms read back, D(f) from consecutive records, and the schedule with the cuts among
+ * them -- all before the tasks of the launch that first encodes the frames are built */
+static int clip_prepass_scenecut(H264E_clip_t *c, int limit)
+{
+    const int n = c->scenecut ? clip_pass_pending(c, &c->sc, "scenecut", limit) : 0, a = limit - n;
+    float ms = 0;
+    int f, b;
+    if (n <= 0) return n;
+    if (h264e_hip_scenecut_frames(c->pool, a % c->resident, n, c->sc_hist + (size_t)a*64, &ms)) return -1;
+    for (f = a; f < limit; f++)
+    {
+        const uint32_t *h = c->sc_hist + (size_t)f*64;
+        uint64_t sum = 0;
+        for (b = 0; f && b < 64; b++) sum += h[b] > h[b - 64] ? h[b] - h[b - 64] : h[b - 64] - h[b];
+        c->sc_dist[f] = (int)(sum*1024u/(2u*(uint64_t)c->seq.width*(uint64_t)c->seq.height));
+    }
+    c->sc_kernel_ms += ms; c->sc_frames += n;
+    clip_pass_made(&c->sc, a, limit);
+    clip_sched_build(c);
+    return 0;
+}
+
+/* the cost pass, in front of a window's plan (or of the motion-compensated denoiser): the cost records read back */
+static int clip_prepass_lookahead(H264E_clip_t *c, int limit)
+{
+    const int n = clip_pass_pending(c, &c->la, "lookahead", limit), a = limit - n;
+    float ms = 0;
+    if (n <= 0) return n;
+    if (c->la_search ? h264e_hip_lookahead_search_frames(c->pool, a, n, c->la_search, (unsigned long long *)(c->la_rec + 3*(size_t)a), &ms)
+                     : h264e_hip_lookahead_frames(c->pool, a, n, (unsigned long long *)(c->la_rec + 3*(size_t)a), &ms)) return -1;
+    c->la_kernel_ms += ms; c->la_frames += n;
+    c->la_any = 1;
+    clip_pass_made(&c->la, a, limit);
+    return 0;
+}
+
+/* the denoiser, in front of the submit */
+static int clip_prepass_denoise(H264E_clip_t *c, int limit)
+{
+    const int n = c->denoise && c->par.speed < 2 ? clip_pass_pending(c, &c->den, "denoise", limit) : 0, a = limit - n;
+    if (n <= 0) return n;
+    if (c->den_motion)
+    {
+        /* the searched cost pass comes first, also with the controller off and constant QP: it then runs for its motion field alone */
+        if (clip_prepass_lookahead(c, limit) || h264e_hip_mcdenoise_frames(c->pool, a, n, c->den_motion, a == 0)) return -1;
+    }
+    else if (h264e_hip_denoise_frames(c->pool, a % c->resident, n, a == 0)) return -1;
+    clip_pass_made(&c->den, a, limit);
     return 0;
 }
 
@@ -2242,29 +2256,6 @@ static void clip_plan_launch(H264E_clip_t *c, const clip_call_t *x, clip_launch_
     l->step = CLIP_GO_ON;
 }
 
-/* the pre-pass in front of the submit, the denoiser: every frame uploaded so far and not yet denoised, in stream order, before the launch
- * that reads them */
-static int clip_prepass_denoise(H264E_clip_t *c, int limit)
-{
-    const int a = c->den_done;
-    if (!c->denoise || c->par.speed >= 2 || a >= limit) return 0;
-    if (limit - a > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "denoise: frames %d..%d do not fit the input ring", a, limit - 1); return -1; }
-    if (c->den_motion)
-    {
-        /* the searched cost pass comes first, also with the controller off and constant QP: it then runs for its motion field alone.
-         * Frame f's field entry cannot have been overwritten: the field ring and the input ring use the same indexing (f % entries,
-         * entries >= resident), so the frame that takes f's entry is one whose input could only be uploaded over f's slot -- after f
-         * was encoded, and this pre-pass runs in front of the launch that first encodes f. */
-        if (clip_prepass_lookahead(c, limit)) return -1;
-        if (h264e_hip_mcdenoise_frames(c->pool, a, limit - a, c->den_motion, a == 0)) return -1;
-    }
-    else if (h264e_hip_denoise_frames(c->pool, a % c->resident, limit - a, a == 0)) return -1;
-    c->den_done = limit;
-    /* frames a.. took the slots of frames a - resident..: what was intact in front of a still is, from limit - resident on */
-    c->den_ring_lo = imax(imin(c->den_ring_lo, a), limit - c->resident);
-    return 0;
-}
-
 /* wait for a job of the running launch, as h264e_hip_stream_done: 1 finished (r filled), 2 aborted, < 0 failed; 0: the launch ended
  * without finishing it */
 static int clip_wait_frame(H264E_clip_t *c, int slot, h264e_hip_result_t *r)
@@ -2345,7 +2336,7 @@ static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_
         c->rc_last_bytes[key] = (int)(x->pos - start);
         /* (scene-cut detection: a frame that has not been analysed has no kind yet -- the launch that analyses it runs its
          * rc_frame_start, on the same controller state) */
-        if (f + 1 < c->nframes && (!c->scenecut || f + 1 < c->sc_done))
+        if (f + 1 < c->nframes && (!c->scenecut || f + 1 < c->sc.done))
         {
             /* the exact QP of the next frame; a frame of this launch that was given another one is stopped */
             const int qp = c->rc_qp = rc_frame_start(&c->rcs, c->par.gop, nmb, c->par.vbv_size_bytes, x->desired_frame_bytes, x->qp_min, x->qp_max, c->sched[f + 1].key);
@@ -2484,7 +2475,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
     memset(&x, 0, sizeof(x));
     g_host_err[0] = 0;
     x.out = out; x.cap = cap; x.frame_bytes = frame_bytes; x.first = c->next;
-    x.nslices = c->par.slices > 1 ? imin(imin(c->par.slices, H264E_HIP_MAX_SLICES), c->seq.nmby) : 1;
+    x.nslices = clip_nslices(c);
     x.no_deblock = (c->par.speed == 8 || c->par.speed == 10);
     x.idr_state = c->par.first_idr_pic_id_state & 1;
     x.desired_frame_bytes = c->par.kbps > 0 ? c->par.kbps*1000/8/30 : 0;

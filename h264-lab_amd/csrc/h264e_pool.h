@@ -181,8 +181,8 @@ struct h264e_hip_pool
      * state; a single-slot pool ping-pongs two frames instead (den_flip: the current one).  NULL until the denoiser is switched on. */
     uint8_t *den;
     int den_frames, den_flip;
-    hipEvent_t ev_copy;                  /* the copy stream's uploads, waited for by a denoise / scene-cut launch */
-    hipEvent_t ev_sc[2];                 /* around the scene-cut / cost-pass launches of one call (their HIP-event time) */
+    hipEvent_t ev_copy;                  /* the copy stream's uploads, waited for by the launches of a frame pass (wait_for_copy_stream) */
+    hipEvent_t ev_pass[2];               /* around the launches of one synchronous pass call, scene-cut or cost pass (their HIP-event time) */
     int *sc_rec;                         /* device [frames_resident][64]: luma histogram records of the scene-cut detector; NULL until it is switched on */
     /* cost pass of the lookahead rate control (enc_lookahead.h); NULL until it first runs */
     uint8_t *la_lo;                      /* device [la_entries][la_entry_bytes]: the half-resolution pictures, frame f in entry f % la_entries */
@@ -327,7 +327,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
         (void)hipEventDestroy(p->ev_t0); (void)hipEventDestroy(p->ev_t1); (void)hipEventDestroy(p->ev_prep); (void)hipEventDestroy(p->ev_copy);
         (void)hipEventDestroy(p->ev_ingest[0]); (void)hipEventDestroy(p->ev_ingest[1]); (void)hipEventDestroy(p->ev_in[0]); (void)hipEventDestroy(p->ev_in[1]);
         (void)hipEventDestroy(p->ev_out[0]); (void)hipEventDestroy(p->ev_out[1]);
-        (void)hipEventDestroy(p->ev_sc[0]); (void)hipEventDestroy(p->ev_sc[1]);
+        (void)hipEventDestroy(p->ev_pass[0]); (void)hipEventDestroy(p->ev_pass[1]);
         (void)hipEventDestroy(p->ev_mcd[0]); (void)hipEventDestroy(p->ev_mcd[1]);
         (void)hipStreamDestroy(p->stream);
         if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
@@ -483,7 +483,7 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     (void)hipEventCreate(&p->ev_t0); (void)hipEventCreate(&p->ev_t1); (void)hipEventCreate(&p->ev_prep); (void)hipEventCreate(&p->ev_copy);
     (void)hipEventCreate(&p->ev_ingest[0]); (void)hipEventCreate(&p->ev_ingest[1]); (void)hipEventCreate(&p->ev_in[0]); (void)hipEventCreate(&p->ev_in[1]);
     (void)hipEventCreate(&p->ev_out[0]); (void)hipEventCreate(&p->ev_out[1]);
-    (void)hipEventCreate(&p->ev_sc[0]); (void)hipEventCreate(&p->ev_sc[1]);
+    (void)hipEventCreate(&p->ev_pass[0]); (void)hipEventCreate(&p->ev_pass[1]);
     (void)hipEventCreate(&p->ev_mcd[0]); (void)hipEventCreate(&p->ev_mcd[1]);
     (void)hipEventCreate(&p->ev_q[0]); (void)hipEventCreate(&p->ev_q[1]);
     p->chains_host = (h264e_chain_dev_t *)calloc((size_t)nchains, sizeof(h264e_chain_dev_t));
@@ -659,6 +659,35 @@ extern "C" int h264e_hip_ssd_frames(h264e_hip_pool_t *p, int n, int in0, int in_
     return ssd_run(p, n, in0, in_mod, (const h264e_chain_dev_t *)p->chains_dev, pic0, pic_mod, out);
 }
 
+/* ---- frame passes: one kernel launch per uploaded frame on the pool's stream, in stream order.  What they share: */
+/* the inputs may have come over the copy stream (asynchronous uploads, device input): the launches wait for everything issued there */
+static int wait_for_copy_stream(h264e_hip_pool_t *p)
+{
+    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
+    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
+    return 0;
+}
+
+/* A device ring of E records of `bytes` each, frame f's in entry f % E, and a call over frames [first, first + n), n <= frames_resident <= E:
+ * no entry is used twice and the entries wrap at most once -- zeroed in front of the launches, copied to the host behind them, in one or two pieces */
+static int ring_records_pieces(h264e_hip_pool_t *p, void *host, void *ring, size_t bytes, int E, int first, int n)
+{
+    for (int done = 0, run; done < n; done += run)
+    {
+        uint8_t *const entry = (uint8_t *)ring + bytes*(size_t)((first + done) % E);
+        run = imin_h(n - done, E - (first + done) % E);
+        if (!host) HIPCHK(hipMemsetAsync(entry, 0, bytes*(size_t)run, p->stream));
+        else HIPCHK(hipMemcpyAsync((uint8_t *)host + bytes*(size_t)done, entry, bytes*(size_t)run, hipMemcpyDeviceToHost, p->stream));
+    }
+    return 0;
+}
+static int ring_records_zero(h264e_hip_pool_t *p, void *ring, size_t bytes, int E, int first, int n) { return ring_records_pieces(p, NULL, ring, bytes, E, first, n); }
+static int ring_records_read(h264e_hip_pool_t *p, void *host, void *ring, size_t bytes, int E, int first, int n) { return ring_records_pieces(p, host, ring, bytes, E, first, n); }
+
+/* the cost pass' block grid: 8x8 blocks of the half-resolution picture; the motion-compensated denoiser's 16x16 luma blocks are the same grid */
+static int la_nbx(const h264e_hip_pool_t *p) { return (p->G.width >> 1) >> 3; }
+static int la_nby(const h264e_hip_pool_t *p) { return (p->G.height >> 1) >> 3; }
+
 /* ---- temporal denoiser (enc_denoise.h): one h264e_denoise_kernel launch per frame on the pool's stream, in stream order */
 
 #ifdef H264E_EMU
@@ -678,6 +707,16 @@ static void bk_launch_denoise(const uint8_t *in, const uint8_t *prev, uint8_t *o
 
 static int den_index(const h264e_hip_pool_t *p, int slot) { return p->frames_resident == 1 ? p->den_flip : slot; }
 static uint8_t *den_frame(const h264e_hip_pool_t *p, int index) { return p->den + p->frame_bytes*(size_t)index; }
+
+/* the frame in input slot s: filtered against the denoised frame *prev -- the zero state for the first frame of a call from zero, else
+ * the one in front -- into the one returned; a single-slot pool ping-pongs, and flips here */
+static int den_step(h264e_hip_pool_t *p, int s, int first_from_zero, int *prev)
+{
+    const int R = p->frames_resident;
+    *prev = first_from_zero ? p->den_frames - 1 : R == 1 ? p->den_flip : (s + R - 1) % R;
+    if (R == 1) p->den_flip ^= 1;
+    return den_index(p, s);
+}
 
 extern "C" int h264e_hip_denoise_reset(h264e_hip_pool_t *p)
 {
@@ -699,16 +738,13 @@ extern "C" int h264e_hip_denoise_frames(h264e_hip_pool_t *p, int first, int n, i
     if (!p || !p->den || first < 0 || first >= R || n < 0 || n > R) FAIL("denoise_frames: bad argument (or the denoiser is not on)");
     if (!n) return 0;
     HIPCHK(hipSetDevice(p->device));
-    /* the inputs may have come over the copy stream (h264e_hip_upload_i420_async): the launches wait for everything issued there */
-    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
-    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
+    if (wait_for_copy_stream(p)) return -1;
     for (int i = 0; i < n; i++)
     {
         const int s = (first + i) % R;
-        const int prev = (i == 0 && from_zero) ? p->den_frames - 1 : R == 1 ? p->den_flip : (s + R - 1) % R;
-        const int out = R == 1 ? p->den_flip ^ 1 : s;
+        int prev;
+        const int out = den_step(p, s, i == 0 && from_zero, &prev);
         bk_launch_denoise(p->clip + p->frame_bytes*(size_t)s, den_frame(p, prev), den_frame(p, out), p->G.width, p->G.height, p->stream);
-        if (R == 1) p->den_flip ^= 1;
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -762,23 +798,20 @@ extern "C" int h264e_hip_mcdenoise_frames(h264e_hip_pool_t *p, int first, int n,
     if (!n) return 0;
     HIPCHK(hipSetDevice(p->device));
     mcdenoise_args_t A;
-    A.width = p->G.width; A.height = p->G.height; A.nbx = (p->G.width >> 1) >> 3; A.nby = (p->G.height >> 1) >> 3;
+    A.width = p->G.width; A.height = p->G.height; A.nbx = la_nbx(p); A.nby = la_nby(p);
     const size_t nblk = (size_t)A.nbx*(size_t)A.nby;
     if (!p->mcd_cells && dev_malloc((void **)&p->mcd_cells, nblk*MCDENOISE_CELL_BYTES*(size_t)p->la_entries)) { p->mcd_cells = 0; FAIL("mcdenoise: device allocation failed (%d vector fields)", p->la_entries); }
     if (mcdenoise_collect(p)) return -1;
-    /* the inputs may have come over the copy stream (h264e_hip_upload_i420_async): the launches wait for everything issued there */
-    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
-    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
+    if (wait_for_copy_stream(p)) return -1;
     HIPCHK(hipEventRecord(p->ev_mcd[0], p->stream));
     for (int i = 0; i < n; i++)
     {
         const int f = first + i, s = f % R, e = f % p->la_entries;
-        const int prev = (i == 0 && from_zero) ? p->den_frames - 1 : R == 1 ? p->den_flip : (s + R - 1) % R;
-        const int out = R == 1 ? p->den_flip ^ 1 : s;
+        int prev;
+        const int out = den_step(p, s, i == 0 && from_zero, &prev);
         A.cur = p->clip + p->frame_bytes*(size_t)s; A.prev = den_frame(p, prev); A.out = den_frame(p, out);
         A.field = p->la_field + nblk*(size_t)e; A.cells = p->mcd_cells + nblk*(size_t)e;
         bk_launch_mcdenoise(A, mode, p->stream);
-        if (R == 1) p->den_flip ^= 1;
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(p->ev_mcd[1], p->stream));
@@ -792,7 +825,7 @@ extern "C" int h264e_hip_mcdenoise_read_vectors(h264e_hip_pool_t *p, int frame, 
     if (!p || !dst || frame < 0) FAIL("mcdenoise_read_vectors: bad argument");
     if (!p->mcd_cells) FAIL("mcdenoise_read_vectors: no frame has been filtered");
     HIPCHK(hipSetDevice(p->device));
-    const size_t bytes = (size_t)((p->G.width >> 1) >> 3)*(size_t)((p->G.height >> 1) >> 3)*MCDENOISE_CELL_BYTES;
+    const size_t bytes = (size_t)la_nbx(p)*(size_t)la_nby(p)*MCDENOISE_CELL_BYTES;
     HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)p->mcd_cells + bytes*(size_t)(frame % p->la_entries), bytes, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     return 0;
@@ -831,28 +864,16 @@ extern "C" int h264e_hip_scenecut_frames(h264e_hip_pool_t *p, int first, int n, 
     if (!n) return 0;
     HIPCHK(hipSetDevice(p->device));
     if (!p->sc_rec && dev_malloc((void **)&p->sc_rec, sizeof(int)*SCENECUT_BINS*(size_t)R)) { p->sc_rec = 0; FAIL("scenecut: device allocation failed (%d records)", R); }
-    /* the inputs may have come over the copy stream (asynchronous uploads, device input): the launches wait for everything issued there */
-    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
-    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
-    HIPCHK(hipEventRecord(p->ev_sc[0], p->stream));
-    for (int done = 0; done < n;)
-    {
-        const int s = (first + done) % R, run = imin_h(n - done, R - s);
-        HIPCHK(hipMemsetAsync(p->sc_rec + (size_t)s*SCENECUT_BINS, 0, sizeof(int)*SCENECUT_BINS*(size_t)run, p->stream));
-        for (int i = 0; i < run; i++)
-            bk_launch_scenecut(p->clip + p->frame_bytes*(size_t)(s + i), (uint32_t)((size_t)p->G.width*p->G.height), p->sc_rec + (size_t)(s + i)*SCENECUT_BINS, p->stream);
-        HIPCHK(hipGetLastError());
-        done += run;
-    }
-    HIPCHK(hipEventRecord(p->ev_sc[1], p->stream));
-    for (int done = 0; done < n;)
-    {
-        const int s = (first + done) % R, run = imin_h(n - done, R - s);
-        HIPCHK(hipMemcpyAsync(hist + (size_t)done*SCENECUT_BINS, p->sc_rec + (size_t)s*SCENECUT_BINS, sizeof(int)*SCENECUT_BINS*(size_t)run, hipMemcpyDeviceToHost, p->stream));
-        done += run;
-    }
+    if (wait_for_copy_stream(p)) return -1;
+    HIPCHK(hipEventRecord(p->ev_pass[0], p->stream));
+    if (ring_records_zero(p, p->sc_rec, sizeof(int)*SCENECUT_BINS, R, first, n)) return -1;
+    for (int i = 0; i < n; i++)
+        bk_launch_scenecut(p->clip + p->frame_bytes*(size_t)((first + i) % R), (uint32_t)((size_t)p->G.width*p->G.height), p->sc_rec + (size_t)((first + i) % R)*SCENECUT_BINS, p->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->ev_pass[1], p->stream));
+    if (ring_records_read(p, hist, p->sc_rec, sizeof(int)*SCENECUT_BINS, R, first, n)) return -1;
     HIPCHK(hipStreamSynchronize(p->stream));
-    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, p->ev_sc[0], p->ev_sc[1]));
+    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, p->ev_pass[0], p->ev_pass[1]));
     return 0;
 }
 
@@ -929,7 +950,7 @@ static int lookahead_frames(h264e_hip_pool_t *p, int first, int n, int range, un
     if (!n) return 0;
     HIPCHK(hipSetDevice(p->device));
     lookahead_args_t A;
-    A.width = p->G.width; A.nbx = (p->G.width >> 1) >> 3; A.nblk = A.nbx*((p->G.height >> 1) >> 3);
+    A.width = p->G.width; A.nbx = la_nbx(p); A.nblk = A.nbx*la_nby(p);
     if (!p->la_lo)
     {
         p->la_entries = R > 1 ? R : 2;
@@ -939,18 +960,9 @@ static int lookahead_frames(h264e_hip_pool_t *p, int first, int n, int range, un
     }
     if (range && !p->la_field && dev_malloc((void **)&p->la_field, (size_t)A.nblk*LOOKAHEAD_FIELD_CELL_BYTES*(size_t)p->la_entries)) { p->la_field = 0; FAIL("lookahead: device allocation failed (%d motion fields)", p->la_entries); }
     const int E = p->la_entries;
-    /* the inputs may have come over the copy stream (asynchronous uploads, device input): the launches wait for everything issued there */
-    HIPCHK(hipEventRecord(p->ev_copy, p->copy_stream));
-    HIPCHK(hipStreamWaitEvent(p->stream, p->ev_copy, 0));
-    HIPCHK(hipEventRecord(p->ev_sc[0], p->stream));
-    /* n <= frames_resident <= entries: no entry is used twice in a call and the entries wrap at most once, so the records are zeroed
-     * in front of the launches and read back behind them in one or two pieces */
-    for (int done = 0; done < n;)
-    {
-        const int e = (first + done) % E, run = imin_h(n - done, E - e);
-        HIPCHK(hipMemsetAsync(p->la_rec + 3*(size_t)e, 0, sizeof(unsigned long long)*3*(size_t)run, p->stream));
-        done += run;
-    }
+    if (wait_for_copy_stream(p)) return -1;
+    HIPCHK(hipEventRecord(p->ev_pass[0], p->stream));
+    if (ring_records_zero(p, p->la_rec, sizeof(unsigned long long)*3, E, first, n)) return -1;
     for (int i = 0; i < n; i++)
     {
         const int f = first + i, e = f % E;
@@ -961,21 +973,16 @@ static int lookahead_frames(h264e_hip_pool_t *p, int first, int n, int range, un
         if (range)
         {
             lookahead_search_args_t S;
-            S.a = A; S.field = p->la_field + (size_t)A.nblk*(size_t)e; S.range = range; S.nby = A.nblk/A.nbx;
+            S.a = A; S.field = p->la_field + (size_t)A.nblk*(size_t)e; S.range = range; S.nby = la_nby(p);
             bk_launch_lookahead_search(S, p->stream);
         }
         else bk_launch_lookahead(A, p->stream);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(p->ev_sc[1], p->stream));
-    for (int done = 0; done < n;)
-    {
-        const int e = (first + done) % E, run = imin_h(n - done, E - e);
-        HIPCHK(hipMemcpyAsync(rec + 3*(size_t)done, p->la_rec + 3*(size_t)e, sizeof(unsigned long long)*3*(size_t)run, hipMemcpyDeviceToHost, p->stream));
-        done += run;
-    }
+    HIPCHK(hipEventRecord(p->ev_pass[1], p->stream));
+    if (ring_records_read(p, rec, p->la_rec, sizeof(unsigned long long)*3, E, first, n)) return -1;
     HIPCHK(hipStreamSynchronize(p->stream));
-    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, p->ev_sc[0], p->ev_sc[1]));
+    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, p->ev_pass[0], p->ev_pass[1]));
     return 0;
 }
 
@@ -993,7 +1000,7 @@ extern "C" int h264e_hip_lookahead_read_field(h264e_hip_pool_t *p, int frame, vo
     if (!p || !dst || frame < 0) FAIL("lookahead_read_field: bad argument");
     if (!p->la_field) FAIL("lookahead_read_field: no frame has been analysed with a search");
     HIPCHK(hipSetDevice(p->device));
-    const size_t bytes = p->la_entry_bytes/LOOKAHEAD_BLOCK_BYTES*LOOKAHEAD_FIELD_CELL_BYTES;
+    const size_t bytes = (size_t)la_nbx(p)*(size_t)la_nby(p)*LOOKAHEAD_FIELD_CELL_BYTES;
     HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)p->la_field + bytes*(size_t)(frame % p->la_entries), bytes, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     return 0;
