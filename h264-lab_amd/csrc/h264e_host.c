@@ -1018,7 +1018,8 @@ int H264E_dev_memcpy(void *dst, const void *src, size_t bytes, int to_device) { 
  * control, reference pictures -- for the next call.  Input frames live in a ring of `resident` HBM slots, so a file of any
  * length streams through a bounded amount of host and device memory (encode_app --clip).
  */
-#define CLIP_KEEP_MAX 8         /* key frames of one stopped launch whose rows are kept */
+#define CLIP_KEEP_MAX 96        /* key frames of one stopped launch whose rows are kept: up to 64 led ones (h264e_pool.h H264E_LEAD_MAX_JOBS: small pictures,
+                                   a budget of 384 rows at 9+ rows each) and the whole ones in front of and between them */
 /* the progress of one frame pass: frames [0, done) are made, [ring_lo, done) still have their entries on the device,
  * which keeps `entries` of them, frame f in entry f % entries (0: the results live on the host only) */
 typedef struct { int done, ring_lo, entries; } clip_pass_t;
@@ -1097,6 +1098,7 @@ struct H264E_clip_tag
      * Collected when a launch has stopped cleanly (clip_keep_collect), used and forgotten by the next plan (clip_plan_launch); an entry
      * carries everything the rows' bits depend on besides the input picture. */
     int keep_on;                            /* H264E_KEEP_KEY_ROWS, read once at open */
+    int key_lead;                           /* H264E_KEY_LEAD, read with it: -1 the default budget, 0 off, N row workgroups */
     int nkeep;
     struct clip_keep { int frame, rows, qp, nslices, speed, denoised; } keep[CLIP_KEEP_MAX];
 };
@@ -1249,6 +1251,9 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     c->narrow_ok = (getenv("H264E_WIDE_WINDOW") || c->seq.nmb > 12000) ? 0 : 1;
     /* ... and so is H264E_KEEP_KEY_ROWS (0 = every launch encodes its key frames from row 0) */
     c->keep_on = getenv("H264E_KEEP_KEY_ROWS") ? atoi(getenv("H264E_KEEP_KEY_ROWS")) != 0 : 1;
+    /* ... and H264E_KEY_LEAD: the coming key frames' rows at the front of every launch's dispatch order (h264e_hip_set_key_lead: 0 off,
+     * N a budget of N row workgroups, unset the default budget).  Off without keeping: what a stopped launch led would be encoded again */
+    c->key_lead = !c->keep_on ? 0 : getenv("H264E_KEY_LEAD") ? imax(atoi(getenv("H264E_KEY_LEAD")), 0) : -1;
     /* ring of picture / result slots = frames per launch + 1.  Not bounded by residency: workgroups only wait for lower
      * block indices, so a launch larger than the GPU simply streams through it in order. */
     /* default: 96 frames per launch at 1080p and above; small pictures have short pipelines and cheap slots, so they get
@@ -1300,6 +1305,7 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
         }
         c->ring = imax(c->launch_base + 1, c->ring/2);
     }
+    h264e_hip_set_key_lead(c->pool, c->key_lead);
     if (par->keep_records)
     {
         c->rec_store = (h264e_hip_mbrec_t **)calloc((size_t)nframes, sizeof(*c->rec_store));
@@ -2100,6 +2106,7 @@ typedef struct
     int qp_task[CLIP_RC_DEPTH_MAX];         /* rate control: the QP the chain's frames were given */
     int hedge_level[CLIP_HEDGE_MAX], hedge_qp[CLIP_HEDGE_MAX];      /* the chain index of the frame a leaf encodes, and its QP */
     int kept_frames, kept_rows;             /* key frames that start below row 0 on what the stopped launch in front left of them, and those rows */
+    int led_frames, led_rows, led_last;     /* key frames whose rows the launch dispatched first (h264e_hip_last_lead), their rows, the last such task (-1: none) */
     int after_stop;                         /* follows a launch that was stopped (mis-speculation, rate-control miss): its first frame pays the refill */
     double t_submit, t_first, t_last;       /* submit; first and last frame consumed */
     double t_prev;                          /* ... and the one in front of the last */
@@ -2390,8 +2397,10 @@ static clip_step_t clip_take_frame(H264E_clip_t *c, clip_call_t *x, clip_launch_
  * is complete when its counter says so; the counters are read with one small copy per
  * key frame, after the drain, when no row moves any more (the finalizer of a stopped job could report the count instead, but it leaves as
  * soon as the verdict in front of its frame is void, at whatever row it follows then, and would under-count; and it would be a change to the
- * kernel; the copy costs some 20 us next to a relaunch of 8 ms).  Key frames are asked in stream order until one has no complete row: the frames behind it
- * were dispatched later still.  The launch's chain owns F different slots, so no other job of it wrote a key frame's slot. */
+ * kernel; the copy costs some 20 us next to a relaunch of 8 ms).  Key frames are asked in stream order until one behind the last LED
+ * one has no complete row: the frames behind it were dispatched later still (the led ones -- the nearest key frames, h264e_pool.h
+ * lead_jobs -- started together at the front of the order, so one of them without a row says nothing about the next).
+ * The launch's chain owns F different slots, so no other job of it wrote a key frame's slot. */
 static int clip_keep_collect(H264E_clip_t *c, const clip_launch_t *l)
 {
     int ti;
@@ -2404,7 +2413,7 @@ static int clip_keep_collect(H264E_clip_t *c, const clip_launch_t *l)
         int rows = 0;
         if (t->slice_type != SLICE_I) continue;
         if (h264e_hip_stream_rows_complete(c->pool, t->slot, &rows)) return -1;
-        if (rows <= 0) break;
+        if (rows <= 0) { if (ti > l->led_last) break; continue; }
         k->frame = l->n + ti; k->rows = rows; k->qp = t->qp; k->nslices = t->nslices; k->speed = t->speed; k->denoised = t->denoised;
         c->nkeep++;
     }
@@ -2463,8 +2472,8 @@ static void clip_debug_line(const H264E_clip_t *c, const clip_call_t *x, const c
     const double t_end = now_ms();
     const int nvalid = l->nvalid;
     const double t_first = nvalid ? l->t_first : t_end, t_last = nvalid ? l->t_last : t_end;     /* no frame of it was delivered: "first frame after" = when its verdict was in */
-    fprintf(stderr, "clip launch %d (first row %d, %s window, %lld far reads): %d frames in flight, %d valid, next %d; first frame after %.2f ms, then %.3f ms/frame, drained %.2f ms after the last, %d key rows kept in %d frames; ended by: %s%s\n",
-            x->stats.rounds, c->tasks[0].first_row, c->tasks[0].narrow_window ? "narrow" : "wide", x->far_reads, l->F, nvalid, c->next, t_first - l->t_submit, nvalid > 1 ? (t_last - t_first)/(nvalid - 1 + (nvalid < l->F)) : 0.0, t_end - t_last, l->kept_rows, l->kept_frames,
+    fprintf(stderr, "clip launch %d (first row %d, %s window, %lld far reads): %d frames in flight, %d valid, next %d; first frame after %.2f ms, then %.3f ms/frame, drained %.2f ms after the last, %d key rows kept in %d frames, led %d key frames, %d rows; ended by: %s%s\n",
+            x->stats.rounds, c->tasks[0].first_row, c->tasks[0].narrow_window ? "narrow" : "wide", x->far_reads, l->F, nvalid, c->next, t_first - l->t_submit, nvalid > 1 ? (t_last - t_first)/(nvalid - 1 + (nvalid < l->F)) : 0.0, t_end - t_last, l->kept_rows, l->kept_frames, l->led_frames, l->led_rows,
             k_clip_ended_by[l->step], l->nh ? " (+ hedge leaves)" : "");
 }
 
@@ -2513,6 +2522,7 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
         x.far_reads = 0;
         l.t_submit = now_ms();
         if (clip_prepass_denoise(c, l.limit) || h264e_hip_submit(c->pool, c->tasks)) return clip_end(c, &x, st, -1);
+        h264e_hip_last_lead(c->pool, &l.led_frames, &l.led_rows, &l.led_last);
         /* consume the frames in stream order while the launch is still running */
         do
         {

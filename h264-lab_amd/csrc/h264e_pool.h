@@ -205,6 +205,7 @@ struct h264e_hip_pool
     h264e_frame_task_t *tasks_dev;       /* ring of TASK_RING task arrays */
     h264e_frame_task_t *tasks_host;      /* [nchains] the task array of the submit being built (fill_task) */
     int *progress_all;
+    int *progress_img;                   /* host image of progress_all for a submit that keeps rows (reset_progress); allocated with the first one */
     int *errflag;
     unsigned long long *mb_counter;      /* device: macroblocks reconstructed by this pool's rows, delivered or not (h264e_hip_mb_counter) */
     uint32_t *order;                     /* device [nchains*(nmby+1)] (job << 16) | row in dispatch order of the current launch shape */
@@ -212,6 +213,9 @@ struct h264e_hip_pool
     uint32_t *order_host;                /* host copy being built (build_order) */
     int order_jobs, order_narrow, order_sliced;   /* the launch shape `order` holds: jobs, window geometry, row-band slices or not (-1: none yet) */
     size_t order_count;                  /* ... and its entries = the launch's workgroups (banded orders carry padding) */
+    uint8_t *order_led, *led;            /* [nchains] each: the led jobs `order` was built for (part of its cache key), and those of the launch being made (lead_jobs) */
+    int key_lead;                        /* h264e_hip_set_key_lead: -1 the default budget, 0 off, N that many row workgroups */
+    int led_jobs, led_rows, led_last;    /* the last launch's led key frames, their row workgroups, the last led job (-1: none) (h264e_hip_last_lead) */
     /* per chain slot: host-mapped result buffers the finalizer workgroups fill while the launch runs */
     h264e_hostdone_t *host_done;         /* [nchains] */
     uint8_t **host_rbsp;                 /* [nchains], each host_rbsp_cap bytes */
@@ -238,6 +242,7 @@ struct h264e_hip_pool
     int waves;                           /* wavefronts per macroblock row forced by H264E_WAVES (1 or 2); 0 = chosen per launch (h264e_hip_submit) */
     int test_upload_fail_at, async_uploads;     /* fault injection (H264E_TEST_KNOBS): the n-th asynchronous upload of this pool fails */
     int test_keep_rows_cap;              /* H264E_TEST_KNOBS: h264e_hip_stream_rows_complete reports at most this many rows; -1 = off */
+    int test_lead_resident;              /* H264E_TEST_KNOBS: the resident workgroups lead_jobs is told (small clips then have led key frames); -1 = off */
     double prof_mb_ms, prof_splice_ms;
     hipStream_t stream;
     hipStream_t copy_stream;             /* uploads that overlap with kernels on `stream` */
@@ -314,7 +319,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     if (p->abort_stream) (void)hipStreamSynchronize(p->abort_stream);
     device_release(p);
     host_free(p->hheap);
-    free(p->host_rbsp); free(p->host_mbrec); free(p->slot_launch); free(p->order_host); free(p->tasks_host);
+    free(p->host_rbsp); free(p->host_mbrec); free(p->slot_launch); free(p->order_host); free(p->order_led); free(p->led); free(p->progress_img); free(p->tasks_host);
     dev_free(p->heap);
     dev_free(p->den);
     dev_free(p->sc_rec);
@@ -343,9 +348,24 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
  * stream (lag*j + 2*row: a counting sort); ties go by j, then member, then row, so several streams are interleaved frame by frame.
  * Every workgroup still only waits for workgroups that precede it in this order (far reads: a bounded distance ahead).  Built for the
  * number of jobs a launch really has, so that a pool with many slots does not dispatch thousands of empty workgroups with every short
- * launch.  Pure: no pool, no runtime call, no environment.  `out` takes rows * (all jobs) words; -1 = out of host memory. */
+ * launch.  Pure: no pool, no runtime call, no environment.  `out` takes rows * (all jobs) words; -1 = out of host memory.
+ *
+ * LED jobs (`led`, one byte per launch job, NULL = none; lead_jobs chooses them): key frames further back in the launch.  A key frame's
+ * row reads no reference and no candidates; it waits for the row above it in its own job and for nothing else, so its ROW workgroups
+ * (row < rows - 1) sort at 2*row, as if the job stood at the launch's start, and take the wave slots that are empty while the chain in
+ * front fills the pipeline.  Its FINALIZER (row == rows - 1) keeps lag*j + 2*(rows - 1): it waits for the verdict of the frame in front,
+ * so it stays behind that frame's finalizer -- and exactly where it was.  Why the order is still safe:
+ * - a led row waits only for the row above it, which has the smaller key; led rows wait for no workgroup that is not led, so they
+ *   always run to their end and give their slots back, whatever stands behind them;
+ * - every other workgroup waits for what it waited for before; of those, the rows of a led job have moved FORWARD (a P row of job j + 1
+ *   and the led job's own finalizer find them earlier), everything else keeps its relative order;
+ * - the far-read bound (h264e_hip_group_join: a far read waits for a workgroup at most (12 - lag) keys ahead of its own, all of which
+ *   must fit the chip with it) counts workgroups between a P row and the rows of the frame it reads: taking led rows out of that
+ *   stretch only shortens it, and a far read into a led key frame looks backwards.  The led rows in front hold at most the budget
+ *   lead_jobs gave them, and only until they end.
+ * With no led job the order is the unled one, word for word. */
 #define H264E_ORDER_MAX_JOBS 65536     /* a job has 16 bits of the order word */
-static int order_by_start_step(uint32_t *out, int rows, int lag, const int *member_jobs, int nmembers)
+static int order_by_start_step(uint32_t *out, int rows, int lag, const int *member_jobs, int nmembers, const uint8_t *led)
 {
     int maxjobs = 0;
     for (int i = 0; i < nmembers; i++) if (member_jobs[i] > maxjobs) maxjobs = member_jobs[i];
@@ -353,12 +373,13 @@ static int order_by_start_step(uint32_t *out, int rows, int lag, const int *memb
     const int maxkey = lag*(maxjobs - 1) + 2*(rows - 1);
     int *start = (int *)calloc((size_t)maxkey + 2, sizeof(int));
     if (!start) return -1;
-    for (int i = 0; i < nmembers; i++) for (int j = 0; j < member_jobs[i]; j++) for (int r = 0; r < rows; r++) start[lag*j + 2*r + 1]++;
+    const auto key = [&](int job, int j, int r) { return (led && led[job] && r < rows - 1) ? 2*r : lag*j + 2*r; };
+    for (int i = 0, base = 0; i < nmembers; base += member_jobs[i], i++) for (int j = 0; j < member_jobs[i]; j++) for (int r = 0; r < rows; r++) start[key(base + j, j, r) + 1]++;
     for (int k = 0; k <= maxkey; k++) start[k + 1] += start[k];
     for (int j = 0; j < maxjobs; j++)
         for (int i = 0, base = 0; i < nmembers; base += member_jobs[i], i++)
             if (j < member_jobs[i])
-                for (int r = 0; r < rows; r++) out[start[lag*j + 2*r]++] = ((uint32_t)(base + j) << 16) | (uint32_t)r;
+                for (int r = 0; r < rows; r++) out[start[key(base + j, j, r)]++] = ((uint32_t)(base + j) << 16) | (uint32_t)r;
     free(start);
     return 0;
 }
@@ -375,8 +396,12 @@ static size_t order_capacity(const h264e_geom_t &G, int jobs) { return (size_t)j
  * are nobody's.  Without that the queues drift apart by a row or two per job, and because workgroups are dispatched strictly in index
  * order, an XCD whose resident workgroups all wait for rows of a queue that lags behind blocks the dispatch of exactly those rows:
  * measured as 2-4 % at 1080p with fixed bands, and as a dead launch ("bounded spin expired") once a launch is long enough -- 600 jobs
- * of 720p, CIF, or 1080p with 8 slices. */
-static size_t order_into_bands(const h264e_geom_t &G, int jobs, const uint32_t *in, int total, uint32_t *out)
+ * of 720p, CIF, or 1080p with 8 slices.
+ * A LED job (order_by_start_step; `led` NULL = none) has its rows long before its finalizer, in front of earlier jobs' rows.  It takes
+ * its `per` entries of every queue in two steps, so that the queues are equally long behind each: per - 1 entries with its rows (a band
+ * has at most per - 1 rows; the padding again behind the job's last row of the queue), and one entry with its finalizer -- the finalizer
+ * in the last band's queue, padding in the other seven. */
+static size_t order_into_bands(const h264e_geom_t &G, int jobs, const uint32_t *in, int total, uint32_t *out, const uint8_t *led)
 {
     const int bands = 8, per = (G.nmby + 7)/8 + 1;
     const size_t qlen = (size_t)per*jobs;
@@ -390,15 +415,23 @@ static size_t order_into_bands(const h264e_geom_t &G, int jobs, const uint32_t *
     for (int i = 0; i < total; i++)
     {
         const int row = (int)(in[i] & 0xffffu), x = (row >= G.nmby ? bands - 1 : imin_h(bands - 1, row*bands/G.nmby)) & 7;      /* band b -> XCD b % 8 */
-        want[8*(in[i] >> 16) + x]++;
+        if (!(led && led[in[i] >> 16] && row >= G.nmby)) want[8*(in[i] >> 16) + x]++;      /* (a led job's finalizer is a step of its own) */
     }
     for (int i = 0; i < total; i++)
     {
         const int row = (int)(in[i] & 0xffffu), jb = (int)(in[i] >> 16), x = (row >= G.nmby ? bands - 1 : imin_h(bands - 1, row*bands/G.nmby)) & 7;
+        const int own = (led && led[jb]) ? per - 1 : per;       /* entries per queue of the step this entry belongs to */
+        if (own < per && row >= G.nmby)
+        {
+            /* a led job's finalizer: one entry in every queue */
+            q[(size_t)x*qlen + cnt[x]] = in[i];
+            for (int y = 0; y < 8; y++) cnt[y]++;
+            continue;
+        }
         /* a picture of fewer than 8 rows leaves queues without a row of this job: they get the job's padding with its first entry */
-        if (row == 0) for (int y = 0; y < 8; y++) if (!want[8*jb + y]) cnt[y] += (size_t)per;
+        if (row == 0) for (int y = 0; y < 8; y++) if (!want[8*jb + y]) cnt[y] += (size_t)own;
         q[(size_t)x*qlen + cnt[x]++] = in[i];
-        if (++fill[8*jb + x] == want[8*jb + x]) cnt[x] += (size_t)(per - want[8*jb + x]);        /* the padding stays H264E_ORDER_PAD */
+        if (++fill[8*jb + x] == want[8*jb + x]) cnt[x] += (size_t)(own - want[8*jb + x]);        /* the padding stays H264E_ORDER_PAD */
     }
     for (size_t k = 0; k < qlen; k++) for (int x = 0; x < 8; x++) out[n++] = q[(size_t)x*qlen + k];
     free(q); free(fill); free(want);
@@ -408,7 +441,7 @@ static size_t order_into_bands(const h264e_geom_t &G, int jobs, const uint32_t *
 /* The order of a pool's own launch of `jobs` jobs into p->order_host / order_count: the one-member case of order_by_start_step, then the
  * bands.  bands = 0: none; 8: banded; -1: the default policy below, or what H264E_XCD_BANDS forces.  The per-XCD queues are sized for
  * eight bands, so any other count is refused.  Fails with the error text set. */
-static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced, int bands)
+static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced, int bands, const uint8_t *led)
 {
     const h264e_geom_t &G = p->G;
     const int rows = G.nmby + 1, total = jobs*rows, lag = narrow ? H264E_NARROW_FRAME_LAG : H264E_FRAME_LAG;
@@ -421,9 +454,9 @@ static int build_order(h264e_hip_pool_t *p, int jobs, int narrow, int sliced, in
     if (bands < 0) bands = getenv("H264E_XCD_BANDS") ? atoi(getenv("H264E_XCD_BANDS")) : (G.nmb >= 30000 && !sliced ? 8 : 0);
     if (bands != 0 && bands != 8) FAIL("dispatch order: %d XCD bands (H264E_XCD_BANDS): only 0 and 8 are supported", bands);
     uint32_t *tmp = bands ? (uint32_t *)malloc(sizeof(uint32_t)*(size_t)total) : p->order_host;
-    int rc = tmp ? order_by_start_step(tmp, rows, lag, &jobs, 1) : -1;
+    int rc = tmp ? order_by_start_step(tmp, rows, lag, &jobs, 1, led) : -1;
     p->order_count = (size_t)total;
-    if (!rc && bands && !(p->order_count = order_into_bands(G, jobs, tmp, total, p->order_host))) rc = -1;
+    if (!rc && bands && !(p->order_count = order_into_bands(G, jobs, tmp, total, p->order_host, led))) rc = -1;
     if (bands) free(tmp);
     if (rc) FAIL("out of host memory");
     return 0;
@@ -454,8 +487,10 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     G.fz_wait_all = getenv("H264E_FZ_WAIT_ALL") ? atoi(getenv("H264E_FZ_WAIT_ALL")) : 0;
     p->test_upload_fail_at = -1;
     p->test_keep_rows_cap = -1;
+    p->test_lead_resident = -1;
     if (knobs)
     {
+        if (getenv("H264E_TEST_LEAD_RESIDENT")) p->test_lead_resident = atoi(getenv("H264E_TEST_LEAD_RESIDENT"));
         if (getenv("H264E_TEST_KEEP_ROWS_CAP")) p->test_keep_rows_cap = atoi(getenv("H264E_TEST_KEEP_ROWS_CAP"));
         if (getenv("H264E_TEST_ROW_BYTES_PER_MB")) { const int b = atoi(getenv("H264E_TEST_ROW_BYTES_PER_MB"))/4; G.row_words = G.nmbx*(b > 1 ? b : 1); }
         if (getenv("H264E_TEST_SPIN_LIMIT")) G.spin_limit = (unsigned)atol(getenv("H264E_TEST_SPIN_LIMIT"));
@@ -579,8 +614,10 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
         FAIL("descriptor upload failed");
     }
     p->order_host = (uint32_t *)malloc(sizeof(uint32_t)*order_capacity(G, nchains));
-    if (!p->order_host) { h264e_hip_pool_destroy(p); FAIL("out of host memory"); }
+    p->order_led = (uint8_t *)calloc((size_t)nchains, 1); p->led = (uint8_t *)calloc((size_t)nchains, 1);
+    if (!p->order_host || !p->order_led || !p->led) { h264e_hip_pool_destroy(p); FAIL("out of host memory"); }
     p->order_jobs = -1;
+    p->key_lead = -1; p->led_last = -1;
     *pool = p;
     return 0;
 }
@@ -1781,6 +1818,45 @@ static int pick_variant(const launch_shape_t &s, int jobs, int nmby)
     if (jobs*(nmby + 1) <= H264E_RESIDENT_WG_V3) return 3;
     return 2;
 }
+/* workgroups of a variant that the chip holds at once */
+static int variant_resident(int variant) { return variant == 3 ? H264E_RESIDENT_WG_V3 : variant == 4 ? 2048 : H264E_RESIDENT_WG_V2; }
+
+/* Which jobs of a launch are LED (order_by_start_step): key frames behind their member's first job whose row workgroups go to the front
+ * of the dispatch order.  What they encode before the launch is stopped is not lost -- the clip encoder keeps a key frame's complete
+ * rows for the next launch (h264e_host.c clip_keep_collect) --, so the slots that are empty while a restarted chain refills the
+ * pipeline go to them.  The launch's jobs are member after member (member_jobs[i] each); key[job] != 0: an active I job that waits for no
+ * other job; first_row[job]: the rows it keeps already.  Candidates in stream order, the nearest first (by job of the member, then
+ * member): a frame that is whole (first_row == nmby) costs nothing and is passed over; the others are led while their row workgroups
+ * (nmby - first_row each) fit `budget`, and the first one that does not fit ends it, so the led frames are always the nearest ones.
+ * Nothing is led: with hedge leaves in the launch (`tree`: nothing is kept there), in an all-intra launch, with budget 0, and where the
+ * whole grid is resident anyway (every workgroup is dispatched at once and the order is moot).  Pure: no pool, no environment.
+ * Returns the led jobs, their mask in led[], their row workgroups in *rows_out, the last of them in *last_out (-1: none). */
+#define H264E_LEAD_MAX_JOBS 64         /* (h264e_host.c CLIP_KEEP_MAX: what a stopped launch can hand on) */
+static int lead_jobs(uint8_t *led, const int *member_jobs, int nmembers, const uint8_t *key, const int *first_row, int nmby, int tree, int all_intra,
+                     int resident, int budget, int *rows_out, int *last_out)
+{
+    int jobs = 0, maxjobs = 0, n = 0, rows = 0, last = -1, full = 0;
+    for (int i = 0; i < nmembers; i++) { jobs += member_jobs[i]; if (member_jobs[i] > maxjobs) maxjobs = member_jobs[i]; }
+    memset(led, 0, (size_t)jobs);
+    if (!tree && !all_intra && budget > 0 && (long long)jobs*(nmby + 1) > resident)
+        for (int j = 1; j < maxjobs && !full; j++)
+            for (int i = 0, base = 0; i < nmembers && !full; base += member_jobs[i], i++)
+            {
+                const int job = base + j;
+                if (j >= member_jobs[i] || !key[job]) continue;
+                const int fr = first_row[job] > 0 ? first_row[job] : 0, cost = nmby - fr;
+                if (cost <= 0) continue;
+                if (rows + cost > budget || n >= H264E_LEAD_MAX_JOBS) { full = 1; break; }
+                led[job] = 1; n++; rows += cost; last = job;
+            }
+    if (rows_out) *rows_out = rows;
+    if (last_out) *last_out = last;
+    return n;
+}
+/* the budget of a launch: a quarter of the variant's resident workgroups (five 1080p key frames from row 0), or what the pool was told */
+static int lead_budget(int key_lead, int resident) { return key_lead >= 0 ? key_lead : resident/4; }
+/* a job that lead_jobs may lead */
+static int lead_candidate(const h264e_frame_task_t &t) { return t.active && t.slice_type == 2 && !t.dep_progress; }
 
 /* the macroblock kernel on `stream`, between two events when they are given; what the launch itself reports */
 static hipError_t launch_mb(const h264e_geom_t &G, int narrow, int variant, int jobs, size_t nblocks, const h264e_frame_task_t *tasks, const uint32_t *order,
@@ -1818,7 +1894,7 @@ static int group_grow(h264e_hip_group_t *g, void **buf, size_t *cap, size_t need
 
 /* ONE launch for the pending members of one window geometry (narrow / wide: different kernels), into td / od: the jobs member after
  * member, the shapes merged -- two or more streams in the grid are parallel work like slices are (a group of one: what solo_launch
- * would decide) --, the dispatch orders interleaved (order_by_start_step).  The four-wave latency variant (512 resident workgroups)
+ * would decide) --, the dispatch orders interleaved (order_by_start_step) with the coming key frames in front (lead_jobs).  The four-wave latency variant (512 resident workgroups)
  * must never carry a grid that does not fit the chip: pick_variant sees the merged job count.  Returns the jobs launched, -1 on failure. */
 static int group_launch_geometry(h264e_hip_group_t *g, int narrow, h264e_frame_task_t *td, uint32_t *od)
 {
@@ -1839,7 +1915,9 @@ static int group_launch_geometry(h264e_hip_group_t *g, int narrow, h264e_frame_t
     if (m.jobs >= H264E_ORDER_MAX_JOBS) return group_fail(g, "group launch: too many jobs");
     h264e_frame_task_t *th = (h264e_frame_task_t *)malloc(sizeof(h264e_frame_task_t)*(size_t)m.jobs);
     uint32_t *oh = (uint32_t *)malloc(sizeof(uint32_t)*total);
-    if (!th || !oh || order_by_start_step(oh, G.nmby + 1, narrow ? H264E_NARROW_FRAME_LAG : H264E_FRAME_LAG, jobs, n)) rc = group_fail(g, "out of host memory");
+    uint8_t *led = (uint8_t *)calloc((size_t)m.jobs, 2);
+    int *fr = (int *)malloc(sizeof(int)*(size_t)m.jobs);
+    if (!th || !oh || !led || !fr) rc = group_fail(g, "out of host memory");
     /* the members prepared their slots (progress counters, ...) on their own streams: the launch waits for all of that */
     for (int i = 0, b = 0; i < n && !rc; b += jobs[i++])
     {
@@ -1847,12 +1925,34 @@ static int group_launch_geometry(h264e_hip_group_t *g, int narrow, h264e_frame_t
         memcpy(th + b, g->member[idx[i]].tasks, sizeof(h264e_frame_task_t)*(size_t)jobs[i]);
         if (hipEventRecord(p->ev_prep, p->stream) != hipSuccess || hipStreamWaitEvent(g->stream, p->ev_prep, 0) != hipSuccess) rc = group_fail(g, "group launch: cannot order the launch behind a member's stream");
     }
+    const int variant = pick_variant(m, m.jobs, G.nmby);
+    if (!rc)
+    {
+        /* led key frames (lead_jobs): the budget is what the members' far-read windows leave of the 1400 workgroups h264e_hip_group_join
+         * counts on, at most the solo budget; a member that switched leading off switches it off for the launch, the smallest explicit
+         * budget holds */
+        const int window = (12 - H264E_NARROW_FRAME_LAG)*(G.nmby + 1)/2, left = 1400 - n*(window > 0 ? window : 1);
+        uint8_t *key = led + m.jobs;
+        int key_lead = -1;
+        for (int i = 0; i < n; i++) { const int k = g->member[idx[i]].pool->key_lead; if (k >= 0 && (key_lead < 0 || k < key_lead)) key_lead = k; }
+        for (int j = 0; j < m.jobs; j++) { key[j] = (uint8_t)lead_candidate(th[j]); fr[j] = th[j].first_row; }
+        const int budget = imin_h(lead_budget(key_lead, variant_resident(variant)), left > 0 ? left : 0);
+        (void)lead_jobs(led, jobs, n, key, fr, G.nmby, m.tree, m.all_intra, variant_resident(variant), budget, 0, 0);
+        for (int i = 0, b = 0; i < n; b += jobs[i++])
+        {
+            h264e_hip_pool_t *p = g->member[idx[i]].pool;
+            p->led_jobs = p->led_rows = 0; p->led_last = -1;
+            for (int j = 0; j < jobs[i]; j++) if (led[b + j]) { p->led_jobs++; p->led_rows += G.nmby - (fr[b + j] > 0 ? fr[b + j] : 0); p->led_last = j; }
+        }
+        if (order_by_start_step(oh, G.nmby + 1, narrow ? H264E_NARROW_FRAME_LAG : H264E_FRAME_LAG, jobs, n, led)) rc = group_fail(g, "out of host memory");
+    }
+    free(led); free(fr);
     if (!rc && (hipMemcpyAsync(td, th, sizeof(h264e_frame_task_t)*(size_t)m.jobs, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
                 hipMemcpyAsync(od, oh, sizeof(uint32_t)*total, hipMemcpyHostToDevice, g->stream) != hipSuccess)) rc = group_fail(g, "group launch: task upload failed");
     free(th); free(oh);            /* pageable sources: staged before the calls return */
     if (!rc)
     {
-        const hipError_t le = launch_mb(G, narrow, pick_variant(m, m.jobs, G.nmby), m.jobs, total, td, od, g->ev_t0[narrow], g->ev_t1[narrow], g->stream);
+        const hipError_t le = launch_mb(G, narrow, variant, m.jobs, total, td, od, g->ev_t0[narrow], g->ev_t1[narrow], g->stream);
         if (le != hipSuccess) rc = group_fail(g, "group launch: %s", hipGetErrorString(le));
         else g->timed[narrow] = 1;
     }
@@ -2113,33 +2213,55 @@ static int fill_task(h264e_hip_pool_t *p, const h264e_hip_task_t *tasks, int c, 
 static int reset_progress(h264e_hip_pool_t *p, const h264e_frame_task_t *host)
 {
     const h264e_geom_t &G = p->G;
-    hipError_t e = hipMemsetAsync(p->progress_all, 0, sizeof(int)*2*(size_t)p->nchains*G.nmby, p->stream);
-    for (int c = 0; c < p->nchains && e == hipSuccess; c++)
-        if (host[c].active && host[c].first_row > 0)
-        {
-            int *done = (int *)malloc(sizeof(int)*(size_t)host[c].first_row), *progress = p->chains_host[host[c].chain].progress;
-            if (!done) { e = hipErrorOutOfMemory; break; }
-            for (int r = 0; r < host[c].first_row; r++) done[r] = G.nmbx + 1;
-            e = hipMemcpyAsync(progress, done, sizeof(int)*(size_t)host[c].first_row, hipMemcpyHostToDevice, p->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(progress + G.nmby, done, sizeof(int)*(size_t)host[c].first_row, hipMemcpyHostToDevice, p->stream);
-            free(done);         /* pageable source: staged before the call returns */
-        }
+    const size_t words = 2*(size_t)p->nchains*G.nmby;
+    int kept = 0;
+    for (int c = 0; c < p->nchains; c++) kept += host[c].active && host[c].first_row > 0;
+    hipError_t e;
+    if (!kept) e = hipMemsetAsync(p->progress_all, 0, sizeof(int)*words, p->stream);
+    else
+    {
+        /* one image of all counters and ONE copy: with led key frames a launch of a small picture starts dozens of jobs below row 0, and
+         * two small copies for each of them were 0.5 ms of host time per launch (352x288 x 3000) */
+        if (!p->progress_img) p->progress_img = (int *)malloc(sizeof(int)*words);
+        int *img = p->progress_img;
+        if (!img) FAIL("out of host memory");
+        memset(img, 0, sizeof(int)*words);
+        for (int c = 0; c < p->nchains; c++)
+            if (host[c].active && host[c].first_row > 0)
+            {
+                int *progress = img + (size_t)host[c].chain*2*G.nmby;       /* = chains_host[chain].progress - progress_all */
+                for (int r = 0; r < host[c].first_row; r++) progress[r] = progress[G.nmby + r] = G.nmbx + 1;
+            }
+        e = hipMemcpyAsync(p->progress_all, img, sizeof(int)*words, hipMemcpyHostToDevice, p->stream);     /* (the image is the pool's: written again only by the next submit with kept rows, which follows a sync) */
+    }
     if (e != hipSuccess) FAIL("progress reset: %s", hipGetErrorString(e));
     return 0;
 }
 
 /* a pool's own launch of the uploaded jobs `slot`: the dispatch order is cached for the launch's shape (jobs up to the last active
- * one; window geometry; sliced or not), the launch is timed when the pool is profiled */
-static int solo_launch(h264e_hip_pool_t *p, const h264e_frame_task_t *slot, const launch_shape_t &s)
+ * one; window geometry; sliced or not; which jobs are led), the launch is timed when the pool is profiled.  `host`: the jobs as uploaded
+ * to `slot`.  The led set (lead_jobs) is part of the cache key as the set itself -- a led job's first_row matters only where it decides
+ * whether the job is in the set --, so a launch whose key frames stand elsewhere builds and uploads its order again: 44 KB for 160 jobs
+ * of 1080p, some 0.1 ms of host time per launch next to the 6-12 ms a relaunch takes to deliver its first frame. */
+static int solo_launch(h264e_hip_pool_t *p, const h264e_frame_task_t *slot, const h264e_frame_task_t *host, const launch_shape_t &s)
 {
-    const int pe = p->ev_pending;
-    if (s.jobs != p->order_jobs || s.narrow != p->order_narrow || s.sliced != p->order_sliced)
+    const int pe = p->ev_pending, variant = pick_variant(s, s.jobs, p->G.nmby), resident = p->test_lead_resident >= 0 ? p->test_lead_resident : variant_resident(variant);
     {
-        if (build_order(p, s.jobs, s.narrow, s.sliced, -1)) return -1;
+        uint8_t *key = (uint8_t *)malloc((size_t)s.jobs);
+        int *fr = (int *)malloc(sizeof(int)*(size_t)s.jobs);
+        if (!key || !fr) { free(key); free(fr); FAIL("out of host memory"); }
+        for (int j = 0; j < s.jobs; j++) { key[j] = (uint8_t)lead_candidate(host[j]); fr[j] = host[j].first_row; }
+        p->led_jobs = lead_jobs(p->led, &s.jobs, 1, key, fr, p->G.nmby, s.tree, s.all_intra, resident, lead_budget(p->key_lead, resident), &p->led_rows, &p->led_last);
+        free(key); free(fr);
+    }
+    if (s.jobs != p->order_jobs || s.narrow != p->order_narrow || s.sliced != p->order_sliced || memcmp(p->led, p->order_led, (size_t)s.jobs))
+    {
+        if (build_order(p, s.jobs, s.narrow, s.sliced, -1, p->led_jobs ? p->led : 0)) return -1;
         HIPCHK(hipMemcpyAsync(p->order, p->order_host, sizeof(uint32_t)*p->order_count, hipMemcpyHostToDevice, p->stream));     /* pageable: staged before the call returns */
         p->order_jobs = s.jobs; p->order_narrow = s.narrow; p->order_sliced = s.sliced;
+        memcpy(p->order_led, p->led, (size_t)s.jobs);
     }
-    const hipError_t e = launch_mb(p->G, s.narrow, pick_variant(s, s.jobs, p->G.nmby), s.jobs, p->order_count, slot, p->order,
+    const hipError_t e = launch_mb(p->G, s.narrow, variant, s.jobs, p->order_count, slot, p->order,
                                    p->profile ? p->ev[pe][0] : 0, p->profile ? p->ev[pe][1] : 0, p->stream);
     if (e != hipSuccess) FAIL("macroblock kernel launch: %s", hipGetErrorString(e));
     if (p->profile)
@@ -2172,7 +2294,17 @@ extern "C" int h264e_hip_submit(h264e_hip_pool_t *p, const h264e_hip_task_t *tas
     if (e != hipSuccess) FAIL("task upload: %s", hipGetErrorString(e));
     if (reset_progress(p, host)) return -1;
     /* member of a launch group: the launch is merged with the other members' and the variant is chosen from the MERGED grid */
-    return p->group ? group_submit(p, host, s) : solo_launch(p, slot, s);
+    return p->group ? group_submit(p, host, s) : solo_launch(p, slot, host, s);
+}
+
+/* Leading the coming key frames (lead_jobs): budget < 0 the default budget, 0 off, N that many row workgroups per launch.  _last_lead:
+ * what the pool's last submit led -- key frames, their row workgroups, and the last led job of the submit (-1: none). */
+extern "C" void h264e_hip_set_key_lead(h264e_hip_pool_t *p, int budget) { if (p) p->key_lead = budget < 0 ? -1 : budget; }
+extern "C" void h264e_hip_last_lead(h264e_hip_pool_t *p, int *jobs, int *rows, int *last)
+{
+    if (jobs) *jobs = p ? p->led_jobs : 0;
+    if (rows) *rows = p ? p->led_rows : 0;
+    if (last) *last = p ? p->led_last : -1;
 }
 
 /* ---- results: every job's finalizer exports them to the host-mapped mirrors of its chain slot */
@@ -2318,7 +2450,7 @@ extern "C" int h264e_hip_rewind_frame(h264e_hip_pool_t *p, int chain)
 extern "C" long h264e_hip_selftest_order(h264e_hip_pool_t *p, int jobs, int narrow, int banded, uint32_t *out, size_t cap)
 {
     if (!p || jobs < 1 || jobs > p->nchains || !out) { snprintf(g_err, sizeof(g_err), "selftest_order: bad argument"); return -1; }
-    const int rc = build_order(p, jobs, narrow, 0, banded ? 8 : 0);
+    const int rc = build_order(p, jobs, narrow, 0, banded ? 8 : 0, 0);
     p->order_jobs = -1;
     if (rc) return -1;
     memcpy(out, p->order_host, sizeof(uint32_t)*(p->order_count < cap ? p->order_count : cap));
@@ -2333,11 +2465,46 @@ extern "C" long h264e_hip_selftest_merged_order(int rows, int lag, const int *me
     for (int i = 0; member_jobs && i < nmembers; i++) jobs += member_jobs[i] > 0 ? (size_t)member_jobs[i] : H264E_ORDER_MAX_JOBS;
     if (rows < 1 || rows > 65536 || lag < 1 || !member_jobs || nmembers < 1 || !out || jobs >= H264E_ORDER_MAX_JOBS) { snprintf(g_err, sizeof(g_err), "selftest_merged_order: bad argument"); return -1; }
     uint32_t *ord = (uint32_t *)malloc(sizeof(uint32_t)*jobs*(size_t)rows);
-    const int rc = ord ? order_by_start_step(ord, rows, lag, member_jobs, nmembers) : -1;
+    const int rc = ord ? order_by_start_step(ord, rows, lag, member_jobs, nmembers, 0) : -1;
     if (!rc) memcpy(out, ord, sizeof(uint32_t)*(jobs*(size_t)rows < cap ? jobs*(size_t)rows : cap));
     free(ord);
     if (rc) { snprintf(g_err, sizeof(g_err), "out of host memory"); return -1; }
     return (long)(jobs*(size_t)rows);
+}
+
+/* test hook: lead_jobs and the order it gives, for a launch that merges `nmembers` streams of member_jobs[i] jobs of nmby rows each (one
+ * member: a pool's own launch).  key / first_row: per launch job, member after member; tree / all_intra: the launch's shape; resident:
+ * the workgroups of its variant that the chip holds; budget: row workgroups that may be led.  banded != 0: through the XCD bands (one
+ * member only).  led_out (may be NULL) gets the led set, one byte per job; out at most cap of the order's entries.  Returns the number
+ * of entries, -1 on failure. */
+extern "C" long h264e_hip_selftest_lead_order(int nmby, int lag, const int *member_jobs, int nmembers, const uint8_t *key, const int *first_row,
+                                              int tree, int all_intra, int resident, int budget, int banded, uint32_t *out, size_t cap, uint8_t *led_out)
+{
+    size_t jobs = 0;
+    for (int i = 0; member_jobs && i < nmembers; i++) jobs += member_jobs[i] > 0 ? (size_t)member_jobs[i] : H264E_ORDER_MAX_JOBS;
+    if (nmby < 1 || nmby >= 65535 || lag < 1 || !member_jobs || nmembers < 1 || !key || !first_row || !out || jobs >= H264E_ORDER_MAX_JOBS || (banded && nmembers != 1))
+    { snprintf(g_err, sizeof(g_err), "selftest_lead_order: bad argument"); return -1; }
+    const size_t rows = (size_t)nmby + 1, total = jobs*rows;
+    h264e_geom_t G;
+    memset(&G, 0, sizeof(G));
+    G.nmby = nmby;
+    const size_t room = banded ? order_capacity(G, (int)jobs) : total;
+    uint32_t *ord = (uint32_t *)malloc(sizeof(uint32_t)*total), *res = banded ? (uint32_t *)malloc(sizeof(uint32_t)*room) : ord;
+    uint8_t *led = (uint8_t *)malloc(jobs);
+    size_t n = total;
+    int rc = (ord && res && led) ? 0 : -1;
+    if (!rc)
+    {
+        const int nled = lead_jobs(led, member_jobs, nmembers, key, first_row, nmby, tree, all_intra, resident, budget, 0, 0);
+        rc = order_by_start_step(ord, (int)rows, lag, member_jobs, nmembers, nled ? led : 0);
+        if (!rc && banded && !(n = order_into_bands(G, (int)jobs, ord, (int)total, res, nled ? led : 0))) rc = -1;
+    }
+    if (!rc) memcpy(out, res, sizeof(uint32_t)*(n < cap ? n : cap));
+    if (!rc && led_out) memcpy(led_out, led, jobs);
+    if (banded) free(res);
+    free(ord); free(led);
+    if (rc) { snprintf(g_err, sizeof(g_err), "out of host memory"); return -1; }
+    return (long)n;
 }
 
 extern "C" int h264e_hip_selftest_nal_escape(h264e_hip_pool_t *p, const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap, uint32_t *out_n)

@@ -222,6 +222,12 @@ int  h264e_hip_stream_abort(h264e_hip_pool_t *pool);
 /* macroblock rows of `slot`, from the top, that the last launch completed (after h264e_hip_sync, before the next submit): what a task
  * for the same frame in the same slot may pass as first_row -- up to all of them, then only the job's finalizer runs */
 int  h264e_hip_stream_rows_complete(h264e_hip_pool_t *pool, int slot, int *rows);
+/* Key frames behind a launch's first job have their row workgroups dispatched FIRST, as far as a budget of row workgroups goes (DESIGN.md
+ * 5; what they encode before a stop is what h264e_hip_stream_rows_complete reports afterwards).  budget < 0: the default (a quarter of
+ * the kernel variant's resident workgroups), 0: off, N: that many.  _last_lead: what the pool's last submit led -- key frames, their
+ * row workgroups, the last led job (-1: none); any pointer may be NULL. */
+void h264e_hip_set_key_lead(h264e_hip_pool_t *pool, int budget);
+void h264e_hip_last_lead(h264e_hip_pool_t *pool, int *jobs, int *rows, int *last);
 int  h264e_hip_busy(h264e_hip_pool_t *pool);
 /* reconstructed picture of the chain's last frame, coded size, packed I420 */
 int  h264e_hip_read_recon(h264e_hip_pool_t *pool, int chain, uint8_t *dst);
@@ -285,6 +291,13 @@ long h264e_hip_selftest_order(h264e_hip_pool_t *pool, int jobs, int narrow, int 
 /* test hook: the unbanded order of a launch that merges several streams (a launch group): member i contributes member_jobs[i] jobs of
  * `rows` workgroups, numbered member after member; entries sorted by lag*j + 2*row, ties by j, then member, then row */
 long h264e_hip_selftest_merged_order(int rows, int lag, const int *member_jobs, int nmembers, uint32_t *out, size_t cap);
+/* test hook: which key frames of such a launch are led -- their row workgroups at the front of the order (h264e_pool.h lead_jobs) -- and
+ * the order that gives.  key / first_row: per launch job, member after member (key != 0: an I job that waits for no other job; the rows
+ * it already has); tree / all_intra: the launch carries hedge leaves / nothing but I jobs; resident: workgroups of the launch's kernel
+ * variant that the chip holds; budget: row workgroups that may be led; banded != 0: through the XCD bands (one member); led_out, when
+ * not NULL, gets one byte per job */
+long h264e_hip_selftest_lead_order(int nmby, int lag, const int *member_jobs, int nmembers, const uint8_t *key, const int *first_row,
+                                   int tree, int all_intra, int resident, int budget, int banded, uint32_t *out, size_t cap, uint8_t *led_out);
 int  h264e_hip_selftest_nal_escape(h264e_hip_pool_t *pool, const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap, uint32_t *out_n);
 /* test hook: one wave-level stage of the macroblock pipeline on caller-supplied operands (h264e_kernels.hip stage_selftest lists
  * the stages and their operand layouts; tests/test_stages.py and tests/test_stage_edges.py compare them with the reference's own functions) */
