@@ -486,6 +486,10 @@ def load(path=None):
     L.H264E_clip_lookahead_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.H264E_clip_set_lookahead_search.argtypes = [C.c_void_p, C.c_int]
     L.H264E_clip_read_lookahead_motion.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.H264E_clip_set_lookahead_tree.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.H264E_clip_read_lookahead_tree.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.H264E_clip_read_lookahead_tree_sums.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.H264E_clip_lookahead_tree_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.H264E_clip_set_denoise_motion.argtypes = [C.c_void_p, C.c_int]
     L.H264E_clip_read_denoised.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.H264E_clip_read_denoise_motion.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -689,7 +693,7 @@ class ClipEncoder:
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
                  clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0,
                  color=None, fps=None, quality=None, qp_schedule=None, abr_kbps=0, lookahead=0, qp_range=(0, 0), lookahead_search=0,
-                 denoise_motion=0):
+                 denoise_motion=0, lookahead_tree=0):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
         self._ssd = self._ssim = None           # the registered metric arrays [nframes][3], owned here while registered
@@ -719,6 +723,8 @@ class ClipEncoder:
                 self.set_lookahead_search(lookahead_search)
             if denoise_motion:
                 self.set_denoise_motion(denoise_motion)
+            if lookahead_tree:
+                self.set_lookahead_tree(*(lookahead_tree if isinstance(lookahead_tree, (tuple, list)) else (lookahead_tree,)))
         except H264EError:
             self.close()
             raise
@@ -868,6 +874,41 @@ class ClipEncoder:
             raise _err(self.L, "H264E_clip_read_lookahead_motion")
         mv = np.stack([(cells & 0xff).astype(np.uint8).view(np.int8), ((cells >> 8) & 0xff).astype(np.uint8).view(np.int8)], axis=-1)
         return mv, (cells >> 16).astype(np.uint16)
+
+    def set_lookahead_tree(self, strength, ahead=-1):
+        """The cost tree over the lookahead's motion field (H264E_clip_set_lookahead_tree): per-frame QP offsets inside a window, strength
+        in quarter QP steps per doubling of a frame's importance (0 = off, 1..16), ahead = frames behind a window that its tree starts
+        from (0..255, below 0 = the default); needs set_lookahead and set_lookahead_search(1..8) first; only while the clip stands at
+        frame 0."""
+        if self.L.H264E_clip_set_lookahead_tree(self.c, int(strength), int(ahead)):
+            raise _err(self.L, "H264E_clip_set_lookahead_tree")
+
+    def read_lookahead_tree(self, frame):
+        """uint64 [nby, nbx]: what the blocks of a frame of a planned window received from the frames behind it
+        (H264E_clip_read_lookahead_tree), as long as the map is in the device's ring"""
+        nbx, nby = C.c_int(), C.c_int()
+        self.L.H264E_clip_read_lookahead_tree(self.c, -1, None, C.byref(nbx), C.byref(nby))
+        cells = np.zeros((nby.value, nbx.value), np.uint64)
+        if self.L.H264E_clip_read_lookahead_tree(self.c, int(frame), cells.ctypes.data, None, None):
+            raise _err(self.L, "H264E_clip_read_lookahead_tree")
+        return cells
+
+    def read_lookahead_tree_sums(self):
+        """(S uint64, delta int8, base_qp uint8) of the frames encoded so far (H264E_clip_read_lookahead_tree_sums): what each frame
+        received in the run that planned its window, the QP offset that became, and its window's base QP"""
+        nxt = C.c_int()
+        self.L.H264E_clip_position(self.c, C.byref(nxt), None)
+        n = nxt.value
+        s, d, q = np.zeros(n, np.uint64), np.zeros(n, np.int8), np.zeros(n, np.uint8)
+        if self.L.H264E_clip_read_lookahead_tree_sums(self.c, 0, n, s.ctypes.data, d.ctypes.data, q.ctypes.data):
+            raise _err(self.L, "H264E_clip_read_lookahead_tree_sums")
+        return s, d, q
+
+    def lookahead_tree_time(self):
+        """(HIP-event milliseconds inside the cost tree's kernel launches since open, frame steps they made)"""
+        ms, n = C.c_double(), C.c_longlong()
+        self.L.H264E_clip_lookahead_tree_time(self.c, C.byref(ms), C.byref(n))
+        return ms.value, n.value
 
     def lookahead_time(self):
         """(HIP-event milliseconds inside the cost pass' kernel launches since open, frames they analysed)"""

@@ -33,6 +33,9 @@
  * a..b, X kbps for a target of K".  Both belong to the clip path and are refused like --keyframes / --scenecut.
  * --lookahead-search R (1..8; 0 = off) lets that controller's cost pass search +-R half-resolution samples per block
  * (H264E_clip_set_lookahead_search); it is refused without --lookahead.
+ * --lookahead-tree S[,A] (S 1..16 quarter QP steps per doubling, 0 = off; A 0..255 frames ahead, default min(W, ring - W)) gives the frames
+ * of a window their own QPs from a cost tree over the search's motion field (H264E_clip_set_lookahead_tree); it is refused without
+ * --lookahead-search.
  * --denoise-motion M (1 = the search's vectors, 2 = refined; 0 = off) filters every frame with this encoder's motion-compensated temporal
  * denoiser in front of the encoder (H264E_clip_set_denoise_motion); it reads the search's motion field and is refused without
  * --lookahead-search.  --denoise alone, the reference's filter, stays refused.
@@ -53,6 +56,7 @@ static struct
     char qp_file[1024];                 /* --qpfile: one QP per frame */
     int lookahead_search;               /* --lookahead-search R */
     int denoise_motion;                 /* --denoise-motion M */
+    int tree, tree_ahead;               /* --lookahead-tree S[,A] (A not given: -1, the default) */
     int have_qp_file, lookahead, lookahead_kbps;      /* --lookahead W (with --kbps K: the window controller; 0 = not given, -1 = the default window) */
     int matrix, full_range, fps_num, fps_den;   /* --colour, --fps (all 0: nothing is signalled) */
     int unsupported;                    /* a reference option this encoder refuses was given: no stream is written, exit 1 */
@@ -114,6 +118,7 @@ static void parse_long(const char *p, const char *val)
     }
     else if (starts("qpfile", p)) { snprintf(cmd.qp_file, sizeof(cmd.qp_file), "%s", v); cmd.have_qp_file = 1; }
     else if (starts("lookahead-search", p)) cmd.lookahead_search = atoi(v);
+    else if (starts("lookahead-tree", p)) { cmd.tree = atoi(v); cmd.tree_ahead = strchr(v, ',') ? atoi(strchr(v, ',') + 1) : -1; }
     else if (starts("lookahead", p)) cmd.lookahead = atoi(v) > 0 ? atoi(v) : -1;
     else if (starts("scenecut", p)) cmd.scenecut = atoi(v) > 0 ? atoi(v) : H264E_SCENECUT_DEFAULT;
     else if (starts("gop", p)) cmd.gop = atoi(v);
@@ -172,6 +177,7 @@ static int read_cmdline(int argc, char **argv)
                "    --qpfile <f>   one QP (10..51) per frame, whitespace separated   (clip path only)\n"
                "    --kbps <n> --lookahead <frames|x>   this encoder's own window rate control instead of the reference's   (clip path only)\n"
                "    --lookahead-search <r>   with --lookahead: motion search of +-r (1..8) half-resolution samples in its cost pass\n"
+               "    --lookahead-tree <s>[,<a>]   with --lookahead-search: per-frame QPs from a cost tree over its motion field, s (1..16) quarter QP steps per doubling, a frames ahead\n"
                "    --denoise-motion 1|2   with --lookahead-search: motion-compensated temporal denoiser from its vectors (2: refined by one sample)\n"
                "    --colour bt709|bt601|bt709-full|bt601-full  --fps <n[/d]>   (signalled in the SPS; the samples are not touched)\n");
         return 0;
@@ -562,6 +568,14 @@ static int run_clip_mode(FILE *fout, int w, int h, long long total)
             cmd.lookahead = W;
             if (cmd.lookahead_search && H264E_clip_set_lookahead_search(s->clip, cmd.lookahead_search)) { printf("ERROR: --lookahead-search: %s\n", H264E_last_error()); goto out; }
             if (cmd.denoise_motion && H264E_clip_set_denoise_motion(s->clip, cmd.denoise_motion)) { printf("ERROR: --denoise-motion: %s\n", H264E_last_error()); goto out; }
+            if (cmd.tree)
+            {
+                /* the horizon's last frame must fit the input ring together with the staging chunk that carries it */
+                const int room = s->par.resident_frames < n ? s->par.resident_frames - s->chunk + 1 - W : n - W;
+                const int ahead = cmd.tree_ahead >= 0 ? cmd.tree_ahead : room < 0 ? 0 : room < W ? room : W;
+                if (s->par.resident_frames < n && ahead <= 255 && W + ahead + s->chunk - 1 > s->par.resident_frames) { printf("ERROR: --lookahead-tree: %d frames ahead of a window of %d do not fit the input ring (%d frames, staged %d at a time)\n", ahead, W, s->par.resident_frames, s->chunk); goto out; }
+                if (H264E_clip_set_lookahead_tree(s->clip, cmd.tree, ahead)) { printf("ERROR: --lookahead-tree: %s\n", H264E_last_error()); goto out; }
+            }
         }
         if (cmd.matrix && H264E_clip_set_color(s->clip, cmd.matrix, cmd.full_range)) { printf("ERROR: --colour: %s\n", H264E_last_error()); goto out; }
         if (cmd.fps_num && H264E_clip_set_frame_rate(s->clip, cmd.fps_num, cmd.fps_den)) { printf("ERROR: --fps: %s\n", H264E_last_error()); goto out; }
@@ -675,6 +689,7 @@ int main(int argc, char **argv)
     }
     if (cmd.lookahead && cmd.kbps <= 0) { printf("ERROR: --lookahead needs --kbps\n"); return 1; }
     if (cmd.lookahead_search && !cmd.lookahead) { printf("ERROR: --lookahead-search needs --lookahead\n"); return 1; }
+    if (cmd.tree && !cmd.lookahead_search) { printf("ERROR: --lookahead-tree needs --lookahead-search\n"); return 1; }
     if (cmd.denoise_motion && !cmd.lookahead_search) { printf("ERROR: --denoise-motion needs --lookahead-search\n"); return 1; }
     if (cmd.lookahead && cmd.have_qp_file) { printf("ERROR: --lookahead and --qpfile exclude each other\n"); return 1; }
     if (cmd.lookahead) { cmd.lookahead_kbps = cmd.kbps; cmd.kbps = 0; }      /* --kbps alone stays the reference's controller */

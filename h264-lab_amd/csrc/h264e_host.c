@@ -1093,6 +1093,14 @@ struct H264E_clip_tag
     /* motion search in the cost pass (H264E_clip_set_lookahead_search): the range, 0 = off; a frame has been analysed since open (its
      * records belong to that range) */
     int la_search, la_any;
+    /* cost tree over the motion field (H264E_clip_set_lookahead_tree, enc_lookahead_tree.h): per-frame QP offsets inside a window.  The
+     * arrays exist once the tree has been switched on; tr counts the frames of the planned windows, whose block maps are in the pool */
+    int la_tree, la_ahead;                  /* strength in quarter QP steps per doubling (0 = off); frames behind a window that its tree starts from */
+    uint64_t *tr_sum;                       /* [nframes] S(f) of the run that planned f's window */
+    int8_t *tr_delta;                       /* [nframes] the offset it became */
+    uint8_t *tr_base, *tr_key;              /* [nframes] the base QP of f's window; scratch: the schedule's key flags for a run */
+    clip_pass_t tr;
+    double tr_kernel_ms; long long tr_steps;
     /* Key frames that a stopped launch left encoded, wholly or down to some macroblock row: a key frame reads no reference
      * picture and no mv_clusters candidates, so what the next launch would make of those rows is what already lies in the frame's slot.
      * Collected when a launch has stopped cleanly (clip_keep_collect), used and forgotten by the next plan (clip_plan_launch); an entry
@@ -1229,6 +1237,7 @@ void H264E_clip_rewind(H264E_clip_t *c)
     c->rc_frame = -1; c->rc_qp = c->par.qp; c->rc_last_bytes[0] = c->rc_last_bytes[1] = 0;
     /* lookahead controller: every pass starts from the same factors and no carry, so it chooses the same QPs again */
     c->la_planned = c->la_closed = 0; c->la_debt = 0;
+    c->tr.done = c->tr.ring_lo = 0;                     /* no window is planned: no frame has a sum, an offset or a map */
     c->la_k[0] = c->la_search ? LOOKAHEAD_K0_SEARCH : LOOKAHEAD_K0_P; c->la_k[1] = LOOKAHEAD_K0_KEY;
 }
 
@@ -1287,7 +1296,7 @@ int H264E_clip_open(H264E_clip_t **out, const H264E_clip_param_t *par, int nfram
     if (getenv("H264E_LAUNCH_BASE")) c->launch_base = atoi(getenv("H264E_LAUNCH_BASE"));      /* experiments */
     c->launch_base = imax(1, imin(c->launch_base, c->ring - 1));
     c->resident = par->resident_frames > 0 ? imin(par->resident_frames, nframes) : nframes;
-    c->den.entries = c->resident; c->la.entries = imax(c->resident, 2);         /* as the pool sizes its rings (h264e_pool.h) */
+    c->den.entries = c->resident; c->la.entries = c->tr.entries = imax(c->resident, 2);         /* as the pool sizes its rings (h264e_pool.h) */
     c->traj = (int32_t *)malloc(sizeof(int32_t)*2*(size_t)c->seq.nmb);
     c->tasks = (h264e_hip_task_t *)calloc((size_t)c->ring, sizeof(*c->tasks));
     c->used = (int32_t (*)[2])calloc((size_t)c->ring, sizeof(int32_t[2]));
@@ -1327,6 +1336,7 @@ void H264E_clip_close(H264E_clip_t *c)
     free(c->traj); free(c->tasks); free(c->used); free(c->big);
     free(c->sched); free(c->forced); free(c->sc_hist); free(c->sc_dist); free(c->sc_cut);
     free(c->qp_sched); free(c->la_rec); free(c->la_bits);
+    free(c->tr_sum); free(c->tr_delta); free(c->tr_base); free(c->tr_key);
     free(c);
 }
 
@@ -1801,6 +1811,7 @@ int H264E_clip_set_lookahead(H264E_clip_t *c, int kbps, int window, int qp_min, 
     g_host_err[0] = 0;
     if (!c || kbps < 0 || window < 0) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: bad argument"); return -1; }
     if (clip_qp_mode_refused(c, "set_lookahead")) return -1;
+    if (!kbps && c->la_tree) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: kbps 0 while the cost tree (strength %d) offsets the controller's QPs: H264E_clip_set_lookahead_tree(clip, 0, 0) first", c->la_tree); return -1; }
     if (!kbps) { c->la_kbps = 0; return 0; }
     if (c->qp_explicit) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: not together with an explicit QP schedule"); return -1; }
     if (c->par.width < 16 || c->par.height < 16) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: pictures below 16x16 have no cost block (%dx%d)", c->par.width, c->par.height); return -1; }
@@ -1810,6 +1821,7 @@ int H264E_clip_set_lookahead(H264E_clip_t *c, int kbps, int window, int qp_min, 
     if (!window) window = imin(LOOKAHEAD_WINDOW_DEFAULT, imin(c->resident, c->ring - 1));
     if (c->resident < c->nframes && window > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: a window of %d frames does not fit the input ring (%d resident frames)", window, c->resident); return -1; }
     if (window > c->ring - 1) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: a window of %d frames does not fit one launch (%d slots)", window, c->ring - 1); return -1; }
+    if (c->la_tree && c->resident < c->nframes && window + c->la_ahead > c->resident) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead: a window of %d frames and the cost tree's %d ahead do not fit the input ring (%d resident frames)", window, c->la_ahead, c->resident); return -1; }
     if (clip_qp_arrays(c) || clip_la_arrays(c)) return -1;
     c->la_kbps = kbps; c->la_window = window; c->la_qmin = qp_min; c->la_qmax = qp_max;
     return 0;
@@ -1848,6 +1860,7 @@ int H264E_clip_set_lookahead_search(H264E_clip_t *c, int range)
     if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
     if (c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: not with keep_records = %d (GOP shards)", c->par.keep_records); return -1; }
     if (!range && c->den_motion) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: range 0 while the motion-compensated denoiser (mode %d) reads the motion field: H264E_clip_set_denoise_motion(clip, 0) first", c->den_motion); return -1; }
+    if (!range && c->la_tree) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: range 0 while the cost tree (strength %d) reads the motion field: H264E_clip_set_lookahead_tree(clip, 0, 0) first", c->la_tree); return -1; }
     if (range != c->la_search && c->la_any)
     {
         snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_search: range %d after frames have been analysed with range %d (their records cannot be made again)", range, c->la_search);
@@ -1876,6 +1889,81 @@ int H264E_clip_lookahead_time(H264E_clip_t *c, double *kernel_ms, long long *fra
     if (!c) return -1;
     if (kernel_ms) *kernel_ms = c->la_kernel_ms;
     if (frames) *frames = c->la_frames;
+    return 0;
+}
+
+/* ---- the cost tree over the motion field (include/h264e_mi355x.h, enc_lookahead_tree.h): per-frame QP offsets inside a window */
+
+int H264E_clip_set_lookahead_tree(H264E_clip_t *c, int strength, int ahead)
+{
+    g_host_err[0] = 0;
+    if (!c) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_tree: bad argument"); return -1; }
+    if (strength < 0 || strength > 16) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_tree: strength %d is outside 0..16", strength); return -1; }
+    if (ahead > 255) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_tree: ahead %d is outside 0..255 (below 0: the default)", ahead); return -1; }
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_tree: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
+    if (!strength) { c->la_tree = 0; return 0; }
+    if (c->par.keep_records) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_tree: not with keep_records = %d (GOP shards)", c->par.keep_records); return -1; }
+    if (!c->la_kbps) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_tree: the lookahead controller is off (0 kbps): call H264E_clip_set_lookahead first"); return -1; }
+    if (!c->la_search) { snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_tree: lookahead search range 0, no frame has a motion field: call H264E_clip_set_lookahead_search first"); return -1; }
+    if (ahead < 0) ahead = imin(imax(imin(c->la_window, c->resident - c->la_window), 0), 255);
+    if (c->resident < c->nframes && c->la_window + ahead > c->resident)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "set_lookahead_tree: a window of %d frames and %d ahead do not fit the input ring (%d resident frames)", c->la_window, ahead, c->resident);
+        return -1;
+    }
+    if (!c->tr_sum)
+    {
+        c->tr_sum = (uint64_t *)calloc((size_t)c->nframes, sizeof(uint64_t));
+        c->tr_delta = (int8_t *)calloc((size_t)c->nframes, 1);
+        c->tr_base = (uint8_t *)calloc((size_t)c->nframes, 1);
+        c->tr_key = (uint8_t *)calloc((size_t)c->nframes, 1);
+        if (!c->tr_sum || !c->tr_delta || !c->tr_base || !c->tr_key)
+        {
+            free(c->tr_sum); free(c->tr_delta); free(c->tr_base); free(c->tr_key);
+            c->tr_sum = NULL; c->tr_delta = NULL; c->tr_base = c->tr_key = NULL;
+            snprintf(g_host_err, sizeof(g_host_err), "out of host memory");
+            return -1;
+        }
+    }
+    c->la_tree = strength; c->la_ahead = ahead;
+    return 0;
+}
+
+int H264E_clip_read_lookahead_tree(H264E_clip_t *c, int frame, void *dst, int *nbx, int *nby)
+{
+    g_host_err[0] = 0;
+    if (!c) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_tree: bad argument"); return -1; }
+    if (nbx) *nbx = (c->par.width >> 1) >> 3;
+    if (nby) *nby = (c->par.height >> 1) >> 3;
+    if (!dst) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_tree: bad argument"); return -1; }
+    if (!c->la_tree) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_tree: the cost tree is off (H264E_clip_set_lookahead_tree), no frame has a block map"); return -1; }
+    if (!clip_pass_resident(&c->tr, frame, "read_lookahead_tree", "block map")) return -1;
+    if (h264e_hip_lookahead_read_tree(c->pool, frame, dst)) { g_host_err[0] = 0; return -1; }
+    return 0;
+}
+
+int H264E_clip_read_lookahead_tree_sums(H264E_clip_t *c, int first, int n, uint64_t *sum, int8_t *delta, uint8_t *base_qp)
+{
+    int i;
+    g_host_err[0] = 0;
+    if (!c || first < 0 || n < 0) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_tree_sums: bad argument"); return -1; }
+    if (!c->la_tree) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_tree_sums: the cost tree is off (H264E_clip_set_lookahead_tree), no frame has a sum"); return -1; }
+    if (first + n > c->tr.done) { snprintf(g_host_err, sizeof(g_host_err), "read_lookahead_tree_sums: the windows of frames %d..%d have not been planned (%d frames have)", first, first + n - 1, c->tr.done); return -1; }
+    for (i = 0; i < n; i++)
+    {
+        if (sum) sum[i] = c->tr_sum[first + i];
+        if (delta) delta[i] = c->tr_delta[first + i];
+        if (base_qp) base_qp[i] = c->tr_base[first + i];
+    }
+    return 0;
+}
+
+/* diagnostic (tools/lookahead_probe.py): HIP-event time of the tree's kernel launches since open, and the frame steps they made */
+int H264E_clip_lookahead_tree_time(H264E_clip_t *c, double *kernel_ms, long long *steps)
+{
+    if (!c) return -1;
+    if (kernel_ms) *kernel_ms = c->tr_kernel_ms;
+    if (steps) *steps = c->tr_steps;
     return 0;
 }
 
@@ -2002,27 +2090,63 @@ static uint64_t clip_la_texture_bits(uint64_t k, uint64_t cost, int q, int key)
     return v > LOOKAHEAD_BITS_MAX ? LOOKAHEAD_BITS_MAX : (uint64_t)v;
 }
 
-/* window j = frames [j*W, (j + 1)*W): one QP, the smallest whose predicted bits fit the window's budget and the clamped carry */
-static void clip_la_plan_window(H264E_clip_t *c, int j)
+/* piecewise-linear log2 of (I + S)/I in 1/256 units, 0 for I = 0 (S <= 2^48 and I < 2^40: the shifted sum fits 64 bits) */
+static int clip_la_tree_log(uint64_t I, uint64_t S)
+{
+    uint64_t r;
+    int e2 = 0;
+    if (!I) return 0;
+    r = ((I + S) << 8)/I;
+    while ((r >> e2) >= 512) e2++;
+    return 256*e2 + (int)((r >> e2) - 256);
+}
+
+/* the tree of window [a, b), run over the frames up to its horizon e: S and the offset of the window's frames; the window's block maps
+ * take the entries of the frames `entries` in front of them */
+static int clip_la_tree_window(H264E_clip_t *c, int a, int b, int e)
+{
+    float ms = 0;
+    int f;
+    if (a < imin(c->la.ring_lo, c->la.done) || e > c->la.done)
+    {
+        snprintf(g_host_err, sizeof(g_host_err), "lookahead tree: frames %d..%d are not all in the cost pass' ring (frames %d..%d are)", a, e - 1, imin(c->la.ring_lo, c->la.done), c->la.done - 1);
+        return -1;
+    }
+    for (f = a; f < e; f++) c->tr_key[f] = c->sched[f].key;
+    if (h264e_hip_lookahead_tree_frames(c->pool, a, e - a, c->tr_key + a, (unsigned long long *)(c->tr_sum + a), &ms)) return -1;
+    c->tr_kernel_ms += ms; c->tr_steps += e - a;
+    for (f = a; f < b; f++)
+        c->tr_delta[f] = (int8_t)-imin(LOOKAHEAD_QP_STEP, (c->la_tree*clip_la_tree_log(c->la_rec[3*(size_t)f], c->tr_sum[f]) + 512) >> 10);
+    c->tr.ring_lo = imax(imin(c->tr.ring_lo, a), e - c->tr.entries);
+    c->tr.done = b;
+    return 0;
+}
+
+/* window j = frames [j*W, (j + 1)*W): one QP, the smallest whose predicted bits fit the window's budget and the clamped carry -- with the
+ * cost tree one BASE QP, every frame at base + its offset, clamped to the QP range */
+static int clip_la_plan_window(H264E_clip_t *c, int j)
 {
     const int W = c->la_window, a = j*W, b = imin(a + W, c->nframes), dfb = c->la_kbps*1000/8/30;
     const long long T = 8LL*dfb*W, carry = c->la_debt > T/2 ? T/2 : c->la_debt < -(T/2) ? -(T/2) : c->la_debt, Tj = 8LL*dfb*(b - a) + carry;
     const int hk = clip_la_header_bits(c, 1), hp = clip_la_header_bits(c, 0);
     /* the factors were measured at the QP of the window before: the table does not carry them far from it */
-    const int prev = j ? c->qp_sched[a - 1] : 0, qlo = prev ? imax(c->la_qmin, prev - LOOKAHEAD_QP_STEP) : c->la_qmin, qhi = prev ? imin(c->la_qmax, prev + LOOKAHEAD_QP_STEP) : c->la_qmax;
+    const int tree = c->la_tree, prev = !j ? 0 : tree ? c->tr_base[a - 1] : c->qp_sched[a - 1], qlo = prev ? imax(c->la_qmin, prev - LOOKAHEAD_QP_STEP) : c->la_qmin, qhi = prev ? imin(c->la_qmax, prev + LOOKAHEAD_QP_STEP) : c->la_qmax;
     int q, f;
+    if (tree && clip_la_tree_window(c, a, b, imin(b + c->la_ahead, c->nframes))) return -1;
     for (q = qlo; q < qhi; q++)
     {
         long long sum = 0;
         for (f = a; f < b; f++)
         {
-            const int key = c->sched[f].key;
-            sum += (key ? hk : hp) + (long long)clip_la_texture_bits(c->la_k[key], c->la_rec[3*(size_t)f + (key ? 0 : 1)], q, key);
+            const int key = c->sched[f].key, qf = tree ? imax(c->la_qmin, imin(c->la_qmax, q + c->tr_delta[f])) : q;
+            sum += (key ? hk : hp) + (long long)clip_la_texture_bits(c->la_k[key], c->la_rec[3*(size_t)f + (key ? 0 : 1)], qf, key);
         }
         if (sum <= Tj) break;
     }
-    memset(c->qp_sched + a, q, (size_t)(b - a));
+    for (f = a; f < b; f++) c->qp_sched[f] = (uint8_t)(tree ? imax(c->la_qmin, imin(c->la_qmax, q + c->tr_delta[f])) : q);
+    if (tree) memset(c->tr_base + a, q, (size_t)(b - a));
     c->la_planned = j + 1;
+    return 0;
 }
 
 /* window j has been accepted: what it missed goes into the carry, and the factors become what would have predicted its frames */
@@ -2510,9 +2634,9 @@ int H264E_clip_encode(H264E_clip_t *c, uint8_t *out, size_t cap, size_t *out_byt
             const int j = l.n/c->la_window, wend = imin((j + 1)*c->la_window, c->nframes);
             if (c->la_planned <= j)
             {
-                if (c->avail < wend) break;
-                if (clip_prepass_lookahead(c, l.limit)) return clip_end(c, &x, st, -1);
-                clip_la_plan_window(c, j);
+                /* (with the cost tree: its frames up to the window's horizon, which the tree starts from) */
+                if (c->avail < imin(wend + (c->la_tree ? c->la_ahead : 0), c->nframes)) break;
+                if (clip_prepass_lookahead(c, l.limit) || clip_la_plan_window(c, j)) return clip_end(c, &x, st, -1);
             }
             l.limit = wend;
         }

@@ -23,6 +23,8 @@
  *   h264e_lookahead_kernel the cost pass of the lookahead rate control (enc_lookahead.h): intra / inter cost sums of one resident input frame.
  *   h264e_lookahead_search_kernel the same pass with a motion search of up to +-8 half-resolution samples per block
  *                        (enc_lookahead_search.h): the sums from the searched inter cost, and a motion field.
+ *   h264e_lookahead_tree_kernel the cost tree over that field (enc_lookahead_tree.h): one frame step of the backward propagation, and
+ *                        the frame's sum of what it received.
  *   h264e_mcdenoise_kernel the motion-compensated temporal denoiser (enc_mcdenoise.h): the denoiser's filter against the previous
  *                        denoised picture displaced by that motion field, refined by one sample per 16x16 block.
  *
@@ -43,6 +45,7 @@
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
 #include "enc_lookahead_search.h"
+#include "enc_lookahead_tree.h"
 #include "enc_mcdenoise.h"
 #include "enc_ssim.h"
 #include "../../include/h264e_hip.h"
@@ -991,6 +994,23 @@ __global__ void __launch_bounds__(64) h264e_lookahead_search_kernel(lookahead_se
     if (lane < 3) lookahead_record_add(S.a.record + lane, (unsigned long long)(lane == 0 ? si : lane == 1 ? sp : sn));
 }
 
+/* one frame step of the cost tree (enc_lookahead_tree.h): one wave per workgroup and 8 consecutive blocks, lane = (block, row).  Lanes
+ * behind the last block load nothing and add nothing, but take part in the butterflies and the reduction. */
+__global__ void __launch_bounds__(64) h264e_lookahead_tree_kernel(lookahead_tree_args_t T)
+{
+    const int lane = (int)threadIdx.x, r = lane & 7;
+    const int b = (int)blockIdx.x*LOOKAHEAD_TREE_WAVE_BLOCKS + (lane >> 3), on = b < T.nblk;
+    lookahead_row_t R = { { 0u, 0u }, { 0u, 0u } };
+    if (on) R = lookahead_tree_row(T, b, r);
+    const int m = (lookahead_oct_sum(lookahead_row_sum(R)) + 32) >> 6;
+    const int intra = lookahead_oct_sum(lookahead_row_intra(R, m));
+    unsigned long long g = 0;
+    if (on && r == 0) g = lookahead_tree_block(T, b, intra);
+    /* 8 values of at most 2^40: the low 21 bits and the 20 above them, each sum below 2^24 */
+    const int s0 = wave_reduce_add((int)(g & 0x1fffffu)), s1 = wave_reduce_add((int)(g >> 21));
+    if (lane == 0) lookahead_record_add(T.sum, (unsigned long long)s0 + ((unsigned long long)s1 << 21));
+}
+
 /* the motion-compensated denoiser (enc_mcdenoise.h): one wave per workgroup and tile of 16x16 luma + 8x8 + 8x8 chroma samples, blockIdx.x
  * / .y the tile.  The only LDS traffic between lanes is inside the one wave: wave_sync orders it. */
 template <int MODE> __global__ void __launch_bounds__(64) h264e_mcdenoise_kernel(mcdenoise_args_t A)
@@ -1104,6 +1124,11 @@ static void bk_launch_lookahead(const lookahead_args_t &A, hipStream_t st)
 static void bk_launch_lookahead_search(const lookahead_search_args_t &S, hipStream_t st)
 {
     hipLaunchKernelGGL(h264e_lookahead_search_kernel, dim3((unsigned)((S.a.nbx + LOOKAHEAD_SEARCH_STRIP - 1)/LOOKAHEAD_SEARCH_STRIP), (unsigned)S.nby), dim3(64), 0, st, S);
+}
+/* one single-wave workgroup per 8 blocks (1080p: 503) */
+static void bk_launch_lookahead_tree(const lookahead_tree_args_t &T, hipStream_t st)
+{
+    hipLaunchKernelGGL(h264e_lookahead_tree_kernel, dim3((unsigned)((T.nblk + LOOKAHEAD_TREE_WAVE_BLOCKS - 1)/LOOKAHEAD_TREE_WAVE_BLOCKS)), dim3(64), 0, st, T);
 }
 static void bk_launch_stage_selftest(int stage, const uint8_t *in, const int *args, uint8_t *out, hipStream_t st)
 {

@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_lookahead_search, bk_launch_mcdenoise, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those eleven are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_lookahead_search, bk_launch_lookahead_tree, bk_launch_mcdenoise, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those twelve are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -20,6 +20,7 @@
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
 #include "enc_lookahead_search.h"
+#include "enc_lookahead_tree.h"
 #include "enc_mcdenoise.h"
 #include "enc_ssim.h"
 
@@ -189,6 +190,10 @@ struct h264e_hip_pool
     unsigned long long *la_rec;          /* device [la_entries][3]: I, P, N of the frame in that entry */
     int la_entries; size_t la_entry_bytes;
     uint32_t *la_field;                  /* device [la_entries][nblk]: the motion fields of the pass with search (enc_lookahead_search.h); NULL until it first runs */
+    /* cost tree over the field (enc_lookahead_tree.h): what every block received, a ring beside la_field with the same entries and
+     * indexing, and the frames' sums; NULL until it first runs */
+    unsigned long long *la_tree;         /* device [la_entries][nblk] */
+    unsigned long long *la_tree_sum;     /* device [la_entries] */
     h264e_color_t cm;                    /* the RGB -> YCbCr matrix of the RGB / RGBP ingest and scale launches (h264e_hip_set_color) */
     hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
     hipEvent_t ev_in[2];                 /* h264e_hip_copy_timer_*: around a caller's launches on the copy stream */
@@ -323,7 +328,7 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     dev_free(p->heap);
     dev_free(p->den);
     dev_free(p->sc_rec);
-    dev_free(p->la_lo); dev_free(p->la_rec); dev_free(p->la_field); dev_free(p->mcd_cells);
+    dev_free(p->la_lo); dev_free(p->la_rec); dev_free(p->la_field); dev_free(p->la_tree); dev_free(p->la_tree_sum); dev_free(p->mcd_cells);
     dev_free(p->qual_dev);
     if (p->stream)
     {
@@ -974,6 +979,20 @@ static void bk_launch_lookahead_search(const lookahead_search_args_t &S, hipStre
         }
     for (int k = 0; k < 3; k++) lookahead_record_add(S.a.record + k, sum[k]);
 }
+/* one frame step of the cost tree: wave after wave, its lanes once as (block, row) and once as the blocks' row-0 lanes */
+static void bk_launch_lookahead_tree(const lookahead_tree_args_t &T, hipStream_t)
+{
+    for (int b0 = 0; b0 < T.nblk; b0 += LOOKAHEAD_TREE_WAVE_BLOCKS)
+    {
+        lookahead_row_t R[64];
+        int s[LOOKAHEAD_TREE_WAVE_BLOCKS] = { 0 }, intra[LOOKAHEAD_TREE_WAVE_BLOCKS] = { 0 };
+        unsigned long long sum = 0;
+        WAVE_FOR(l) if (b0 + (l >> 3) < T.nblk) { R[l] = lookahead_tree_row(T, b0 + (l >> 3), l & 7); s[l >> 3] += lookahead_row_sum(R[l]); }
+        WAVE_FOR(l) if (b0 + (l >> 3) < T.nblk) intra[l >> 3] += lookahead_row_intra(R[l], (s[l >> 3] + 32) >> 6);
+        WAVE_FOR(l) if (b0 + (l >> 3) < T.nblk && !(l & 7)) sum += lookahead_tree_block(T, b0 + (l >> 3), intra[l >> 3]);
+        lookahead_record_add(T.sum, sum);
+    }
+}
 #endif
 
 /* frames first, first + 1, ... of the STREAM (input slot f % frames_resident): their records into rec [n][3] on return; range 0 = the
@@ -1039,6 +1058,59 @@ extern "C" int h264e_hip_lookahead_read_field(h264e_hip_pool_t *p, int frame, vo
     HIPCHK(hipSetDevice(p->device));
     const size_t bytes = (size_t)la_nbx(p)*(size_t)la_nby(p)*LOOKAHEAD_FIELD_CELL_BYTES;
     HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)p->la_field + bytes*(size_t)(frame % p->la_entries), bytes, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+/* ---- cost tree over the motion field (enc_lookahead_tree.h): one h264e_lookahead_tree_kernel launch per frame on the pool's stream, in
+ * REVERSE frame order: the launch of frame f reads what the launch of frame f + 1 has added */
+extern "C" int h264e_hip_lookahead_tree_frames(h264e_hip_pool_t *p, int first, int n, const uint8_t *key, unsigned long long *sums, float *kernel_ms)
+{
+    if (!p || !key || !sums || first < 0 || n < 0) FAIL("lookahead_tree_frames: bad argument");
+    if (!p->la_field) FAIL("lookahead_tree_frames: no frame of this pool has a motion field (h264e_hip_lookahead_search_frames comes first)");
+    const int E = p->la_entries;
+    if (n > E) FAIL("lookahead_tree_frames: %d frames do not fit the field ring (%d entries)", n, E);
+    if (kernel_ms) *kernel_ms = 0;
+    if (!n) return 0;
+    HIPCHK(hipSetDevice(p->device));
+    lookahead_tree_args_t T;
+    T.nbx = la_nbx(p); T.nby = la_nby(p); T.nblk = T.nbx*T.nby;
+    const size_t nblk = (size_t)T.nblk;
+    if (!p->la_tree)
+    {
+        if (dev_malloc((void **)&p->la_tree, nblk*LOOKAHEAD_TREE_CELL_BYTES*(size_t)E)) { p->la_tree = 0; FAIL("lookahead_tree: device allocation failed (%d block maps)", E); }
+        if (dev_malloc((void **)&p->la_tree_sum, sizeof(unsigned long long)*(size_t)E)) { dev_free(p->la_tree); p->la_tree = 0; p->la_tree_sum = 0; FAIL("lookahead_tree: device allocation failed (%d sums)", E); }
+    }
+    HIPCHK(hipEventRecord(p->ev_pass[0], p->stream));
+    if (ring_records_zero(p, p->la_tree, nblk*LOOKAHEAD_TREE_CELL_BYTES, E, first, n) || ring_records_zero(p, p->la_tree_sum, sizeof(unsigned long long), E, first, n)) return -1;
+    for (int i = n - 1; i >= 0; i--)
+    {
+        const int f = first + i, e = f % E;
+        T.lo = p->la_lo + p->la_entry_bytes*(size_t)e;
+        T.field = p->la_field + nblk*(size_t)e;
+        T.in = p->la_tree + nblk*(size_t)e;
+        T.out = i && !key[i] ? p->la_tree + nblk*(size_t)((f - 1) % E) : NULL;
+        T.sum = p->la_tree_sum + e;
+        bk_launch_lookahead_tree(T, p->stream);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(p->ev_pass[1], p->stream));
+    if (ring_records_read(p, sums, p->la_tree_sum, sizeof(unsigned long long), E, first, n)) return -1;
+    HIPCHK(hipStreamSynchronize(p->stream));
+    for (int i = 0; i < n; i++) if (sums[i] > LOOKAHEAD_TREE_SUM_MAX) sums[i] = LOOKAHEAD_TREE_SUM_MAX;
+    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, p->ev_pass[0], p->ev_pass[1]));
+    return 0;
+}
+
+/* the block map of STREAM frame `frame` from its ring entry: what is there is the caller's to know */
+extern "C" int h264e_hip_lookahead_read_tree(h264e_hip_pool_t *p, int frame, void *dst)
+{
+    if (!p || !dst || frame < 0) FAIL("lookahead_read_tree: bad argument");
+    if (!p->la_field) FAIL("lookahead_read_tree: no frame of this pool has a motion field (h264e_hip_lookahead_search_frames comes first)");
+    if (!p->la_tree) FAIL("lookahead_read_tree: no cost tree has been run");
+    HIPCHK(hipSetDevice(p->device));
+    const size_t bytes = (size_t)la_nbx(p)*(size_t)la_nby(p)*LOOKAHEAD_TREE_CELL_BYTES;
+    HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)p->la_tree + bytes*(size_t)(frame % p->la_entries), bytes, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     return 0;
 }

@@ -175,6 +175,16 @@ int  h264e_hip_lookahead_search_frames(h264e_hip_pool_t *pool, int first, int n,
 /* The field ring's entry of STREAM frame `frame` (entry frame % max(frames_resident, 2)) into dst [nbx*nby*4 bytes]; the call waits for
  * the stream.  Which frame the entry holds is the caller's to know.  Refused before the first call with a search. */
 int  h264e_hip_lookahead_read_field(h264e_hip_pool_t *pool, int frame, void *dst);
+/* Cost tree over the motion field (enc_lookahead_tree.h): one run over STREAM frames [first, first + n), n at most the field ring's
+ * entries, whose half-resolution pictures and fields are in their rings (analysed with a search, and not overwritten since).  The
+ * frames' block maps in_f -- uint64 [nby][nbx], in a ring beside the field ring with the same entries and indexing, allocated on first
+ * use -- are zeroed, then one kernel launch per frame runs on the pool's stream in REVERSE frame order: frame f adds what it received
+ * into its sum and, unless key[f - first] is set or f == first, passes its blocks' amounts on into in_{f-1}.  sums [n] on return (the
+ * call waits for the stream): S(f) = min(sum over the blocks of min(in_f, 2^40), 2^48).  kernel_ms (optional): as above.  read_tree: the
+ * map ring's entry of STREAM frame `frame` into dst [nbx*nby*8 bytes]; which frame and which run the entry holds is the caller's to
+ * know.  Both are refused while the pool has no field ring. */
+int  h264e_hip_lookahead_tree_frames(h264e_hip_pool_t *pool, int first, int n, const uint8_t *key, unsigned long long *sums, float *kernel_ms);
+int  h264e_hip_lookahead_read_tree(h264e_hip_pool_t *pool, int frame, void *dst);
 /* Motion-compensated temporal denoiser (enc_mcdenoise.h), a sibling of h264e_hip_denoise_frames: STREAM frames first, first + 1, ...
  * (input slot f % frames_resident, n <= frames_resident) are filtered against the previous denoised picture displaced by frame f's
  * entry of the field ring, one kernel launch per frame in order on the pool's stream after every upload issued on the copy stream.

@@ -481,6 +481,38 @@ int  H264E_clip_set_lookahead_search(H264E_clip_t *clip, int range);
 int  H264E_clip_read_lookahead_motion(H264E_clip_t *clip, int frame, void *dst, int *nbx, int *nby);
 /* diagnostic: HIP-event time of the cost pass' kernel launches since open, and the frames they analysed (tools/lookahead_probe.py) */
 int  H264E_clip_lookahead_time(H264E_clip_t *clip, double *kernel_ms, long long *frames);
+/* Cost tree over the motion field: per-frame QP offsets inside a window, from cost propagated backwards through the fields of the
+ * searched cost pass -- x264's macroblock tree summed to frame level (enc_lookahead_tree.h, tests/lookahead_tree_model.py).  strength 0
+ * = off (the default: nothing is launched or allocated, every record and byte is as without the call), 1..16 = quarter QP steps per
+ * doubling of a frame's importance; ahead 0..255 = frames behind a window that its tree starts from, below 0 = min(W, resident_frames -
+ * W), at least 0.  With key(f) the key-frame schedule (periodic, forced and scene-cut), window j = [a, b) and horizon e = min(b + ahead,
+ * nframes): in_f(t) = 0 for every block t of every frame in [a, e); for f = e - 1 down to a + 1, unless key(f), every block s = (sx, sy)
+ * of frame f: i = intra_f(s), c = min(i, inter_f(s)), g = min(in_f(s), 2^40); amt = g when i == 0, else ((i + g)*(i - c))/i floored;
+ * x = 8sx + dx, y = 8sy + dy with (dx, dy) = mv_f(s); tx = x >> 3, ox = x & 7, ty = y >> 3, oy = y & 7; the four targets (tx + u,
+ * ty + v), u, v in {0, 1}, have the weights wx = u ? ox : 8 - ox times wy = v ? oy : 8 - oy, a target of weight 0 is left out, and each
+ * gets in_{f-1}(target) += (amt*wx*wy) >> 6.  Then S(f) = min(sum_t min(in_f(t), 2^40), 2^48); lg(f) = 0 when I(f) == 0, else with
+ * r = ((I(f) + S(f)) << 8)/I(f) and e2 = floor(log2 r) - 8: lg = 256*e2 + ((r >> e2) - 256), a piecewise-linear log2 in 1/256 units;
+ * delta(f) = -min(6, (strength*lg(f) + 512) >> 10): a key frame passes nothing back and receives from its followers, and the cap is the
+ * controller's one doubling of the quantiser step.
+ *   Controller with the tree: window j has a BASE QP Q_j and frame f of it q_f = clamp(Q_j + delta(f), qp_min, qp_max); Q_j = the smallest
+ * value in [lo_j, hi_j] whose predicted window sum, each frame at its own q_f, is <= T_j, else hi_j; [lo_j, hi_j] lies around Q_{j-1}, the
+ * base of the window before, not around a frame's QP; a window is planned only when the frames up to its horizon are uploaded; only
+ * delta(f) of [a, b) is used, and a frame's S, delta and block map are those of the run that planned its own window.  k, H(f), the
+ * carry and the calibration stay as above.  While the clip stands at frame 0; the setting is kept across a rewind, sums and offsets
+ * belong to a window's plan and are made again with it.  Refused -- nothing changes, H264E_last_error names the value -- with strength
+ * outside 0..16 or ahead above 255, with the controller off, with search range 0, with keep_records, and when W + ahead exceeds a
+ * bounded input ring's resident_frames; while it is on, H264E_clip_set_lookahead(kbps 0) and H264E_clip_set_lookahead_search(0) are. */
+int  H264E_clip_set_lookahead_tree(H264E_clip_t *clip, int strength, int ahead);
+/* What the blocks of a frame received, in_f: nbx*nby uint64, row by row, into dst.  Size-only call and *nbx, *nby as for
+ * H264E_clip_read_lookahead_motion.  The maps live in a ring beside the field ring: -1, with the readable frames named in
+ * H264E_last_error, when the frame's window has not been planned in this pass, when its entry has been taken by a later run, and when
+ * the tree is off. */
+int  H264E_clip_read_lookahead_tree(H264E_clip_t *clip, int frame, void *dst, int *nbx, int *nby);
+/* S(f), delta(f) and the base QP of the window of frames first .. first + n - 1; each pointer may be NULL.  -1 when the window of one
+ * of them has not been planned in this pass, or the tree is off. */
+int  H264E_clip_read_lookahead_tree_sums(H264E_clip_t *clip, int first, int n, uint64_t *sum, int8_t *delta, uint8_t *base_qp);
+/* diagnostic: HIP-event time of the tree's kernel launches since open, and the frame steps they made (tools/lookahead_probe.py) */
+int  H264E_clip_lookahead_tree_time(H264E_clip_t *clip, double *kernel_ms, long long *steps);
 /* Motion-compensated temporal denoiser: THIS PROJECT'S OWN filter, a mode of the denoiser above.  mode 0 = off, 1 = the previous
  * denoised picture is displaced by the motion field of the searched cost pass, 2 = by that field refined (enc_mcdenoise.h,
  * tests/mcdenoise_model.py).  Per frame f: cur = the RAW input, D_{f-1} = the previous output of this filter (zeros in front of frame 0),

@@ -16,6 +16,13 @@ still for its first half and sliding down 8 samples a frame afterwards, 128 fram
 --search and without; prints per window the QP and the coded bits against the budget 8*dfb*W.
 
     python tools/lookahead_calibrate.py --step [--search R]
+
+--step --tree S[+S..][,A] replays the controller with the cost tree's QP offsets instead (tests/lookahead_tree_model.py; A frames ahead,
+default W) on CIF x 128 of synth, pan, scene and that still-then-sliding clip, GOP 30, W = 16, 300 kbit/s, once per strength and once
+with strength 0 in the same run: total bits, mean and minimum luma PSNR of the oracle's reconstruction, and the per-frame PSNR around
+the key frame at 30 and the window boundary at 32 (does quality pump?).  Prints the table that DESIGN.md 4.5n quotes.
+
+    python tools/lookahead_calibrate.py --step --search 8 --tree 2+4+8,16
 """
 import os
 import sys
@@ -28,6 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import clips  # noqa: E402
 import lookahead_model as M  # noqa: E402
 import lookahead_motion_model as ML  # noqa: E402
+import lookahead_tree_model as MT  # noqa: E402
 import oracle_lib  # noqa: E402
 import scenecut_model  # noqa: E402
 
@@ -67,13 +75,50 @@ def step_report(search):
         print("| %d | %d..%d | %d | %d / %d = %.2f | %d | %d / %d = %.2f |" % (j, j * W, j * W + W - 1, q0, b0, budget, b0 / budget, q1, b1, budget, b1 / budget))
 
 
+def tree_report(search, strengths, ahead):
+    w, h, n, gop, W, kbps = 352, 288, 128, 30, 16, 300
+    kinds = [int(k) for k in scenecut_model.kinds(n, gop, [])]
+    target = 8 * (kbps * 1000 // 8 // 30) * n
+    shown = (28, 29, 30, 31, 32, 33)
+    print("| clip | strength | bits | bits / target | mean PSNR-Y | min PSNR-Y | offsets of window 1 | base QPs | PSNR-Y of frames %s |" % ", ".join(str(f) for f in shown))
+    print("|---|---|---|---|---|---|---|---|---|")
+    for name in ("synth", "pan", "scene", "vpan"):
+        c = clips.vpan(w, h, n, 8, lambda t: t >= n // 2) if name == "vpan" else clips.make(name, w, h, n)
+        hdr = (40, 40 + 8 * M.parameter_set_bytes(oracle_lib.encode_clip(c[:1], w, h, gop=gop, qp=26)[0]))
+        rec, fields, intra = MT.analyse(c, w, h, search)
+        for s in [0] + strengths:
+            deltas = MT.windows(rec, fields, intra, kinds, W, s, ahead)[2] if s else np.zeros(n, np.int8)
+            e = oracle_lib.Encoder(w, h, gop=gop, qp=26)
+            bits, psnr, base = [], [], []
+            for a in range(0, n, W):
+                qp, bq = MT.plan(rec, kinds, hdr, bits + [0] * (n - len(bits)), kbps, W, deltas, search=search)
+                base.append(int(bq[a]))
+                for f in range(a, min(a + W, n)):
+                    assert oracle_lib.lib().h264o_set_run_param(e.e, 0, 0, 0, int(qp[f]), int(qp[f]), 0) == 0
+                    bits.append(8 * len(e.encode(c[f])))
+                    buf, cw, ch = e.recon()
+                    d = buf[: cw * ch].reshape(ch, cw)[:h, :w].astype(np.int64) - c[f][: w * h].reshape(h, w)
+                    mse = float((d * d).mean())
+                    psnr.append(10 * np.log10(255.0 * 255.0 / mse) if mse else 99.0)
+            e.close()
+            print("| %s | %d | %d | %.3f | %.2f | %.2f | %s | %s | %s |" % (name, s, sum(bits), sum(bits) / target, np.mean(psnr), np.min(psnr), deltas[W:2 * W].tolist(), base,
+                                                                       " ".join("%.2f" % psnr[f] for f in shown)))
+
+
 def main():
     argv = sys.argv[1:]
     search = 0
+    tree = None
+    if "--tree" in argv:
+        i = argv.index("--tree")
+        tree = argv[i + 1].split(",")
+        del argv[i:i + 2]
     if "--search" in argv:
         i = argv.index("--search")
         search = int(argv[i + 1])
         del argv[i:i + 2]
+    if "--step" in argv and tree:
+        return tree_report(search or ML.MAX_RANGE, [int(v) for v in tree[0].split("+")], int(tree[1]) if len(tree) > 1 else 16)
     if "--step" in argv:
         return step_report(search or ML.MAX_RANGE)
     n = int(argv[0]) if len(argv) > 0 else 24
