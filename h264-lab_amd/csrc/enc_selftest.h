@@ -1,6 +1,8 @@
 /*
  * enc_selftest.h -- device-level code that only tests and the bench input use: the per-stage test hook (one wave-level stage of the
  * macroblock pipeline on caller-supplied operands), the finalizer test hook and the synth_v1 clip generator.  Wave64 model like the rest (wave.h).
+ * Not here: the hand-offs between the waves of a row (what the reconstruction wave knows of the inter decision, and when) -- their arrival
+ * orders are scripted in the emulation, tests/emu/emu_handoffs.h, and tested by tests/test_emu_handoffs.py and tests/test_gpu_handoffs.py.
  */
 #ifndef H264E_ENC_SELFTEST_H
 #define H264E_ENC_SELFTEST_H

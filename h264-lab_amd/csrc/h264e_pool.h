@@ -502,6 +502,11 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
         if (getenv("H264E_TEST_STALL_ROW")) G.test_stall_row = atoi(getenv("H264E_TEST_STALL_ROW"));
         if (getenv("H264E_TEST_UPLOAD_FAIL_AT")) p->test_upload_fail_at = atoi(getenv("H264E_TEST_UPLOAD_FAIL_AT"));
     }
+#if defined(H264E_EMU) && defined(H264E_EMU_HANDOFFS_H)
+    /* the emulation only, where its translation unit has included tests/emu/emu_handoffs.h in front of this file: the arrival order of the
+     * macroblock step's wave hand-offs, as a script */
+    if (emu_handoffs_configure(knobs ? getenv("H264E_EMU_HANDOFFS") : NULL)) { free(p); FAIL("H264E_EMU_HANDOFFS: unknown schedule"); }
+#endif
     p->frame_bytes = (size_t)width*height*3/2;
     p->waves = getenv("H264E_WAVES") ? atoi(getenv("H264E_WAVES")) : 0;                  /* 1 / 2 / 3 / 4: forced (A-B measurements, tests); else chosen per launch */
     if (p->waves != 1 && p->waves != 2 && p->waves != 3 && p->waves != 4) p->waves = 0;

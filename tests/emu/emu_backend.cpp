@@ -2,8 +2,9 @@
  * emu_backend.cpp -- TEST ONLY: the lane-loop emulation of the macroblock kernels (h264-lab_amd/csrc/wave.h, -DH264E_EMU) behind the
  * product's own host layer.  The kernel HEADERS (enc_*.h) are the product's; a "launch" here runs the jobs of the launch one after
  * the other, every macroblock row as one call sequence row_begin / row_step ... / row_end, then the job's finalizer -- the order the
- * GPU's dependency counters would allow anyway.  It checks kernel LOGIC without a GPU; address spaces, the memory model and the
- * wave pipeline's hand-offs are what the -m gpu tests are for.  Never linked into libh264e_mi355x.so.
+ * GPU's dependency counters would allow anyway.  It checks kernel LOGIC without a GPU; address spaces and the memory model are what the
+ * -m gpu tests are for.  Of the wave pipeline's hand-offs, WHAT the reconstruction side has seen of the inter decision when it decides can
+ * be scripted (emu_handoffs.h); the waits themselves run on the GPU only.  Never linked into libh264e_mi355x.so.
  */
 #ifndef H264E_EMU
 #error "the emulation is built with -DH264E_EMU (tests/emu/Makefile)"
@@ -46,6 +47,7 @@ extern "C" void emu_check_global(const void *p, size_t n, const char *file, int 
 #include "../../h264-lab_amd/csrc/enc_row.h"
 #include "../../h264-lab_amd/csrc/enc_selftest.h"
 #include "../../include/h264e_hip.h"
+#include "emu_handoffs.h"
 
 /* H264E_EMU_LAUNCH_LOG=path: every launch appends one line with what the host layer decided for it -- the decisions that never change a
  * byte of the emulated stream (tests/test_emu_launch_plan.py).  The order words are hashed with 32-bit FNV-1a, low byte first. */
@@ -82,6 +84,14 @@ static void bk_launch_mb(const h264e_geom_t &G, int narrow, int variant, int njo
             const RowTask RT = rowtask_load(T);
             for (int x = 0; x < G.nmbx; x++)
             {
+                /* a scripted arrival order of the wave hand-offs (emu_handoffs.h) instead of "everything is there" */
+                if (g_handoff.on)
+                {
+                    if (variant == 0) { row_prefetch<GEOM_INTRA>(*L, G, RT, row, x); handoff_row_step<GEOM_INTRA>(*L, G, C, RT, T.in[0], row, x, row0, row1); }
+                    else if (narrow) { row_prefetch<GEOM_NARROW>(*L, G, RT, row, x); handoff_row_step<GEOM_NARROW>(*L, G, C, RT, T.in[0], row, x, row0, row1); }
+                    else { row_prefetch<GEOM_WIDE>(*L, G, RT, row, x); handoff_row_step<GEOM_WIDE>(*L, G, C, RT, T.in[0], row, x, row0, row1); }
+                    continue;
+                }
                 if (variant == 0) { row_prefetch<GEOM_INTRA>(*L, G, RT, row, x); row_step<GEOM_INTRA>(*L, G, C, RT, row, x, row0, row1); }
                 else if (narrow) { row_prefetch<GEOM_NARROW>(*L, G, RT, row, x); row_step<GEOM_NARROW>(*L, G, C, RT, row, x, row0, row1); }
                 else { row_prefetch<GEOM_WIDE>(*L, G, RT, row, x); row_step<GEOM_WIDE>(*L, G, C, RT, row, x, row0, row1); }

@@ -1,5 +1,7 @@
 """CPU: the HIP kernel sources, compiled as the test-only lane-loop emulation (tests/emu), against the oracle and
-the reference's golden vectors.  This checks kernel LOGIC without a GPU; the GPU tests check the real thing."""
+the reference's golden vectors.  This checks kernel LOGIC without a GPU; the GPU tests check the real thing.
+Everything here runs the macroblock step with the inter decision complete before the intra candidates start; the orders in which the
+search wave's bounds and decision can reach the reconstruction wave are scheduled and tested in tests/test_emu_handoffs.py."""
 import hashlib
 import json
 import os
