@@ -1,11 +1,9 @@
 /*
- * enc_row.h -- row driver (row_begin / row_step / row_end) and the slice splice (splice_frame / finalize_commit), wave64 model.
+ * enc_row.h -- row driver (row_begin / row_step / row_end), wave64 model.  What follows a frame's rows -- the slice splice, the exact
+ * mv_clusters walk, the export -- is the finalizer's: enc_finalize.h.
  *
  * row_step = the reference's mb_encode (h264-lab.h:5724-5812) for macroblock (x, row): neighbour records of
  * the row above come from HBM (written by that row's wavefront), the left neighbour is in LDS.
- * splice_frame = the tail of encode_slice (h264-lab.h:6451-6456): concatenates the row bit buffers behind
- * the slice header, resolves mb_skip_run across rows, adds the RBSP trailing bits, and evaluates the
- * mv_clusters speculation.
  */
 #ifndef H264E_ENC_ROW_H
 #define H264E_ENC_ROW_H
@@ -531,396 +529,6 @@ DEV void row_end(RowLds &L, const h264e_geom_t &G, const ChainG &C, int row)
     }
     wave_sync();
     PROF_ROW_END(L, C);
-}
-
-/* ------------------------------------------------------------------ slice splice (one wavefront per chain) */
-
-struct SpliceState { GLOBAL_AS uint32_t *out; uint32_t wpos; uint32_t carry; int cbits; uint32_t cap_words; int overflow; };
-
-/* append nbits (<= 64) right-aligned bits */
-DEV void splice_put(SpliceState &s, int nbits, uint64_t v)
-{
-    while (nbits > 0)
-    {
-        int take = imin(nbits, 32 - s.cbits);
-        uint32_t part = (uint32_t)((v >> (nbits - take)) & ((take == 32) ? 0xffffffffu : ((1u << take) - 1)));
-        s.carry = (take == 32) ? part : ((s.carry << take) | part);
-        s.cbits += take;
-        nbits -= take;
-        if (s.cbits == 32)
-        {
-            if (s.wpos < s.cap_words) s.out[s.wpos] = bswap32(s.carry); else s.overflow = 1;
-            s.wpos++;
-            s.carry = 0; s.cbits = 0;
-        }
-    }
-}
-
-/* append the first nbits of an MSB-first word buffer, 64 words per pass */
-DEV void splice_words(SpliceState &s, const GLOBAL_AS uint32_t *w, uint32_t nbits)
-{
-    const uint32_t nfull = nbits >> 5;
-    const int cb = s.cbits;
-    const uint32_t carry = s.carry;
-    for (uint32_t base = 0; base < nfull; base += 64)
-    {
-        WAVE_FOR(l)
-        {
-            uint32_t k = base + (uint32_t)l;
-            if (k < nfull)
-            {
-                uint32_t prev = k ? w[k - 1] : carry, cur = w[k];
-                uint32_t o = cb ? ((prev << (32 - cb)) | (cur >> cb)) : cur;
-                if (s.wpos + k < s.cap_words) s.out[s.wpos + k] = bswap32(o);
-            }
-        }
-    }
-    if (s.wpos + nfull > s.cap_words) s.overflow = 1;
-    if (nfull)
-    {
-        s.wpos += nfull;
-        s.carry = cb ? (w[nfull - 1] & ((1u << cb) - 1)) : 0;
-    }
-    const int rem = (int)(nbits & 31);
-    if (rem) splice_put(s, rem, (uint64_t)(w[nfull] >> (32 - rem)));
-}
-
-DEV void put_ue64(SpliceState &s, uint32_t v)
-{
-    int n = 2*(32 - clz32(v + 1)) - 1;
-    splice_put(s, n, (uint64_t)v + 1);
-}
-
-DEV void clusters_step(mv32 c[2], mv32 mv)                                  /* h264-lab.h:5263-5278 */
-{
-    int n = mvx(mv)*mvx(mv) + mvy(mv)*mvy(mv);
-    int n0 = mvx(c[0])*mvx(c[0]) + mvy(c[0])*mvy(c[0]), n1 = mvx(c[1])*mvx(c[1]) + mvy(c[1])*mvy(c[1]);
-    if (n < n1) c[0] = mvmk((63*mvx(c[0]) + mvx(mv) + 32) >> 6, (63*mvy(c[0]) + mvy(mv) + 32) >> 6);
-    if (n >= n0) c[1] = mvmk((63*mvx(c[1]) + mvx(mv) + 32) >> 6, (63*mvy(c[1]) + mvy(mv) + 32) >> 6);
-}
-
-/*
- * The exact mv_clusters walk of one frame on the device (what h264e_host.c clusters_walk does on the host): from state s, in
- * raster order -- restarting from s at every slice of a multi-slice frame -- compare the rounded candidates every macroblock
- * CONSUMED (the frame-constant pair or its entry of the per-macroblock array) with the exact ones, then apply its update
- * (h264-lab.h:5263-5278).  The chain is serial, but almost no macroblock moves the state: 64 macroblocks per pass, a ballot
- * finds the next one that moves it or mismatches, everything in front of it is settled at once.  traj (optional) receives the
- * state in front of every macroblock.  Returns the first mismatching macroblock or -1; s = state behind the frame.
- */
-/* macroblocks [k0, k1) of one slice, continuing from state s / verdict first_bad (the finalizer walks a frame row by row as its rows
- * complete; batches of 64 inside the range) */
-DEV void clusters_walk_range(const h264e_frame_task_t &T, const GLOBAL_AS h264e_mbrec_t *rec, mv32 s[2], int &first_bad, GLOBAL_AS mv32 *traj, int k0, int k1)
-{
-    const GLOBAL_AS mv32 *per_mb = (const GLOBAL_AS mv32 *)T.clusters_per_mb;
-    const mv32 u_frame0 = T.clusters[0], u_frame1 = T.clusters[1];
-    for (int base = k0; base < k1; base += 64)
-    {
-        int start = 0;
-        /* the state in front of every macroblock of the batch, one per lane (wave.h V64) */
-        V64 mine0 = v64_make([&](int) -> int { return s[0]; }), mine1 = v64_make([&](int) -> int { return s[1]; });
-        for (;;)
-        {
-            const mv32 c0 = s[0], c1 = s[1];
-            const int fb = first_bad;
-            const uint64_t ev = wave_ballot([&](int l) -> int {
-                const int k = base + l;
-                if (l < start || k >= k1) return 0;
-                const mv32 mv0 = rec[k].mv0;
-                const int type = rec[k].type;
-                int hit = 0;
-                if (fb < 0 && rec[k].used_cand)
-                {
-                    const mv32 u0 = per_mb ? per_mb[2*k] : u_frame0, u1 = per_mb ? per_mb[2*k + 1] : u_frame1;
-                    if (mvround(u0) != mvround(c0) || mvround(u1) != mvround(c1)) hit = 1;
-                }
-                if (type < 5)
-                {
-                    mv32 c[2] = { c0, c1 };
-                    clusters_step(c, mv0);
-                    if (c[0] != c0 || c[1] != c1) hit = 1;
-                }
-                return hit;
-            });
-            if (!ev) break;
-            const int e = __builtin_ctzll(ev), ke = base + e;
-            /* macroblock ke: mismatch check first (against the state in front of it), then its update */
-            if (first_bad < 0 && rec[ke].used_cand)
-            {
-                const mv32 u0 = per_mb ? per_mb[2*ke] : u_frame0, u1 = per_mb ? per_mb[2*ke + 1] : u_frame1;
-                if (mvround(u0) != mvround(s[0]) || mvround(u1) != mvround(s[1])) first_bad = ke;
-            }
-            if (rec[ke].type < 5) clusters_step(s, rec[ke].mv0);
-            s[0] = (mv32)uni(s[0]); s[1] = (mv32)uni(s[1]); first_bad = uni(first_bad);
-            start = e + 1;
-            mine0 = v64_map(mine0, [&](int l, int v) -> int { return l >= start ? s[0] : v; });
-            mine1 = v64_map(mine1, [&](int l, int v) -> int { return l >= start ? s[1] : v; });
-            if (start >= 64) break;
-        }
-        if (traj)
-        {
-            v64_each(mine0, [&](int l, int v) { const int k = base + l; if (k < k1) traj[2*k] = v; });
-            v64_each(mine1, [&](int l, int v) { const int k = base + l; if (k < k1) traj[2*k + 1] = v; });
-        }
-    }
-}
-
-/* the whole frame at once (the walk of a complete frame: tests, tools) */
-DEV int device_clusters_walk(const h264e_geom_t &G, const h264e_frame_task_t &T, const GLOBAL_AS h264e_mbrec_t *rec, mv32 s[2], GLOBAL_AS mv32 *traj)
-{
-    const mv32 s0[2] = { s[0], s[1] };
-    int first_bad = -1;
-    for (int band = 0; band < T.nslices; band++)
-    {
-        s[0] = s0[0]; s[1] = s0[1];
-        clusters_walk_range(T, rec, s, first_bad, traj, T.slice_row[band]*G.nmbx, T.slice_row[band + 1]*G.nmbx);
-    }
-    if (T.nslices > 1) { s[0] = s0[0]; s[1] = s0[1]; }      /* the parent's state never moves in the row-band build (h264-lab.h:6526) */
-    wave_sync();
-    return first_bad;
-}
-
-/*
- * The finalizer's walk, ROW BY ROW as the rows complete (JobWalk::rows is called from the splice below, for the rows whose counters say
- * complete, once the state in front of the frame is known): the verdict of a frame is known a walk of ONE row after its last row ended.
- * The walk goes on behind a mismatch, over every row, as the whole-frame walk does: the trajectory behind the mismatch is the speculation
- * for the next encode of those rows, and it is a good one (the vectors of macroblocks that consumed slightly wrong candidates are mostly
- * the right ones).  Stopping the launch as soon as the row with the first mismatch has ended, with the state at the stop as the
- * trajectory of everything behind it, was built and measured in round 4: it wins a little where a frame fails once (1080p 4 Mbit/s:
- * +2.5 %) and loses badly where the state keeps moving through a frame (8K 60 Mbit/s, two slices: 50 launches instead of 22, the
- * re-encodes advance two or three rows at a time) -- not kept.
- */
-struct JobWalk
-{
-    mv32 s0[2], s[2];
-    int first_bad, next_row;
-    DEVM void begin(const mv32 st[2]) { s0[0] = s[0] = st[0]; s0[1] = s[1] = st[1]; first_bad = -1; next_row = 0; }
-    /* walks the rows up to and including `upto` that have not been walked yet (all of them complete) */
-    DEVM void rows(const h264e_geom_t &G, const h264e_frame_task_t &T, const GLOBAL_AS h264e_mbrec_t *rec, GLOBAL_AS mv32 *traj, int upto)
-    {
-        for (; next_row <= upto; next_row++)
-        {
-            const int r = next_row;
-            for (int k = 0; k < T.nslices; k++) if (r == T.slice_row[k]) { s[0] = s0[0]; s[1] = s0[1]; }      /* every slice starts from the state in front of the frame */
-            clusters_walk_range(T, rec, s, first_bad, traj, r*G.nmbx, (r + 1)*G.nmbx);
-        }
-    }
-    /* behind the last row: the state to hand on */
-    DEVM void end(const h264e_frame_task_t &T)
-    {
-        if (T.nslices > 1) { s[0] = s0[0]; s[1] = s0[1]; }      /* the parent's state never moves in the row-band build (h264-lab.h:6526) */
-        wave_sync();
-    }
-};
-
-struct SpliceOut { uint32_t start, nbytes; int overflow, all_skipped, far_reads; };
-
-/* The slices' RBSPs from the row bit buffers.  on_row(first row of the slice, row) is called before a row is touched: the caller waits
- * for the row there (and walks it); a non-zero return ends the splice with that code (nothing is committed). */
-template <class ROW> DEV int splice_frame(const h264e_geom_t &G, const ChainG &C, const h264e_frame_task_t &T, SpliceOut &o, ROW on_row)
-{
-    SpliceState s;
-    const uint32_t start = T.arena_reset ? 0u : ((*C.cursor + 15u) & ~15u);
-    uint32_t off = 0;                                                           /* of the current slice, relative to start */
-    int overflow = 0, all_skipped = 0, spl_overflow = 0, far_reads = 0;
-    GLOBAL_AS h264e_frameout_t &F = C.fout[T.frame_slot];
-    /* one RBSP per slice (row band); the slices of a frame lie behind each other, each starting 16-byte aligned */
-    for (int k = 0; k < T.nslices; k++)
-    {
-        const int r0 = T.slice_row[k], r1 = T.slice_row[k + 1];
-        const uint32_t room = start + off < C.arena_cap ? C.arena_cap - (start + off) : 0u;
-        s.out = (GLOBAL_AS uint32_t *)(C.arena + start + off);
-        s.wpos = 0; s.carry = 0; s.cbits = 0; s.overflow = 0;
-        s.cap_words = room >> 2;
-        splice_put(s, 8, (uint64_t)(uint32_t)T.hdr_nal);
-        put_ue64(s, (uint32_t)(r0*G.nmbx));                                     /* first_mb_in_slice, h264-lab.h:4247 */
-        splice_put(s, T.hdr_nbits, T.hdr_bits);
-        int run = 0;
-        for (int row = r0; row < r1; row++)
-        {
-            const int stop = on_row(r0, row);
-            if (stop) return stop;
-            const GLOBAL_AS h264e_rowmeta_t &M = C.rowmeta[row];
-            overflow |= M.overflow;
-            far_reads += C.far_reads[row];      /* the frame's own rows only: a frame that was stopped leaves nothing behind in one that ends */
-            run += M.lead_skips;
-            if (M.lead_skips < G.nmbx || M.nbits)
-            {
-                if (T.slice_type != 2) put_ue64(s, (uint32_t)run);
-                wave_sync();
-                splice_words(s, C.rowbits + (size_t)row*G.row_words, M.nbits);
-                wave_sync();
-                run = M.trail_skips;
-            }
-        }
-        /* rc_frame_end's skip flag (h264-lab.h:6596): in the row-band build the parent's skip_run is never touched, so it is 0 there */
-        if (T.nslices == 1) all_skipped = run == G.nmb;
-        if (run) put_ue64(s, (uint32_t)run);                                    /* h264-lab.h:6451-6454 */
-        splice_put(s, 1, 1);                                                    /* rbsp_stop_one_bit, h264-lab.h:3999 */
-        const uint32_t nbytes = s.wpos*4 + (uint32_t)((s.cbits + 7) >> 3);
-        if (s.cbits) { int pad = 32 - s.cbits; splice_put(s, pad, 0); }
-        spl_overflow |= s.overflow;
-        F.slice_nbytes[k] = nbytes;
-        if (k + 1 < T.nslices) off += (nbytes + 15u) & ~15u; else off += nbytes;
-        wave_sync();
-    }
-    o.start = start; o.nbytes = off; o.overflow = overflow | spl_overflow; o.all_skipped = all_skipped; o.far_reads = far_reads;
-    return 0;
-}
-
-/* mv_clusters speculation check of the frame-at-a-time path (its host walks exactly when this says "moved"): is the speculated state
- * a fixed point of every update of this frame?  Frames validated by the device walk do not need it. */
-DEV int clusters_moved(const h264e_geom_t &G, const h264e_frame_task_t &T, const GLOBAL_AS h264e_mbrec_t *rec)
-{
-    int moved = 0;
-    if (!T.clusters_per_mb && !T.walk_on_device)
-    {
-        for (int base = 0; base < G.nmb; base += 64)
-        {
-            uint64_t bad = wave_ballot([&](int l) -> int {
-                int k = base + l;
-                if (k >= G.nmb || rec[k].type >= 5) return 0;
-                mv32 c[2] = { T.clusters[0], T.clusters[1] };
-                clusters_step(c, rec[k].mv0);
-                return c[0] != T.clusters[0] || c[1] != T.clusters[1];
-            });
-            if (bad) moved = 1;
-        }
-    }
-    return moved;
-}
-
-/* ... and the frame's result record, once the frame stands */
-DEV void finalize_commit(const h264e_geom_t &G, const ChainG &C, const h264e_frame_task_t &T, const SpliceOut &o, GLOBAL_AS int *stepflags)
-{
-    GLOBAL_AS h264e_frameout_t &F = C.fout[T.frame_slot];
-    const int moved = clusters_moved(G, T, C.mbrec + (size_t)T.frame_slot*G.nmb);
-    F.offset = o.start;
-    F.nbytes = o.nbytes;
-    F.nslices = T.nslices;
-    F.all_skipped = o.all_skipped;
-    F.clusters_moved = moved;
-    F.overflow = o.overflow;
-    F.far_reads = o.far_reads;
-    *C.cursor = o.start + ((o.nbytes + 15u) & ~15u);
-    stepflags[0] = moved;
-    stepflags[1] = o.overflow;
-    wave_sync();
-}
-
-/*
- * RBSP -> Annex-B NAL on the device: 4-byte start code + payload with emulation prevention (h264-lab.h:3926-4022 nal_count_esc /
- * nal_put_esc: a 0x03 goes in front of every byte <= 3 that follows two zero bytes; the zero count restarts behind it).
- * The escape automaton is sequential, but it can only fire where the RAW bytes read 00 00 0x -- once per ~4 MB of CAVLC data.
- * So: 256-byte blocks, one dword per lane; a ballot finds the blocks that contain such a triple (two bytes of look-back across
- * the block edge); all other blocks are copied by the whole wave (shifted by the escapes inserted so far), a block with a
- * candidate is run through the automaton byte by byte by one lane with the exact carried zero count.
- * dst: 16-byte aligned (host-mapped memory or HBM).  Returns the NAL size; sets overflow when it does not fit cap.
- */
-DEV uint32_t nal_escape_copy(GLOBAL_AS uint8_t *dst, uint32_t cap, const GLOBAL_AS uint8_t *src, uint32_t n, int &overflow)
-{
-    uint32_t esc = 0;           /* escapes inserted so far (wave-uniform) */
-    int cntz = 0;               /* the automaton's zero count in front of the current block (exact whenever it matters) */
-    if (n + 4u > cap) { overflow = 1; return 0; }
-    if (wave_lane() == 0) gstore32((gu8 *)dst, 0x01000000u);                /* 00 00 00 01 */
-    for (uint32_t base = 0; base < n; base += 256)
-    {
-        const uint32_t len = n - base < 256u ? n - base : 256u;
-        const uint64_t cand = wave_ballot([&](int l) -> int {
-            const uint32_t o = base + 4u*(uint32_t)l;
-            if (o >= n) return 0;
-            /* six raw bytes: two of look-back (0xff in front of the payload) and this lane's dword (the arena is zero-padded to a
-             * dword behind the payload: at worst a false candidate, which only selects the byte-wise path for this block) */
-            const uint32_t cur = gload32((const gu8 *)(src + o)), prev = o ? gload32((const gu8 *)(src + o - 4)) : 0xffffffffu;
-            const uint64_t w = ((uint64_t)cur << 16) | (uint64_t)(prev >> 16);
-            int hit = 0;
-            for (int k = 0; k < 4; k++)
-                if (((w >> (8*k)) & 0xffffu) == 0 && ((w >> (8*(k + 2))) & 0xffu) <= 3u) hit = 1;
-            return hit;
-        });
-        if (!cand)
-        {
-            /* no escape can fire inside this block: whole-wave copy, shifted by the escapes so far */
-            if (4u + base + esc + len > cap) { overflow = 1; return 0; }
-            WAVE_FOR(l)
-            {
-                const uint32_t o = 4u*(uint32_t)l;
-                if (o < len)
-                {
-                    GLOBAL_AS uint8_t *d = dst + 4u + base + esc + o;
-                    if (o + 4u <= len) gstore32((gu8 *)d, gload32((const gu8 *)(src + base + o)));
-                    else for (uint32_t k = o; k < len; k++) dst[4u + base + esc + k] = src[base + k];
-                }
-            }
-            /* zero count behind a block without escapes = its trailing raw zeros (at most 2, else it had a candidate) */
-            {
-                const uint32_t e = base + len;
-                cntz = src[e - 1] ? 0 : (e >= 2 && src[e - 2] == 0) ? 2 : 1;
-            }
-        } else
-        {
-            if (4u + base + esc + len + len/2 + 2u > cap) { overflow = 1; return 0; }
-            if (wave_lane() == 0)
-            {
-                uint32_t j = 4u + base + esc;
-                for (uint32_t i = 0; i < len; i++)
-                {
-                    const uint8_t b = src[base + i];
-                    if (cntz == 2 && b <= 3) { dst[j++] = 3; cntz = 0; esc++; }
-                    cntz = b ? 0 : cntz + 1;
-                    dst[j++] = b;
-                }
-            }
-            esc = (uint32_t)uni((int)esc);       /* lane 0 ran the automaton: its counters are the wave's */
-            cntz = uni(cntz);
-        }
-        wave_sync();
-    }
-    return 4u + n + esc;
-}
-
-/* finished frame -> every slice as a complete Annex-B NAL (start code + escaped payload) in the slot's device NAL arena, the NALs
- * behind each other at 16-byte aligned offsets; then NALs (when they fit the host-mapped mirror, which is sized for ordinary
- * frames: in_device = 0) and macroblock records to host-mapped memory, 16 bytes per lane per pass.  Returns the NAL sizes. */
-DEV void export_frame(const h264e_geom_t &G, const ChainG &C, const h264e_frame_task_t &T, uint32_t *nal_bytes /* [H264E_MAX_SLICES], uniform */, uint32_t &total, int &overflow, int &in_device)
-{
-    const GLOBAL_AS h264e_frameout_t &F = C.fout[T.frame_slot];
-    uint32_t soff = 0, doff = 0;
-    overflow = 0;
-    for (int k = 0; k < H264E_MAX_SLICES; k++)
-    {
-        nal_bytes[k] = 0;
-        if (k < F.nslices)
-        {
-            const uint32_t n = F.slice_nbytes[k];
-            const uint32_t room = doff < C.nal_cap ? C.nal_cap - doff : 0u;
-            const uint32_t w = nal_escape_copy(C.nal_arena + doff, room, C.arena + F.offset + soff, n, overflow);
-            nal_bytes[k] = w;
-            soff += (n + 15u) & ~15u;
-            doff += (w + 15u) & ~15u;
-        }
-    }
-    total = doff;
-    in_device = doff > T.host_rbsp_cap;
-    if (!in_device)
-    {
-        drain_stores();                          /* the NAL arena was written by this wave just now */
-        wave_sync();
-        const uint32_t nw = (doff + 15u) >> 4;
-        const GLOBAL_AS u32x4 *src = (const GLOBAL_AS u32x4 *)C.nal_arena;
-        GLOBAL_AS u32x4 *dst = (GLOBAL_AS u32x4 *)T.host_rbsp;
-        for (uint32_t base = 0; base < nw; base += 64)
-        {
-            WAVE_FOR(l) { if (base + (uint32_t)l < nw) dst[base + l] = src[base + l]; }
-        }
-    }
-    const uint32_t nr = ((uint32_t)G.nmb*(uint32_t)sizeof(h264e_mbrec_t) + 15u) >> 4;
-    const GLOBAL_AS u32x4 *rs = (const GLOBAL_AS u32x4 *)(C.mbrec + (size_t)T.frame_slot*G.nmb);
-    GLOBAL_AS u32x4 *rd = (GLOBAL_AS u32x4 *)T.host_mbrec;
-    for (uint32_t base = 0; base < nr; base += 64)
-    {
-        WAVE_FOR(l) { if (base + (uint32_t)l < nr) rd[base + l] = rs[base + l]; }
-    }
-    wave_sync();
 }
 
 #endif

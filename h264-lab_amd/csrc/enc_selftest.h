@@ -7,6 +7,7 @@
 #ifndef H264E_ENC_SELFTEST_H
 #define H264E_ENC_SELFTEST_H
 #include "enc_row.h"
+#include "enc_finalize.h"
 
 /* ------------------------------------------------------------------ per-stage test hook (tests/test_stages.py, tests/test_stage_edges.py)
  * Runs ONE of the macroblock pipeline's wave-level stages on caller-supplied operands, so that each can be compared with the
@@ -301,7 +302,7 @@ DEV void stage_selftest(StageLds &S, RowLds &L, int stage, const GLOBAL_AS uint8
 }
 
 /* ------------------------------------------------------------------ finalizer test hook (tests/test_finalizer.py)
- * Runs the finalizer wave's own functions (enc_row.h "slice splice") on caller-supplied operands, in the geometry of the pool (nmbx, nmby,
+ * Runs the finalizer wave's own functions (enc_finalize.h, from "slice splice" up to export_frame) on caller-supplied operands, in the geometry of the pool (nmbx, nmby,
  * row_words).  The host side (h264e_pool.h h264e_hip_selftest_finalizer) builds the task and the chain descriptor in device memory as a
  * submit would, pointing at the operands; nothing here waits: on_row returns 0 at once, no counter, abort word or verdict is polled.
  *   1 splice   splice_frame (splice_put / splice_words / put_ue64) over C.rowmeta / C.far_reads / C.rowbits into C.arena

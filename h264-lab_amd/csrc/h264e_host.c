@@ -275,7 +275,7 @@ static void slice_header_bits(const seq_t *s, int key, int frame_num, int idr_pi
 }
 
 /* the slices of one frame as the kernel exports them (h264e_hip_result_t): complete NALs -- start code + payload with the
- * emulation-prevention bytes already inserted on the device (enc_row.h nal_escape_copy) -- behind each other at 16-byte
+ * emulation-prevention bytes already inserted on the device (enc_finalize.h nal_escape_copy) -- behind each other at 16-byte
  * aligned offsets; they are concatenated in order (h264-lab.h:6565-6569), cb as in nal_end.  Returns bytes written, 0 when
  * cap is too small */
 static size_t emit_slices(uint8_t *d, size_t cap, const uint8_t *nals, const h264e_hip_result_t *r, nalu_cb_t cb, void *token)

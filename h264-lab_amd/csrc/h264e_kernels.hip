@@ -8,7 +8,8 @@
  *                        consecutive frames of a stream run as a temporal wavefront a few steps apart.  Hand-off: per-row
  *                        progress counters, payload stored write-through (sc1), relaxed polls, one acquire per hand-off
  *                        (cdna_hip_programming.md Guideline 16 R1).  The finalizer splices the row bit buffers into the
- *                        slice RBSP (there is no separate splice kernel) and exports the frame to host-mapped memory.
+ *                        slice RBSP (there is no separate splice kernel) and exports the frame to host-mapped memory: its body is
+ *                        enc_finalize.h job_finalize, shared with the emulation; its waits, fences and scopes are FinalizerOnDevice below.
  *   h264e_synth_kernel   fills resident input frames with the synth_v1 clip (bench / test input in HBM).
  *   h264e_denoise_kernel the temporal denoiser (enc_denoise.h) over one frame: raw input + previous denoised picture -> new
  *                        denoised picture, out of place, one launch per frame in stream order.
@@ -35,6 +36,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "enc_row.h"
+#include "enc_finalize.h"
 #include "enc_selftest.h"
 #include "enc_denoise.h"
 #include "enc_ingest.h"
@@ -144,12 +146,77 @@ struct InterFromSearchWave
     DEVM bool wait_noskip_or_ready() const { return wait_either(&L->f_noskip); }
     DEVM bool wait_bound_or_ready() const { return wait_either(&L->f_bound); }
 };
+/* the finalizer's view of time and memory (enc_finalize.h job_finalize lists the members): relaxed polls of counters and flags at agent
+ * scope with s_sleep between them, every spin bounded by G.spin_limit, ONE acquire behind a poll that succeeded; a record goes out as
+ * plain stores of one lane (the caller's guard), a release fence, a drain and the relaxed store of its flag -- at agent scope for the
+ * frame behind, at system scope for the host */
+struct FinalizerOnDevice
+{
+    const h264e_geom_t &G;
+    const ChainG &C;
+    const h264e_frame_task_t &T;
+    GLOBAL_AS int *errflag;
+    DEVM const GLOBAL_AS int *prev_flag() const { return &((const GLOBAL_AS h264e_walkrec_t *)T.walk_prev)->flag; }
+    DEVM void converge() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
+    DEVM void acquire() const { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); converge(); }
+    DEVM int rows_reached() const
+    {
+        int st = 0, seen = 0;
+        for (int r = G.nmby - 1; r >= 0 && !st; r--) st = poll_progress(C.progress + r, G.nmbx + 1, seen, G.spin_limit);
+        return st;
+    }
+    template <class IDLE> DEVM int wait_row(int r, IDLE idle) const
+    {
+        for (unsigned spins = 0;; spins++)
+        {
+            const int seen = uni(__hip_atomic_load(C.progress + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            if (seen >= G.nmbx + 1) break;
+            if (seen < 0) return seen;
+            if (spins > G.spin_limit) return -1;
+            if (idle()) return 1;
+            __builtin_amdgcn_s_sleep(H264E_POLL_SLEEP);
+        }
+        acquire();
+        return 0;
+    }
+    DEVM bool prev_up() const { return uni(__hip_atomic_load(prev_flag(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >= T.launch_id; }
+    DEVM bool wait_prev() const { int sf = 0; return poll_progress(prev_flag(), T.launch_id, sf, G.spin_limit) == 0; }
+    DEVM void acquire_prev() const { acquire(); }
+    DEVM void publish_verdict(GLOBAL_AS h264e_walkrec_t *w) const
+    {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(&w->flag, T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    DEVM void before_export() const { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent"); converge(); }
+    DEVM void publish_host(GLOBAL_AS h264e_hostdone_t *hd, int sign) const
+    {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");                 /* system scope: the host reads these */
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(&hd->done, sign*T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    DEVM void raise_abort() const { __hip_atomic_store((GLOBAL_AS int *)T.abort_word, T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    DEVM void raise_err() const { *errflag = 1; }
+#ifdef H264E_STAMPS
+    unsigned long long fz_t = wall_clock64();
+    /* 32..36: the time since the stamp before; 37: a count */
+    DEVM void stamp(int id)
+    {
+        if (id == 37) { if (LANE == 0 && C.prof) atomicAdd(C.prof + 37, 1ull); return; }
+        const unsigned long long n = wall_clock64();
+        if (LANE == 0 && C.prof) atomicAdd(C.prof + id, n - fz_t);
+        fz_t = n;
+    }
+#else
+    DEVM void stamp(int) const {}
+#endif
+};
 
 /*
  * Grid: njobs x (nmby + 1) workgroups of one wavefront -- or of two (WAVES = 2): the macroblock loop as a two-stage pipeline, one
  * wavefront searching macroblock x + 1 while the other reconstructs and writes x (enc_row.h).  Workgroup `row < nmby` encodes macroblock row
  * `row` of its job's frame; workgroup `nmby` is the job's finalizer: it follows the frame's rows as they end -- splices each into the
- * slice (enc_row.h splice_frame), walks its records (exact mv_clusters validation, JobWalk) -- and, in streaming use, exports the result
+ * slice (enc_finalize.h splice_frame), walks its records (exact mv_clusters validation, JobWalk) -- and, in streaming use, exports the result
  * to host-mapped memory and raises the job's done word, so the host consumes frames while later frames of the same launch are still
  * being encoded.  Padding entries of a banded dispatch order (H264E_ORDER_PAD) are workgroups that exit at once.
  * Every workgroup waits for workgroups with a lower index (rows above; rows of the reference frame's job inside the
@@ -195,186 +262,8 @@ __global__ void __launch_bounds__(64*WAVES, OCC) h264e_mb_kernel(h264e_geom_t G,
     const ChainG C = chain_view(*T.chain_desc);
     GLOBAL_AS int *errflag = (GLOBAL_AS int *)uniptr(T.errflag);
 
-    if (row == G.nmby)
-    {
-        /* ---- finalizer (one wavefront; the second one of a two-wave workgroup has nothing to do here) */
-        if (wv) return;
-#ifdef H264E_STAMPS
-        unsigned long long fz_t = wall_clock64();
-#define FZ_STAMP(id) do { const unsigned long long n_ = wall_clock64(); if (LANE == 0 && C.prof) atomicAdd(C.prof + (id), n_ - fz_t); fz_t = n_; } while (0)
-#else
-#define FZ_STAMP(id) do { } while (0)
-#endif
-        int st = 0, seen = 0;
-        GLOBAL_AS h264e_hostdone_t *hd = (GLOBAL_AS h264e_hostdone_t *)T.host_done;
-        GLOBAL_AS h264e_walkrec_t *wout = (GLOBAL_AS h264e_walkrec_t *)T.walk_out;
-        /* The finalizer follows its frame ROW BY ROW (enc_row.h JobWalk / splice_frame): a row whose counter says complete is spliced
-         * while the rows below it are still being encoded, and walked (exact mv_clusters validation) as soon as the state in front of
-         * the frame is known -- the verdict of the frame in front, which usually arrives when this frame is nearly done: the rows
-         * completed by then are walked in one go (also while this wave waits for its next row: the frame-to-frame chain of verdicts
-         * must carry the walk alone, never a wait or the splice), and the verdict goes out right behind the walk of the last row. */
-        int wstatus = 0, first_bad = -1, have_prev = !(T.walk_on_device && T.walk_prev), published = 0;
-        mv32 ws[2] = { T.exact_state[0], T.exact_state[1] };
-        const GLOBAL_AS h264e_walkrec_t *wp = (const GLOBAL_AS h264e_walkrec_t *)T.walk_prev;
-        const GLOBAL_AS h264e_mbrec_t *rec = C.mbrec + (size_t)T.frame_slot*G.nmb;
-        JobWalk W;
-        W.begin(ws);
-        /* Row-band slices: every slice of every frame starts from the state in front of the STREAM (the parent's state never moves,
-         * h264-lab.h:6526), so the walk needs nothing of the frame in front but its status, and only to publish: the chain of verdicts
-         * carries no walk at all (it was what bounded an 8-slice stream: one walk of ~0.26 ms per frame, 3830 frames/s) */
-        const bool state_fixed = T.nslices > 1;
-        /* the verdict of the frame in front has arrived: take its state (or its failure) */
-        const auto take_prev = [&]() {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            if (uni(wp->status) != H264E_WALK_OK) wstatus = H264E_WALK_VOID;
-            else if (!state_fixed) { ws[0] = (mv32)uni(wp->state_out[0]); ws[1] = (mv32)uni(wp->state_out[1]); W.begin(ws); }
-            have_prev = 1;
-        };
-        /* this frame's verdict, for the frame behind */
-        const auto publish_verdict = [&]() {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            if (LANE == 0 && wout)
-            {
-                wout->state_out[0] = ws[0]; wout->state_out[1] = ws[1]; wout->status = wstatus; wout->first_bad = first_bad;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(&wout->flag, T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            published = 1;
-        };
-        /* rows up to `upto` are complete: walk what the walk may have; behind the last row the verdict goes out.  Returns non-zero
-         * when the frame does not stand (mismatch, or void because the frame in front does not) */
-        const auto walk_upto = [&](int upto) -> int {
-            if (!T.walk_on_device || published) return 0;
-            if (!have_prev && uni(__hip_atomic_load(&wp->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >= T.launch_id) take_prev();
-            if (!have_prev && !state_fixed) return 0;
-            if (!wstatus)
-            {
-                W.rows(G, T, rec, (GLOBAL_AS mv32 *)T.traj_out, upto);
-                if (W.next_row < G.nmby) return 0;
-                if (!have_prev)
-                {
-                    /* walked to the end on the fixed state: the verdict still has to wait for the status of the frame in front */
-                    int sf = 0;
-                    if (poll_progress(&wp->flag, T.launch_id, sf, G.spin_limit)) { wstatus = H264E_WALK_VOID; have_prev = 1; }
-                    else take_prev();
-                }
-            }
-            if (!wstatus)
-            {
-                W.end(T);
-                first_bad = W.first_bad;
-                ws[0] = W.s[0]; ws[1] = W.s[1];
-                wstatus = first_bad >= 0 ? H264E_WALK_BAD : H264E_WALK_OK;
-            }
-            publish_verdict();
-            return wstatus != H264E_WALK_OK;
-        };
-        SpliceOut so;
-        if (G.fz_wait_all) for (int r = G.nmby - 1; r >= 0 && !st; r--) st = poll_progress(C.progress + r, G.nmbx + 1, seen, G.spin_limit);
-        if (!st) st = splice_frame(G, C, T, so, [&](int, int r) -> int {
-            for (unsigned spins = 0;; spins++)
-            {
-                seen = uni(__hip_atomic_load(C.progress + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                if (seen >= G.nmbx + 1) break;
-                if (seen < 0) return seen;
-                if (spins > G.spin_limit) return -1;
-                /* waiting for row r: the rows above it are complete (and acquired) -- is their walk due? */
-                if (r > 0 && walk_upto(r - 1)) return 1;
-                __builtin_amdgcn_s_sleep(H264E_POLL_SLEEP);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            return walk_upto(r);
-        });
-        FZ_STAMP(32);               /* followed the frame's rows: waits, the splice of every completed row, the walk once its start state was in */
-        if (st < 0)
-        {
-            /* a row of the frame was stopped or failed */
-            if (LANE == 0)
-            {
-                if (st == -1) *errflag = 1;
-                if (T.walk_on_device && wout && !published)
-                {
-                    /* the frames behind wait for this verdict: never leave them spinning */
-                    wout->status = H264E_WALK_VOID; wout->first_bad = -1;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(&wout->flag, T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if (hd) { hd->walk_status = H264E_WALK_VOID; __hip_atomic_store(&hd->done, -T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-            }
-            return;
-        }
-        if (T.walk_on_device)
-        {
-            if (!published)
-            {
-                /* every row is spliced and the state in front of the frame is still out: wait for it, walk the frame in one go */
-                if (!have_prev)
-                {
-                    int sf = 0;
-                    if (poll_progress(&wp->flag, T.launch_id, sf, G.spin_limit)) { wstatus = H264E_WALK_VOID; have_prev = 1; }
-                    else take_prev();
-                }
-                FZ_STAMP(33);       /* waited for the verdict of the frame in front */
-                (void)walk_upto(G.nmby - 1);
-                FZ_STAMP(34);       /* the exact walk behind the splice (the frame in front was late) */
-            }
-            if (wstatus != H264E_WALK_OK)
-            {
-                if (LANE == 0)
-                {
-                    /* a mismatch stops the whole launch through the abort word (a leaf's concerns nobody but itself) */
-                    if (wstatus == H264E_WALK_BAD && T.abort_word && !T.walk_quiet)
-                        __hip_atomic_store((GLOBAL_AS int *)T.abort_word, T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (hd)
-                    {
-                        hd->walk_status = wstatus; hd->first_bad = first_bad; hd->state_out[0] = ws[0]; hd->state_out[1] = ws[1];
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        __hip_atomic_store(&hd->done, -T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                }
-                return;
-            }
-        }
-        finalize_commit(G, C, T, so, (GLOBAL_AS int *)T.stepflags);
-        FZ_STAMP(35);               /* the last row's splice + the result record */
-        if (hd)
-        {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            uint32_t nal_bytes[H264E_MAX_SLICES], nal_total = 0;
-            int exp_overflow = 0, in_device = 0;
-            export_frame(G, C, T, nal_bytes, nal_total, exp_overflow, in_device);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            if (LANE == 0)
-            {
-                const GLOBAL_AS h264e_frameout_t &F = C.fout[T.frame_slot];
-                hd->nbytes = nal_total; hd->all_skipped = F.all_skipped;
-                hd->nslices = F.nslices; hd->in_device = in_device;
-#pragma unroll
-                for (int k = 0; k < H264E_MAX_SLICES; k++) hd->slice_nbytes[k] = nal_bytes[k];
-                hd->clusters_moved = F.clusters_moved; hd->overflow = F.overflow | exp_overflow; hd->far_reads = F.far_reads;
-                hd->walk_status = wstatus; hd->first_bad = first_bad; hd->state_out[0] = ws[0]; hd->state_out[1] = ws[1];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");                 /* system scope: the host reads these */
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(&hd->done, T.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-        FZ_STAMP(36);               /* NAL escaping + export to host-mapped memory */
-#ifdef H264E_STAMPS
-        if (LANE == 0 && C.prof) atomicAdd(C.prof + 37, 1ull);
-#endif
-        return;
-    }
+    /* ---- finalizer (one wavefront; the others of a multi-wave workgroup have nothing to do here) */
+    if (row == G.nmby) { if (!wv) job_finalize(G, C, T, FinalizerOnDevice{ G, C, T, errflag }); return; }
 
     /* ---- macroblock row */
     if (row < T.first_row) return;          /* kept from the previous encode of this frame (its counter already says complete) */

@@ -504,8 +504,11 @@ extern "C" int h264e_hip_pool_create(h264e_hip_pool_t **pool, int device, int wi
     }
 #if defined(H264E_EMU) && defined(H264E_EMU_HANDOFFS_H)
     /* the emulation only, where its translation unit has included tests/emu/emu_handoffs.h in front of this file: the arrival order of the
-     * macroblock step's wave hand-offs, as a script */
+     * macroblock step's wave hand-offs, and of the verdict in front of a finalizer, as scripts */
     if (emu_handoffs_configure(knobs ? getenv("H264E_EMU_HANDOFFS") : NULL)) { free(p); FAIL("H264E_EMU_HANDOFFS: unknown schedule"); }
+#ifdef H264E_EMU_VERDICT_SCHEDULES       /* (its own mark, so that an emu_handoffs.h written before the verdict schedules still builds) */
+    if (emu_verdict_configure(knobs ? getenv("H264E_EMU_VERDICT") : NULL)) { free(p); FAIL("H264E_EMU_VERDICT: unknown schedule"); }
+#endif
 #endif
     p->frame_bytes = (size_t)width*height*3/2;
     p->waves = getenv("H264E_WAVES") ? atoi(getenv("H264E_WAVES")) : 0;                  /* 1 / 2 / 3 / 4: forced (A-B measurements, tests); else chosen per launch */

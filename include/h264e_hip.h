@@ -59,7 +59,7 @@ typedef struct
     /* ... and a frame whose failed validation concerns nobody but itself (a leaf): it reports the verdict but does not stop the launch */
     int walk_quiet;
     /* stream mode: the job's finalizer validates the mv_clusters speculation ON THE DEVICE (exact walk over the frame's records,
-     * enc_row.h device_clusters_walk): task 0 of a submit starts from exact_state, task i from the verdict of task i-1; a mismatch
+     * enc_finalize.h device_clusters_walk): task 0 of a submit starts from exact_state, task i from the verdict of task i-1; a mismatch
      * stops the launch (device abort word) and is reported in the result (walk_status, first_bad, state_out); the walked
      * per-macroblock trajectory stays on the device and becomes the candidates of a re-encode with traj_from_device */
     int walk_on_device;
@@ -292,7 +292,7 @@ int  h264e_hip_stamps_read(h264e_hip_pool_t *pool, unsigned long long *dst /* [3
 /* wall clock of a region on the pool's stream, by HIP events */
 int  h264e_hip_timer_start(h264e_hip_pool_t *pool);
 int  h264e_hip_timer_stop(h264e_hip_pool_t *pool, double *ms);
-/* self-test hook: runs the device's NAL emulation-prevention pass (enc_row.h nal_escape_copy, one wavefront) on n payload bytes;
+/* self-test hook: runs the device's NAL emulation-prevention pass (enc_finalize.h nal_escape_copy, one wavefront) on n payload bytes;
  * dst receives start code + escaped payload, *out_n its size.  Used by tests with adversarial inputs (real streams need an
  * escape about once per 4 MB). */
 /* test hook: the dispatch order of a launch of `jobs` jobs as (job << 16 | row) entries, 0xffffffff = padding (banded orders: eight

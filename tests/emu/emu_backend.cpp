@@ -2,9 +2,11 @@
  * emu_backend.cpp -- TEST ONLY: the lane-loop emulation of the macroblock kernels (h264-lab_amd/csrc/wave.h, -DH264E_EMU) behind the
  * product's own host layer.  The kernel HEADERS (enc_*.h) are the product's; a "launch" here runs the jobs of the launch one after
  * the other, every macroblock row as one call sequence row_begin / row_step ... / row_end, then the job's finalizer -- the order the
- * GPU's dependency counters would allow anyway.  It checks kernel LOGIC without a GPU; address spaces and the memory model are what the
+ * GPU's dependency counters would allow anyway.  The finalizer is the product's own (enc_finalize.h job_finalize) under a policy that
+ * finds everything there (FinalizerInOrder below).  It checks kernel LOGIC without a GPU; address spaces and the memory model are what the
  * -m gpu tests are for.  Of the wave pipeline's hand-offs, WHAT the reconstruction side has seen of the inter decision when it decides can
- * be scripted (emu_handoffs.h); the waits themselves run on the GPU only.  Never linked into libh264e_mi355x.so.
+ * be scripted, and so can WHEN a finalizer sees the verdict of the frame in front (emu_handoffs.h); the waits themselves run on the GPU
+ * only.  Never linked into libh264e_mi355x.so.
  */
 #ifndef H264E_EMU
 #error "the emulation is built with -DH264E_EMU (tests/emu/Makefile)"
@@ -45,8 +47,30 @@ extern "C" void emu_check_global(const void *p, size_t n, const char *file, int 
 }
 
 #include "../../h264-lab_amd/csrc/enc_row.h"
+#include "../../h264-lab_amd/csrc/enc_finalize.h"
 #include "../../h264-lab_amd/csrc/enc_selftest.h"
 #include "../../include/h264e_hip.h"
+
+/* job_finalize's policy (enc_finalize.h) where the jobs of a launch run one after the other: everything is there.  A row is complete when
+ * asked; nobody else is running, so a verdict flag that is not up will not come up, and the bounded wait for it is one look; a record
+ * goes out with the plain store of its flag */
+struct FinalizerInOrder
+{
+    const h264e_frame_task_t &T;
+    int rows_reached() const { return 0; }
+    template <class IDLE> int wait_row(int, IDLE) const { return 0; }
+    bool prev_up() const { return T.walk_prev->flag >= T.launch_id; }
+    bool wait_prev() const { return prev_up(); }
+    void acquire_prev() const {}
+    void converge() const {}
+    void publish_verdict(h264e_walkrec_t *w) const { w->flag = T.launch_id; }
+    void before_export() const {}
+    void publish_host(h264e_hostdone_t *hd, int sign) const { hd->done = sign*T.launch_id; }
+    void raise_abort() const { *(int *)T.abort_word = T.launch_id; }
+    void raise_err() const {}
+    void stamp(int) const {}
+};
+
 #include "emu_handoffs.h"
 
 /* H264E_EMU_LAUNCH_LOG=path: every launch appends one line with what the host layer decided for it -- the decisions that never change a
@@ -99,55 +123,9 @@ static void bk_launch_mb(const h264e_geom_t &G, int narrow, int variant, int njo
             row_end(*L, G, C, row);
             free(L);
         }
-        /* the job's finalizer (h264e_kernels.hip, workgroup `nmby`): the same row-by-row walk + splice; every row is complete here */
-        int wstatus = 0, first_bad = -1;
-        mv32 ws[2] = { T.exact_state[0], T.exact_state[1] };
-        if (T.walk_on_device && T.walk_prev)
-        {
-            if (T.walk_prev->flag != T.launch_id || T.walk_prev->status != H264E_WALK_OK) wstatus = H264E_WALK_VOID;
-            else { ws[0] = T.walk_prev->state_out[0]; ws[1] = T.walk_prev->state_out[1]; }
-        }
-        JobWalk W;
-        W.begin(ws);
-        SpliceOut so;
-        const bool walking = T.walk_on_device && !wstatus;
-        const h264e_mbrec_t *rec = C.mbrec + (size_t)T.frame_slot*G.nmb;
-        if (!wstatus)
-            (void)splice_frame(G, C, T, so, [&](int, int r) -> int { if (walking) W.rows(G, T, rec, T.traj_out, r); return 0; });
-        if (T.walk_on_device)
-        {
-            if (!wstatus)
-            {
-                W.end(T);
-                first_bad = W.first_bad;
-                ws[0] = W.s[0]; ws[1] = W.s[1];
-                wstatus = first_bad >= 0 ? H264E_WALK_BAD : H264E_WALK_OK;
-            }
-            if (T.walk_out) { T.walk_out->state_out[0] = ws[0]; T.walk_out->state_out[1] = ws[1]; T.walk_out->status = wstatus; T.walk_out->first_bad = first_bad; T.walk_out->flag = T.launch_id; }
-            if (wstatus != H264E_WALK_OK)
-            {
-                if (T.host_done)
-                {
-                    T.host_done->walk_status = wstatus; T.host_done->first_bad = first_bad; T.host_done->state_out[0] = ws[0]; T.host_done->state_out[1] = ws[1];
-                    T.host_done->done = -T.launch_id;
-                }
-                continue;
-            }
-        }
-        finalize_commit(G, C, T, so, T.stepflags);
-        if (T.host_done)
-        {
-            uint32_t nal_bytes[H264E_MAX_SLICES], nal_total = 0;
-            int exp_overflow = 0, in_device = 0;
-            export_frame(G, C, T, nal_bytes, nal_total, exp_overflow, in_device);
-            const h264e_frameout_t &F = C.fout[T.frame_slot];
-            T.host_done->nbytes = nal_total; T.host_done->all_skipped = F.all_skipped;
-            T.host_done->nslices = F.nslices; T.host_done->in_device = in_device;
-            for (int k = 0; k < H264E_MAX_SLICES; k++) T.host_done->slice_nbytes[k] = nal_bytes[k];
-            T.host_done->clusters_moved = F.clusters_moved; T.host_done->overflow = F.overflow | exp_overflow; T.host_done->far_reads = F.far_reads;
-            T.host_done->walk_status = wstatus; T.host_done->first_bad = first_bad; T.host_done->state_out[0] = ws[0]; T.host_done->state_out[1] = ws[1];
-            T.host_done->done = T.launch_id;
-        }
+        /* the job's finalizer (h264e_kernels.hip, workgroup `nmby`): the product's job_finalize; every row is complete here */
+        if (g_verdict.on) verdict_job_finalize(G, C, T);
+        else job_finalize(G, C, T, FinalizerInOrder{ T });
     }
 }
 

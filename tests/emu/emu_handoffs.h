@@ -276,4 +276,115 @@ extern "C" int h264e_emu_handoff_records(int frame, size_t frame_bytes, int32_t 
     return n;
 }
 
+/*
+ * The same for the finalizer (enc_finalize.h job_finalize): on the GPU the verdict of the frame in front arrives whenever the clock has
+ * it -- before this frame's first row, somewhere in the middle, behind its last row.  Here the frame in front is always done, so WHEN its
+ * flag reads "up" is a script.  H264E_EMU_VERDICT (H264E_TEST_KNOBS=1, read with H264E_EMU_HANDOFFS) selects it:
+ *   from_start       up at the first look (what FinalizerInOrder shows)
+ *   at_row@K         not up until the finalizer asks for row K of its own frame
+ *   after_last       not up at any look; it arrives in a wait
+ * A wait for the flag is where time passes: it ends with the flag up under every schedule (a verdict that never comes is a launch failure,
+ * and not scripted).  A row is "late" once: what the finalizer does while it waits for a row runs once in front of every row.
+ * Every run of a finalizer leaves a record (verdict_rec_t, 8 words), in the order they ran, read with h264e_emu_verdict_records.
+ */
+#define H264E_EMU_VERDICT_SCHEDULES      /* h264e_pool.h configures the schedule where it sees this */
+enum { VERDICT_NOT_NEEDED, VERDICT_BY_LOOK, VERDICT_BY_WAIT_IN_SPLICE, VERDICT_BY_WAIT_BEHIND, VERDICT_NEVER };
+typedef struct
+{
+    int32_t frame;                      /* filled in by the reader: the input frame's place, like h264e_emu_handoff_records */
+    int32_t launch_id;
+    int32_t how, row;                   /* VERDICT_*: how the verdict of the frame in front was taken, and the row asked for then (nmby behind the splice) */
+    int32_t status, first_bad;          /* the verdict this frame published (0: none) */
+    int32_t fixed;                      /* the walk ran on the fixed state (more than one slice) */
+    int32_t nmby;
+} verdict_rec_t;
+
+enum { VS_FROM_START, VS_AT_ROW, VS_AFTER_LAST };
+static struct
+{
+    int on, kind, arg;
+    std::vector<std::pair<const uint8_t *, verdict_rec_t> > *runs;
+} g_verdict = { 0, 0, 0, 0 };
+
+/* NULL or "": off.  Returns -1 for a schedule it does not know. */
+static int emu_verdict_configure(const char *s)
+{
+    int rc = 0, v = 0;
+    pthread_mutex_lock(&g_handoff.mu);
+    if (!g_verdict.runs) g_verdict.runs = new std::vector<std::pair<const uint8_t *, verdict_rec_t> >();
+    g_verdict.runs->clear();
+    g_verdict.on = 0; g_verdict.arg = 0;
+    if (s && s[0])
+    {
+        if (!strcmp(s, "from_start")) g_verdict.kind = VS_FROM_START;
+        else if (!strcmp(s, "after_last")) g_verdict.kind = VS_AFTER_LAST;
+        else if (sscanf(s, "at_row@%d", &v) == 1 && v >= 0) { g_verdict.kind = VS_AT_ROW; g_verdict.arg = v; }
+        else rc = -1;
+        g_verdict.on = !rc;
+    }
+    pthread_mutex_unlock(&g_handoff.mu);
+    return rc;
+}
+
+struct FinalizerScripted : FinalizerInOrder
+{
+    verdict_rec_t *r;
+    int kind, arg;
+    int cur_row = 0, spliced = 0, waited = 0;
+    template <class IDLE> int wait_row(int row, IDLE idle) { cur_row = row; return idle() ? 1 : 0; }
+    bool prev_up()
+    {
+        waited = 0;
+        return (kind == VS_FROM_START || (kind == VS_AT_ROW && cur_row >= arg)) && FinalizerInOrder::prev_up();
+    }
+    bool wait_prev()
+    {
+        waited = 1;
+        const bool up = FinalizerInOrder::prev_up();
+        if (!up) r->how = VERDICT_NEVER;
+        return up;
+    }
+    void acquire_prev()
+    {
+        r->how = !waited ? VERDICT_BY_LOOK : spliced ? VERDICT_BY_WAIT_BEHIND : VERDICT_BY_WAIT_IN_SPLICE;
+        r->row = spliced ? r->nmby : cur_row;
+    }
+    void publish_verdict(h264e_walkrec_t *w) const { r->status = w->status; r->first_bad = w->first_bad; FinalizerInOrder::publish_verdict(w); }
+    void stamp(int id) { if (id == 32) spliced = 1; }      /* stamp 32: the splice is over */
+};
+
+static void verdict_job_finalize(const h264e_geom_t &G, const ChainG &C, const h264e_frame_task_t &T)
+{
+    verdict_rec_t r;
+    memset(&r, 0, sizeof(r));
+    r.launch_id = T.launch_id; r.how = VERDICT_NOT_NEEDED; r.row = -1; r.first_bad = -1; r.fixed = T.nslices > 1; r.nmby = G.nmby;
+    FinalizerScripted s{ { T }, &r, g_verdict.kind, g_verdict.arg };
+    job_finalize(G, C, T, s);
+    pthread_mutex_lock(&g_handoff.mu);
+    g_verdict.runs->push_back(std::make_pair(T.in[0], r));
+    pthread_mutex_unlock(&g_handoff.mu);
+}
+
+/* every finalizer run since the schedule was set, in the order they ran; `frame` = the input's place, in frames of `frame_bytes` behind
+ * the lowest input address among them.  Returns their number, -1 when dst is too small. */
+extern "C" int h264e_emu_verdict_records(size_t frame_bytes, int32_t *dst, int cap_records)
+{
+    pthread_mutex_lock(&g_handoff.mu);
+    int n = g_verdict.runs ? (int)g_verdict.runs->size() : 0;
+    if (n > cap_records) n = -1;
+    else if (n)
+    {
+        const uint8_t *base = (*g_verdict.runs)[0].first;
+        for (int i = 0; i < n; i++) if ((*g_verdict.runs)[(size_t)i].first < base) base = (*g_verdict.runs)[(size_t)i].first;
+        for (int i = 0; i < n; i++)
+        {
+            verdict_rec_t r = (*g_verdict.runs)[(size_t)i].second;
+            r.frame = (int32_t)((size_t)((*g_verdict.runs)[(size_t)i].first - base)/frame_bytes);
+            memcpy(dst + 8*i, &r, sizeof(r));
+        }
+    }
+    pthread_mutex_unlock(&g_handoff.mu);
+    return n;
+}
+
 #endif

@@ -1,4 +1,4 @@
-"""Plain models of what the frame finalizer computes (h264-lab_amd/csrc/enc_row.h, "slice splice"), for tests/test_finalizer.py:
+"""Plain models of what the frame finalizer computes (h264-lab_amd/csrc/enc_finalize.h, "slice splice"), for tests/test_finalizer.py:
   * the slice writer, macroblock-serial as the reference writes a slice (h264-lab.h:4247 header, 6451-6456 / 3999 tail), on Python integers
     used as bit strings -- no rows, no words, no carries;
   * what a row wave leaves behind for the finalizer (h264e_rowmeta_t + the row's bits), built from the same per-macroblock bits;

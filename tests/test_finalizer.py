@@ -1,4 +1,4 @@
-"""The frame finalizer's own functions (h264-lab_amd/csrc/enc_row.h "slice splice": splice_frame / splice_words / splice_put / put_ue64,
+"""The frame finalizer's own functions (h264-lab_amd/csrc/enc_finalize.h "slice splice": splice_frame / splice_words / splice_put / put_ue64,
 clusters_step / clusters_walk_range / JobWalk / device_clusters_walk, the `moved` check of finalize_commit) and the host's clusters_walk,
 run through the test hook h264e_hip_selftest_finalizer on operands chosen for their edges, bit exact against tests/finalizer_model.py
 and tests/golden/finalizer.json (made by `oracle/stage_harness.c finalizer` from the reference's own mv_clusters_update and
