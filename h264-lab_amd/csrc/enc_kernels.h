@@ -117,7 +117,8 @@ DEV void bw_ue(BitW &b, uint32_t v)                                             
     bw_put(b, n, v + 1);
 }
 DEV void bw_se(BitW &b, int v) { bw_ue(b, (uint32_t)(v > 0 ? 2*v - 1 : -2*v)); }   /* H:2760 */
-DEV int se_len(int v) { return ue_len((uint32_t)(v > 0 ? 2*v - 1 : -2*v)); }        /* H:3410 */
+/* (the code number + 1 is 2v for v > 0 and 1 - 2v otherwise: the larger of the two, without a branch on a per-lane v) */
+DEV int se_len(int v) { return 2*(32 - clz32((uint32_t)imax(2*v, 1 - 2*v))) - 1; }  /* H:3410 */
 DEV uint32_t bw_bits(const BitW &b) { return b.pos*32u + (uint32_t)b.nacc; }
 
 /* ------------------------------------------------------------------ picture access */

@@ -14,6 +14,16 @@
 #include <stddef.h>
 #include "enc_kernels.h"
 
+/* hooks for test counters of what a partition search met: empty unless defined in front of this header (tests/emu/scan_counters.h) */
+#ifndef SCAN_COUNT_SEARCH
+#define SCAN_COUNT_SEARCH() do { } while (0)
+#define SCAN_COUNT_CHAIN() do { } while (0)
+#define SCAN_COUNT_CLIP(x, y, range) do { } while (0)
+#define SCAN_COUNT_TRUNC(take, b0, b1, b2, b3) do { } while (0)
+#define SCAN_COUNT_MOVE(win, d0) do { } while (0)
+#define SCAN_COUNT_RESTART() do { } while (0)
+#endif
+
 /* predictor context of the motion search (H:3646-3671 saves and restores it around every partitioning; here every partition type works on
  * its own copy): the left column, the top-left column and the top row (+ top-right) of 4x4-block vectors */
 struct GCtx { mv32 mv_left[4], mv_tl[4], mv_top[8]; };
@@ -236,33 +246,38 @@ DEV int diamond_g(RowLds &L, const MbBuf &B, const MbCtx &m, int px, int py, mv3
 {
     const RefView &R = m.rv;
     const uint8_t *b = B.inp + 16*py + px;
-    /* the reference's uint16 cache[8] (H:4993-4997): the SADs of the centre's four neighbours (c0..c3: +x, -x, +y, -y) and of the previous
-     * centre's (p0..p3), 0xffff = not evaluated -- the truncation to 16 bits and the sentinel are observable */
-    int c0, c1, c2, c3, p0, p1, p2, p3;
-#define DX(d) ((d) == 0 ? 4 : (d) == 1 ? -4 : 0)
-#define DY(d) ((d) == 2 ? 4 : (d) == 3 ? -4 : 0)
-#define SEL4(d, a0, a1, a2, a3) ((d) == 0 ? (a0) : (d) == 1 ? (a1) : (d) == 2 ? (a2) : (a3))
+    /* the reference's uint16 cache[8] (H:4993-4997): the SADs of the centre's four neighbours (+x, -x, +y, -y) and of the previous
+     * centre's, 0xffff = not evaluated -- the truncation to 16 bits and the sentinel are observable.  Held PACKED: halfword
+     * d of `cur` / `prv` is cache[d] / cache[4 + d], and what the scan decides per neighbour is a bit d of a 4-bit mask */
+    uint64_t cur, prv;
+    SCAN_COUNT_SEARCH();
+#define HW(c, d) ((uint32_t)((c) >> (16*(d))) & 0xffffu)
     int cost;
     mv32 v;
     const int g = w >> 2, npass = (g*h) >> 4;
+    const int prx = mvx(mv_pred), pry = mvy(mv_pred);
+    int x = mvx(mv), y = mvy(mv), lx, ly;               /* the centre, and the code lengths of its two vector differences */
     for (;;)
     {
         /* H:4999-5051, one CENTRE per iteration instead of one direction: the reference scans the four neighbours of the centre in the order
          * d0, d0+1, d0+2, d0+3 (d0 = the direction it arrived from; 0 at the start), skips those outside the range or already in the cache,
          * caches every cost it takes and moves to the FIRST neighbour that improves on the centre.  With the four SADs taken in one batch that
          * is a priority pick: the improving neighbour with the smallest scan position wins, the neighbours scanned up to it enter the cache. */
-        int d0 = 0, dir_prev = -1;
-        c0 = c1 = c2 = c3 = p0 = p1 = p2 = p3 = 0xffff;
+        int d0 = 0;
+        cur = prv = ~0ull;
+        lx = se_len(x - prx); ly = se_len(y - pry);
+        SCAN_COUNT_CHAIN();
         for (;;)
         {
             /* (the centre lies inside the range -- set_range clips the start vector into it, a move only goes to a neighbour inside it -- so a
              * neighbour can leave it on its own side only: one comparison each instead of in_rect's four) */
-            const int e0 = mvx(mv) + 4 <= range.x1 && c0 == 0xffff, e1 = mvx(mv) - 4 >= range.x0 && c1 == 0xffff;
-            const int e2 = mvy(mv) + 4 <= range.y1 && c2 == 0xffff, e3 = mvy(mv) - 4 >= range.y0 && c3 == 0xffff;
-            if (!(e0 | e1 | e2 | e3)) break;
-            const int want = e0 | (e1 << 1) | (e2 << 2) | (e3 << 3);
+            const uint32_t c01 = (uint32_t)cur, c23 = (uint32_t)(cur >> 32);
+            const int en = ((x + 4 <= range.x1 && (c01 & 0xffffu) == 0xffffu) ? 1 : 0) | ((x - 4 >= range.x0 && c01 >= 0xffff0000u) ? 2 : 0)
+                         | ((y + 4 <= range.y1 && (c23 & 0xffffu) == 0xffffu) ? 4 : 0) | ((y - 4 >= range.y0 && c23 >= 0xffff0000u) ? 8 : 0);
+            SCAN_COUNT_CLIP(x, y, range);
+            if (!en) break;
             int s4[4];
-            const int cx = px + (mvx(mv) >> 2), cy = py + (mvy(mv) >> 2);
+            const int cx = px + (x >> 2), cy = py + (y >> 2);
             if (rv_inside(R, cx - 1, cy - 1, cx + w, cy + h))
             {
                 const lu8 *base = rv_ptr(R, cx, cy);
@@ -289,63 +304,74 @@ DEV int diamond_g(RowLds &L, const MbBuf &B, const MbCtx &m, int px, int py, mv3
                     {
                         const int d = i + 16*k, r = d >> (g >> 1), c4 = d & (g - 1);
                         const uint32_t in4 = lds32(b + 16*r + 4*c4);
-                        if (want & 1) t0 = sad4_u8(ref_load4(R.P, cx + 4*c4 + 1, cy + r), in4, t0);
-                        if (want & 2) t1 = sad4_u8(ref_load4(R.P, cx + 4*c4 - 1, cy + r), in4, t1);
-                        if (want & 4) t2 = sad4_u8(ref_load4(R.P, cx + 4*c4, cy + r + 1), in4, t2);
-                        if (want & 8) t3 = sad4_u8(ref_load4(R.P, cx + 4*c4, cy + r - 1), in4, t3);
+                        if (en & 1) t0 = sad4_u8(ref_load4(R.P, cx + 4*c4 + 1, cy + r), in4, t0);
+                        if (en & 2) t1 = sad4_u8(ref_load4(R.P, cx + 4*c4 - 1, cy + r), in4, t1);
+                        if (en & 4) t2 = sad4_u8(ref_load4(R.P, cx + 4*c4, cy + r + 1), in4, t2);
+                        if (en & 8) t3 = sad4_u8(ref_load4(R.P, cx + 4*c4, cy + r - 1), in4, t3);
                     }
                     sv[0] = (int)t0; sv[1] = (int)t1; sv[2] = (int)t2; sv[3] = (int)t3;
                 }, s4);
             }
-            /* SAD + vector cost of the four neighbours */
+            /* SAD + vector cost of the four neighbours (H:4952: lambda * (se bits of dx + se bits of dy) >> 4).  A neighbour differs from the
+             * centre on one axis: one new code length each, the other axis keeps the centre's */
             int c4v[4];
-            grp_eval4([&](int d) -> int { return mv_cost(m, mvadd(mv, mvmk(DX(d), DY(d))), mv_pred); }, c4v);
+            grp_eval4([&](int d) -> int {
+                const int step = 4 - 8*(d & 1);
+                return MUL_LAMBDA(se_len(((d & 2) ? y - pry : x - prx) + step) + ((d & 2) ? lx : ly), m.lambda_mv);
+            }, c4v);
             const int b0 = s4[0] + c4v[0], b1 = s4[1] + c4v[1], b2 = s4[2] + c4v[2], b3 = s4[3] + c4v[3];
-            /* scan position of every direction, 4 = "does not improve"; the first improving one wins */
-            const int o0 = (0 - d0) & 3, o1 = (1 - d0) & 3, o2 = (2 - d0) & 3, o3 = (3 - d0) & 3;
-            const int wk = imin(imin((e0 && b0 < min_sad) ? o0 : 4, (e1 && b1 < min_sad) ? o1 : 4), imin((e2 && b2 < min_sad) ? o2 : 4, (e3 && b3 < min_sad) ? o3 : 4));
-            const int lim = wk < 4 ? wk : 3;
-            if (e0 && o0 <= lim) c0 = b0 & 0xffff;
-            if (e1 && o1 <= lim) c1 = b1 & 0xffff;
-            if (e2 && o2 <= lim) c2 = b2 & 0xffff;
-            if (e3 && o3 <= lim) c3 = b3 & 0xffff;
-            if (wk == 4) break;
+            /* the improving neighbours among those taken, turned into scan order (bit k = direction d0 + k): the lowest bit is the winner,
+             * and the bits up to it -- all four when nobody improves -- are the positions the reference's loop has scanned */
+            const int imp = en & ((b0 < min_sad ? 1 : 0) | (b1 < min_sad ? 2 : 0) | (b2 < min_sad ? 4 : 0) | (b3 < min_sad ? 8 : 0));
+            const int r = ((imp | (imp << 4)) >> d0) & 15;
+            const int sm = ((r ^ (r - 1)) & 15) << d0, take = en & (sm | (sm >> 4));
+            {
+                /* cache what was scanned and taken: one masked merge of the four truncated costs */
+                const uint32_t n01 = ((uint32_t)b0 & 0xffffu) | ((uint32_t)b1 << 16), n23 = ((uint32_t)b2 & 0xffffu) | ((uint32_t)b3 << 16);
+                const uint32_t m01 = ((take & 1) ? 0xffffu : 0u) | ((take & 2) ? 0xffff0000u : 0u), m23 = ((take & 4) ? 0xffffu : 0u) | ((take & 8) ? 0xffff0000u : 0u);
+                cur = (uint64_t)((c01 & ~m01) | (n01 & m01)) | ((uint64_t)((c23 & ~m23) | (n23 & m23)) << 32);
+                SCAN_COUNT_TRUNC(take, b0, b1, b2, b3);
+            }
+            if (!r) break;
             {
                 /* H:5021-5040: move to the winner; the cache follows (the previous centre becomes the neighbour behind, and the
-                 * neighbour the last two moves enclose -- the "corner" -- is known from the centre before) */
-                const int win = (d0 + wk) & 3;
-                const int corner = dir_prev >= 0 ? SEL4(win, p0, p1, p2, p3) : 0xffff;
-                const int back = win ^ 1, side = dir_prev >= 0 ? (dir_prev ^ 1) : -1;
-                p0 = c0; p1 = c1; p2 = c2; p3 = c3;
-                c0 = back == 0 ? (min_sad & 0xffff) : side == 0 ? corner : 0xffff;
-                c1 = back == 1 ? (min_sad & 0xffff) : side == 1 ? corner : 0xffff;
-                c2 = back == 2 ? (min_sad & 0xffff) : side == 2 ? corner : 0xffff;
-                c3 = back == 3 ? (min_sad & 0xffff) : side == 3 ? corner : 0xffff;
-                min_sad = SEL4(win, b0, b1, b2, b3);
-                mv = mvadd(mv, mvmk(DX(win), DY(win)));
-                dir_prev = win;
+                 * neighbour the last two moves enclose -- the "corner" -- is known from the centre before: halfword `win` of prv, still
+                 * the sentinel on the first move, when d0 is not a direction arrived from) */
+                const int win = (d0 + ctz32((uint32_t)r)) & 3, back = win ^ 1, side = d0 ^ 1;
+                const uint64_t corner = HW(prv, win) ^ 0xffffu, behind = ((uint32_t)min_sad & 0xffffu) ^ 0xffffu;
+                SCAN_COUNT_MOVE(win, d0);
+                prv = cur;
+                cur = ~((((corner << (16*side)) & ~(0xffffull << (16*back)))) | (behind << (16*back)));
+                min_sad = (win & 2) ? ((win & 1) ? b3 : b2) : ((win & 1) ? b1 : b0);
+                /* one step on the winner's axis; that axis' code length is the winner's */
+                const bool vert = (win & 2) != 0;
+                const int at = (vert ? y : x) + 4 - 8*(win & 1), len = se_len(at - (vert ? pry : prx));
+                x = vert ? x : at; y = vert ? at : y;
+                lx = vert ? lx : len; ly = vert ? len : ly;
                 d0 = win;
             }
         }
 
-        const int pri = c3 >= c2 ? 2 : 3, sec = c1 >= c0 ? 0 : 1;
-        v = mvadd(mv, mvmk(DX(pri) + DX(sec), DY(pri) + DY(sec)));
-        if (in_rect(v, range))
+        const int pri = HW(cur, 3) >= HW(cur, 2) ? 2 : 3, sec = HW(cur, 1) >= HW(cur, 0) ? 0 : 1;
+        const int vx = x + (sec ? -4 : 4), vy = y + (pri == 2 ? 4 : -4);
+        v = mvmk(vx, vy);
+        if (vy >= range.y0 && vy <= range.y1 && vx >= range.x0 && vx <= range.x1)
         {
-            cost = grp_sad_ref(R, px + (mvx(v) >> 2), py + (mvy(v) >> 2), b, w, h) + mv_cost(m, v, mv_pred);
+            cost = grp_sad_ref(R, px + (vx >> 2), py + (vy >> 2), b, w, h) + mv_cost(m, v, mv_pred);
             if (cost < min_sad)
             {
-                mv = v;
+                x = vx; y = vy;
                 min_sad = cost;
+                SCAN_COUNT_RESTART();
                 continue;       /* H:5074 goto restart */
             }
         }
         break;
     }
+    mv = mvmk(x, y);
+    const int c0 = (int)HW(cur, 0), c1 = (int)HW(cur, 1), c2 = (int)HW(cur, 2), c3 = (int)HW(cur, 3);
+#undef HW
     STAMP(L, 25);
-#undef SEL4
-#undef DX
-#undef DY
 
 #ifdef H264E_ABLATE
     if (H264E_ABLATE == 3) { grp_interp_luma(R, px, py, mv, w, h, dst); return min_sad; }
@@ -418,9 +444,13 @@ DEV int diamond_g(RowLds &L, const MbBuf &B, const MbCtx &m, int px, int py, mv3
         {
             const int pax = hp_pq_vertical, p_step = pax ? mvy(pq) : mvx(pq), s_step = pax ? mvx(sq) : mvy(sq);
             const int p_mv = pax ? mvy(mv) : mvx(mv), s_mv = pax ? mvx(mv) : mvy(mv), p_pr = pax ? mvy(mv_pred) : mvx(mv_pred), s_pr = pax ? mvx(mv_pred) : mvy(mv_pred);
-            int P[4], S[4];
-            grp_eval4([&](int k) -> int { return se_len((int16_t)(p_mv + k*p_step) - p_pr); }, P);
-            grp_eval4([&](int k) -> int { return se_len((int16_t)(s_mv + k*s_step) - s_pr); }, S);
+            /* (the lengths at 0 steps are the centre's, which the scan carried along; the four at 1 and 2 steps take one evaluation) */
+            int PS[4];
+            grp_eval4([&](int k) -> int {
+                const int n = (k & 1) + 1;
+                return se_len((int16_t)((k & 2) ? s_mv + n*s_step : p_mv + n*p_step) - ((k & 2) ? s_pr : p_pr));
+            }, PS);
+            const int P[3] = { pax ? ly : lx, PS[0], PS[1] }, S[3] = { pax ? lx : ly, PS[2], PS[3] };
             c8[0] = MUL_LAMBDA(P[2] + S[0], m.lambda_mv); c8[1] = MUL_LAMBDA(P[1] + S[0], m.lambda_mv); c8[2] = MUL_LAMBDA(P[0] + S[2], m.lambda_mv);
             c8[3] = MUL_LAMBDA(P[0] + S[1], m.lambda_mv); c8[4] = MUL_LAMBDA(P[1] + S[1], m.lambda_mv); c8[5] = MUL_LAMBDA(P[2] + S[2], m.lambda_mv);
             c8[6] = MUL_LAMBDA(P[2] + S[1], m.lambda_mv);

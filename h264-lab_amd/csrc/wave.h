@@ -83,6 +83,7 @@ DEV uint32_t sad4_u8(uint32_t a, uint32_t b, uint32_t acc)
     return acc;
 }
 DEV int clz32(uint32_t v) { return __builtin_clz(v); }
+DEV int ctz32(uint32_t v) { return __builtin_ctz(v); }
 DEV uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
 
 /* ---- lane groups (see the device build below): the emulation runs the four groups one after the other */
@@ -268,6 +269,7 @@ template <class F> DEV void wave_sum8(F f, int out[8])
 template <class F> DEV uint64_t wave_ballot(F f) { return __ballot(f(LANE)); }
 DEV uint32_t sad4_u8(uint32_t a, uint32_t b, uint32_t acc) { return __builtin_amdgcn_sad_u8(a, b, acc); }
 DEV int clz32(uint32_t v) { return __clz((int)v); }
+DEV int ctz32(uint32_t v) { return __builtin_ctz(v); }                                  /* v != 0 */
 DEV uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
 
 /*
