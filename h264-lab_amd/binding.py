@@ -82,6 +82,15 @@ _DEV_FORMATS["i444"] = DEV_FORMAT_I444
 # the names of the 16-bit formats: (layout bits, the only depth the name allows or None for depth=)
 _HBD_FORMATS = {"i420_16": (DEV_FORMAT_I420, None), "nv12_16": (DEV_FORMAT_NV12, None), "i444_16": (DEV_FORMAT_I444, None),
                 "p010": (DEV_FORMAT_NV12, 16), "p016": (DEV_FORMAT_NV12, 16)}
+# capture and pro-video surfaces: 4:2:2 chroma (bit 14: I420 and NV12) and its packed orders (bits 2-3: on I420 | 4:2:2 alone)
+DEV_CHROMA_422, DEV_PACK_YUYV, DEV_PACK_UYVY = 0x4000, 0x4, 0x8
+DEV_FORMAT_I422, DEV_FORMAT_NV16 = DEV_FORMAT_I420 | DEV_CHROMA_422, DEV_FORMAT_NV12 | DEV_CHROMA_422
+DEV_FORMAT_YUYV, DEV_FORMAT_UYVY = DEV_FORMAT_I422 | DEV_PACK_YUYV, DEV_FORMAT_I422 | DEV_PACK_UYVY
+DEV_FORMAT_P216 = DEV_FORMAT_P210 = DEV_FORMAT_NV16 | DEV_DEPTH(16)
+DEV_FORMAT_Y216 = DEV_FORMAT_Y210 = DEV_FORMAT_YUYV | DEV_DEPTH(16)
+_DEV_FORMATS.update({"i422": DEV_FORMAT_I422, "nv16": DEV_FORMAT_NV16, "yuyv": DEV_FORMAT_YUYV, "yuy2": DEV_FORMAT_YUYV, "uyvy": DEV_FORMAT_UYVY})
+_HBD_FORMATS.update({"i422_16": (DEV_FORMAT_I422, None), "nv16_16": (DEV_FORMAT_NV16, None), "yuyv_16": (DEV_FORMAT_YUYV, None), "uyvy_16": (DEV_FORMAT_UYVY, None),
+                     "p210": (DEV_FORMAT_NV16, 16), "p216": (DEV_FORMAT_NV16, 16), "y210": (DEV_FORMAT_YUYV, 16), "y216": (DEV_FORMAT_YUYV, 16)})
 # float planar RGB: format code -> (bytes per sample, the torch dtype's name, the __cuda_array_interface__ typestr or None)
 _FLOAT_SAMPLES = {DEV_FORMAT_RGBP_F16: (2, "float16", "<f2"), DEV_FORMAT_RGBP_BF16: (2, "bfloat16", None), DEV_FORMAT_RGBP_F32: (4, "float32", "<f4")}
 
@@ -215,6 +224,37 @@ def _hbd_planes(frame, f, name, w, h):
     return [(ptr, w * sb, st), (ptr + w * h * sb, w // 2 * sb, st), (ptr + (w * h + (w // 2) * (h // 2)) * sb, w // 2 * sb, st)]
 
 
+def _c422_planes(frame, f, name, w, h):
+    """the planes of a 4:2:2 frame of 8- or 16-bit samples: [(pointer, row stride in bytes, stream)]"""
+    sb = 2 if f & 0xf00 else 1
+    u16 = name if sb == 2 else None
+    several = isinstance(frame, (tuple, list)) and not all(isinstance(x, int) for x in frame)
+    if f & (DEV_PACK_YUYV | DEV_PACK_UYVY):
+        if several and len(frame) == 1:
+            frame = frame[0]
+        ptr, shape, strides, st = _dev_array(frame, u16=u16)
+        if shape is not None and not ((tuple(shape) == (h, 2 * w) and strides[1] == sb) or (tuple(shape) == (h, w, 2) and tuple(strides[1:]) == (2 * sb, sb))):
+            raise H264EError("device input: packed 4:2:2 must be a (%d, %d) or (%d, %d, 2) array whose rows are contiguous (any row stride), got shape %r strides %r (bytes)"
+                             % (h, 2 * w, h, w, shape, strides))
+        return [(ptr, strides[0], st)]
+    if several and len(frame) == (2 if (f & 3) == DEV_FORMAT_NV12 else 3):
+        if (f & 3) == DEV_FORMAT_NV12:
+            return [_plane_n(frame[0], h, w, sb, "Y", u16), _plane_n(frame[1], h, w, sb, "UV", u16)]
+        return [_plane_n(frame[0], h, w, sb, "Y", u16), _plane_n(frame[1], h, w // 2, sb, "U", u16), _plane_n(frame[2], h, w // 2, sb, "V", u16)]
+    if several:
+        raise H264EError("device input: %s takes %s or one (%d, %d) array" % ("NV16" if (f & 3) == DEV_FORMAT_NV12 else "I422", "(y, uv)" if (f & 3) == DEV_FORMAT_NV12 else "(y, u, v)", 2 * h, w))
+    ptr, shape, strides, st = _dev_array(frame, u16=u16)
+    if (f & 3) == DEV_FORMAT_NV12:                  # the luma rows, then as many rows of U,V pairs: any row stride
+        if shape is not None and (tuple(shape) != (2 * h, w) or strides[1] != sb):
+            raise H264EError("device input: NV16 in one array must be (%d, %d) with a contiguous last axis, got shape %r strides %r (bytes)" % (2 * h, w, shape, strides))
+        return [(ptr, strides[0], st), (ptr + h * strides[0], strides[0], st)]
+    if shape is not None and (tuple(shape) != (2 * h, w) or tuple(strides) != (w * sb, sb)):
+        raise H264EError("device input: packed I422 must be a contiguous (%d, %d) array, got shape %r strides %r (bytes)" % (2 * h, w, shape, strides))
+    if shape is None and strides[0] != w * sb:
+        raise H264EError("device input: packed I422 has row stride %d, got %d" % (w * sb, strides[0]))
+    return [(ptr, w * sb, st), (ptr + w * h * sb, w // 2 * sb, st), (ptr + (w * h + (w // 2) * h) * sb, w // 2 * sb, st)]
+
+
 def _require_uint8(a):
     """planar RGB takes unsigned 8-bit samples only: anything else is refused here, with its type in the message"""
     if hasattr(a, "data_ptr") and hasattr(a, "stride"):
@@ -252,7 +292,7 @@ def _float_plane(a, f, rows, w, what):
 def dev_format(fmt, frame=None, depth=None):
     """the H264E_DEV_FORMAT_* code of a format name or number; "rgbpf" is float planar RGB with the sample type of `frame` (a float16,
     bfloat16 or float32 array, or three such planes); depth: the significant bits (9 .. 16, default 16) of the 16-bit names "i420_16",
-    "nv12_16" and "i444_16" ("p010" and "p016" are MSB aligned: 16)"""
+    "nv12_16", "i444_16", "i422_16", "nv16_16", "yuyv_16" and "uyvy_16" ("p010", "p016", "p210", "p216", "y210" and "y216" are MSB aligned: 16)"""
     if isinstance(fmt, str) and fmt in _HBD_FORMATS:
         base, fixed = _HBD_FORMATS[fmt]
         d = 16 if depth is None else int(depth)
@@ -278,13 +318,18 @@ def dev_frame(frame, fmt, w, h, stream=None, depth=None):
     samples in [0, 1], and "rgbpf" whichever of the three the array's dtype says; "i444": three (h, w) planes (y, u, v) or one (3, h, w)
     array with any channel and row strides; "i420_16", "nv12_16" ("p010", "p016"), "i444_16": the same shapes as their 8-bit layouts of
     torch.uint16 / torch.int16 ("<u2" / "<i2") samples with `depth` significant bits, LSB aligned (default 16: an MSB-aligned decoder
-    surface), quantised to 8 bits as they are loaded.  Arrays: torch tensors, anything with
+    surface), quantised to 8 bits as they are loaded.  4:2:2, chroma of the luma's height and half its width: "i422" three planes (y, u of
+    (h, w/2), v) or one contiguous (2h, w) array in ffmpeg's buffer order; "nv16" (y, uv of (h, w)) or one (2h, w) array, luma rows first;
+    "yuyv" (alias "yuy2") and "uyvy" ONE (h, 2w) or (h, w, 2) array with any row stride; "i422_16", "nv16_16", "yuyv_16", "uyvy_16" the same
+    shapes of 16-bit samples with `depth`, "p210" / "p216" (nv16_16) and "y210" / "y216" (yuyv_16) MSB aligned.  Arrays: torch tensors, anything with
     __cuda_array_interface__ (no bfloat16 there), or (pointer, row stride in bytes) pairs.  stream: the hipStream_t (an int) that writes
     the frame; by default torch's current stream for torch tensors.  Returns (DevFrame, the objects that must stay alive during the call)."""
     f = dev_format(fmt, frame, depth)
     pb, planes = 0, []
     _one_runtime()
-    if f & 0x1f00 and not f & ~0x1f03 and (f & 3) < 2:
+    if f & DEV_CHROMA_422 and not f & ~0x4f0d and (f & 3) < 2:
+        planes = _c422_planes(frame, f, fmt, w, h)
+    elif f & 0x1f00 and not f & ~0x1f03 and (f & 3) < 2:
         planes = _hbd_planes(frame, f, fmt, w, h)
     elif f == DEV_FORMAT_I420:
         if isinstance(frame, (tuple, list)) and len(frame) == 3:
@@ -620,7 +665,7 @@ class Encoder:
         """H264E_encode_device: the frame is taken from GPU memory (see dev_frame for what `frame` may be: fmt "i420", "nv12", "rgb", "rgbp" or float "rgbp_f16" / "rgbp_bf16" / "rgbp_f32" / "rgbpf");
         needs const_input=1.  The frame's memory may be reused as soon as this returns.  src_size=(w, h): the frame has that size and is
         reduced to the encoder's picture (H264E_encode_device_scaled), crop=(x, y, w, h): only that window of it.  depth: the significant
-        bits of the 16-bit formats "i420_16" / "nv12_16" / "i444_16" (9 .. 16, default 16)."""
+        bits of the 16-bit formats "i420_16" / "nv12_16" / "i444_16" / "i422_16" / "nv16_16" / "yuyv_16" / "uyvy_16" (9 .. 16, default 16)."""
         win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)
         d, _keep = dev_frame(frame, fmt, sw, sh, stream, depth)
         self.rp.frame_type = frame_type
@@ -932,7 +977,7 @@ class ClipEncoder:
         """H264E_clip_upload_device: `frames` is a sequence of frames in GPU memory (see dev_frame: fmt "i420", "nv12", "rgb", "rgbp" or float "rgbp_f16" / "rgbp_bf16" / "rgbp_f32" / "rgbpf"), frame
         first + i from frames[i].  Their memory may be reused as soon as this returns.  src_size=(w, h): the frames have that size and are
         reduced to the clip's picture (H264E_clip_upload_device_scaled), crop=(x, y, w, h): only that window of them.  depth: the
-        significant bits of the 16-bit formats "i420_16" / "nv12_16" / "i444_16" (9 .. 16, default 16)."""
+        significant bits of the 16-bit formats "i420_16" / "nv12_16" / "i444_16" / "i422_16" / "nv16_16" / "yuyv_16" / "uyvy_16" (9 .. 16, default 16)."""
         win, (sw, sh) = dev_window(src_size, crop, self.w, self.h)
         made = [dev_frame(f, fmt, sw, sh, stream, depth) for f in frames]
         arr = (DevFrame * max(len(made), 1))(*[m[0] for m in made])

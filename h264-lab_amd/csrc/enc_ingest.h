@@ -52,6 +52,7 @@ typedef struct
     int sample;                         /* H264E_SAMPLE_*: RGBP only, the launch picks the kernel by it (strides stay in bytes) */
     int depth, c444;                    /* enc_hbd.h: 16-bit samples with `depth` significant bits (0: 8-bit samples); U and V of the luma's size */
     int qround, qshift;                 /* ... and their quantiser: 1 << (depth - 9), depth - 8 */
+    int c422, pack;                     /* enc_422.h: U and V of the luma's height and half its width; H264E_PACK_*: all three in plane[0] */
 } h264e_ingest_src_t;
 
 /* the first nb of NB source bytes at p into v, byte k in bits 8*(k & 3) of v[k >> 2]: dwords where p is dword aligned and all NB

@@ -54,6 +54,7 @@ typedef struct
     int sample;                         /* H264E_SAMPLE_*: planar RGB only; float planes have step = the sample's bytes */
     int depth, c444, thc, tiles_y;      /* enc_hbd.h: 16-bit samples (0: 8-bit); 4:4:4 chroma, its destination rows per tile, and the rows of tiles of the plane with the most */
     int qround, qshift;                 /* ... the 16-bit quantiser: 1 << (depth - 9), depth - 8 */
+    int c422, pack;                     /* enc_422.h: 4:2:2 chroma (rows per tile in thc); the three components share one packed plane */
 } h264e_scale_src_t;
 
 typedef struct

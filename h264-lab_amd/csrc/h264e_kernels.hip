@@ -18,6 +18,7 @@
  *   h264e_scale_kernel   the same as the ingest for a source of another size (enc_scale.h): a window of an I420 / NV12 frame, box-filtered down to the slot.
  *   h264e_scale_rgb_kernel  ... of a planar RGB frame (enc_scale_rgb.h): the three channels box-filtered into LDS, converted to I420 from there.
  *   h264e_ingest_hbd_kernel<SB, C444>, h264e_scale_hbd_kernel<SB>  the I420 / NV12 paths for 16-bit samples and 4:4:4 chroma (enc_hbd.h).
+ *   h264e_ingest_422_kernel<SB, PACK>, h264e_scale_422_kernel<SB>  4:2:2 input: I422, NV16 and packed YUYV / UYVY, 8- or 16-bit (enc_422.h).
  *   h264e_ingest_float_kernel<ST>, h264e_scale_rgb_float_kernel<ST>, h264e_egress_float_kernel<ST>  the planar RGB paths for float16 /
  *                        bfloat16 / float32 samples in [0, 1], quantised on the way in and divided by 255 on the way out.
  *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
@@ -44,6 +45,7 @@
 #include "enc_scale.h"
 #include "enc_scale_rgb.h"
 #include "enc_hbd.h"
+#include "enc_422.h"
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
 #include "enc_lookahead_search.h"
@@ -664,6 +666,15 @@ template <int SB, int C444> __global__ void __launch_bounds__(256) h264e_ingest_
     else ingest_hbd_chroma<SB, C444>(S, (GLOBAL_AS uint8_t *)dst, g, y);
 }
 
+/* ... of 4:2:2 sources (enc_422.h): the same grid (a chroma row of the picture is a pair of source rows); PACK = H264E_PACK_*: the one
+ * plane of YUYV / UYVY.  Kernels of their own again: the existing formats launch what they launched */
+template <int SB, int PACK> __global__ void __launch_bounds__(256) h264e_ingest_422_kernel(h264e_ingest_src_t S, uint8_t *dst)
+{
+    const int g = (int)(blockIdx.x*blockDim.x + threadIdx.x), y = (int)blockIdx.y;
+    if (blockIdx.z == 0) ingest_422_luma<SB, PACK>(S, (GLOBAL_AS uint8_t *)dst, g, y);
+    else ingest_422_chroma<SB, PACK>(S, (GLOBAL_AS uint8_t *)dst, g, y);
+}
+
 /* device-resident output over one picture (enc_egress.h): grid.z = 0 luma / 1 both chroma planes for I420 and NV12, grid.y = row; the RGB
  * formats have grid.z = 0 alone and grid.y = a PAIR of rows (one chroma row); grid.x * 256 lanes x 4 samples along the row.  Every workgroup
  * reads its own bytes of the picture and writes its own bytes of the destination (no inter-workgroup traffic, no LDS). */
@@ -711,6 +722,29 @@ template <int SB> __global__ void __launch_bounds__(256) h264e_scale_hbd_kernel(
     for (int it = (int)threadIdx.x; it < items; it += 256)
     {
         if (SB == 2) scale_hpass_hbd(L, S.c[comp], T, S.qround, S.qshift, it); else scale_hpass(L, S.c[comp], T, it);
+    }
+    __syncthreads();
+    for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_vpass(L, T, (GLOBAL_AS uint8_t *)(dst + scale_plane_offset(S, comp)), it);
+}
+
+/* ... of 4:2:2 sources (enc_422.h): the chroma planes have half the window's width and all of its height.  8-bit taps of planes and U,V
+ * pairs go through scale_hpass as they are, those of a packed row (steps 2 and 4) through scale_hpass_pk, 16-bit taps through
+ * scale_hpass_hbd at any step.  S.pack is uniform per launch */
+template <int SB> __global__ void __launch_bounds__(256) h264e_scale_422_kernel(h264e_scale_src_t S, uint8_t *dst)
+{
+    __shared__ __attribute__((aligned(16))) ScaleLds lds;
+    LDS_AS ScaleLds *L = (LDS_AS ScaleLds *)&lds;
+    const int comp = (int)blockIdx.z;
+    ScaleTile T;
+    if (!scale_tile_422(S, comp, (int)blockIdx.x, (int)blockIdx.y, T)) return;  /* uniform per workgroup */
+    scale_tables(L, T, (int)threadIdx.x);
+    __syncthreads();
+    const int items = scale_src_rows(L, T) << 6;
+    for (int it = (int)threadIdx.x; it < items; it += 256)
+    {
+        if (SB == 2) scale_hpass_hbd(L, S.c[comp], T, S.qround, S.qshift, it);
+        else if (S.pack) scale_hpass_pk(L, S.c[comp], T, it);
+        else scale_hpass(L, S.c[comp], T, it);
     }
     __syncthreads();
     for (int it = (int)threadIdx.x; it < T.nrows*16; it += 256) scale_vpass(L, T, (GLOBAL_AS uint8_t *)(dst + scale_plane_offset(S, comp)), it);
@@ -963,6 +997,17 @@ static void bk_launch_denoise(const uint8_t *in, const uint8_t *prev, uint8_t *o
 static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t st)
 {
     const unsigned gx = (unsigned)((((S.width + 3) >> 2) + 255) >> 8);
+    if (S.c422)
+    {
+        const dim3 grid(gx, (unsigned)S.height, 2);
+#define LAUNCH_422(PACK) do { if (S.depth) hipLaunchKernelGGL((h264e_ingest_422_kernel<2, PACK>), grid, dim3(256), 0, st, S, dst); \
+                              else hipLaunchKernelGGL((h264e_ingest_422_kernel<1, PACK>), grid, dim3(256), 0, st, S, dst); } while (0)
+        if (S.pack == H264E_PACK_YUYV) LAUNCH_422(H264E_PACK_YUYV);
+        else if (S.pack == H264E_PACK_UYVY) LAUNCH_422(H264E_PACK_UYVY);
+        else LAUNCH_422(H264E_PACK_NONE);
+#undef LAUNCH_422
+        return;
+    }
     if (S.depth || S.c444)
     {
         const dim3 grid(gx, (unsigned)S.height, 2);
@@ -981,6 +1026,13 @@ static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hi
 }
 static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t st)
 {
+    if (S.c422)
+    {
+        const dim3 grid((unsigned)((S.dw + SCL_TW - 1)/SCL_TW), (unsigned)S.tiles_y, 3);
+        if (S.depth) hipLaunchKernelGGL(h264e_scale_422_kernel<2>, grid, dim3(256), 0, st, S, dst);
+        else hipLaunchKernelGGL(h264e_scale_422_kernel<1>, grid, dim3(256), 0, st, S, dst);
+        return;
+    }
     if (S.depth || S.c444)
     {
         const dim3 grid((unsigned)((S.dw + SCL_TW - 1)/SCL_TW), (unsigned)S.tiles_y, 3);

@@ -17,6 +17,7 @@
 #include "enc_scale.h"
 #include "enc_scale_rgb.h"
 #include "enc_hbd.h"
+#include "enc_422.h"
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
 #include "enc_lookahead_search.h"
@@ -1170,9 +1171,22 @@ template <int SB, int C444> static void emu_ingest_hbd(const h264e_ingest_src_t 
     for (int y = 0; y < S.height; y++)
         for (int g = 0; g < (S.width + 3)/4; g++) { ingest_hbd_luma<SB>(S, dst, g, y); ingest_hbd_chroma<SB, C444>(S, dst, g, y); }
 }
+/* ... of 4:2:2 sources (enc_422.h) */
+template <int SB, int PACK> static void emu_ingest_422(const h264e_ingest_src_t &S, uint8_t *dst)
+{
+    for (int y = 0; y < S.height; y++)
+        for (int g = 0; g < (S.width + 3)/4; g++) { ingest_422_luma<SB, PACK>(S, dst, g, y); ingest_422_chroma<SB, PACK>(S, dst, g, y); }
+}
+template <int SB> static void emu_ingest_422_by_pack(const h264e_ingest_src_t &S, uint8_t *dst)
+{
+    if (S.pack == H264E_PACK_YUYV) emu_ingest_422<SB, H264E_PACK_YUYV>(S, dst);
+    else if (S.pack == H264E_PACK_UYVY) emu_ingest_422<SB, H264E_PACK_UYVY>(S, dst);
+    else emu_ingest_422<SB, H264E_PACK_NONE>(S, dst);
+}
 static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStream_t)
 {
-    if (S.depth && S.c444) emu_ingest_hbd<2, 1>(S, dst);
+    if (S.c422) { if (S.depth) emu_ingest_422_by_pack<2>(S, dst); else emu_ingest_422_by_pack<1>(S, dst); }
+    else if (S.depth && S.c444) emu_ingest_hbd<2, 1>(S, dst);
     else if (S.depth) emu_ingest_hbd<2, 0>(S, dst);
     else if (S.c444) emu_ingest_hbd<1, 1>(S, dst);
     else EMU_BY_SAMPLE(S.sample, emu_ingest, S, dst);
@@ -1194,6 +1208,28 @@ static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_
 {
     ScaleLds *L = (ScaleLds *)malloc(sizeof(ScaleLds));
     if (!L) return;
+    if (S.c422)                         /* enc_422.h: the kernel's choice of horizontal pass */
+    {
+        for (int comp = 0; comp < 3; comp++)
+            for (int ty = 0; ty < S.tiles_y; ty++)
+                for (int tx = 0; tx < (S.dw + SCL_TW - 1)/SCL_TW; tx++)
+                {
+                    ScaleTile T;
+                    if (!scale_tile_422(S, comp, tx, ty, T)) continue;
+                    memset(L, 0xEE, sizeof(*L));
+                    for (int t = 0; t < 256; t++) scale_tables(L, T, t);
+                    const int items = scale_src_rows(L, T) << 6;
+                    for (int it = 0; it < items; it++)
+                    {
+                        if (S.depth) scale_hpass_hbd(L, S.c[comp], T, S.qround, S.qshift, it);
+                        else if (S.pack) scale_hpass_pk(L, S.c[comp], T, it);
+                        else scale_hpass(L, S.c[comp], T, it);
+                    }
+                    for (int it = 0; it < T.nrows*16; it++) scale_vpass(L, T, dst + scale_plane_offset(S, comp), it);
+                }
+        free(L);
+        return;
+    }
     if (S.depth || S.c444)              /* enc_hbd.h: a source geometry per plane, 16-bit taps quantised by the horizontal pass */
     {
         for (int comp = 0; comp < 3; comp++)
@@ -1272,18 +1308,20 @@ static int ingest_is_device_memory(const h264e_hip_pool_t *p, const void *q, siz
 #endif
 
 /* H264E_dev_frame_t.format: the layout in bits 0-1, the sample type in bits 4-5 (planar RGB only) and, on the way in alone (hbd != NULL),
- * the depth of 16-bit samples in bits 8-11 (depth - 8: I420 and NV12) and 4:4:4 chroma in bit 12 (I420); nothing else.  *sb = a sample's
- * bytes, hbd[0] = the depth (0: 8-bit samples), hbd[1] = 4:4:4 */
+ * the depth of 16-bit samples in bits 8-11 (depth - 8: I420 and NV12), 4:4:4 chroma in bit 12 (I420), 4:2:2 chroma in bit 14 (I420 and
+ * NV12) and its packed orders in bits 2-3 (I420 | 4:2:2); nothing else.  *sb = a sample's bytes, hbd[0] = the depth (0: 8-bit samples),
+ * hbd[1] = 4:4:4, hbd[2] = 4:2:2, hbd[3] = H264E_PACK_* */
 #define H264E_SAMPLE_U16 4              /* the name of a 16-bit sample in the messages */
-static const char *const k_format_names[4] = { "I420", "NV12", "RGB", "RGBP" }, *const k_sample_names[5] = { "u8", "f16", "bf16", "f32", "u16" };
+static const char *const k_format_names[4] = { "I420", "NV12", "RGB", "RGBP" }, *const k_sample_names[5] = { "u8", "f16", "bf16", "f32", "u16" },
+                  *const k_pack_names[3] = { "", "YUYV", "UYVY" };
 static int dev_format_split(const char *who, int format, int *base, int *sample, int *sb, int *hbd)
 {
-    const int dcode = hbd ? (format >> 8) & 15 : 0, c444 = hbd ? (format >> 12) & 1 : 0;
-    if (format & ~(hbd ? 0x1f33 : 0x33) || dcode > 8) FAIL("%s: unknown format %d", who, format);
+    const int dcode = hbd ? (format >> 8) & 15 : 0, c444 = hbd ? (format >> 12) & 1 : 0, c422 = hbd ? (format >> 14) & 1 : 0, pk = hbd ? (format >> 2) & 3 : 0;
+    if (format & ~(hbd ? 0x5f3f : 0x33) || dcode > 8) FAIL("%s: unknown format %d", who, format);
     *base = format & 3; *sample = (format >> 4) & 3;
     if (hbd)
     {
-        hbd[0] = dcode ? dcode + 8 : 0; hbd[1] = c444;
+        hbd[0] = dcode ? dcode + 8 : 0; hbd[1] = c444; hbd[2] = c422; hbd[3] = pk;
         if (dcode && *sample)
             FAIL("%s: format %d asks for both %d-bit integer samples (0x%x) and %s samples (0x%x) of %s (format %d): one sample type", who, format, dcode + 8, dcode << 8,
                  k_sample_names[*sample], *sample << 4, k_format_names[*base], *base);
@@ -1292,6 +1330,18 @@ static int dev_format_split(const char *who, int format, int *base, int *sample,
                  dcode ? "16-bit samples" : "4:4:4 chroma", k_format_names[*base], *base);
         if (c444 && *base == H264E_INGEST_NV12)
             FAIL("%s: format %d asks for 4:4:4 chroma (0x1000) of NV12 (format %d): 4:4:4 is three planes, I420 (format %d) only", who, format, *base, H264E_INGEST_I420);
+        if (pk == 3) FAIL("%s: format %d sets both pack bits (0xc): one order of the packed samples, YUYV (0x4) or UYVY (0x8)", who, format);
+        if (pk && !c422)
+            FAIL("%s: unknown format %d: packed %s samples (0x%x) come with 4:2:2 chroma (0x4000) alone", who, format, k_pack_names[pk], pk << 2);
+        if (c422 && c444) FAIL("%s: format %d asks for both 4:2:2 chroma (0x4000) and 4:4:4 chroma (0x1000): one chroma geometry", who, format);
+        if (c422 && *sample)
+            FAIL("%s: format %d asks for 4:2:2 chroma (0x4000) of %s samples (0x%x): 4:2:2 takes 8-bit samples or 16-bit integer words", who, format, k_sample_names[*sample], *sample << 4);
+        if (c422 && (*base == H264E_INGEST_RGB || *base == H264E_INGEST_RGBP))
+            FAIL("%s: format %d asks for %s of %s (format %d): 4:2:2 chroma is I420 and NV12 only, packed samples I420 only", who, format,
+                 pk ? "packed 4:2:2 samples" : "4:2:2 chroma", k_format_names[*base], *base);
+        if (pk && *base == H264E_INGEST_NV12)
+            FAIL("%s: format %d asks for packed %s samples (0x%x) of NV12 (format %d): a packed frame is one plane, on I420 (format %d) only", who, format, k_pack_names[pk], pk << 2,
+                 *base, H264E_INGEST_I420);
     }
     *sb = *sample == H264E_SAMPLE_F32 ? 4 : *sample || dcode ? 2 : 1;
     if (*sample && *base != H264E_INGEST_RGBP)
@@ -1319,7 +1369,7 @@ extern "C" int h264e_hip_set_color(h264e_hip_pool_t *p, int bt709, int full_rang
 /* everything that is refused, without a launch; fills the kernel's view of the source */
 static int ingest_check(const h264e_hip_pool_t *p, int slot, int dev_format, const void *const planes[3], const int strides[3], int pixel_bytes, h264e_ingest_src_t *S)
 {
-    int format, sample, sb, hbd[2];
+    int format, sample, sb, hbd[4];
     if (!p || !planes || !strides) FAIL("ingest_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("ingest_device: slot %d outside the %d resident frames", slot, p->frames_resident);
     if (dev_format_split("ingest_device", dev_format, &format, &sample, &sb, hbd)) return -1;
@@ -1328,18 +1378,20 @@ static int ingest_check(const h264e_hip_pool_t *p, int slot, int dev_format, con
     S->format = format; S->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1; S->sample = sample;
     S->width = p->G.width; S->height = p->G.height;
     S->cm = p->cm;
-    S->depth = hbd[0]; S->c444 = hbd[1];
+    S->depth = hbd[0]; S->c444 = hbd[1]; S->c422 = hbd[2]; S->pack = hbd[3];
     if (hbd[0]) { S->qround = 1 << (hbd[0] - 9); S->qshift = hbd[0] - 8; }
-    const int nplanes = format == H264E_INGEST_I420 || format == H264E_INGEST_RGBP ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
+    const int nplanes = hbd[3] ? 1 : format == H264E_INGEST_I420 || format == H264E_INGEST_RGBP ? 3 : format == H264E_INGEST_NV12 ? 2 : 1;
     for (int k = 0; k < nplanes; k++)
     {
-        /* bytes and rows of source plane k: RGB pixels; full-size luma, R, G, B and 4:4:4 chroma planes (sb bytes per sample); half-size chroma (NV12: U,V pairs, so `width` samples again) */
-        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP || hbd[1]) ? S->width*sb : (S->width/2)*sb;
+        /* bytes and rows of source plane k: RGB pixels; full-size luma, R, G, B and 4:4:4 chroma planes (sb bytes per sample); half-size chroma (NV12: U,V pairs, so `width` samples again);
+         * a packed 4:2:2 row holds two samples per pixel; 4:2:2 chroma planes have all the rows */
+        const int row_bytes = format == H264E_INGEST_RGB ? S->width*pixel_bytes : hbd[3] ? 2*S->width*sb
+                            : (k == 0 || format == H264E_INGEST_NV12 || format == H264E_INGEST_RGBP || hbd[1]) ? S->width*sb : (S->width/2)*sb;
         if (!planes[k]) FAIL("ingest_device: plane %d is NULL", k);
         if (dev_sample_aligned("ingest_device", k, planes[k], strides[k], sb, sample)) return -1;
         if (strides[k] < row_bytes) FAIL("ingest_device: stride %d of plane %d is below its %d row bytes", strides[k], k, row_bytes);
 #ifndef H264E_EMU
-        const int rows = k == 0 || format == H264E_INGEST_RGBP || hbd[1] ? S->height : S->height/2;
+        const int rows = k == 0 || format == H264E_INGEST_RGBP || hbd[1] || hbd[2] ? S->height : S->height/2;
         const void *q = planes[k];
         if (!ingest_is_device_memory(p, q, (size_t)(rows - 1)*(size_t)strides[k] + (size_t)row_bytes))
             FAIL("ingest_device: plane %d (%p, %d rows %d bytes apart) is not memory of device %d, or not inside one allocation", k, planes[k], rows, strides[k], p->device);
@@ -1406,7 +1458,7 @@ extern "C" int h264e_hip_ingest_device(h264e_hip_pool_t *p, int slot, int format
  * device memory inside one allocation is [the window's first byte, the last byte of its last row] of every plane. */
 static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, const void *const planes[3], const int strides[3], const int *win, h264e_scale_src_t *S)
 {
-    int format, sample, sb, hbd[2];
+    int format, sample, sb, hbd[4];
     if (!p || !planes || !strides || !win) FAIL("scale_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("scale_device: slot %d outside the %d resident frames", slot, p->frames_resident);
     if (dev_format_split("scale_device", dev_format, &format, &sample, &sb, hbd)) return -1;
@@ -1431,6 +1483,9 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, cons
         FAIL("scale_device: 4:4:4 window width %d is more than %d times the picture's %d (its chroma planes are reduced to %d columns: at most %d to 1)", sw, SCL_MAX_RATIO/2, dw, dw/2, SCL_MAX_RATIO);
     if (hbd[1] && sh > SCL_MAX_RATIO/2*dh)
         FAIL("scale_device: 4:4:4 window height %d is more than %d times the picture's %d (its chroma planes are reduced to %d rows: at most %d to 1)", sh, SCL_MAX_RATIO/2, dh, dh/2, SCL_MAX_RATIO);
+    /* a 4:2:2 chroma plane goes from half the window's width and all of its height to half the picture: 16:1 in width as it is, 8:1 in height */
+    if (hbd[2] && sh > SCL_MAX_RATIO/2*dh)
+        FAIL("scale_device: 4:2:2 window height %d is more than %d times the picture's %d (its chroma planes are reduced to %d rows: at most %d to 1)", sh, SCL_MAX_RATIO/2, dh, dh/2, SCL_MAX_RATIO);
     memset(S, 0, sizeof(*S));
     S->sw = sw; S->sh = sh; S->dw = dw; S->dh = dh;
     S->cm = p->cm; S->sample = sample;
@@ -1438,19 +1493,21 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, cons
     if (S->th > SCL_TH_MAX) S->th = SCL_TH_MAX;
     const int rgbp = format == H264E_INGEST_RGBP;
     if (rgbp) S->th &= ~1;                                      /* a tile of all three output planes: whole 2x2 blocks (>= 4 rows at 16:1) */
-    S->depth = hbd[0]; S->c444 = hbd[1];
+    S->depth = hbd[0]; S->c444 = hbd[1]; S->c422 = hbd[2]; S->pack = hbd[3];
     if (hbd[0]) { S->qround = 1 << (hbd[0] - 9); S->qshift = hbd[0] - 8; }
-    S->thc = (int)((long long)(SCL_ROWS - 2)*(dh/2)/sh);        /* 4:4:4 chroma: sh rows -> dh/2, so thc*sh/(dh/2) + 2 source rows at most (>= 4 rows at 8:1) */
+    S->thc = (int)((long long)(SCL_ROWS - 2)*(dh/2)/sh);        /* 4:4:4 and 4:2:2 chroma: sh rows -> dh/2, so thc*sh/(dh/2) + 2 source rows at most (>= 4 rows at 8:1) */
     if (S->thc > SCL_TH_MAX) S->thc = SCL_TH_MAX;
     S->tiles_y = (dh + S->th - 1)/S->th;
-    if (hbd[1] && (dh/2 + S->thc - 1)/S->thc > S->tiles_y) S->tiles_y = (dh/2 + S->thc - 1)/S->thc;
-    const int nplanes = format == H264E_INGEST_NV12 ? 2 : 3, cw = (srcw + 1)/2;
+    if ((hbd[1] || hbd[2]) && (dh/2 + S->thc - 1)/S->thc > S->tiles_y) S->tiles_y = (dh/2 + S->thc - 1)/S->thc;
+    const int nplanes = hbd[3] ? 1 : format == H264E_INGEST_NV12 ? 2 : 3, cw = (srcw + 1)/2;
     for (int k = 0; k < nplanes; k++)
     {
-        /* bytes of a source row, and the window in this plane: x0 bytes into row y0, wbytes x rows (planar RGB: every plane as luma, sb bytes per sample) */
-        const int nv = k && format == H264E_INGEST_NV12, full = k == 0 || rgbp || hbd[1];
-        const int row_bytes = full ? srcw*sb : nv ? 2*cw*sb : cw*sb;
-        const int x0 = full ? cx*sb : nv ? cx*sb : cx/2*sb, y0 = full ? cy : cy/2, wbytes = full ? sw*sb : nv ? sw*sb : sw/2*sb, rows = full ? sh : sh/2;
+        /* bytes of a source row, and the window in this plane: x0 bytes into row y0, wbytes x rows (planar RGB: every plane as luma, sb bytes per sample;
+         * a packed 4:2:2 plane: two samples per pixel; 4:2:2 chroma: all the window's rows) */
+        const int nv = k && format == H264E_INGEST_NV12, full = k == 0 || rgbp || hbd[1], pk = hbd[3];
+        const int row_bytes = pk ? 2*srcw*sb : full ? srcw*sb : nv ? 2*cw*sb : cw*sb;
+        const int x0 = pk ? 2*cx*sb : full ? cx*sb : nv ? cx*sb : cx/2*sb, y0 = full || hbd[2] ? cy : cy/2;
+        const int wbytes = pk ? 2*sw*sb : full ? sw*sb : nv ? sw*sb : sw/2*sb, rows = full || hbd[2] ? sh : sh/2;
         if (!planes[k]) FAIL("scale_device: plane %d is NULL", k);
         if (dev_sample_aligned("scale_device", k, planes[k], strides[k], sb, sample)) return -1;
         if (strides[k] < row_bytes) FAIL("scale_device: stride %d of plane %d is below the %d bytes of a source row", strides[k], k, row_bytes);
@@ -1461,10 +1518,12 @@ static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, cons
             FAIL("scale_device: plane %d (%p, source %d x %d, window %d x %d at (%d, %d), rows %d bytes apart) is not memory of device %d, or not inside one allocation",
                  k, planes[k], srcw, srch, sw, sh, cx, cy, strides[k], p->device);
 #endif
-        for (int c = k; c < (nv ? 3 : k + 1); c++)
+        for (int c = k; c < (pk || nv ? 3 : k + 1); c++)
         {
-            S->c[c].base = lo + (nv && c == 2 ? sb : 0); S->c[c].lo = lo; S->c[c].hi = lo + nbytes;
-            S->c[c].stride = strides[k]; S->c[c].step = nv ? 2*sb : sb;
+            /* a packed group of four samples: Y0 U Y1 V (YUYV) or U Y0 V Y1 (UYVY) */
+            const int at = !pk ? (nv && c == 2 ? 1 : 0) : pk == H264E_PACK_YUYV ? (c == 0 ? 0 : c == 1 ? 1 : 3) : (c == 0 ? 1 : c == 1 ? 0 : 2);
+            S->c[c].base = lo + at*sb; S->c[c].lo = lo; S->c[c].hi = lo + nbytes;
+            S->c[c].stride = strides[k]; S->c[c].step = pk ? (c ? 4*sb : 2*sb) : nv ? 2*sb : sb;
         }
     }
     return 0;

@@ -221,6 +221,19 @@ typedef struct
  *                luma's size.  Luma is copied (or quantised); U(i,j) = (a + b + c + d + 2) >> 2 over the 2x2 block of the 8-bit
  *                (quantised first) chroma samples, the rounded mean of the RGB path; V likewise.  The slot is that of an I420 frame
  *                with those chroma planes.
+ *          I420 | H264E_DEV_CHROMA_422, NV12 | H264E_DEV_CHROMA_422 (bit 14 -- bit 13 stays unassigned and refused: H264E_DEV_FORMAT_I422 = ffmpeg's yuv422p, _NV16; with or
+ *                without a depth; together with 4:4:4, on RGB and RGBP, with a float sample type and on the way out they are refused):
+ *                what capture cards, pro-video decoders and MJPEG cameras leave.  U and V have the luma's HEIGHT and half its width:
+ *                plane[1], plane[2] = width/2 x height samples each, or for NV16 plane[1] = height rows of width/2 U,V pairs.  Luma
+ *                is copied (or quantised); U(i,j) = (a + b + 1) >> 1 with a = U422(i, 2j) and b = U422(i, 2j + 1), the 8-bit
+ *                (quantised first, the order 4:4:4 uses) samples of one column in a pair of rows; V likewise.  The slot is that of an
+ *                I420 frame with those chroma planes (tests/c422_model.py restates it).
+ *          I420 | H264E_DEV_CHROMA_422 | H264E_DEV_PACK_YUYV or _UYVY (bits 2-3: H264E_DEV_FORMAT_YUYV = YUY2, _UYVY; valid only with
+ *                bit 14 on the I420 layout; both bits, a pack bit without bit 14 or on NV12 are refused): ONE plane, only plane[0] and
+ *                stride[0] are read.  A row is 2 * width samples in groups of four, Y0 U Y1 V (YUYV) or U Y0 V Y1 (UYVY); the samples
+ *                are de-interleaved as they are loaded and the arithmetic is that of I422.  With H264E_DEV_DEPTH(d) all four 4:2:2
+ *                layouts hold 16-bit little-endian words, quantised as above: H264E_DEV_FORMAT_P210 / _P216 = NV16 | DEPTH(16) and
+ *                _Y210 / _Y216 = YUYV | DEPTH(16) are MSB aligned like P010; yuv422p10le is I422 | DEPTH(10).
  * stride: bytes from row to row, at least the row's bytes; no alignment is asked of pointers or strides of 8-bit samples.  producer_stream: the
  * hipStream_t on which the work that writes the frame was queued -- the encoder waits for everything queued there so far -- or NULL
  * when the caller has synchronised.  Every call that takes such frames returns when they have been read: the memory may be reused
@@ -238,9 +251,20 @@ typedef struct
 #define H264E_DEV_FORMAT_I444  (H264E_DEV_FORMAT_I420 | H264E_DEV_CHROMA_444)
 #define H264E_DEV_FORMAT_P016  (H264E_DEV_FORMAT_NV12 | H264E_DEV_DEPTH(16))
 #define H264E_DEV_FORMAT_P010  H264E_DEV_FORMAT_P016       /* MSB aligned: the unused low bits take part in the rounding, as they should */
+#define H264E_DEV_CHROMA_422   0x4000       /* U and V of the luma's height and half its width, OR-ed into format: I420 and NV12, input only */
+#define H264E_DEV_PACK_YUYV    0x4          /* one plane, Y0 U Y1 V: only with H264E_DEV_CHROMA_422 on I420, input only */
+#define H264E_DEV_PACK_UYVY    0x8          /* one plane, U Y0 V Y1: likewise */
+#define H264E_DEV_FORMAT_I422  (H264E_DEV_FORMAT_I420 | H264E_DEV_CHROMA_422)
+#define H264E_DEV_FORMAT_NV16  (H264E_DEV_FORMAT_NV12 | H264E_DEV_CHROMA_422)
+#define H264E_DEV_FORMAT_YUYV  (H264E_DEV_FORMAT_I422 | H264E_DEV_PACK_YUYV)
+#define H264E_DEV_FORMAT_UYVY  (H264E_DEV_FORMAT_I422 | H264E_DEV_PACK_UYVY)
+#define H264E_DEV_FORMAT_P216  (H264E_DEV_FORMAT_NV16 | H264E_DEV_DEPTH(16))
+#define H264E_DEV_FORMAT_P210  H264E_DEV_FORMAT_P216       /* MSB aligned, like P010 */
+#define H264E_DEV_FORMAT_Y216  (H264E_DEV_FORMAT_YUYV | H264E_DEV_DEPTH(16))
+#define H264E_DEV_FORMAT_Y210  H264E_DEV_FORMAT_Y216
 typedef struct
 {
-    int format;                             /* H264E_DEV_FORMAT_*, for RGBP | H264E_DEV_SAMPLE_*, for I420 / NV12 | H264E_DEV_DEPTH(d), for I420 | H264E_DEV_CHROMA_444 */
+    int format;                             /* H264E_DEV_FORMAT_*, for RGBP | H264E_DEV_SAMPLE_*, for I420 / NV12 | H264E_DEV_DEPTH(d), for I420 | H264E_DEV_CHROMA_444, for I420 / NV12 | H264E_DEV_CHROMA_422 (| H264E_DEV_PACK_*) */
     int pixel_bytes;                        /* RGB: 3 or 4; ignored otherwise (RGBP included) */
     const void *plane[3];
     int stride[3];
@@ -267,7 +291,10 @@ int  H264E_encode_device(H264E_persist_t *enc, H264E_scratch_t *scratch, const H
  * 16-bit samples: likewise, the filter runs on the quantised samples of every plane.  4:4:4 (H264E_DEV_CHROMA_444): a chroma plane's
  * window is the luma's, Sw x Sh at (crop_x, crop_y), reduced directly to Dw/2 x Dh/2 by the same formula -- at Sw = Dw exactly the 2x2
  * rounded mean of the plain ingest, so a pure crop equals the ingest of the cropped region; no plane is reduced by more than 16:1, so a
- * 4:4:4 window may be at most 8 times the picture in an axis.
+ * 4:4:4 window may be at most 8 times the picture in an axis.  4:2:2 (H264E_DEV_CHROMA_422, planes, U,V pairs or packed): a chroma
+ * plane's window is Sw/2 x Sh at (crop_x/2, crop_y), reduced directly to Dw/2 x Dh/2 by the same formula -- at Sw = Dw, Sh = Dh exactly
+ * (a + b + 1) >> 1 of the plain ingest, so a pure crop equals the ingest of the cropped region; a 4:2:2 window may be at most 16 times the
+ * picture in width and 8 times in height.
  * Refused (H264E_last_error names the value): interleaved RGB
  * with a window, odd or negative crop values, a window that leaves the source, is smaller than the picture in an axis (no upscaling),
  * larger than 4096 samples or more than 16 times the picture in an axis, a stride below the source row's bytes, and planes that are

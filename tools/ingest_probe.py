@@ -7,7 +7,11 @@ torch, (x * 255).round().clamp(0, 255).to(uint8), and handed over as "rgbp", the
 with --fmt also the decoder surfaces, "i420_16" / "nv12_16" / "i444" / "i444_16": the same picture as 10-bit words in int16 tensors and /
 or with chroma of the luma's size through the kernels of enc_hbd.h, and "i420_16_via_torch" / ...: those tensors quantised by torch,
 ((x.int() + r) >> s).clamp(max=255).to(uint8) per plane, plus the rounded 2x2 mean for 4:4:4, and handed over as "i420" / "nv12", the steps
-the new formats replace):
+the new formats replace);
+with --fmt also 4:2:2, "i422" / "nv16" / "yuyv" / "uyvy" and their "_16" names: the same picture with every chroma row twice, as planes, U,V
+pairs or one packed plane, of bytes or of 10-bit words in int16 tensors, through the kernels of enc_422.h, and "i422_via_torch" / ...: those
+tensors de-interleaved, quantised and reduced by torch, (a + b + 1) >> 1 over the row pairs, and handed over as "i420", the steps the 4:2:2
+formats replace):
 the time per frame of H264E_clip_upload_device over `--frames` frames handed over in one call (one ingest kernel launch per frame, one
 wait at the end: launch + kernel, host wall clock around a call that ends in a device synchronise), next to H264E_clip_upload of the
 same frames from host memory -- the copy it replaces.  Then the per-frame API: H264E_encode (host planes) against H264E_encode_device
@@ -35,7 +39,39 @@ W, H, QP, GOP = 1920, 1080, 26, 30
 FORMATS = ("i420", "nv12", "rgb3", "rgb4", "rgbp", "rgbp_bt709_full", "rgbp_via_permute")
 FLOAT_FORMATS = tuple("rgbp_" + k + v for k in ("f16", "bf16", "f32") for v in ("", "_via_quantise"))
 HBD_FORMATS = tuple(k + v for k in ("i420_16", "nv12_16", "i444", "i444_16") for v in ("", "_via_torch"))
+C422_FORMATS = tuple(k + s16 + v for k in ("i422", "nv16", "yuyv", "uyvy") for s16 in ("", "_16") for v in ("", "_via_torch"))
 HBD_DEPTH = 10
+
+
+def c422_sources(torch, c, base, w=W, h=H):
+    """the frames of the packed I420 clip c (w x h) as the 4:2:2 format `base` takes them: every chroma row twice, 10-bit words
+    (sample << 2) in int16 tensors for the "_16" names -- both quantise / average back to c"""
+    import c422_model as C4
+    out = []
+    for f in c:
+        y, u, v = f[:w * h].reshape(h, w), f[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), f[w * h * 5 // 4:].reshape(h // 2, w // 2)
+        planes = C4.from_420(y, u, v)
+        if base.endswith("_16"):
+            planes = [(p.astype(np.int16) << (HBD_DEPTH - 8)) for p in planes]
+        arrays = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in C4.layout(planes, base)]
+        out.append(arrays[0] if len(arrays) == 1 else tuple(arrays))
+    return out
+
+
+def c422_two_step(torch, frame, base):
+    """what a caller writes today in front of "i420": de-interleave, quantise, the rounded mean of the row pairs -- (frame, format name)"""
+    parts = [frame] if not isinstance(frame, tuple) else list(frame)
+    if base.endswith("_16"):
+        r, s = 1 << (HBD_DEPTH - 9), HBD_DEPTH - 8
+        parts = [((x.int() + r) >> s).clamp(max=255).to(torch.uint8) for x in parts]
+    if base.startswith("i422"):
+        y, u, v = parts
+    elif base.startswith("nv16"):
+        y, u, v = parts[0], parts[1][:, 0::2], parts[1][:, 1::2]
+    else:
+        iy, iu = (0, 1) if base.startswith("yuyv") else (1, 0)
+        y, u, v = parts[0][:, iy::2].contiguous(), parts[0][:, iu::4], parts[0][:, iu + 2::4]
+    return (y,) + tuple(((x[0::2].int() + x[1::2] + 1) >> 1).to(torch.uint8) for x in (u, v)), "i420"
 
 
 def hbd_sources(torch, c, base):
@@ -102,19 +138,21 @@ def main():
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--perframe", type=int, default=60)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--fmt", default=",".join(FORMATS), help="comma-separated, of: %s" % ", ".join(FORMATS + FLOAT_FORMATS + HBD_FORMATS))
+    ap.add_argument("--fmt", default=",".join(FORMATS), help="comma-separated, of: %s" % ", ".join(FORMATS + FLOAT_FORMATS + HBD_FORMATS + C422_FORMATS))
     a = ap.parse_args()
     fmts = [f for f in a.fmt.split(",") if f]
     for f in fmts:
-        if f not in FORMATS + FLOAT_FORMATS + HBD_FORMATS:
-            ap.error("--fmt %s: one of %s" % (f, ", ".join(FORMATS + FLOAT_FORMATS + HBD_FORMATS)))
+        if f not in FORMATS + FLOAT_FORMATS + HBD_FORMATS + C422_FORMATS:
+            ap.error("--fmt %s: one of %s" % (f, ", ".join(FORMATS + FLOAT_FORMATS + HBD_FORMATS + C422_FORMATS)))
     import torch
     P = pkg.load_pkg()
     c = host_frames(P, max(a.frames, a.perframe))
     line = {"clip": "1080p synth_v1, QP %d, GOP %d" % (QP, GOP), "frames": a.frames, "reps": a.reps, "formats": {}}
     for fmt in fmts:
         base = fmt[: -len("_via_torch")] if fmt.endswith("_via_torch") else fmt
-        if fmt in HBD_FORMATS:
+        if fmt in C422_FORMATS:
+            src, name, model = c422_sources(torch, c[: a.frames], base), base, c[: a.frames]
+        elif fmt in HBD_FORMATS:
             src, name, model = hbd_sources(torch, c[: a.frames], base), base, c[: a.frames]
         else:
             src, name, model = sources(torch, c[: a.frames], fmt)
@@ -126,9 +164,9 @@ def main():
             if fmt == "rgbp_via_permute":
                 ce.upload_device([t.permute(1, 2, 0).contiguous() for t in src], "rgb")
             elif fmt.endswith("_via_torch"):
-                made = [hbd_two_step(torch, f, base) for f in src]
+                made = [(c422_two_step if fmt in C422_FORMATS else hbd_two_step)(torch, f, base) for f in src]
                 ce.upload_device([m[0] for m in made], made[0][1])
-            elif fmt in HBD_FORMATS:
+            elif fmt in HBD_FORMATS + C422_FORMATS:
                 ce.upload_device(src, name, **(dict(depth=HBD_DEPTH) if name.endswith("_16") else {}))
             elif fmt.endswith("_via_quantise"):
                 ce.upload_device([(t * 255).round().clamp(0, 255).to(torch.uint8) for t in src], "rgbp")

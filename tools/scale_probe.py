@@ -12,9 +12,12 @@ without the planar format pays first, torch's permute(1, 2, 0).contiguous() of t
 words in int16 tensors) through h264e_scale_hbd_kernel, next to the two steps they replace -- torch's quantiser per plane,
 ((x.int() + r) >> s).clamp(max=255).to(uint8), plus the rounded 2x2 mean for 4:4:4 (torch events around a batch of them), followed by the
 existing 8-bit "i420" / "nv12" window of the result.
+--c422 times the 4:2:2 layouts (enc_422.h): 1920x1080 at the picture's size (h264e_ingest_422_kernel) and 3840x2160 -> 1920x1080
+(h264e_scale_422_kernel) of "i422", "nv16", "yuyv", "uyvy" and their "_16" names, next to the two steps they replace -- torch de-interleaves, quantises and takes (a + b + 1) >> 1 over the row
+pairs, then the existing "i420" ingest or window of the result -- and next to the existing "nv12" and "p010" kernels on the same picture.
 Prints one JSON line.
 
-    python tools/scale_probe.py [--batch 8] [--reps 25] [--warmup 3] [--hbd]
+    python tools/scale_probe.py [--batch 8] [--reps 25] [--warmup 3] [--hbd | --c422]
 """
 import argparse
 import json
@@ -121,15 +124,97 @@ def hbd_main(a):
     print(json.dumps(line))
 
 
+def c422_main(a):
+    """1080p at the picture's size and 4K -> 1080p through the window: the 4:2:2 layouts against torch's de-interleave / quantiser / row mean
+    in front of the existing "i420" path, and against the existing "nv12" and "p010" kernels on the same picture (the 4:2:0 frame whose chroma
+    rows the 4:2:2 frame holds twice).  Kernel times are HIP events on the encoder's copy stream (H264E_clip_input_time), torch's part torch events"""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import c422_model as C4
+    import hbd_model as HM
+    from ingest_probe import c422_two_step
+    P = pkg.load_pkg()
+    assert P.load().h264e_hip_device_count() > 0, "no HIP device visible"
+    rng = np.random.default_rng(3)
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    out = {"batch": a.batch, "reps": a.reps, "warmup": a.warmup, "depth": HBD_DEPTH, "cases": {}}
+    for case, (sw, sh), (dw, dh) in (("ingest_1920x1080", (1920, 1080), (1920, 1080)), ("scale_3840x2160_to_1920x1080", (3840, 2160), (1920, 1080))):
+        win = dict(src_size=(sw, sh)) if (sw, sh) != (dw, dh) else {}
+        line = {"us_per_frame": {}, "min_max_us": {}, "source_mbytes": {}}
+        base8 = [[rng.integers(0, 256, s).astype(np.uint8) for s in ((sh, sw), (sh // 2, sw // 2), (sh // 2, sw // 2))] for _ in range(a.batch)]
+        want = M.scale_i420(*base8[0], dw, dh) if win else HM.pack(*base8[0])
+
+        def timed(ce, dev, fmt, kw, ms, keep):
+            before = ce.input_time(True)
+            ce.upload_device(dev, fmt, **win, **kw)
+            after = ce.input_time(True)
+            if keep:
+                ms.append((after[0] - before[0]) / a.batch)
+
+        def report(name, ms):
+            line["us_per_frame"][name] = round(1e3 * statistics.median(ms), 2)
+            line["min_max_us"][name] = [round(1e3 * min(ms), 2), round(1e3 * max(ms), 2)]
+
+        # the yardsticks: the existing kernels on the same picture
+        for fmt in ("nv12", "p010"):
+            planes = [[f[0], HM.interleave(f[1], f[2])] for f in base8]
+            if fmt == "p010":
+                planes = [[(p.astype(np.uint16) << 8).view(np.int16) for p in f] for f in planes]
+            dev = [tuple(torch.from_numpy(p).cuda() for p in f) for f in planes]
+            ce = P.ClipEncoder(dw, dh, a.batch, gop=30, qp=26)
+            ms = []
+            for rep in range(a.warmup + a.reps):
+                timed(ce, dev, fmt, {}, ms, rep >= a.warmup)
+            assert np.array_equal(ce.download(0, 1)[0], want), fmt + ": the slot differs from the model"
+            ce.close()
+            report(fmt, ms)
+            line["source_mbytes"][fmt] = round(sum(p.nbytes for p in planes[0]) / 1e6, 2)
+        for fmt in C4.FORMATS:
+            host = [C4.from_420(*f) for f in base8]
+            if C4.is_16(fmt):
+                host = [[(p.astype(np.int16) << (HBD_DEPTH - 8)) for p in f] for f in host]
+            arrays = [C4.layout(f, fmt) for f in host]
+            dev = [tuple(torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in f) for f in arrays]
+            dev = [f[0] if len(f) == 1 else f for f in dev]
+            kw = dict(depth=HBD_DEPTH) if C4.is_16(fmt) else {}
+            ce, ce8 = (P.ClipEncoder(dw, dh, a.batch, gop=30, qp=26) for _ in range(2))
+            ce.upload_device(dev, fmt, **win, **kw)
+            assert np.array_equal(ce.download(0, 1)[0], C4.slot(host[0], fmt, HBD_DEPTH, dw, dh) if win else C4.slot(host[0], fmt, HBD_DEPTH)), fmt + ": the slot differs from the model"
+            new_ms, torch_ms, old_ms = [], [], []
+            for rep in range(a.warmup + a.reps):
+                timed(ce, dev, fmt, kw, new_ms, rep >= a.warmup)
+                ev[0].record()
+                made = [c422_two_step(torch, f, fmt) for f in dev]
+                ev[1].record()
+                ev[1].synchronize()
+                timed(ce8, [m[0] for m in made], "i420", {}, old_ms, rep >= a.warmup)
+                if rep >= a.warmup:
+                    torch_ms.append(ev[0].elapsed_time(ev[1]) / a.batch)
+            # every chroma row comes twice here, so the two paths are the same arithmetic (tests/test_c422_model.py)
+            assert np.array_equal(ce8.download(0, 1)[0], ce.download(0, 1)[0]), fmt + ": the two paths differ"
+            ce.close()
+            ce8.close()
+            for name, ms in ((fmt, new_ms), (fmt + "_torch_part", torch_ms), (fmt + "_i420_part", old_ms), (fmt + "_via_torch", [x + y for x, y in zip(torch_ms, old_ms)])):
+                report(name, ms)
+            line["source_mbytes"][fmt] = round(sum(p.nbytes for p in arrays[0]) / 1e6, 2)
+            line[fmt + "_over_via_torch"] = round(line["us_per_frame"][fmt] / line["us_per_frame"][fmt + "_via_torch"], 3)
+        line["us_per_source_mbyte"] = {k: round(line["us_per_frame"][k] / v, 3) for k, v in line["source_mbytes"].items()}
+        out["cases"][case] = line
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--hbd", action="store_true", help="time the 16-bit and 4:4:4 layouts (enc_hbd.h) against torch + the 8-bit window instead")
+    ap.add_argument("--c422", action="store_true", help="time the 4:2:2 layouts (enc_422.h) against torch + the 8-bit window and the existing nv12 / p010 kernels instead")
     a = ap.parse_args()
     if a.hbd:
         return hbd_main(a)
+    if a.c422:
+        return c422_main(a)
     import torch
     P = pkg.load_pkg()
     assert P.load().h264e_hip_device_count() > 0, "no HIP device visible"
