@@ -13,6 +13,7 @@ from .binding import (  # noqa: F401
     DEV_FORMAT_P210, DEV_FORMAT_P216, DEV_FORMAT_Y210, DEV_FORMAT_Y216,
     DEV_SAMPLE_U8, DEV_SAMPLE_F16, DEV_SAMPLE_BF16, DEV_SAMPLE_F32, dev_format, H264E_SCENECUT_DEFAULT,
     MATRIX_UNSPECIFIED, MATRIX_BT709, MATRIX_BT601,
+    TONEMAP_OFF, TONEMAP_PQ, TONECURVE_HABLE, TONECURVE_REINHARD, TONECURVE_CLIP, tonemap_args, tonemap_tables,
     STATUS_SUCCESS, STATUS_BAD_ARGUMENT, STATUS_BAD_PARAMETER, STATUS_BAD_FRAME_TYPE, FRAME_TYPE_DEFAULT, FRAME_TYPE_KEY, FRAME_TYPE_P,
 )
 from .shard import StreamShard, shard_ranges  # noqa: F401

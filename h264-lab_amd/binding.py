@@ -424,6 +424,47 @@ def color_pair(color):
         raise H264EError("color %r: one of %s, or a (matrix, full_range) pair" % (color, ", ".join(sorted(_COLORS))))
 
 
+TONEMAP_OFF, TONEMAP_PQ = 0, 1                                 # include/h264e_mi355x.h
+TONECURVE_HABLE, TONECURVE_REINHARD, TONECURVE_CLIP = 0, 1, 2
+_TRANSFERS = {"off": TONEMAP_OFF, "pq": TONEMAP_PQ}
+_CURVES = {"hable": TONECURVE_HABLE, "reinhard": TONECURVE_REINHARD, "clip": TONECURVE_CLIP}
+
+
+def tonemap_args(tonemap):
+    """(transfer, curve, peak_nits, ref_white_nits) of a tonemap option: "pq" (or "off" / None), or a dict {"transfer": "pq", "curve":
+    "hable" | "reinhard" | "clip", "peak": 1000, "ref_white": 203} with any of the last three left out (the library checks the values)"""
+    what = "tonemap %r: \"pq\", \"off\" or a dict with transfer, curve (%s), peak, ref_white" % (tonemap, ", ".join(sorted(_CURVES)))
+    if tonemap is None:
+        return TONEMAP_OFF, TONECURVE_HABLE, 0.0, 0.0
+    if isinstance(tonemap, str):
+        tonemap = {"transfer": tonemap}
+    if not isinstance(tonemap, dict) or set(tonemap) - {"transfer", "curve", "peak", "ref_white"}:
+        raise H264EError(what)
+    transfer, curve = tonemap.get("transfer", "pq"), tonemap.get("curve", "hable")
+    if isinstance(transfer, str):
+        if transfer not in _TRANSFERS:
+            raise H264EError(what)
+        transfer = _TRANSFERS[transfer]
+    if isinstance(curve, str):
+        if curve not in _CURVES:
+            raise H264EError(what)
+        curve = _CURVES[curve]
+    try:
+        return int(transfer), int(curve), float(tonemap.get("peak", 0) or 0), float(tonemap.get("ref_white", 0) or 0)
+    except (TypeError, ValueError):
+        raise H264EError(what)
+
+
+def tonemap_tables(tonemap="pq", lib=None):
+    """H264E_tonemap_tables: the tables the tone-map kernel will use for this option (a pure host function): (ycc int32[8], eotf
+    float32[1024], scale float32[1024], thresh float32[256])"""
+    L = load(lib)
+    ycc, eotf, scale, thresh = np.zeros(8, np.int32), np.zeros(1024, np.float32), np.zeros(1024, np.float32), np.zeros(256, np.float32)
+    if L.H264E_tonemap_tables(*tonemap_args(tonemap), ycc.ctypes.data, eotf.ctypes.data, scale.ctypes.data, thresh.ctypes.data):
+        raise _err(L, "H264E_tonemap_tables")
+    return ycc, eotf, scale, thresh
+
+
 def fps_pair(fps):
     """(num, den) of a frame-rate option: an int, or a (num, den) pair"""
     if isinstance(fps, (tuple, list)):
@@ -502,6 +543,11 @@ def load(path=None):
     L.H264E_set_frame_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.H264E_clip_set_color.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.H264E_clip_set_frame_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.H264E_set_tonemap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
+    L.H264E_clip_set_tonemap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
+    L.H264E_tonemap_tables.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.H264E_tonemap_state.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+    L.H264E_clip_tonemap_state.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     L.H264E_close.argtypes = [C.c_void_p]
     L.H264E_close.restype = None
     L.H264E_set_device.argtypes = [C.c_int]
@@ -604,7 +650,7 @@ class Encoder:
     """Frame-at-a-time encoder through the reference API: H264E_sizeof -> H264E_init -> H264E_encode."""
 
     def __init__(self, width, height, gop=20, qp=33, speed=0, kbps=0, const_input=1, vbv_size_bytes=100000 // 8, lib=None, slices=0, denoise=False,
-                 color=None, fps=None):
+                 color=None, fps=None, tonemap=None):
         self.L = load(lib)
         self.w, self.h = width, height
         self.cp = CreateParam(width=width, height=height, gop=gop, vbv_size_bytes=vbv_size_bytes, const_input_flag=const_input,
@@ -627,6 +673,8 @@ class Encoder:
             self.set_color(color)
         if fps is not None:
             self.set_frame_rate(fps)
+        if tonemap is not None:
+            self.set_tonemap(tonemap)
         self.rp = RunParam(encode_speed=speed)
         if kbps:
             self.rp.desired_frame_bytes = kbps * 1000 // 8 // 30  # minih264e_test.c:596-600
@@ -710,6 +758,20 @@ class Encoder:
         if st:
             raise _err(self.L, "H264E_set_color status %d" % st)
 
+    def set_tonemap(self, tonemap):
+        """H264E_set_tonemap: 16-bit "i420_16" / "nv12_16" / "p010" / "p016" device frames of depth 10 .. 16 are taken as HDR10 (PQ,
+        BT.2020) and tone-mapped to the 8-bit BT.709 picture; "pq", a dict (see tonemap_args), or "off" / None; only before the first frame."""
+        st = self.L.H264E_set_tonemap(self.persist, *tonemap_args(tonemap))
+        if st:
+            raise _err(self.L, "H264E_set_tonemap status %d" % st)
+
+    def tonemap_state(self):
+        """(on, bytes of the device table buffer, bytes of the window surface): 0 = not allocated"""
+        s = (C.c_longlong * 3)()
+        if self.L.H264E_tonemap_state(self.persist, s):
+            raise _err(self.L, "H264E_tonemap_state")
+        return tuple(s)
+
     def set_frame_rate(self, fps):
         """H264E_set_frame_rate: an int or a (num, den) pair, (0, 0) = none; only before the first frame."""
         st = self.L.H264E_set_frame_rate(self.persist, *fps_pair(fps))
@@ -738,7 +800,7 @@ class ClipEncoder:
     def __init__(self, width, height, nframes, gop=30, qp=26, speed=0, device=0, max_chains=0, lib=None,
                  clusters_in=(0, 0), idr_state=0, slices=0, kbps=0, resident=0, keep_records=0, denoise=False, key_frames=None, scenecut=0,
                  color=None, fps=None, quality=None, qp_schedule=None, abr_kbps=0, lookahead=0, qp_range=(0, 0), lookahead_search=0,
-                 denoise_motion=0, lookahead_tree=0):
+                 denoise_motion=0, lookahead_tree=0, tonemap=None):
         self.L = load(lib)
         self.w, self.h, self.n = width, height, nframes
         self._ssd = self._ssim = None           # the registered metric arrays [nframes][3], owned here while registered
@@ -758,6 +820,8 @@ class ClipEncoder:
                 self.set_color(color)
             if fps is not None:
                 self.set_frame_rate(fps)
+            if tonemap is not None:
+                self.set_tonemap(tonemap)
             if quality:
                 self.set_quality(**(quality if isinstance(quality, dict) else {}))
             if qp_schedule is not None and len(qp_schedule):
@@ -843,6 +907,19 @@ class ClipEncoder:
         frames in the input ring keep the bytes they were converted to."""
         if self.L.H264E_clip_set_color(self.c, *color_pair(color)):
             raise _err(self.L, "H264E_clip_set_color")
+
+    def set_tonemap(self, tonemap):
+        """H264E_clip_set_tonemap (see Encoder.set_tonemap): only while the clip stands at frame 0, and BEFORE the frames are uploaded;
+        kept across a rewind."""
+        if self.L.H264E_clip_set_tonemap(self.c, *tonemap_args(tonemap)):
+            raise _err(self.L, "H264E_clip_set_tonemap")
+
+    def tonemap_state(self):
+        """(on, bytes of the device table buffer, bytes of the window surface): 0 = not allocated"""
+        s = (C.c_longlong * 3)()
+        if self.L.H264E_clip_tonemap_state(self.c, s):
+            raise _err(self.L, "H264E_clip_tonemap_state")
+        return tuple(s)
 
     def set_frame_rate(self, fps):
         """H264E_clip_set_frame_rate: an int or a (num, den) pair, (0, 0) = none; only while the clip stands at frame 0."""
@@ -1114,7 +1191,7 @@ class ClipEncoder:
 def encode_ladder(frames, fmt, src_size, rungs, crop=None, depth=None, **common):
     """One source in GPU memory, several encodes of it at different sizes.  frames: the device frames (see dev_frame), all of
     src_size=(w, h); rungs: a list of (width, height, dict of ClipEncoder options); crop=(x, y, w, h): the window of the source that every
-    rung shows; common: ClipEncoder options of all rungs (a rung's own win).  One ClipEncoder per rung is fed from the same frames -- by
+    rung shows; common: ClipEncoder options of all rungs (a rung's own win), tonemap="pq" for an HDR10 source among them.  One ClipEncoder per rung is fed from the same frames -- by
     the scaling kernel, or the plain ingest where a rung has the window's size -- rungs of equal picture size are encoded at the same
     time (ClipEncoder.encode_multi), the others one after another.  depth: the significant bits of a 16-bit fmt (see dev_frame).
     Returns one (bytes, sizes, stats) per rung, in the order given."""

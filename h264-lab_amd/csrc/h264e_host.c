@@ -748,6 +748,33 @@ int H264E_set_color(H264E_persist_t *p, int matrix, int full_range)
     return color_apply(&e->seq, mm.pool, matrix, full_range) ? H264E_STATUS_BAD_ARGUMENT : H264E_STATUS_SUCCESS;
 }
 
+/* HDR10 device input (include/h264e_mi355x.h): the pool holds the setting, so both encoders' device frames go the same way.  The rule
+ * and the statuses are H264E_set_color's; the refusals of the values are the device layer's (H264E_last_error -> its text) */
+int H264E_set_tonemap(H264E_persist_t *p, int transfer, int curve, double peak_nits, double ref_white_nits)
+{
+    henc_t *e = (henc_t *)p;
+    impl_t mm;
+    g_host_err[0] = 0;
+    if (!impl_of(e, &mm)) return H264E_STATUS_BAD_PARAMETER;
+    if (e->frames_in) { snprintf(g_host_err, sizeof(g_host_err), "set_tonemap: only before the first frame (%d encoded)", e->frames_in); return H264E_STATUS_BAD_PARAMETER; }
+    if (h264e_hip_tonemap_check("set_tonemap", transfer, curve, peak_nits, ref_white_nits)) return H264E_STATUS_BAD_PARAMETER;
+    return h264e_hip_tonemap_set(mm.pool, "set_tonemap", transfer, curve, peak_nits, ref_white_nits) ? H264E_STATUS_BAD_ARGUMENT : H264E_STATUS_SUCCESS;
+}
+
+int H264E_tonemap_tables(int transfer, int curve, double peak_nits, double ref_white_nits, int ycc[8], float eotf[1024], float scale[1024], float thresh[256])
+{
+    g_host_err[0] = 0;
+    return h264e_hip_tonemap_tables(transfer, curve, peak_nits, ref_white_nits, ycc, eotf, scale, thresh);
+}
+
+int H264E_tonemap_state(H264E_persist_t *p, long long state[3])
+{
+    impl_t mm;
+    g_host_err[0] = 0;
+    if (!impl_of((henc_t *)p, &mm)) return H264E_STATUS_BAD_PARAMETER;
+    return h264e_hip_tonemap_state(mm.pool, state) ? H264E_STATUS_BAD_ARGUMENT : H264E_STATUS_SUCCESS;
+}
+
 int H264E_set_frame_rate(H264E_persist_t *p, int num, int den)
 {
     henc_t *e = (henc_t *)p;
@@ -1660,6 +1687,23 @@ int H264E_clip_set_color(H264E_clip_t *c, int matrix, int full_range)
     if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "clip_set_color: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
     if (color_refused("clip_set_color", matrix, full_range)) return -1;
     return color_apply(&c->seq, c->pool, matrix, full_range);
+}
+
+/* H264E_set_tonemap for the clip: while it stands at frame 0; the pool keeps the setting, so a rewind does.  Frames uploaded before the
+ * call keep the bytes they were converted to */
+int H264E_clip_set_tonemap(H264E_clip_t *c, int transfer, int curve, double peak_nits, double ref_white_nits)
+{
+    g_host_err[0] = 0;
+    if (!c) return -1;
+    if (c->next) { snprintf(g_host_err, sizeof(g_host_err), "clip_set_tonemap: only at frame 0 (after open or rewind), not at frame %d", c->next); return -1; }
+    return h264e_hip_tonemap_set(c->pool, "clip_set_tonemap", transfer, curve, peak_nits, ref_white_nits);
+}
+
+int H264E_clip_tonemap_state(H264E_clip_t *c, long long state[3])
+{
+    g_host_err[0] = 0;
+    if (!c) return -1;
+    return h264e_hip_tonemap_state(c->pool, state);
 }
 
 int H264E_clip_set_frame_rate(H264E_clip_t *c, int num, int den)

@@ -19,6 +19,7 @@
  *   h264e_scale_rgb_kernel  ... of a planar RGB frame (enc_scale_rgb.h): the three channels box-filtered into LDS, converted to I420 from there.
  *   h264e_ingest_hbd_kernel<SB, C444>, h264e_scale_hbd_kernel<SB>  the I420 / NV12 paths for 16-bit samples and 4:4:4 chroma (enc_hbd.h).
  *   h264e_ingest_422_kernel<SB, PACK>, h264e_scale_422_kernel<SB>  4:2:2 input: I422, NV16 and packed YUYV / UYVY, 8- or 16-bit (enc_422.h).
+ *   h264e_tonemap_kernel<LAYOUT>  HDR10 input (enc_tonemap.h): a 16-bit PQ / BT.2020 surface tone-mapped to the 8-bit picture, at size or into the scratch surface of a window.
  *   h264e_ingest_float_kernel<ST>, h264e_scale_rgb_float_kernel<ST>, h264e_egress_float_kernel<ST>  the planar RGB paths for float16 /
  *                        bfloat16 / float32 samples in [0, 1], quantised on the way in and divided by 255 on the way out.
  *   h264e_scenecut_kernel scene-cut detection (enc_scenecut.h): the 64-bin luma histogram of one resident input frame.
@@ -46,6 +47,7 @@
 #include "enc_scale_rgb.h"
 #include "enc_hbd.h"
 #include "enc_422.h"
+#include "enc_tonemap.h"
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
 #include "enc_lookahead_search.h"
@@ -675,6 +677,21 @@ template <int SB, int PACK> __global__ void __launch_bounds__(256) h264e_ingest_
     else ingest_422_chroma<SB, PACK>(S, (GLOBAL_AS uint8_t *)dst, g, y);
 }
 
+/* HDR10 input (enc_tonemap.h): grid.y = TM_WG_ROWS PAIRS of rows (chroma rows), grid.x * 256 lanes x 4 luma columns along them; LAYOUT =
+ * H264E_INGEST_I420 / _NV12.  The tables are staged once per workgroup (9 KB for up to 48 KB of samples in and out); from there every
+ * workgroup reads its own source bytes and writes its own bytes of the destination (no inter-workgroup traffic).  No lane leaves before
+ * the barrier; tonemap_group itself refuses a row pair or a column beyond the picture */
+#define TM_WG_ROWS 4
+template <int LAYOUT> __global__ void __launch_bounds__(256) h264e_tonemap_kernel(h264e_tonemap_src_t S, uint8_t *dst)
+{
+    __shared__ float tab[TM_TABLE_FLOATS];
+    tm_stage((LDS_AS float *)tab, S.tables, (int)threadIdx.x);
+    __syncthreads();
+    S.format = LAYOUT;
+    for (int i = 0; i < TM_WG_ROWS; i++)
+        tonemap_group(S, (const LDS_AS float *)tab, (GLOBAL_AS uint8_t *)dst, (int)(blockIdx.x*blockDim.x + threadIdx.x), (int)blockIdx.y*TM_WG_ROWS + i);
+}
+
 /* device-resident output over one picture (enc_egress.h): grid.z = 0 luma / 1 both chroma planes for I420 and NV12, grid.y = row; the RGB
  * formats have grid.z = 0 alone and grid.y = a PAIR of rows (one chroma row); grid.x * 256 lanes x 4 samples along the row.  Every workgroup
  * reads its own bytes of the picture and writes its own bytes of the destination (no inter-workgroup traffic, no LDS). */
@@ -1017,6 +1034,12 @@ static void bk_launch_ingest(const h264e_ingest_src_t &S, uint8_t *dst, hipStrea
         return;
     }
     LAUNCH_BY_SAMPLE(S.sample, h264e_ingest_kernel, h264e_ingest_float_kernel, dim3(gx, (unsigned)S.height, 2), st, S, dst);
+}
+static void bk_launch_tonemap(const h264e_tonemap_src_t &S, uint8_t *dst, hipStream_t st)
+{
+    const dim3 grid((unsigned)((((S.width + 3) >> 2) + 255) >> 8), (unsigned)(((S.height >> 1) + TM_WG_ROWS - 1)/TM_WG_ROWS), 1);
+    if (S.format == H264E_INGEST_NV12) hipLaunchKernelGGL(h264e_tonemap_kernel<H264E_INGEST_NV12>, grid, dim3(256), 0, st, S, dst);
+    else hipLaunchKernelGGL(h264e_tonemap_kernel<H264E_INGEST_I420>, grid, dim3(256), 0, st, S, dst);
 }
 static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hipStream_t st)
 {

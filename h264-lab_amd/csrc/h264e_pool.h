@@ -3,7 +3,7 @@
  *
  * Written ONCE against the HIP runtime API and five launch functions (bk_launch_mb, bk_launch_synth, bk_launch_ssd,
  * bk_launch_nal_selftest, bk_launch_stage_selftest) that the including translation unit defines in front of it (the product also
- * defines bk_launch_denoise, bk_launch_ingest, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_lookahead_search, bk_launch_lookahead_tree, bk_launch_mcdenoise, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those twelve are lane loops in this file):
+ * defines bk_launch_denoise, bk_launch_ingest, bk_launch_tonemap, bk_launch_egress, bk_launch_scale, bk_launch_scale_rgb, bk_launch_scenecut, bk_launch_lookahead, bk_launch_lookahead_search, bk_launch_lookahead_tree, bk_launch_mcdenoise, bk_launch_ssim and bk_launch_finalizer_selftest; the emulation's versions of those thirteen are lane loops in this file):
  *   - h264e_kernels.hip : the product -- the real HIP runtime, the kernels launched with hipLaunchKernelGGL;
  *   - tests/emu/emu_backend.cpp : the test-only emulation -- a host-memory stand-in for the handful of runtime calls used here
  *     (tests/emu/emu_hip.h) and launch functions that run the same kernel sources as lane loops, row after row.
@@ -18,6 +18,7 @@
 #include "enc_scale_rgb.h"
 #include "enc_hbd.h"
 #include "enc_422.h"
+#include "enc_tonemap.h"
 #include "enc_scenecut.h"
 #include "enc_lookahead.h"
 #include "enc_lookahead_search.h"
@@ -196,6 +197,11 @@ struct h264e_hip_pool
     unsigned long long *la_tree;         /* device [la_entries][nblk] */
     unsigned long long *la_tree_sum;     /* device [la_entries] */
     h264e_color_t cm;                    /* the RGB -> YCbCr matrix of the RGB / RGBP ingest and scale launches (h264e_hip_set_color) */
+    /* HDR10 input (enc_tonemap.h, h264e_hip_tonemap_set): while tm_on, 16-bit I420 / NV12 device frames are tone-mapped on their way in */
+    int tm_on;
+    float *tm_tables;                    /* device [TM_TABLE_FLOATS]: eotf, scale, thresh; NULL until tone mapping is first switched on */
+    uint8_t *tm_scratch;                 /* device: the tone-mapped window of a scaled frame, packed 8-bit I420; NULL until the first one, grows with the largest window */
+    size_t tm_scratch_bytes;
     hipEvent_t ev_ingest[2];             /* what a device-input ingest waits for: the producer's stream, this pool's own stream */
     hipEvent_t ev_in[2];                 /* h264e_hip_copy_timer_*: around a caller's launches on the copy stream */
     h264e_icolor_t icm;                  /* the YCbCr -> RGB matrix of the RGB / RGBP egress launches: the inverse of cm (h264e_hip_set_color) */
@@ -329,6 +335,8 @@ extern "C" void h264e_hip_pool_destroy(h264e_hip_pool_t *p)
     dev_free(p->heap);
     dev_free(p->den);
     dev_free(p->sc_rec);
+    dev_free(p->tm_tables);
+    dev_free(p->tm_scratch);
     dev_free(p->la_lo); dev_free(p->la_rec); dev_free(p->la_field); dev_free(p->la_tree); dev_free(p->la_tree_sum); dev_free(p->mcd_cells);
     dev_free(p->qual_dev);
     if (p->stream)
@@ -1202,6 +1210,17 @@ template <int ST> static void emu_egress(const h264e_egress_dst_t &D, const uint
                 if constexpr (ST == H264E_SAMPLE_U8) egress_group(D, src, g, y, part); else egress_rgb<0, ST>(D, src, g, y);
             }
 }
+/* HDR10 input (enc_tonemap.h): the tables staged as the kernel's 256 lanes stage them, then one lane per group of every row pair */
+static void bk_launch_tonemap(const h264e_tonemap_src_t &S, uint8_t *dst, hipStream_t)
+{
+    float *L = (float *)malloc(sizeof(float)*TM_TABLE_FLOATS);
+    if (!L) return;
+    memset(L, 0xEE, sizeof(float)*TM_TABLE_FLOATS);
+    for (int t = 0; t < 256; t++) tm_stage(L, S.tables, t);
+    for (int j = 0; j < S.height/2; j++)
+        for (int g = 0; g < (S.width + 3)/4; g++) tonemap_group(S, L, dst, g, j);
+    free(L);
+}
 static void bk_launch_egress(const h264e_egress_dst_t &D, const uint8_t *src, hipStream_t) { EMU_BY_SAMPLE(D.sample, emu_egress, D, src); }
 /* ... and the scaler's (enc_scale.h): tile by tile, each of the kernel's three steps as a lane loop over the tile's LDS */
 static void bk_launch_scale(const h264e_scale_src_t &S, uint8_t *dst, hipStream_t)
@@ -1366,6 +1385,71 @@ extern "C" int h264e_hip_set_color(h264e_hip_pool_t *p, int bt709, int full_rang
     return 0;
 }
 
+/* ---- HDR10 input (enc_tonemap.h): a setting of the pool.  The tables go to the device when it is switched on (the buffer appears with
+ * the first time); switching it off keeps the buffer and launches what the pool launched before */
+extern "C" int h264e_hip_tonemap_tables(int transfer, int curve, double peak_nits, double ref_white_nits, int ycc[8], float eotf[1024], float scale[1024], float thresh[256])
+{
+    float t[TM_TABLE_FLOATS];
+    if (!ycc || !eotf || !scale || !thresh) FAIL("tonemap_tables: null argument");
+    if (tonemap_params("tonemap_tables", transfer, curve, &peak_nits, &ref_white_nits, g_err, sizeof(g_err))) return -1;
+    tonemap_tables(curve, peak_nits, ref_white_nits, ycc, t);
+    memcpy(eotf, t + TM_EOTF, sizeof(float)*1024); memcpy(scale, t + TM_SCALE, sizeof(float)*1024); memcpy(thresh, t + TM_THRESH, sizeof(float)*256);
+    return 0;
+}
+
+/* the refusals of the parameters alone (0 = they would be accepted) */
+extern "C" int h264e_hip_tonemap_check(const char *who, int transfer, int curve, double peak_nits, double ref_white_nits)
+{
+    return tonemap_params(who ? who : "set_tonemap", transfer, curve, &peak_nits, &ref_white_nits, g_err, sizeof(g_err));
+}
+
+extern "C" int h264e_hip_tonemap_set(h264e_hip_pool_t *p, const char *who, int transfer, int curve, double peak_nits, double ref_white_nits)
+{
+    float t[TM_TABLE_FLOATS];
+    int ycc[8];
+    if (!p) FAIL("%s: null argument", who ? who : "set_tonemap");
+    if (tonemap_params(who ? who : "set_tonemap", transfer, curve, &peak_nits, &ref_white_nits, g_err, sizeof(g_err))) return -1;
+    if (transfer == H264E_TM_OFF) { p->tm_on = 0; return 0; }
+    HIPCHK(hipSetDevice(p->device));
+    tonemap_tables(curve, peak_nits, ref_white_nits, ycc, t);
+    if (!p->tm_tables && dev_malloc((void **)&p->tm_tables, sizeof(t))) { p->tm_tables = 0; FAIL("%s: device allocation failed (%zu bytes)", who ? who : "set_tonemap", sizeof(t)); }
+    HIPCHK(hipStreamSynchronize(p->copy_stream));           /* a launch of the tables' earlier contents has read them */
+    HIPCHK(hipMemcpy(p->tm_tables, t, sizeof(t), hipMemcpyHostToDevice));
+    p->tm_on = 1;
+    return 0;
+}
+
+/* state[0] = on, state[1] = bytes of the device table buffer (0: none), state[2] = bytes of the scratch surface (0: none) */
+extern "C" int h264e_hip_tonemap_state(const h264e_hip_pool_t *p, long long state[3])
+{
+    if (!p || !state) FAIL("tonemap_state: null argument");
+    state[0] = p->tm_on; state[1] = p->tm_tables ? (long long)(sizeof(float)*TM_TABLE_FLOATS) : 0; state[2] = p->tm_scratch ? (long long)p->tm_scratch_bytes : 0;
+    return 0;
+}
+
+/* while tone mapping is on a device frame is HDR10: 16-bit words of 10 .. 16 significant bits in the I420 or NV12 layout, 4:2:0 */
+static int tonemap_format_refused(const char *who, int dev_format, int format, int sample, const int *hbd)
+{
+    char what[64];
+    if (format == H264E_INGEST_RGB || format == H264E_INGEST_RGBP) snprintf(what, sizeof(what), "%s%s%s", k_format_names[format], sample ? " of " : "", sample ? k_sample_names[sample] : "");
+    else if (hbd[2]) snprintf(what, sizeof(what), "4:2:2 %s%s", hbd[3] ? "packed " : k_format_names[format], hbd[3] ? k_pack_names[hbd[3]] : "");
+    else if (hbd[1]) snprintf(what, sizeof(what), "4:4:4 %s", k_format_names[format]);
+    else if (!hbd[0]) snprintf(what, sizeof(what), "8-bit %s", k_format_names[format]);
+    else if (hbd[0] < 10) snprintf(what, sizeof(what), "%s of depth %d", k_format_names[format], hbd[0]);
+    else return 0;
+    FAIL("%s: format %d is %s, but tone mapping is on: HDR10 frames are I420 or NV12 (P010 / P016) with H264E_DEV_DEPTH(10 .. 16)", who, dev_format, what);
+}
+
+/* the tone-map kernel's view of a w x h picture whose planes begin at plane[] (a frame, or the window of one) */
+static void tonemap_src(const h264e_hip_pool_t *p, int format, int depth, const uint8_t *const plane[3], const int stride[3], int w, int h, h264e_tonemap_src_t *T)
+{
+    memset(T, 0, sizeof(*T));
+    for (int k = 0; k < (format == H264E_INGEST_NV12 ? 2 : 3); k++) { T->plane[k] = plane[k]; T->stride[k] = stride[k]; }
+    T->format = format; T->width = w; T->height = h;
+    T->qshift = depth - 10; T->qround = T->qshift ? 1 << (T->qshift - 1) : 0;
+    T->cm = p->cm; T->tables = p->tm_tables;
+}
+
 /* everything that is refused, without a launch; fills the kernel's view of the source */
 static int ingest_check(const h264e_hip_pool_t *p, int slot, int dev_format, const void *const planes[3], const int strides[3], int pixel_bytes, h264e_ingest_src_t *S)
 {
@@ -1374,6 +1458,7 @@ static int ingest_check(const h264e_hip_pool_t *p, int slot, int dev_format, con
     if (slot < 0 || slot >= p->frames_resident) FAIL("ingest_device: slot %d outside the %d resident frames", slot, p->frames_resident);
     if (dev_format_split("ingest_device", dev_format, &format, &sample, &sb, hbd)) return -1;
     if (format == H264E_INGEST_RGB && pixel_bytes != 3 && pixel_bytes != 4) FAIL("ingest_device: RGB pixels of %d bytes (3 or 4)", pixel_bytes);
+    if (p->tm_on && tonemap_format_refused("ingest_device", dev_format, format, sample, hbd)) return -1;
     memset(S, 0, sizeof(*S));
     S->format = format; S->pixel_bytes = format == H264E_INGEST_RGB ? pixel_bytes : 1; S->sample = sample;
     S->width = p->G.width; S->height = p->G.height;
@@ -1433,7 +1518,13 @@ static int ingest_enqueue(h264e_hip_pool_t *p, int slot, int format, const void 
     if (p) HIPCHK(hipSetDevice(p->device));
     if (ingest_check(p, slot, format, planes, strides, pixel_bytes, &S)) return -1;
     if (ingest_order(p, producer_stream)) return -1;
-    bk_launch_ingest(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
+    if (p->tm_on)                       /* enc_tonemap.h: the checked frame is HDR10 */
+    {
+        h264e_tonemap_src_t T;
+        tonemap_src(p, S.format, S.depth, S.plane, S.stride, S.width, S.height, &T);
+        bk_launch_tonemap(T, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
+    }
+    else bk_launch_ingest(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1456,12 +1547,13 @@ extern "C" int h264e_hip_ingest_device(h264e_hip_pool_t *p, int slot, int format
 /* everything that is refused, without a launch; fills the kernel's view of the source.  win = {src_width, src_height, crop_x, crop_y,
  * crop_width, crop_height}, crop_width 0 = the whole source.  Plane extents come from the SOURCE size and the window: what must be
  * device memory inside one allocation is [the window's first byte, the last byte of its last row] of every plane. */
-static int scale_check(const h264e_hip_pool_t *p, int slot, int dev_format, const void *const planes[3], const int strides[3], const int *win, h264e_scale_src_t *S)
+static int scale_check(const h264e_hip_pool_t *p, int tm, int slot, int dev_format, const void *const planes[3], const int strides[3], const int *win, h264e_scale_src_t *S)
 {
     int format, sample, sb, hbd[4];
     if (!p || !planes || !strides || !win) FAIL("scale_device: null argument");
     if (slot < 0 || slot >= p->frames_resident) FAIL("scale_device: slot %d outside the %d resident frames", slot, p->frames_resident);
     if (dev_format_split("scale_device", dev_format, &format, &sample, &sb, hbd)) return -1;
+    if (tm && tonemap_format_refused("scale_device", dev_format, format, sample, hbd)) return -1;
     if (format == H264E_INGEST_RGB) FAIL("scale_device: interleaved RGB (format %d) cannot be combined with a window: convert at the picture's size, or hand over planar RGB (format %d), I420 or NV12", format, H264E_INGEST_RGBP);
     const int srcw = win[0], srch = win[1], dw = p->G.width, dh = p->G.height;
     if (srcw <= 0 || srch <= 0) FAIL("scale_device: source of %d x %d samples", srcw, srch);
@@ -1533,14 +1625,45 @@ extern "C" int h264e_hip_scale_check(h264e_hip_pool_t *p, int slot, int format, 
 {
     h264e_scale_src_t S;
     if (p) (void)hipSetDevice(p->device);
-    return scale_check(p, slot, format, planes, strides, win, &S);
+    return scale_check(p, p ? p->tm_on : 0, slot, format, planes, strides, win, &S);
+}
+
+/* HDR10 input through a window (enc_tonemap.h): S is the checked 16-bit source.  Its window is tone-mapped at the source's resolution into
+ * the pool's scratch surface, an 8-bit packed I420 picture of the window's size, and the existing scale kernel runs from there as for
+ * any I420 source of that size: two launches on the copy stream, one behind the other, so the surface is reused frame after frame */
+static int tonemap_scale(h264e_hip_pool_t *p, int slot, int dev_format, const h264e_scale_src_t &S, void *producer_stream)
+{
+    const size_t need = (size_t)S.sw*(size_t)S.sh*3/2;
+    if (p->tm_scratch_bytes < need)
+    {
+        HIPCHK(hipStreamSynchronize(p->copy_stream));       /* an earlier frame's launches may still use the smaller surface */
+        dev_free(p->tm_scratch);
+        p->tm_scratch = 0; p->tm_scratch_bytes = 0;
+        if (dev_malloc((void **)&p->tm_scratch, need)) { p->tm_scratch = 0; FAIL("scale_device: device allocation failed (%zu bytes for the tone-mapped window of %d x %d)", need, S.sw, S.sh); }
+        p->tm_scratch_bytes = need;
+    }
+    const uint8_t *src[3] = { S.c[0].base, S.c[1].base, S.c[2].base };
+    const int sst[3] = { S.c[0].stride, S.c[1].stride, S.c[2].stride };
+    h264e_tonemap_src_t T;
+    tonemap_src(p, dev_format & 3, S.depth, src, sst, S.sw, S.sh, &T);
+    const void *planes[3] = { p->tm_scratch, p->tm_scratch + (size_t)S.sw*S.sh, p->tm_scratch + (size_t)S.sw*S.sh + (size_t)(S.sw/2)*(S.sh/2) };
+    const int strides[3] = { S.sw, S.sw/2, S.sw/2 }, win[6] = { S.sw, S.sh, 0, 0, 0, 0 };
+    h264e_scale_src_t S8;
+    if (scale_check(p, 0, slot, H264E_INGEST_I420, planes, strides, win, &S8)) return -1;
+    if (ingest_order(p, producer_stream)) return -1;
+    bk_launch_tonemap(T, p->tm_scratch, p->copy_stream);
+    HIPCHK(hipGetLastError());
+    bk_launch_scale(S8, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 extern "C" int h264e_hip_scale_device_async(h264e_hip_pool_t *p, int slot, int format, const void *const planes[3], const int strides[3], const int *win, void *producer_stream)
 {
     h264e_scale_src_t S;
     if (p) HIPCHK(hipSetDevice(p->device));
-    if (scale_check(p, slot, format, planes, strides, win, &S)) return -1;
+    if (scale_check(p, p ? p->tm_on : 0, slot, format, planes, strides, win, &S)) return -1;
+    if (p->tm_on) return tonemap_scale(p, slot, format, S, producer_stream);
     if (ingest_order(p, producer_stream)) return -1;
     if ((format & 3) == H264E_INGEST_RGBP) bk_launch_scale_rgb(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);
     else bk_launch_scale(S, p->clip + p->frame_bytes*(size_t)slot, p->copy_stream);

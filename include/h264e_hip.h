@@ -127,6 +127,21 @@ int  h264e_hip_ingest_device_async(h264e_hip_pool_t *pool, int slot, int format,
 /* The matrix that later RGB / RGBP ingest and scale launches of this pool convert with: bt709 0 = BT.601, 1 = BT.709; full_range 0 =
  * limited (16..235 / 16..240), 1 = full (0..255).  A new pool has (0, 0).  Slots already written keep their bytes. */
 int  h264e_hip_set_color(h264e_hip_pool_t *pool, int bt709, int full_range);
+/* HDR10 input (enc_tonemap.h): while it is on, h264e_hip_ingest_device / _scale_device and their _async and _check forms take only 16-bit
+ * I420 / NV12 frames of depth 10 .. 16 (every other format is refused by name, nothing is launched) and tone-map them -- PQ transfer,
+ * BT.2020 NCL limited range in; 8-bit BT.709 R'G'B' converted by the matrix of h264e_hip_set_color out -- by ONE launch of
+ * h264e_tonemap_kernel on the copy stream, ordered and completed like the ingest.  Through a window: that launch writes the tone-mapped
+ * window into a scratch surface of the pool (8-bit I420, sized on first use, reused, freed with the pool) and the scale kernel of an
+ * I420 source runs from it: two launches.  transfer 0 = off (a new pool; launches, bytes and allocations are those of a pool that never
+ * heard of it), 1 = PQ; curve 0 = hable, 1 = reinhard, 2 = clip; peak_nits 0 = 1000, ref_white_nits 0 = 203.  _set uploads the tables
+ * (9 KB of device memory, allocated the first time it is switched on); `who` names the caller in the refusals.  _check: the refusals of
+ * the parameters alone.  _tables: the tables the kernel will use for these parameters, by the one function _set uses; ycc = ky, crv,
+ * cgu, cgv, cbu in Q14, then 64, 512, 14.  _state: state[0] = on, state[1] = bytes of the device table buffer, state[2] = bytes of the
+ * scratch surface (0 = not allocated). */
+int  h264e_hip_tonemap_check(const char *who, int transfer, int curve, double peak_nits, double ref_white_nits);
+int  h264e_hip_tonemap_set(h264e_hip_pool_t *pool, const char *who, int transfer, int curve, double peak_nits, double ref_white_nits);
+int  h264e_hip_tonemap_tables(int transfer, int curve, double peak_nits, double ref_white_nits, int ycc[8], float eotf[1024], float scale[1024], float thresh[256]);
+int  h264e_hip_tonemap_state(const h264e_hip_pool_t *pool, long long state[3]);
 /* Device-resident input of another size (enc_scale.h): a window of an I420 or NV12 source frame is reduced to the pool's picture by an
  * exact area filter, by ONE kernel launch on the copy stream, ordered and completed like h264e_hip_ingest_device.  Planar RGB (format 3,
  * enc_scale_rgb.h): each channel is reduced by that filter at luma geometry, the result converted as the ingest does.  win = six ints:

@@ -423,6 +423,52 @@ int  H264E_ssim_planes(int device, const void *a, int a_stride, const void *b, i
  * made again from the first frame that is uploaded again.  The sums of squared differences compare the RAW input with the
  * reconstruction, as the reference's --psnr does.  Refused with keep_records (GOP shards).  0 = done, -1 = refused. */
 int  H264E_clip_set_denoise(H264E_clip_t *clip, int on);
+/* HDR10 device input: tone mapping.  A setting of the encoder, not a format bit, off by default; with it off no byte, record, launch or
+ * allocation differs from an encoder that never heard of it.  While it is on, the 16-bit device frames of H264E_encode_device[_scaled]
+ * and H264E_clip_upload_device[_scaled] are taken as HDR10 -- PQ transfer (SMPTE ST 2084), BT.2020 primaries, BT.2020 non-constant
+ * luminance Y'CbCr in limited range -- and tone-mapped by one gfx950 kernel to an 8-bit SDR R'G'B' picture with BT.709 primaries and
+ * transfer, which is converted to the 4:2:0 input exactly as an RGB device frame is, with the matrix H264E_set_color selected (the
+ * pairing that players expect is H264E_MATRIX_BT709: the stream then says what it holds).  Host-frame calls are unchanged.
+ *   Accepted while on: I420 | H264E_DEV_DEPTH(d) and NV12 | H264E_DEV_DEPTH(d), d = 10 .. 16 (H264E_DEV_FORMAT_P010 / _P016 included).
+ *   Every other device format -- 8-bit, RGB, RGBP, 4:2:2, 4:4:4 -- and d = 9 is refused by name; the refusal moves nothing.  4:2:2 and
+ *   4:4:4 HDR surfaces and the HLG transfer are out of scope.
+ * The definition (the reference has none; tests/tonemap_model.py restates it bit for bit; integers, or single float32 operations each
+ * rounded on its own, never fused).  Per 2x2 luma block with its one chroma pair; chroma is REPLICATED over the block, the siting
+ * shift is ignored as elsewhere:
+ *   1. word to 10-bit code: c = min(1023, (v + r) >> s), s = d - 10, r = s ? 1 << (s - 1) : 0 -- a 12-bit source is reduced to 10-bit codes;
+ *   2. to R'G'B' codes 0 .. 1023 in Q14, y = Y - 64, u = Cb - 512, v = Cr - 512, arithmetic shift, clamp to 0 .. 1023:
+ *          R = clamp((ky y + crv v + 8192) >> 14), G = clamp((ky y - cgu u - cgv v + 8192) >> 14), B = clamp((ky y + cbu u + 8192) >> 14)
+ *      ky = 19133, crv = 27584, cgu = 3078, cgv = 10688, cbu = 35194: rint(16384 x) of 1023/876, 1.4746 * 1023/896,
+ *      (0.0593 * 1.8814 / 0.6780) * 1023/896, (0.2627 * 1.4746 / 0.6780) * 1023/896, 1.8814 * 1023/896;
+ *   3. m = max(R, G, B) of the codes; L_ch = eotf[ch] * scale[m], one multiply per channel.  eotf[c] = float32 of
+ *      10000 PQ_EOTF(c / 1023) / ref_white; scale[c] = float32 of t(min(x, p)) / x, x that value before it is rounded to float32,
+ *      p = peak / ref_white, 1 where x = 0.  t: clip min(x, 1); reinhard x (1 + x / p^2) / (1 + x); hable h(x) / h(p) with
+ *      h(x) = (x (A x + C B) + D E) / (x (A x + B) + D F) - E / F, A .. F = .15, .50, .10, .20, .02, .30.  t(p) = 1 for all three;
+ *   4. gamut, BT.2020 to BT.709 (BT.2087): o = (m0 L_R + m1 L_G) + m2 L_B with the rows 1.6605 -0.5876 -0.0728 / -0.1246 1.1329 -0.0083 /
+ *      -0.0182 -0.1006 1.1187 as float32 constants.  Colours outside BT.709 are CLIPPED by the next step, not compressed;
+ *   5. BT.709 OETF, exactly rounded: code = #{k in 1 .. 255 : o >= thresh[k]}, thresh[k] = float32 of the inverse OETF at (k - 0.5) / 255
+ *      (x / 4.5 below 4.5 * 0.018, ((x + 0.099) / 1.099)^(1 / 0.45) above);
+ *   6. the 8-bit R'G'B' picture to Y, U, V by the integer rows of the RGB device input above.
+ * Through an H264E_dev_window_t (crop values even, as for I420): the window is tone-mapped at the source's resolution into an 8-bit I420
+ * surface that the encoder owns (sized on first use, reused, freed with the encoder), and the I420 window path runs from it: by
+ * construction what the tone-mapped crop fed as I420 with that source size gives; the limits and refusals are I420's.
+ * peak_nits: the brightest light of the source that is kept apart from white (0 = 1000); ref_white_nits: the light that becomes SDR
+ * white 1.0 (0 = 203).  Refused, with the value in H264E_last_error: an unknown transfer or curve, non-finite values, a reference white
+ * outside 50 .. 1000, a peak below the reference white or above 10000.  Accepted where H264E_set_color / H264E_clip_set_color are --
+ * before the first frame, while the clip stands at frame 0 -- with their statuses; a rewind keeps the setting.
+ * H264E_tonemap_tables: a pure host function, the tables the kernel will use for these parameters (0 = done, -1 = refused);
+ * ycc = ky, crv, cgu, cgv, cbu, then 64, 512, 14. */
+#define H264E_TONEMAP_OFF 0
+#define H264E_TONEMAP_PQ  1                 /* ST 2084, BT.2020 non-constant luminance, limited range */
+#define H264E_TONECURVE_HABLE 0
+#define H264E_TONECURVE_REINHARD 1
+#define H264E_TONECURVE_CLIP 2
+int  H264E_set_tonemap(H264E_persist_t *enc, int transfer, int curve, double peak_nits, double ref_white_nits);
+int  H264E_clip_set_tonemap(H264E_clip_t *clip, int transfer, int curve, double peak_nits, double ref_white_nits);
+int  H264E_tonemap_tables(int transfer, int curve, double peak_nits, double ref_white_nits, int ycc[8], float eotf[1024], float scale[1024], float thresh[256]);
+/* state[0] = tone mapping is on, state[1] = bytes of the device table buffer, state[2] = bytes of the window surface (0 = not allocated) */
+int  H264E_tonemap_state(H264E_persist_t *enc, long long state[3]);
+int  H264E_clip_tonemap_state(H264E_clip_t *clip, long long state[3]);
 /* H264E_set_color / H264E_set_frame_rate for the clip encoder (see there) */
 int  H264E_clip_set_color(H264E_clip_t *clip, int matrix, int full_range);
 int  H264E_clip_set_frame_rate(H264E_clip_t *clip, int num, int den);
