@@ -620,6 +620,24 @@ DEV void hp_row_load(const lu8 *q, uint32_t &a, uint32_t &b, uint32_t &c)
     a = alignbyte32(d1, d0, sh); b = alignbyte32(d2, d1, sh); c = alignbyte32(d3, d2, sh);
 }
 
+/* The half-sample filters below run on sample PAIRS (wave.h pk16): every first-stage value fits 16 bits -- tap6 of bytes lies in [-2550, 10710] -- and so do
+ * the three symmetric pair sums of the second stage, [-5100, 21420], the outer one with the rounding term 512 too; only the second stage's
+ * weighted sum needs 32 bits. */
+DEV pk16 pk_tap6(pk16 a, pk16 b, pk16 c, pk16 d, pk16 e, pk16 f)
+{
+    return pk_mad(pk_add(b, e), -5, pk_mad(pk_add(c, d), 20, pk_add(a, f)));
+}
+/* samples (k, k + 1) of the eight bytes hi:lo as a pair, k = 0 .. 6 */
+DEV pk16 pk_bytes(uint32_t hi, uint32_t lo, int k) { return pk_from_u32(perm32(hi, lo, 0x0c010c00u + 0x00010001u*(uint32_t)k)); }
+/* the low bytes of two pairs as four packed samples (the pairs hold 0 .. 255) */
+DEV uint32_t pk_pack_u8(pk16 lo, pk16 hi) { return perm32(pk_to_u32(hi), pk_to_u32(lo), 0x06040200u); }
+/* (v + 16) >> 5 clamped to 0 .. 255, on two pairs, packed */
+DEV uint32_t pk_round5_u8(pk16 lo, pk16 hi)
+{
+    const pk16 r = pk_make(16, 16);
+    return pk_pack_u8(pk_clip255(pk_sra(pk_add(lo, r), 5)), pk_clip255(pk_sra(pk_add(hi, r), 5)));
+}
+
 /*
  * The same three half-sample planes for `nrows` (1, 2 or 4) CONSECUTIVE rows of one 4-sample column group: row k needs the horizontal
  * filters of window rows k-2 .. k+3, so consecutive rows share five of their six -- nrows + 5 filtered rows instead of 6 * nrows (a lane
@@ -631,8 +649,11 @@ DEV void hp_row_load(const lu8 *q, uint32_t &a, uint32_t &b, uint32_t &c)
  */
 template <class EMIT> DEV void halfpel3_rows(const lu8 *at, int ox, int oy, int nrows, EMIT emit)
 {
-    int th[6][4];
-    uint32_t cx[6];
+    pk16 th[6][2];                      /* per window row: its horizontal filter, two pairs */
+    uint32_t cx[6];                     /* ... and the integer columns the vertical filter runs on as packed bytes, unpacked where they are used:
+                                         * kept as pairs they are twelve registers more, and the allocation of the whole kernel is at its limit */
+    uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;        /* the columns of the last four rows, oldest first */
+    const uint32_t cx_sel = 0x03020100u + 0x01010101u*(uint32_t)ox;
 #pragma unroll
     for (int j = 0; j < 9; j++)
     {
@@ -641,30 +662,44 @@ template <class EMIT> DEV void halfpel3_rows(const lu8 *at, int ox, int oy, int 
             const int s = j % 6;
             uint32_t a, b, c;
             hp_row_load(at + (j - 2)*WIN_STRIDE, a, b, c);
-            int p[12];
-#pragma unroll
-            for (int k = 0; k < 4; k++) { p[k] = (int)((a >> (8*k)) & 255); p[4 + k] = (int)((b >> (8*k)) & 255); p[8 + k] = (int)((c >> (8*k)) & 255); }
-#pragma unroll
-            for (int i = 0; i < 4; i++) th[s][i] = tap6(p[i + 2], p[i + 3], p[i + 4], p[i + 5], p[i + 6], p[i + 7]);
-            cx[s] = ox ? alignbyte32(c, b, 1) : b;                 /* the integer columns the vertical filter runs on */
+            {
+                /* the row's twelve samples p0 .. p11 = a | b | c as the pairs (p2,p3) .. (p9,p10) */
+                const pk16 p4 = pk_bytes(c, b, 0), p5 = pk_bytes(c, b, 1), p6 = pk_bytes(c, b, 2), p7 = pk_bytes(c, b, 3);
+                th[s][0] = pk_tap6(pk_bytes(b, a, 2), pk_bytes(b, a, 3), p4, p5, p6, p7);
+                th[s][1] = pk_tap6(p4, p5, p6, p7, pk_bytes(c, b, 4), pk_bytes(c, b, 5));
+            }
+            cx[s] = perm32(c, b, cx_sel);
+            /* (the full-sample row through scalars: a select between two elements of the unrolled array becomes a select of the INDEX, and
+             * the indexed read a compare chain over all six elements) */
+            q0 = q1; q1 = q2; q2 = q3; q3 = cx[s];
             if (j >= 5)
             {
                 /* rows j-5 .. j are in the sets: output row j - 5 */
                 const int r0 = (j - 5) % 6, r1 = (j - 4) % 6, r2 = (j - 3) % 6, r3 = (j - 2) % 6, r4 = (j - 1) % 6, r5 = j % 6;
                 hp4_t o;
-                o.x = oy ? cx[r3] : cx[r2];
-                o.y = o.z = o.w = 0;
-#pragma unroll
-                for (int i = 0; i < 4; i++)
+                o.x = oy ? q1 : q0;                 /* row j - 2 or j - 3 */
                 {
-#define CXB(r) ((int)((cx[r] >> (8*i)) & 255))
+                    const pk16 h0 = oy ? th[r3][0] : th[r2][0], h1 = oy ? th[r3][1] : th[r2][1];
+                    o.y = pk_round5_u8(h0, h1);
+                }
+#define CXP(r, k) pk_bytes(0u, cx[r], k)
+                o.z = pk_round5_u8(pk_tap6(CXP(r0, 0), CXP(r1, 0), CXP(r2, 0), CXP(r3, 0), CXP(r4, 0), CXP(r5, 0)),
+                                   pk_tap6(CXP(r0, 2), CXP(r1, 2), CXP(r2, 2), CXP(r3, 2), CXP(r4, 2), CXP(r5, 2)));
+#undef CXP
+                o.w = 0;
+#pragma unroll
+                for (int h = 0; h < 2; h++)
+                {
+                    /* the second stage: its symmetric pair sums on pairs, the weighted sum in 32 bits -- a dot product with (k, 0) or (0, k)
+                     * takes the wanted half of a pair there, weighted, and adds it (the first term has nothing to add to: a 24-bit multiply
+                     * that sign-extends its half in the operand select) */
+                    const pk16 af = pk_add(pk_add(th[r0][h], th[r5][h]), pk_make(512, 512)), be = pk_add(th[r1][h], th[r4][h]), cd = pk_add(th[r2][h], th[r3][h]);
+                    const int w0 = pk_dot2(af, pk_make(1, 0), pk_dot2(cd, pk_make(20, 0), -5*pk_lo(be)));
+                    const int w1 = pk_dot2(af, pk_make(0, 1), pk_dot2(cd, pk_make(0, 20), -5*pk_hi(be)));
                     /* shr_opaque: keeps the compiler from fusing "shift, clamp, pack" of two results into v_ashr_pk_u8_i32, whose
                      * results did not match the separate instructions on gfx950 (ROCm 7.2) in this function (tests/gpu_repro/ashr_pk.hip) */
-                    const int fh = clip255(shr_opaque((oy ? th[r3][i] : th[r2][i]) + 16, 5));
-                    const int fv = clip255(shr_opaque(tap6(CXB(r0), CXB(r1), CXB(r2), CXB(r3), CXB(r4), CXB(r5)) + 16, 5));
-                    const int fd = clip255(shr_opaque(tap6w(th[r0][i], th[r1][i], th[r2][i], th[r3][i], th[r4][i], th[r5][i]) + 512, 10));
-#undef CXB
-                    o.y |= (uint32_t)fh << (8*i); o.z |= (uint32_t)fv << (8*i); o.w |= (uint32_t)fd << (8*i);
+                    const int d0 = clip255(shr_opaque(w0, 10)), d1 = clip255(shr_opaque(w1, 10));
+                    o.w |= ((uint32_t)d0 | ((uint32_t)d1 << 8)) << (16*h);
                 }
                 emit(j - 5, o);
             }
@@ -727,9 +762,7 @@ DEV void wave_avg(const uint8_t *a, const uint8_t *b, uint8_t *d, int w, int h)
         if (l < n)
         {
             int r = l >> (g >> 1), c = l & (g - 1);              /* g is 2 or 4 */
-            uint32_t x = lds32(a + 16*r + 4*c), y = lds32(b + 16*r + 4*c), o = 0;
-            for (int k = 0; k < 4; k++) o |= ((((x >> (8*k)) & 255) + ((y >> (8*k)) & 255) + 1) >> 1) << (8*k);
-            lds32_store(d + 16*r + 4*c, o);
+            lds32_store(d + 16*r + 4*c, avg4_u8(lds32(a + 16*r + 4*c), lds32(b + 16*r + 4*c)));
         }
     }
     wave_sync();

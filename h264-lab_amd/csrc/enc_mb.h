@@ -402,7 +402,6 @@ DEV int diamond_g(RowLds &L, const MbBuf &B, const MbCtx &m, int px, int py, mv3
         if (!inside) rv_wait_rect_g(R, fy0 - 3, fx0 + w + 4, fy0 + h + 3);
         /* the 2x2 integer cell that holds the three half-sample positions: vdg = (+-1, +-1) says on which side of (x,y) it lies */
         const int hp_ox = mvx(vdg) < 0 ? 1 : 0, hp_oy = mvy(vdg) < 0 ? 1 : 0, hp_pq_vertical = mvx(pq) == 0;
-#define AVG4(x, y) (((x) | (y)) - ((((x) ^ (y)) >> 1) & 0x7f7f7f7fu))                    /* per-byte (x + y + 1) >> 1 */
         grp_sum8([&](int i, int *sv) {
             uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
             /* a lane owns `npass` CONSECUTIVE rows of one 4-sample column group (not every 16th dword as elsewhere): consecutive rows share
@@ -411,7 +410,9 @@ DEV int diamond_g(RowLds &L, const MbBuf &B, const MbCtx &m, int px, int py, mv3
             const auto probe = [&](int r, uint32_t q00, uint32_t q02, uint32_t q20, uint32_t q22) {
                 const int o = w*r + 4*c4;
                 const uint32_t in4 = lds32(b + 16*r + 4*c4);
-                const uint32_t q01 = AVG4(q00, q02), q10 = AVG4(q00, q20), q11 = AVG4(q02, q20), q12 = AVG4(q22, q02);
+                #define AVG4F(x, y) (((x) | (y)) - ((((x) ^ (y)) >> 1) & 0x7f7f7f7fu))
+                const uint32_t q01 = AVG4F(q00, q02), q10 = AVG4F(q00, q20), q11 = AVG4F(q02, q20), q12 = AVG4F(q22, q02);
+#undef AVG4F
                 lds32_store(scr + o, q00); lds32_store(scr + plane + o, q02); lds32_store(scr + 2*plane + o, q20); lds32_store(scr + 3*plane + o, q22);
                 t0 = sad4_u8(q02, in4, t0); t1 = sad4_u8(q01, in4, t1); t2 = sad4_u8(q20, in4, t2);
                 t3 = sad4_u8(q10, in4, t3); t4 = sad4_u8(q11, in4, t4); t5 = sad4_u8(q22, in4, t5);
@@ -467,10 +468,9 @@ DEV int diamond_g(RowLds &L, const MbBuf &B, const MbCtx &m, int px, int py, mv3
             {
                 const int d = i + 16*k, r = d >> (g >> 1), c4 = d & (g - 1), o = w*r + 4*c4;
                 const uint32_t x = lds32(scr + pa*plane + o), y = lds32(scr + pb*plane + o);
-                lds32_store(dst + 16*r + 4*c4, AVG4(x, y));          /* the average of a plane with itself is the plane */
+                lds32_store(dst + 16*r + 4*c4, avg4_u8(x, y));          /* the average of a plane with itself is the plane */
             }
         }
-#undef AVG4
         wave_sync();
         mv = vbest;
     }

@@ -29,6 +29,7 @@
  *  13 partition_hints                          in: n x int32 sad[4]                    args: n <= 64           out: n x int32 mode[4]
  *  14 mv_cost                                  in: n x int32 (mv x, y, pred x, y, qp)  args: n <= 256          out: n x int32 cost
  *  15 bit writer (bw_put, bw_ue, bw_se)        in: n x int32 (kind 0/1/2, value, length)   args: n <= 64       out: int32 nbits, overflow | bytes
+ *  16 packed byte average (avg4_u8)            in: none (the 65 536 byte pairs are made on the device)   out: 16 384 dwords, pair n = 256*x + y in byte n
  * `window` = 1 reads the reference samples through the LDS window like the macroblock loop, 0 through the HBM path.
  */
 struct StageLds
@@ -49,6 +50,7 @@ struct StageLds
 #define STAGE_IN_MAX (96*96 + 256)
 #define STAGE_NARGS 24
 #define STAGE_OUT_MAX (16 + 16*64 + 32 + 32 + 256)
+#define STAGE_AVG4_DWORDS 16384         /* stage 16 alone writes more than STAGE_OUT_MAX: 4 bytes each */
 DEV void stage_selftest(StageLds &S, RowLds &L, int stage, const GLOBAL_AS uint8_t *in, const int *args, GLOBAL_AS uint8_t *out)
 {
     int a[STAGE_NARGS];
@@ -298,6 +300,17 @@ DEV void stage_selftest(StageLds &S, RowLds &L, int stage, const GLOBAL_AS uint8
         const uint32_t nbits = bw_bits(b);
         if (b.nacc) bw_put(b, 32 - b.nacc, 0);
         if (wave_lane() == 0) { oi[0] = (int32_t)nbits; oi[1] = b.overflow; }
+    } else if (stage == 16)
+    {
+        /* every pair of bytes once: byte j of dword k holds the pair number n = 4*k + j, x = n >> 8 and y = n & 255 */
+        WAVE_FOR(l)
+        {
+            for (int k = l; k < STAGE_AVG4_DWORDS; k += 64)
+            {
+                const uint32_t x = (uint32_t)(k >> 6)*0x01010101u, y = (uint32_t)((4*k) & 255)*0x01010101u + 0x03020100u;
+                gstore32((gu8 *)out + 4*k, avg4_u8(x, y));
+            }
+        }
     }
 }
 

@@ -2794,11 +2794,12 @@ extern "C" int h264e_hip_selftest_nal_escape(h264e_hip_pool_t *p, const uint8_t 
 
 extern "C" int h264e_hip_selftest_stage(h264e_hip_pool_t *p, int stage, const uint8_t *in, uint32_t nin, const int *args /* [24] */, uint8_t *out, uint32_t nout)
 {
-    if (!p || !in || !args || !out || stage < 1 || stage > 15 || nin > STAGE_IN_MAX || nout > STAGE_OUT_MAX) FAIL("selftest_stage: bad argument");
+    const uint32_t out_max = stage == 16 ? 4*STAGE_AVG4_DWORDS : STAGE_OUT_MAX;          /* stage 16 writes all of it, whatever nout asks for */
+    if (!p || !in || !args || !out || stage < 1 || stage > 16 || nin > STAGE_IN_MAX || nout > out_max) FAIL("selftest_stage: bad argument");
     uint8_t *buf = 0;
     HIPCHK(hipSetDevice(p->device));
-    if (hipMalloc((void **)&buf, STAGE_IN_MAX + STAGE_OUT_MAX + 256) != hipSuccess) FAIL("selftest_stage: device allocation failed");
-    hipError_t e = hipMemset(buf, 0, STAGE_IN_MAX + STAGE_OUT_MAX + 256);
+    if (hipMalloc((void **)&buf, STAGE_IN_MAX + out_max + 256) != hipSuccess) FAIL("selftest_stage: device allocation failed");
+    hipError_t e = hipMemset(buf, 0, STAGE_IN_MAX + out_max + 256);
     if (e == hipSuccess) e = hipMemcpy(buf, in, nin, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(buf + STAGE_IN_MAX, args, STAGE_NARGS*sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess)

@@ -17,6 +17,9 @@
 
 #include <stdint.h>
 #include <string.h>
+#ifdef H264E_EMU
+#include <assert.h>
+#endif
 
 /* explicit address spaces: HBM pointers that were loaded from memory would otherwise be generic (FLAT instructions) */
 #ifdef H264E_EMU
@@ -81,6 +84,35 @@ DEV uint32_t sad4_u8(uint32_t a, uint32_t b, uint32_t acc)
         acc += (uint32_t)(d < 0 ? -d : d);
     }
     return acc;
+}
+/* per-byte (x + y + 1) >> 1 of two packed dwords.  The emulation states the result by the carry-free formula, the device build (below) is
+ * the one instruction the machine has for it: two independent statements of the same sixteen-bit table (tests/test_emu_subpel_arith.py) */
+DEV uint32_t avg4_u8(uint32_t x, uint32_t y) { return (x | y) - (((x ^ y) >> 1) & 0x7f7f7f7fu); }
+/* ---- pk16: two 16-bit samples in one register (the half-sample filters of enc_kernels.h run on sample PAIRS).  Every operation wraps at 16
+ * bits per half like the device's packed instructions; the emulation computes in int and truncates */
+struct pk16 { int16_t lo, hi; };
+DEV pk16 pk_make(int lo, int hi) { pk16 r; r.lo = (int16_t)lo; r.hi = (int16_t)hi; return r; }
+DEV pk16 pk_from_u32(uint32_t v) { return pk_make((int)(v & 0xffffu), (int)(v >> 16)); }
+DEV uint32_t pk_to_u32(pk16 a) { return (uint32_t)(uint16_t)a.lo | ((uint32_t)(uint16_t)a.hi << 16); }
+DEV int pk_lo(pk16 a) { return a.lo; }
+DEV int pk_hi(pk16 a) { return a.hi; }
+DEV pk16 pk_add(pk16 a, pk16 b) { return pk_make(a.lo + b.lo, a.hi + b.hi); }
+DEV pk16 pk_mad(pk16 a, int k, pk16 c) { return pk_make(a.lo*k + c.lo, a.hi*k + c.hi); }          /* a*k + c, k a small constant */
+DEV pk16 pk_sra(pk16 a, int s) { return pk_make(a.lo >> s, a.hi >> s); }
+DEV pk16 pk_clip255(pk16 a) { return pk_make(a.lo < 0 ? 0 : a.lo > 255 ? 255 : a.lo, a.hi < 0 ? 0 : a.hi > 255 ? 255 : a.hi); }
+DEV int pk_dot2(pk16 a, pk16 b, int acc) { return a.lo*b.lo + a.hi*b.hi + acc; }
+/* v_perm_b32 for the selectors 0-7 and 0x0c: byte k of the result is byte sel[k] of the eight bytes hi:lo (0-3 lo, 4-7 hi), or zero for 0x0c */
+DEV uint32_t perm32(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+    const uint64_t src = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (int k = 0; k < 4; ++k)
+    {
+        const unsigned s = (sel >> (8*k)) & 255;
+        assert(s < 8 || s == 0x0c);         /* the other selectors (sign replication, 0xff) are not modelled: add them before using them */
+        if (s < 8) r |= (uint32_t)((src >> (8*s)) & 255) << (8*k);
+    }
+    return r;
 }
 DEV int clz32(uint32_t v) { return __builtin_clz(v); }
 DEV int ctz32(uint32_t v) { return __builtin_ctz(v); }
@@ -268,6 +300,25 @@ template <class F> DEV void wave_sum8(F f, int out[8])
 }
 template <class F> DEV uint64_t wave_ballot(F f) { return __ballot(f(LANE)); }
 DEV uint32_t sad4_u8(uint32_t a, uint32_t b, uint32_t acc) { return __builtin_amdgcn_sad_u8(a, b, acc); }
+/* per-byte (x + y + 1) >> 1: v_lerp_u8 with a rounding bit of one in every byte */
+DEV uint32_t avg4_u8(uint32_t x, uint32_t y) { return __builtin_amdgcn_lerp(x, y, 0x01010101u); }
+/* ---- pk16: two 16-bit samples in one register, on the packed instructions (v_pk_add_u16, v_pk_mad_u16, v_pk_ashrrev_i16, v_pk_max_i16 /
+ * v_pk_min_i16).  Sums and products go through the unsigned type: they wrap at 16 bits by definition */
+typedef short pk16 __attribute__((ext_vector_type(2)));
+typedef unsigned short pk16u __attribute__((ext_vector_type(2)));
+DEV pk16 pk_make(int lo, int hi) { pk16 r; r.x = (short)lo; r.y = (short)hi; return r; }
+DEV pk16 pk_from_u32(uint32_t v) { return __builtin_bit_cast(pk16, v); }
+DEV uint32_t pk_to_u32(pk16 a) { return __builtin_bit_cast(uint32_t, a); }
+DEV int pk_lo(pk16 a) { return a.x; }
+DEV int pk_hi(pk16 a) { return a.y; }
+DEV pk16 pk_add(pk16 a, pk16 b) { return (pk16)((pk16u)a + (pk16u)b); }
+DEV pk16 pk_mad(pk16 a, int k, pk16 c) { const pk16u kk = (pk16u)(unsigned short)k; return (pk16)((pk16u)a*kk + (pk16u)c); }
+DEV pk16 pk_sra(pk16 a, int s) { return a >> (pk16)(short)s; }
+DEV pk16 pk_clip255(pk16 a) { return __builtin_elementwise_min(__builtin_elementwise_max(a, (pk16)(short)0), (pk16)(short)255); }
+/* a.lo*b.lo + a.hi*b.hi + acc in 32 bits (v_dot2_i32_i16): with b = (k, 0) or (0, k) it takes ONE half of a pair to 32 bits, weighted, in one
+ * instruction -- no unpacking */
+DEV int pk_dot2(pk16 a, pk16 b, int acc) { return __builtin_amdgcn_sdot2(a, b, acc, false); }
+DEV uint32_t perm32(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
 DEV int clz32(uint32_t v) { return __clz((int)v); }
 DEV int ctz32(uint32_t v) { return __builtin_ctz(v); }                                  /* v != 0 */
 DEV uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }

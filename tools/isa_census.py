@@ -22,7 +22,7 @@ CSRC = os.path.join(ROOT, "h264-lab_amd", "csrc")
 PHASES = ["row_begin", "row_end", "finalize_frame", "export_frame", "device_clusters_walk", "load_top", "load_input", "wave_load_window", "window_advance", "row_prefetch",
           "diamond_g", "search_type", "search_8x8_wave", "inter_choose", "intra16_cost", "intra4_choose", "intra_merge", "mb_decide", "mb_write", "df_strength",
           "predict_chroma_inter", "wave_pred_chroma", "mb_recon_front", "mb_recon_back", "mb_intra_decide", "mb_search", "mb_ctx_init", "rowtask_load", "poll_progress", "lds_wait"]
-SUBS = ["wave_xform_quant", "xform_quant_recon", "wave_recon", "cavlc_block", "cavlc_block_v", "bw_put", "bw_ue", "quant_luma_dc", "quant_chroma_dc", "halfpel3_win", "interp_core", "interp4_win", "interp4_hbm",
+SUBS = ["wave_xform_quant", "xform_quant_recon", "wave_recon", "cavlc_block", "cavlc_block_v", "bw_put", "bw_ue", "quant_luma_dc", "quant_chroma_dc", "halfpel3_rows", "interp_core", "interp4_win", "interp4_hbm",
         "wave_i4_choose", "i4_block_code", "wave_deblock", "rv_wait_rect", "rv_wait_rect_g", "ref_load4", "mv_cost", "mvp_get_arr", "mvp_put_arr", "set_range",
         "grp_sad_ref", "wave_sad_ref_q", "wave_sad_ref", "wave_interp_chroma", "wave_interp_luma", "grp_interp_luma", "wave_copy_wh", "wave_pred16", "skip_chroma_ok",
         "partition_hints", "v16_fwd4x4", "v16_inv4x4"]
